@@ -11,13 +11,25 @@ is.  The default (--steps 3) is exactly one configs[1] job.
 
 Inputs are generated on the device (splitmix64 stream of SURVEY.md 8c, tools/synth_reads.c is the same
 stream as text) before the timed region, so `value` is whole-job symbols / wall time with inputs resident
-in HBM.  Beside it the line reports
+in HBM.  A plain run does only that: set up, warm up, time the K steps, print the line (`ms_per_step` =
+wall time of the timed region / K).  With --full the line also reports
+  kernels_ms       every kernel group's hipEvent time over one more job run behind the clock
   value_host_api   the same job through rb2_hip_insert_multi on HOST buffers (what mr_insert_multi does:
                    one PCIe crossing per batch, no capacity hint) -- PCIe-inclusive, never `value`
+  roofline.traffic HBM bytes per k_merge launch (two rocprofv3 PMC passes of a plain run)
   whole_process    the CLI end to end on the same reads (text in, 6.0 GB .fmd out): main.c:340's number
+  secondary        the configs[2] / configs[3] / coverage30x shapes on one GPU
   cpu_baseline     the real reference (oracle/_ref) on a bounded sample of the same stream
+(--no-extras, --no-secondary, --no-pmc, --no-cpu-baseline drop legs of --full; --configs3-full and
+--cpu-full-config add legs and imply --full.)
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+--dump-outputs DIR writes, after the timed steps, what the index holds after the last one (the BWT a caller
+of mr_insert_multi would read back): DIR/counts.npy (the 6 x 6 count matrix, rope.h:19) and a fixed, seeded
+sample of the six ropes -- DIR/bwt_sample_pos.npy (positions in the concatenated BWT), bwt_sample_sym.npy
+(the symbol there) and bwt_sample_rank.npy (rope_rank1a before it: occurrences of the six symbols).  Same
+arguments, same inputs, same files.
+
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...
 
 N > 1: ONE index, its 31 sub-ropes sharded over the ranks (rb2_hip_default_owners), per round a sum of the
@@ -426,6 +438,47 @@ def secondary_coverage(L=101):
             "what": "coverage30x: %d x %d bp windows of one random %d bp genome (30x), RLO, -m1g batches on 1 GPU; inputs generated on the device, inserts timed" % (reads, L, glen)}
 
 
+DUMP_SAMPLE_PER_ROPE = 65536        # positions per rope in --dump-outputs (one rank_batch launch per rope)
+DUMP_SAMPLE_PER_ROPE_MULTI = 2048   # the same through rank1a (one query per call) on a handle of several ranks
+DUMP_SEED = 20240601
+
+
+def dump_outputs(bwt, out_dir):
+    """--dump-outputs: the count matrix and a fixed, seeded sample of the six ropes of the index as it stands.  Positions depend
+    only on the rope lengths (the count matrix), so two builds that compute the same BWT write the same files."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    counts = bwt.counts()
+    np.save(os.path.join(out_dir, "counts.npy"), counts.astype(np.float64))
+    if isinstance(bwt, Multi) and bwt.m.world > bwt.m.n:
+        sys.stderr.write("[bench] --dump-outputs: the ropes are spread over several processes; counts.npy only\n")
+        return
+    single = not isinstance(bwt, Multi)
+    per = DUMP_SAMPLE_PER_ROPE if single else DUMP_SAMPLE_PER_ROPE_MULTI
+    rng = np.random.default_rng(DUMP_SEED)
+    pos, sym, rank = [], [], []
+    base = 0
+    for b in range(6):
+        n = int(counts[b].sum())                       # symbols in rope b
+        xs = rng.integers(0, n, per) if n > 0 else np.zeros(0, np.int64)
+        xs = np.unique(xs).astype(np.int64)            # sorted; an empty rope gives none
+        q = np.concatenate([xs, xs + 1])
+        if single:
+            r = bwt.b.rank_batch(b, q)
+        else:
+            r = np.array([bwt.m.rank1a(b, int(x)) for x in q], np.int64).reshape(-1, 6)
+        before, after = r[:len(xs)], r[len(xs):]
+        d = after - before                             # one-hot: the symbol at x
+        assert len(xs) == 0 or (d.sum(axis=1) == 1).all(), "rank rows of rope %d do not step by one symbol" % b
+        pos.append(base + xs)
+        sym.append(d.argmax(axis=1))
+        rank.append(before)
+        base += n
+    np.save(os.path.join(out_dir, "bwt_sample_pos.npy"), np.concatenate(pos).astype(np.float64))
+    np.save(os.path.join(out_dir, "bwt_sample_sym.npy"), np.concatenate(sym).astype(np.float32))
+    np.save(os.path.join(out_dir, "bwt_sample_rank.npy"), np.concatenate(rank).astype(np.float64))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -436,14 +489,19 @@ def main():
     ap.add_argument("--batch", type=float, default=4.0, help="-m in GiB")
     ap.add_argument("--order", default="rlo", choices=["io", "rlo", "rclo"])
     ap.add_argument("--mode", default="weak", choices=["weak", "strong", "independent"], help="what N > 1 ranks do (see module docstring)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip the value_host_api / whole_process / secondary / PMC legs (profiling runs)")
-    ap.add_argument("--no-secondary", action="store_true", help="skip the configs[2]-shape leg")
-    ap.add_argument("--no-pmc", action="store_true", help="do not measure roofline.traffic in-run (use the committed summary if it matches the sources)")
+    ap.add_argument("--full", action="store_true", help="everything beyond the headline: per-group kernel times, host-API, PMC, whole-process, "
+                                                        "secondary and CPU-baseline legs (module docstring)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="after the timed steps, write the count matrix and a seeded sample of the BWT as DIR/*.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="(--full) skip the cpu_baseline leg")
+    ap.add_argument("--no-extras", action="store_true", help="(--full) skip the value_host_api / whole_process / secondary / PMC legs (profiling runs)")
+    ap.add_argument("--no-secondary", action="store_true", help="(--full) skip the configs[2]-shape leg")
+    ap.add_argument("--no-pmc", action="store_true", help="(--full) do not measure roofline.traffic in-run (use the committed summary if it matches the sources)")
     ap.add_argument("--cpu-sample-reads", type=int, default=10_000_000, help="reads of the reference's bounded sample (10 M: ~25 s of inserts)")
-    ap.add_argument("--configs3-full", action="store_true", help="also run BASELINE.json configs[3] at FULL size on one GPU (10 M x 10 kbp, ten -m10g batches, ~40 s): secondary.configs3_full_1gpu")
-    ap.add_argument("--cpu-full-config", action="store_true", help="re-measure cpu_baseline.full_config: the reference on ALL reads of configs[1] (~6.5 min of host time)")
+    ap.add_argument("--configs3-full", action="store_true", help="also run BASELINE.json configs[3] at FULL size on one GPU (10 M x 10 kbp, ten -m10g batches, ~40 s): secondary.configs3_full_1gpu; implies --full")
+    ap.add_argument("--cpu-full-config", action="store_true", help="re-measure cpu_baseline.full_config: the reference on ALL reads of configs[1] (~6.5 min of host time); implies --full")
     args = ap.parse_args()
+    if args.configs3_full or args.cpu_full_config:
+        args.full = True
 
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
@@ -570,8 +628,10 @@ def main():
     prof = bwt.eng.profile_get()
     counts = bwt.counts()
     ok_counts = int(counts.sum()) == sum(sizes[:last]) and int(counts[:, 0].sum()) == sum(n for _, n in job[:last])
+    if args.dump_outputs and rank == 0:
+        dump_outputs(bwt, args.dump_outputs)
     prof_all, prof_all_steps = prof, args.steps
-    if not full_prof:                                          # the per-group breakdown: one more job, every group timed, behind the clock
+    if args.full and not full_prof:                            # the per-group breakdown: one more job, every group timed, behind the clock
         bwt.eng.profile(1)
         bwt.eng.profile_get(reset=True)
         bwt.reset()
@@ -581,7 +641,7 @@ def main():
         prof_all, prof_all_steps = bwt.eng.profile_get(), nb
     mstats = bwt.stats() if isinstance(bwt, Multi) else None
     host_api = host_api_pinned = None
-    if rank == 0 and n_ranks == 1 and not args.no_extras:
+    if args.full and rank == 0 and n_ranks == 1 and not args.no_extras:
         bwt.reset()
         host_api = host_api_rate(HipBwt, so, dev, [p[0] for p in bufs], sizes)
         try:
@@ -635,17 +695,18 @@ def main():
                      "algorithmic_bytes_per_symbol": ALG_BYTES_PER_SYMBOL,
                      "algorithmic_bytes_per_launch": ALG_BYTES_PER_SYMBOL * units / max(1, mk["launches"]),
                      "note": None if not sharded else "rank 0 only; units per launch approximated by strings / active ranks"},
-        "kernels_ms": {k: round(v["ms"], 3) for k, v in prof_all.items()},
-        "kernels_ms_steps": prof_all_steps,
-        "kernels_ms_note": ("hipEvent scopes of every kernel group over the timed steps" if full_prof else
-                            "hipEvent scopes of every kernel group over ONE more job (%d steps) run behind the clock; inside the timed region only the k_merge launches carry events "
-                            "(roofline.avg_launch_ms)" % nb),
     }
+    if args.full or full_prof:                                 # (a plain run times only the k_merge launches: roofline.avg_launch_ms)
+        out["kernels_ms"] = {k: round(v["ms"], 3) for k, v in prof_all.items()}
+        out["kernels_ms_steps"] = prof_all_steps
+        out["kernels_ms_note"] = ("hipEvent scopes of every kernel group over the timed steps" if full_prof else
+                                  "hipEvent scopes of every kernel group over ONE more job (%d steps) run behind the clock; inside the timed region only the k_merge launches carry events "
+                                  "(roofline.avg_launch_ms)" % nb)
     # HBM bytes per k_merge launch: measured now (two PMC passes of one configs[1] job -- the per-launch average does not depend on
     # K because every job is the same job); else the committed summary of the same command, but only if it was taken from the
     # kernels that are being benchmarked (sha of the kernel sources)
     is_cfg1 = n_ranks == 1 and args.reads == 100_000_000 and args.batch == 4.0 and args.order == "rlo" and L == 101
-    if is_cfg1 and not args.no_extras and not args.no_pmc:
+    if args.full and is_cfg1 and not args.no_extras and not args.no_pmc:
         tr = measure_traffic()
         if tr is not None:
             out["roofline"]["traffic"] = tr["bytes_per_launch"]
@@ -682,7 +743,7 @@ def main():
         out["value_host_api"] = host_api
     if host_api_pinned is not None:
         out["value_host_api_pinned"] = host_api_pinned
-    if n_ranks == 1 and not args.no_extras:
+    if args.full and n_ranks == 1 and not args.no_extras:
         wp = whole_process(args.reads, L, so_flag, args.batch)
         if wp is not None:
             out["whole_process"] = wp
@@ -706,7 +767,7 @@ def main():
                     out.setdefault("secondary", {})["coverage30x_1gpu"] = cv
             except Exception as e:  # noqa: BLE001
                 sys.stderr.write("[bench] secondary coverage leg failed: %r\n" % (e,))
-    if not args.no_cpu_baseline and n_ranks == 1:
+    if args.full and not args.no_cpu_baseline and n_ranks == 1:
         out["cpu_baseline"] = cpu_baseline(L, so_flag, args.cpu_sample_reads)
         if args.cpu_full_config and is_cfg1:
             full = cpu_baseline(L, so_flag, args.reads, budget_s=900)

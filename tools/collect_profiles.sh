@@ -14,7 +14,7 @@ S=$O/summary
 mkdir -p $O $S
 cd /tmp && export TMPDIR=/tmp
 # 1. the driver's line (with all legs)
-timeout 1200 python $R/bench.py --gpus 1 --steps $STEPS --warmup $WARM > $O/bench.json 2> $O/bench.err
+timeout 1200 python $R/bench.py --gpus 1 --steps $STEPS --warmup $WARM --full > $O/bench.json 2> $O/bench.err
 # 2. kernel trace + stats of the same job
 timeout 900 rocprofv3 --kernel-trace --stats -d $O -o ktrace -- python $R/bench.py --steps $STEPS --warmup $WARM --no-cpu-baseline --no-extras > $O/ktrace.log 2>&1
 # 3. HBM traffic: FETCH_SIZE and WRITE_SIZE in separate passes (TCC slot limits), kernel-trace only

@@ -10,8 +10,8 @@ mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
 export RB2_BENCH_DEVICES=${RB2_BENCH_DEVICES:-0,0,0,0,0,0,0,0}
 {
-echo "# RB2_BENCH_DEVICES=$RB2_BENCH_DEVICES python bench.py --mode strong --steps 6 --warmup 1 --no-cpu-baseline --no-extras"
-python $R/bench.py --mode strong --steps 6 --warmup 1 --no-cpu-baseline --no-extras 2>/dev/null | python -c "
+echo "# RB2_BENCH_DEVICES=$RB2_BENCH_DEVICES python bench.py --mode strong --steps 6 --warmup 1 --full --no-cpu-baseline --no-extras"
+python $R/bench.py --mode strong --steps 6 --warmup 1 --full --no-cpu-baseline --no-extras 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.readline()); print('value', round(d['value'],2), 'Gsym/s  ms_per_step', round(d['ms_per_step'],1), d['config']['multi_stats'], {k: round(v) for k,v in d['kernels_ms'].items()})"
 timeout 900 rocprofv3 --kernel-trace --stats -d $O -o kt -- python $R/bench.py --mode strong --steps 3 --warmup 0 --no-cpu-baseline --no-extras > $O/kt.log 2>&1
