@@ -136,6 +136,32 @@ void rb2_hip_rank1a(rb2_hip_t *h, int b, int64_t x, int64_t cx[6]);
  * that ask millions of ranks (x, out: host memory). */
 void rb2_hip_rank_batch(rb2_hip_t *h, int b, int64_t n, const int64_t *x, int64_t *out);
 
+/* ---- FM-index queries on the device index ---------------------------------------------------
+ * The BWT this engine builds is an FM-index of the strings as read (they are inserted reversed, mr_insert_multi).  Coordinates:
+ *   rows     global row numbers of the concatenated BWT, rope 0 ($) through rope 5 (N): what the six rb2_hip_download_rope streams
+ *            give one after the other, what an .fmd of the index holds.  Rope b is its pieces (b,$), (b,A) .. (b,N) in that order.
+ *   C[a]     rows in front of rope a = sum over b < a of row b of rb2_hip_get_counts (e->cnt[a] of rld0 after rld_enc_finish).
+ *   occ(a,x) number of a's in global rows [0, x): the counts of the pieces in front of x plus a rank inside the piece that holds x.
+ *   pattern  nt6 codes in text order: 1..5 anywhere, 0 ($) only as the last symbol, where it anchors the pattern at a string end.
+ *            Backward search consumes a pattern from its last symbol.
+ * Every query waits for a lazy insert first (as every entry point does), reads the index and nothing else, and is fatal on one rank of a
+ * sharded index (rb2_hip_multi_*), like rb2_hip_rank_batch.  The host variants stage through device buffers in chunks of at most 2^24
+ * queries (RB2_QUERY_CHUNK in the environment lowers it: tests).  Kernels: k_bsearch, k_extend, k_extract (csrc/rb2_query.h). */
+/* n patterns concatenated in pat[off[i] .. off[i+1]) (off: n + 1 non-decreasing values); out[3*i ..] = lo, hi, m: m is the length of the
+ * longest suffix of pattern i that occurs and [lo, hi) its interval, so count = hi - lo when m == the pattern's length, else 0.  The empty
+ * pattern gives (0, N, 0), N = rows; a malformed pattern (a code above 5, a `$` before its end) gives (-1, -1, -1) and is not an error. */
+void rb2_hip_backward_search(rb2_hip_t *h, int64_t n, const uint8_t *pat, const int64_t *off, int64_t *out);
+/* the same with pat, off and out in this device's memory, asynchronous on the handle's stream */
+void rb2_hip_backward_search_dev(rb2_hip_t *h, int64_t n, const uint8_t *pat, const int64_t *off, int64_t *out);
+/* rld_extend (rld0.c:474-490) on n bi-intervals ik[3*i ..] = x[0], x[1], x[2] (size): ok[18*i + 3*a + j] = x[j] of the extension by
+ * a, x[is_back] in the complement order $ T G C A N.  Meaningful when the index holds both strands of every string (as fermi requires):
+ * the caller's responsibility. */
+void rb2_hip_extend(rb2_hip_t *h, int64_t n, const int64_t *ik, int is_back, int64_t *ok);
+/* inverse BWT from rows of the $ block [0, C[1]): the string of row rows[i] in text order into out[i*max_len ..), len[i] its length,
+ * -1 when it is longer than max_len, -2 for a row outside the $ block.  In input order (RB2_SO_IO) row k is the k-th string inserted.
+ * Returns the number of rows whose string fitted. */
+int64_t rb2_hip_extract(rb2_hip_t *h, int64_t n, const int64_t *rows, int64_t max_len, uint8_t *out, int64_t *len);
+
 /* 64-bit checksum of rope b computed on the device (position-weighted sum over the packed words of its pieces): equal for
  * equal symbol sequences however the index was built (one engine, N ranks, an .fmr loaded back), sensitive to order.  Lets
  * tests compare indexes of 10^11 symbols without moving them off the device (the reference has no counterpart; its ropes are

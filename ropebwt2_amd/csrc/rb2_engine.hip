@@ -16,6 +16,7 @@
 #include <condition_variable>
 #include "rb2_hip.h"
 #include "rb2_kernels.h"
+#include "rb2_query.h"
 
 using namespace rb2;
 
@@ -232,6 +233,8 @@ struct rb2_hip_s {
 	bool want_respread = false;         // k_split met a superblock without a free slot: re-spread (sparse -> sparse) before the next round
 	int64_t n_respread = 0;
 	DevBuf<uint64_t> qbuf;              // rank queries and their answers
+	DevBuf<QTab> qtab;                  // FM-index queries (rb2_query.h): the piece table of the launch ...
+	DevBuf<uint8_t> qbytes; DevBuf<int64_t> qin, qout;   // ... and the staging buffers of the host variants
 	uint64_t sp_nsb = 0;                // superblocks of the sparse pool (upper bound)
 	DevBuf<LeafDesc> LD;
 	DevBuf<uint8_t> A[2], INS_A, sbuf;   // A: symbol (+ flags) of every string this round; the other side receives next round's from k_advance
@@ -1010,7 +1013,7 @@ void rb2_hip_destroy(rb2_hip_t *h)
 	HIPCHK(hipSetDevice(h->dev));
 	if (h->own_stream) HIPCHK(hipStreamSynchronize(h->st)); else HIPCHK(hipDeviceSynchronize());   /* a caller's stream (rb2_hip_use_stream) may be gone already */
 	for (int i = 0; i < 2; ++i) { h->pool[i].release(); h->L[i].release(); h->U[i].release(); h->W[i].release(); }
-	h->START.release(); h->SIZE.release(); h->INS_E.release(); h->RKREL.release(); h->RKOLD.release(); h->SPL.release(); h->qbuf.release(); h->zblk.release();
+	h->START.release(); h->SIZE.release(); h->INS_E.release(); h->RKREL.release(); h->RKOLD.release(); h->SPL.release(); h->qbuf.release(); h->zblk.release(); h->qtab.release(); h->qbytes.release(); h->qin.release(); h->qout.release();
 	h->LD.release(); h->A[0].release(); h->A[1].release(); h->INS_A.release(); h->sbuf.release(); h->sbuf2.release();
 	if (h->st_copy) HIPCHK(hipStreamDestroy(h->st_copy));
 	h->trec.release(); h->tsc.release(); h->tfix.release(); h->cpart.release(); h->sbtot.release();
@@ -1434,6 +1437,108 @@ void rb2_hip_rank1a(rb2_hip_t *h, int b, int64_t x, int64_t cx[6])
 { finish_pending(h);
 	if (x < 0) x = 0;
 	rb2_hip_rank_batch(h, b, 1, &x, cx);
+}
+
+/* ---- FM-index queries (rb2_query.h): one DPP row of 16 lanes per query ---- */
+
+/* queries per launch: 16 threads each, so 2^24 stay far below the 2^32 threads of one launch; RB2_QUERY_CHUNK lowers it (tests of the chunking) */
+static int64_t query_chunk(rb2_hip_t *h)
+{
+	(void)h;
+	const int64_t CH = 1 << 24;
+	const char *e = getenv("RB2_QUERY_CHUNK");
+	const int64_t v = e ? atoll(e) : 0;
+	return v > 0 ? std::min(v, CH) : CH;
+}
+
+/* what every query does first: wait for a lazy insert, refuse a shard, build the piece table of the index as it is now */
+static void query_begin(rb2_hip_t *h, const char *who)
+{
+	finish_pending(h);
+	HIPCHK(hipSetDevice(h->dev));
+	if (h->nranks > 1) rb2_fatal("[rb2_hip] %s: this handle holds only its own sub-ropes of a sharded index; queries need the whole index on one engine\n", who);
+	require_plain(h, who);
+	h->qtab.ensure(1);
+	hipLaunchKernelGGL(k_qtab, dim3(1), dim3(64), 0, h->st, (const Ctl*)h->ctl, h->side, h->pool[h->pside].view(), h->qtab.p);
+	HIPCHK(hipGetLastError());
+}
+
+static void launch_bsearch(rb2_hip_t *h, int64_t n, const uint8_t *pat, const int64_t *off, int64_t base, int64_t *out)
+{
+	const PoolView pv = h->pool[h->pside].view();
+	if (h->sparse) hipLaunchKernelGGL(k_bsearch<true>, dim3(cdiv((uint64_t)n, QPB)), dim3(256), 0, h->st, (const QTab*)h->qtab.p, pv, pat, off, base, (uint64_t)n, out);
+	else hipLaunchKernelGGL(k_bsearch<false>, dim3(cdiv((uint64_t)n, QPB)), dim3(256), 0, h->st, (const QTab*)h->qtab.p, pv, pat, off, base, (uint64_t)n, out);
+	HIPCHK(hipGetLastError());
+}
+
+void rb2_hip_backward_search(rb2_hip_t *h, int64_t n, const uint8_t *pat, const int64_t *off, int64_t *out)
+{
+	query_begin(h, "backward_search");
+	if (n <= 0) return;
+	for (int64_t i = 0; i < n; ++i)
+		if (off[i + 1] < off[i] || off[0] < 0) { rb2_fatal("[rb2_hip] backward_search: pattern offsets must be non-negative and non-decreasing (off[%lld])\n", (long long)i); }
+	const int64_t CH = query_chunk(h);
+	for (int64_t i0 = 0; i0 < n; i0 += CH) {
+		const int64_t nc = std::min(CH, n - i0), b0 = off[i0], nb = off[i0 + nc] - b0;
+		h->qin.ensure((size_t)nc + 1); h->qout.ensure((size_t)nc * 3); h->qbytes.ensure((size_t)std::max<int64_t>(nb, 1));
+		HIPCHK(hipMemcpyAsync(h->qin.p, off + i0, (size_t)(nc + 1) * 8, hipMemcpyHostToDevice, h->st));
+		if (nb) HIPCHK(hipMemcpyAsync(h->qbytes.p, pat + b0, (size_t)nb, hipMemcpyHostToDevice, h->st));
+		launch_bsearch(h, nc, h->qbytes.p, h->qin.p, b0, h->qout.p);
+		HIPCHK(hipMemcpyAsync(out + 3 * i0, h->qout.p, (size_t)nc * 24, hipMemcpyDeviceToHost, h->st));
+		HIPCHK(hipStreamSynchronize(h->st));
+	}
+}
+
+void rb2_hip_backward_search_dev(rb2_hip_t *h, int64_t n, const uint8_t *pat, const int64_t *off, int64_t *out)
+{
+	query_begin(h, "backward_search_dev");
+	const int64_t CH = query_chunk(h);
+	for (int64_t i0 = 0; i0 < n; i0 += CH) launch_bsearch(h, std::min(CH, n - i0), pat, off + i0, 0, out + 3 * i0);
+}
+
+void rb2_hip_extend(rb2_hip_t *h, int64_t n, const int64_t *ik, int is_back, int64_t *ok)
+{
+	query_begin(h, "extend");
+	if (n <= 0) return;
+	is_back = is_back ? 1 : 0;
+	const int64_t CH = query_chunk(h);
+	const PoolView pv = h->pool[h->pside].view();
+	h->qin.ensure((size_t)std::min(CH, n) * 3); h->qout.ensure((size_t)std::min(CH, n) * 18);
+	for (int64_t i0 = 0; i0 < n; i0 += CH) {
+		const int64_t nc = std::min(CH, n - i0);
+		HIPCHK(hipMemcpyAsync(h->qin.p, ik + 3 * i0, (size_t)nc * 24, hipMemcpyHostToDevice, h->st));
+		if (h->sparse) hipLaunchKernelGGL(k_extend<true>, dim3(cdiv((uint64_t)nc, QPB)), dim3(256), 0, h->st, (const QTab*)h->qtab.p, pv, (const int64_t*)h->qin.p, is_back, (uint64_t)nc, h->qout.p);
+		else hipLaunchKernelGGL(k_extend<false>, dim3(cdiv((uint64_t)nc, QPB)), dim3(256), 0, h->st, (const QTab*)h->qtab.p, pv, (const int64_t*)h->qin.p, is_back, (uint64_t)nc, h->qout.p);
+		HIPCHK(hipGetLastError());
+		HIPCHK(hipMemcpyAsync(ok + 18 * i0, h->qout.p, (size_t)nc * 144, hipMemcpyDeviceToHost, h->st));
+		HIPCHK(hipStreamSynchronize(h->st));
+	}
+}
+
+int64_t rb2_hip_extract(rb2_hip_t *h, int64_t n, const int64_t *rows, int64_t max_len, uint8_t *out, int64_t *len)
+{
+	query_begin(h, "extract");
+	if (n <= 0) return 0;
+	if (max_len < 0) max_len = 0;
+	int64_t CH = query_chunk(h);
+	if (max_len > 0) CH = std::max<int64_t>(1, std::min<int64_t>(CH, (int64_t)(256u << 20) / max_len));   // at most 256 MiB of strings staged per launch
+	const PoolView pv = h->pool[h->pside].view();
+	h->qin.ensure((size_t)std::min(CH, n) * 2); h->qbytes.ensure((size_t)std::max<int64_t>(std::min(CH, n) * max_len, 1));
+	int64_t fit = 0;
+	for (int64_t i0 = 0; i0 < n; i0 += CH) {
+		const int64_t nc = std::min(CH, n - i0);
+		int64_t *d_rows = h->qin.p, *d_len = h->qin.p + nc;
+		HIPCHK(hipMemcpyAsync(d_rows, rows + i0, (size_t)nc * 8, hipMemcpyHostToDevice, h->st));
+		if (h->sparse) hipLaunchKernelGGL(k_extract<true>, dim3(cdiv((uint64_t)nc, QPB)), dim3(256), 0, h->st, (const QTab*)h->qtab.p, pv, (const int64_t*)d_rows, (uint64_t)nc, max_len, h->qbytes.p, d_len);
+		else hipLaunchKernelGGL(k_extract<false>, dim3(cdiv((uint64_t)nc, QPB)), dim3(256), 0, h->st, (const QTab*)h->qtab.p, pv, (const int64_t*)d_rows, (uint64_t)nc, max_len, h->qbytes.p, d_len);
+		HIPCHK(hipGetLastError());
+		HIPCHK(hipMemcpyAsync(len + i0, d_len, (size_t)nc * 8, hipMemcpyDeviceToHost, h->st));
+		if (nc * max_len) HIPCHK(hipMemcpyAsync(out + i0 * max_len, h->qbytes.p, (size_t)(nc * max_len), hipMemcpyDeviceToHost, h->st));
+		HIPCHK(hipStreamSynchronize(h->st));
+		for (int64_t i = i0; i < i0 + nc; ++i)                  // the walk spells a string from its last symbol: text order is the reverse
+			if (len[i] >= 0) { std::reverse(out + i * max_len, out + i * max_len + len[i]); ++fit; }
+	}
+	return fit;
 }
 
 /* checksum of sub-rope r (k_piece_hash); the handle must hold the piece in the dense layout */

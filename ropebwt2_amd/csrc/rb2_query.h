@@ -1,0 +1,204 @@
+// rb2_query.h -- FM-index queries on the device index: backward search, bi-interval extension (rld_extend), inverse BWT.
+//
+// Coordinates (include/rb2_hip.h): global rows run over the concatenated BWT, rope 0 ($) .. rope 5 (N); rope b is its pieces (b,$) ..
+// (b,N) in index order, so the sub-rope numbers r = 0 .. NR-1 are already the order of the rows.  C[a] = rows in front of rope a.
+//
+// The one primitive is the GLOBAL RANK qrank(): the six counts in front of a global row.  A per-launch table (QTab, built by k_qtab from
+// ctl->rope[side] on the device, copied to LDS by every block) gives each piece its first row, the counts of the rows in front of it and
+// sb_cum() of its first superblock; qrank() finds the piece of the row, ranks inside it exactly as wave_rank_all does (dense: leaf =
+// p >> 10 and LeafMeta; sparse: locate(), the directory prefix, two-plane leaves) and adds the piece's counts in front.
+//
+// One query = one DPP row of 16 lanes, four queries per wave: lane g of the row reads group g of the leaf (three coalesced 128-byte
+// lines per row), popcounts its share of [0, off) and the row sums the packed counts with four row_ror steps, so every lane of the row
+// ends up with the six counts (wave_rank_all spends a whole wave on one query and leaves 48 lanes idle).  All 16 lanes of a row carry the
+// same query and take the same branches; different rows of a wave diverge freely (the DPP moves never leave a row).
+// Queries read the pool, the directory and ctl->rope only: they never write the index, the Ctl or a buffer an insert reads.
+#pragma once
+#include "rb2_device.h"
+
+namespace rb2 {
+
+struct QTab {
+	uint64_t row0[NR + 1];     // first global row of piece r; [NR] = N, the number of rows
+	uint64_t pre[NR][6];       // symbol counts of the global rows in front of piece r
+	uint64_t sbc[NR][6];       // sb_cum(pv, rope[r].sb0, a) (0 for an empty piece)
+	RopeDesc rd[NR];           // ctl->rope[side]
+};
+
+// the table of the current index: one thread per piece copies its descriptor and reads its sb_cum(), thread 0 sums the rows and counts
+__global__ void k_qtab(const Ctl *ctl, int side, PoolView pv, QTab *T)
+{
+	const int r = (int)threadIdx.x;
+	if (blockIdx.x != 0) return;
+	if (r < NR) {
+		const RopeDesc d = ctl->rope[side][r];
+		T->rd[r] = d;
+		for (int a = 0; a < 6; ++a) T->sbc[r][a] = d.nleaves ? sb_cum(pv, d.sb0, a) : 0;
+	}
+	if (r != 0) return;
+	uint64_t row = 0, pre[6] = {0, 0, 0, 0, 0, 0};
+	for (int q = 0; q < NR; ++q) {
+		const RopeDesc &d = ctl->rope[side][q];
+		T->row0[q] = row;
+		for (int a = 0; a < 6; ++a) { T->pre[q][a] = pre[a]; pre[a] += d.cnt[a]; }
+		row += d.n;
+	}
+	T->row0[NR] = row;
+}
+
+// block prologue of every query kernel: the table to LDS
+__device__ __forceinline__ void qtab_load(const QTab *g, QTab &s)
+{
+	const uint32_t *src = (const uint32_t*)g; uint32_t *dst = (uint32_t*)&s;
+	for (uint32_t i = threadIdx.x; i < sizeof(QTab) / 4; i += blockDim.x) dst[i] = src[i];
+	__syncthreads();
+}
+
+__device__ __forceinline__ uint32_t row_sum16(uint32_t v)     // sum over the 16 lanes of a DPP row, in every lane of it (row_ror 8, 4, 2, 1)
+{
+	v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x128, 0xf, 0xf, false);
+	v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x124, 0xf, 0xf, false);
+	v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x122, 0xf, 0xf, false);
+	v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x121, 0xf, 0xf, false);
+	return v;
+}
+
+// the piece that holds global row x (x < N), or the last piece for x == N: the last r with row0[r] <= x -- a piece that holds x when
+// x < N (empty pieces share their first row with the next one)
+__device__ __forceinline__ int qpiece(const QTab &T, uint64_t x)
+{
+	int lo = 0, hi = NR - 1;
+	while (lo < hi) { const int mid = (lo + hi + 1) >> 1; if (T.row0[mid] <= x) lo = mid; else hi = mid - 1; }
+	return lo;
+}
+
+// occ(a, x) for all six a (x <= N); *sym (if asked, x < N): the symbol at row x.  All 16 lanes of the row call it with the same x.
+template <bool SPARSE> __device__ inline void qrank(const QTab &T, const PoolView &pv, uint64_t x, uint64_t out[6], uint32_t *sym = nullptr)
+{
+	const int r = qpiece(T, x);
+	const RopeDesc &rp = T.rd[r];
+	const uint64_t p = x - T.row0[r];
+	if (p >= rp.n) {
+#pragma unroll
+		for (int s = 0; s < 6; ++s) out[s] = T.pre[r][s] + rp.cnt[s];
+		return;
+	}
+	uint64_t gl; uint32_t off; bool p2 = true;
+	if (SPARSE) { const Loc lc = locate(pv, rp, p); gl = lc.gl; off = (uint32_t)(p - lc.s); p2 = lc.p2 != 0; }
+	else { gl = rp.leaf0 + (p >> LEAF_SH); off = (uint32_t)(p & (LEAF - 1)); }
+	const uint32_t g = (uint32_t)lane_id() & 15u, b = g << 6;
+	const uint64_t *lw = leaf_words(pv.data, gl);
+	const uint64_t b0 = lw[g], b1 = lw[LEAFG + g], b2 = leaf_p2(p2, b0, b1, p2 ? lw[2 * LEAFG + g] : 0);
+	PlAcc A;
+	pl_acc(A, b0, b1, b2, off > b ? bits_below(min(off - b, 64u)) : 0ull);
+	uint32_t sv = 0;
+	if (sym && (off >> 6) == g) { const uint32_t k = off & 63u; sv = (uint32_t)((b0 >> k) & 1u) | (uint32_t)((b1 >> k) & 1u) << 1 | (uint32_t)((b2 >> k) & 1u) << 2; }
+	const uint32_t r0 = row_sum16(A.p0 | A.p1 << 16), r1 = row_sum16(A.p2 | A.p01 << 16), r2 = row_sum16(A.p02 | sv << 16);
+	PlAcc S;
+	S.p0 = r0 & 0xffffu; S.p1 = r0 >> 16; S.p2 = r1 & 0xffffu; S.p01 = r1 >> 16; S.p02 = r2 & 0xffffu;
+	if (sym) *sym = r2 >> 16;
+	uint32_t c[6];
+	pl_finish(S, off, c);
+	uint32_t pc[6];                                            // the leaves of the superblock in front of this one
+	if (SPARSE) {
+#pragma unroll
+		for (int s = 0; s < 6; ++s) pc[s] = dir_prefix(pv, gl / SB, 1 + s, (uint32_t)(gl % SB));
+	} else {
+		const LeafMeta m = pv.meta[gl];
+#pragma unroll
+		for (int s = 0; s < 6; ++s) pc[s] = m.c[s];
+	}
+#pragma unroll
+	for (int s = 0; s < 6; ++s) out[s] = T.pre[r][s] + (sb_cum(pv, gl / SB, s) - T.sbc[r][s]) + pc[s] + c[s];
+}
+
+__device__ __forceinline__ uint64_t qC(const QTab &T, int a) { return T.row0[rope_of(a, 0)]; }   // C[a]: rows in front of rope a
+
+constexpr int QPB = 256 / 16;              // queries per block of 256 threads
+
+// backward search: n patterns pat[off[i] - base, off[i+1] - base), out[3i..] = lo, hi, m (include/rb2_hip.h)
+template <bool SPARSE> __global__ __launch_bounds__(256) void k_bsearch(const QTab *Tg, PoolView pv, const uint8_t *pat, const int64_t *off, int64_t base,
+                                                                        uint64_t n, int64_t *out)
+{
+	__shared__ QTab T;
+	qtab_load(Tg, T);
+	const uint64_t i = (uint64_t)blockIdx.x * QPB + (threadIdx.x >> 4);
+	if (i >= n) return;
+	const int64_t s0 = off[i] - base, s1 = off[i + 1] - base;
+	int64_t lo = 0, hi = (int64_t)T.row0[NR], m = 0;
+	bool bad = s1 < s0 || s0 < 0;
+	for (int64_t j = s0; !bad && j < s1; ++j) { const uint8_t c = pat[j]; bad = c > 5 || (c == 0 && j != s1 - 1); }
+	if (bad) lo = hi = m = -1;
+	else {
+		for (int64_t j = s1 - 1; j >= s0; --j) {
+			const int c = pat[j];
+			uint64_t cl[6], ch[6];
+			qrank<SPARSE>(T, pv, (uint64_t)lo, cl);
+			qrank<SPARSE>(T, pv, (uint64_t)hi, ch);
+			const uint64_t C = qC(T, c), nl = C + cl[c], nh = C + ch[c];
+			if (nl >= nh) break;                               // the suffix one longer does not occur: stop early
+			lo = (int64_t)nl; hi = (int64_t)nh; ++m;
+		}
+	}
+	const uint32_t g = (uint32_t)lane_id() & 15u;
+	if (g < 3) out[3 * i + g] = g == 0 ? lo : g == 1 ? hi : m;
+}
+
+// rld_extend (rld0.c:474-490) on n bi-intervals: ok[18i + 3a + j]
+template <bool SPARSE> __global__ __launch_bounds__(256) void k_extend(const QTab *Tg, PoolView pv, const int64_t *ik, int is_back, uint64_t n, int64_t *ok)
+{
+	__shared__ QTab T;
+	qtab_load(Tg, T);
+	const uint64_t i = (uint64_t)blockIdx.x * QPB + (threadIdx.x >> 4);
+	if (i >= n) return;
+	const int fb = !is_back;
+	const uint64_t x0 = (uint64_t)ik[3 * i + fb], sz = (uint64_t)ik[3 * i + 2], xb = (uint64_t)ik[3 * i + is_back];
+	uint64_t tk[6], tl[6];
+	qrank<SPARSE>(T, pv, x0, tk);
+	if (sz) qrank<SPARSE>(T, pv, x0 + sz, tl);
+	else for (int a = 0; a < 6; ++a) tl[a] = tk[a];
+	int64_t xf[6], sz6[6], xo[6];                              // x[!is_back], x[2], x[is_back] of the six extensions
+#pragma unroll
+	for (int a = 0; a < 6; ++a) { xf[a] = (int64_t)(qC(T, a) + tk[a]); sz6[a] = (int64_t)(tl[a] - tk[a]); }
+	xo[0] = (int64_t)xb;                                       // the other end in the complement order $ T G C A N
+	xo[4] = xo[0] + sz6[0];
+	xo[3] = xo[4] + sz6[4];
+	xo[2] = xo[3] + sz6[3];
+	xo[1] = xo[2] + sz6[2];
+	xo[5] = xo[1] + sz6[1];
+	const uint32_t g = (uint32_t)lane_id() & 15u;               // 18 words: lanes 0..15, then lanes 0..1 again
+#pragma unroll
+	for (int k = 0; k < 18; ++k)
+		if ((uint32_t)(k & 15) == g) ok[18 * i + k] = k % 3 == 2 ? sz6[k / 3] : k % 3 == fb ? xf[k / 3] : xo[k / 3];
+}
+
+// inverse BWT from rows of the $ block: the string of row rows[i], LAST symbol first, into out[i * max_len ..) (the host reverses it);
+// len[i] = its length, -1 when longer than max_len, -2 for a row outside [0, C[1])
+template <bool SPARSE> __global__ __launch_bounds__(256) void k_extract(const QTab *Tg, PoolView pv, const int64_t *rows, uint64_t n, int64_t max_len,
+                                                                        uint8_t *out, int64_t *len)
+{
+	__shared__ QTab T;
+	qtab_load(Tg, T);
+	const uint64_t i = (uint64_t)blockIdx.x * QPB + (threadIdx.x >> 4);
+	if (i >= n) return;
+	const uint32_t g = (uint32_t)lane_id() & 15u;
+	const int64_t row = rows[i];
+	int64_t k = 0;
+	if (row < 0 || (uint64_t)row >= qC(T, 1)) k = -2;
+	else {
+		uint64_t x = (uint64_t)row;
+		uint8_t *o = out + i * (uint64_t)max_len;
+		for (;;) {
+			uint64_t c6[6]; uint32_t c;
+			qrank<SPARSE>(T, pv, x, c6, &c);
+			if (c == 0) break;                                 // back at the string's own '$' row
+			if (k == max_len) { k = -1; break; }
+			if (g == 0) o[k] = (uint8_t)c;
+			++k;
+			x = qC(T, (int)c) + c6[c];                         // LF
+		}
+	}
+	if (g == 0) len[i] = k;
+}
+
+} // namespace rb2

@@ -46,6 +46,10 @@ def load_hip_lib():
         "rb2_hip_load_ropes": (None, [vp, vp, vp]),
         "rb2_hip_rank1a": (None, [vp, i32, i64, vp]),
         "rb2_hip_rank_batch": (None, [vp, i32, i64, vp, vp]),
+        "rb2_hip_backward_search": (None, [vp, i64, vp, vp, vp]),
+        "rb2_hip_backward_search_dev": (None, [vp, i64, vp, vp, vp]),
+        "rb2_hip_extend": (None, [vp, i64, vp, i32, vp]),
+        "rb2_hip_extract": (i64, [vp, i64, vp, i64, vp, vp]),
         "rb2_hip_reserve": (None, [vp, i64, i64, i64]),
         "rb2_hip_num_subropes": (i32, []),
         "rb2_hip_memcpy": (None, [vp, vp, vp, i64, i32]),
@@ -107,7 +111,8 @@ def load_hip_lib():
 ABI_SYMBOLS = [
     "rb2_hip_device_count", "rb2_hip_set_fatal_handler", "rb2_hip_create", "rb2_hip_destroy", "rb2_hip_sorting_order", "rb2_hip_reset",
     "rb2_hip_insert_multi", "rb2_hip_insert_multi_dev", "rb2_hip_set_lazy", "rb2_hip_wait", "rb2_hip_last_batch_counts", "rb2_hip_prefetch", "rb2_hip_mem_info", "rb2_hip_get_counts", "rb2_hip_rope_bytes",
-    "rb2_hip_download_rope", "rb2_hip_stream_rope", "rb2_hip_load_ropes", "rb2_hip_rank1a", "rb2_hip_rank_batch", "rb2_hip_reserve", "rb2_hip_dev_alloc",
+    "rb2_hip_download_rope", "rb2_hip_stream_rope", "rb2_hip_load_ropes", "rb2_hip_rank1a", "rb2_hip_rank_batch", "rb2_hip_reserve",
+    "rb2_hip_backward_search", "rb2_hip_backward_search_dev", "rb2_hip_extend", "rb2_hip_extract", "rb2_hip_dev_alloc",
     "rb2_hip_num_subropes", "rb2_hip_memcpy", "rb2_hip_use_stream",
     "rb2_hip_dev_free", "rb2_hip_synth_reads", "rb2_hip_synth_reads_cov", "rb2_hip_synth_reads_skew", "rb2_hip_sync", "rb2_hip_sparse_stats", "rb2_hip_layout_stats", "rb2_hip_window_stats", "rb2_hip_host_register", "rb2_hip_host_unregister", "rb2_hip_profile",
     "rb2_hip_profile_get", "rb2_hip_kernel_name", "rb2_hip_layout",
@@ -116,6 +121,33 @@ ABI_SYMBOLS = [
     "rb2_hip_multi_get_counts", "rb2_hip_multi_rope_bytes", "rb2_hip_multi_download_rope", "rb2_hip_multi_stream_rope",
     "rb2_hip_multi_load_ropes", "rb2_hip_multi_reserve", "rb2_hip_multi_rope_hash", "rb2_hip_rope_hash", "rb2_hip_multi_plan_host", "rb2_hip_multi_reset", "rb2_hip_multi_sync", "rb2_hip_multi_rank1a", "rb2_hip_multi_stats", "rb2_hip_multi_text_bytes",
 ]
+
+
+_NT6 = np.full(256, 255, dtype=np.uint8)     # pattern letters: ACGTN in either case, '$' (a string end); anything else is refused
+for _i, _ch in enumerate("$ACGTN"):
+    _NT6[ord(_ch)] = _NT6[ord(_ch.lower())] = _i
+
+
+def encode_pattern(p):
+    """a pattern as nt6 codes in text order: str / bytes over $ACGTN (any case), or an array of codes (taken as they are)"""
+    if isinstance(p, str):
+        p = p.encode("ascii")
+    if isinstance(p, (bytes, bytearray)):
+        a = _NT6[np.frombuffer(bytes(p), dtype=np.uint8)]
+        if (a == 255).any():
+            raise ValueError("pattern %r: only the letters $ACGTN are allowed" % (p,))
+        return a
+    return np.asarray(p, dtype=np.uint8).reshape(-1)
+
+
+def pack_patterns(patterns):
+    """list of patterns -> (concatenated nt6 codes, offsets of n + 1 values): the layout of rb2_hip_backward_search"""
+    enc = [encode_pattern(p) for p in patterns]
+    off = np.zeros(len(enc) + 1, np.int64)
+    if enc:
+        off[1:] = np.cumsum([len(e) for e in enc])
+    pat = np.concatenate(enc) if enc and off[-1] else np.zeros(1, np.uint8)
+    return np.ascontiguousarray(pat, dtype=np.uint8), off
 
 
 def expand_runs(rle):
@@ -243,6 +275,56 @@ class HipBwt:
         if len(xs):
             self.L.rb2_hip_rank_batch(self.h, b, len(xs), xs.ctypes.data, out.ctypes.data)
         return out
+
+    # -- FM-index queries (include/rb2_hip.h: global rows over ropes $ .. N, patterns in text order) ------------------------
+    def backward_search(self, patterns):
+        """lo, hi, m (int64 arrays): [lo, hi) is the interval of the longest suffix of each pattern that occurs, m its length;
+        (0, N, 0) for the empty pattern, (-1, -1, -1) for a malformed one ('$' anywhere but at the end)"""
+        pat, off = pack_patterns(patterns)
+        n = len(off) - 1
+        out = np.zeros((n, 3), np.int64)
+        if n:
+            self.L.rb2_hip_backward_search(self.h, n, pat.ctypes.data, off.ctypes.data, out.ctypes.data)
+        return out[:, 0], out[:, 1], out[:, 2]
+
+    def backward_search_dev(self, n, pat_dev, off_dev, out_dev):
+        """rb2_hip_backward_search_dev: all three pointers in this device's memory; asynchronous on the handle's stream"""
+        self.L.rb2_hip_backward_search_dev(self.h, n, pat_dev, off_dev, out_dev)
+
+    def count(self, patterns):
+        """occurrences of every pattern (str / bytes over $ACGTN, or nt6 arrays) in the indexed strings"""
+        lens = np.array([len(encode_pattern(p)) for p in patterns], np.int64)
+        lo, hi, m = self.backward_search(patterns)
+        return np.where(m == lens, hi - lo, 0)
+
+    def extend(self, ik, is_back):
+        """rld_extend on bi-intervals ik (n, 3) = x[0], x[1], x[2]: an (n, 6, 3) array, [i, a] = the extension of ik[i] by a"""
+        ik = np.ascontiguousarray(np.asarray(ik, dtype=np.int64).reshape(-1, 3))
+        ok = np.zeros((len(ik), 6, 3), np.int64)
+        if len(ik):
+            self.L.rb2_hip_extend(self.h, len(ik), ik.ctypes.data, int(bool(is_back)), ok.ctypes.data)
+        return ok
+
+    def extract(self, rows, max_len):
+        """the strings of rows of the $ block, in text order (one nt6 array per row); None where the string is longer than
+        max_len; a row outside the $ block raises ValueError"""
+        rows = np.ascontiguousarray(np.asarray(rows, dtype=np.int64).reshape(-1))
+        n = len(rows)
+        out = np.zeros(max(n * max_len, 1), np.uint8)
+        ln = np.zeros(n, np.int64)
+        if n:
+            self.L.rb2_hip_extract(self.h, n, rows.ctypes.data, max_len, out.ctypes.data, ln.ctypes.data)
+        if (ln == -2).any():
+            raise ValueError("rows outside the $ block: %s" % rows[ln == -2][:5].tolist())
+        return [out[i * max_len:i * max_len + ln[i]].copy() if ln[i] >= 0 else None for i in range(n)]
+
+    def extract_raw(self, rows, max_len):
+        """rb2_hip_extract as it is: (number of rows that fitted, out (n, max_len) uint8, len (n,) int64)"""
+        rows = np.ascontiguousarray(np.asarray(rows, dtype=np.int64).reshape(-1))
+        out = np.zeros((len(rows), max_len), np.uint8)
+        ln = np.zeros(len(rows), np.int64)
+        fit = self.L.rb2_hip_extract(self.h, len(rows), rows.ctypes.data, max_len, out.ctypes.data, ln.ctypes.data) if len(rows) else 0
+        return int(fit), out, ln
 
     # -- measurement helpers ----------------------------------------------------------------
     def dev_alloc(self, nbytes):
