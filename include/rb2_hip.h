@@ -286,6 +286,13 @@ void rb2_hip_sparse_stats(rb2_hip_t *h, int64_t out[4]);
  * of a dense batch were being queued (each one is a device-wide wait in the middle of the batch: 0 unless a sizing rule is missing);
  * out[7] reserved */
 void rb2_hip_layout_stats(rb2_hip_t *h, int64_t out[8]);
+/* void in-place rounds the host took back from behind the rounds it had queued after them (one engine queues in-place rounds without
+ * waiting for their verdict; a void round makes every kernel behind it return, and the host rewinds its own bookkeeping when it finds
+ * out): out[0] such rewinds, out[1] queued rounds taken back in all (the void round included: depth = rounds queued from it on),
+ * out[2] the deepest rewind, out[3] rewinds of even depth (the descriptor and array sides stay where they are).  Every void round
+ * of a single-engine insert is counted here unless RB2_LAZY_VERDICT=0; RB2_VERDICT_POLL=0 (tests) defers the host's look at the
+ * verdict to the next drain, which makes rewinds deep. */
+void rb2_hip_rewind_stats(rb2_hip_t *h, int64_t out[4]);
 /* window formats of the dense layout (a window = 4 leaves = 4096 symbols; csrc/rb2_merge.h): out[0..3] = windows the dense merge wrote
  * plain (three bit planes) / compact with no, one, two lines of exception positions -- counted on the device only when the handle was
  * created with RB2_COMPACT_STATS=1 in the environment (zeros otherwise) --, out[4] = dense rounds that were allowed to write compact

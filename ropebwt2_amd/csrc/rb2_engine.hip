@@ -211,6 +211,9 @@ struct rb2_hip_s {
 	uint64_t spec_rounds = 0;
 	int run_ahead = 3;                  // ... and at most this many in-place rounds ahead of what the device reports done (h_flag[2]): a re-spread asked for by round r takes place this
 	                                    // many rounds late at worst (RB2_RUN_AHEAD)
+	int verdict_poll = 1;               // RB2_VERDICT_POLL=0 (tests): the host does not poll the verdict word while it queues rounds -- it learns of a void round only when it
+	                                    // drains the stream (a re-layout, a widening, the end of the batch), so a void round is taken back from behind every round queued since
+	int64_t n_rewind = 0, n_rewound = 0, rewind_max = 0, n_rewind_even = 0;   // void rounds taken back from behind queued rounds: how many, rounds taken back, deepest, of even depth (rb2_hip_rewind_stats)
 	unsigned long long *pair_d = nullptr, *pair_h = nullptr;   // k_pair_hist: what the batch just uploaded adds to the count matrix (device, pinned host)
 	bool pair_valid = false;
 	bool pending_end = false;           // rb2_hip_insert_multi returned with the batch queued but not awaited (finish_pending); lazy_insert: it may
@@ -474,15 +477,17 @@ uint32_t verdict_check(rb2_hip_t *h, bool drain);
 // Leave the narrow storage mode when a piece could reach POS32_LIMIT symbols in round r.  What the host knows: the largest piece as
 // k_setup last reported it to pinned memory, for some round q < r (lock-free, possibly many rounds stale -- the host queues rounds
 // ahead of the device), and that a piece grows by at most the m strings of the batch per round.
-void maybe_widen(rb2_hip_t *h, BatchState &B, uint64_t r)
+// Returns the verdict of the in-place rounds queued behind (verdict_check) when the drain in front of a widening found one of them void: nothing was
+// widened, the caller rolls back first and comes here again.
+uint32_t maybe_widen(rb2_hip_t *h, BatchState &B, uint64_t r)
 {
-	if (!h->pos32) return;
+	if (!h->pos32) return 0;
 	const unsigned long long v = ((volatile unsigned long long*)(h->h_flag + 4))[0];
 	uint64_t known = h->pos_m0, since = r + 1;                   // rounds the bound must cover
 	if (v != 0) { known = v & ((1ull << 40) - 1); const uint64_t q = v >> 40; since = r >= q ? r - q : r + 1; }   // (the report of round q is the size AFTER round q)
 	const char *e = getenv("RB2_POS_WIDEN_AT");
-	if (known + (since + 1) * B.m < POS32_LIMIT && !(e && (uint64_t)atoll(e) == r)) return;
-	if (verdict_check(h, true)) return;                        // (an in-place round queued behind is void: the caller rolls back first and comes here again)
+	if (known + (since + 1) * B.m < POS32_LIMIT && !(e && (uint64_t)atoll(e) == r)) return 0;
+	if (const uint32_t v = verdict_check(h, true)) return v;   // (an in-place round queued behind is void)
 	// widen L and U of the current side (what the next kernels read); scratch arrays are per round
 	hipStream_t st = h->st;
 	const int cur = B.cur;
@@ -493,6 +498,7 @@ void maybe_widen(rb2_hip_t *h, BatchState &B, uint64_t r)
 	h->pos32 = false;
 	B.counted = (uint64_t)-1;                                  // a counting phase queued ahead wrote INS_E in the narrow form (k_sym's fused k_prep): count again
 	if (h->trace) fprintf(stderr, "[rb2_hip] round %llu: positions widened to 64 bits (largest piece known: %llu symbols, %llu rounds ago)\n", (unsigned long long)r, (unsigned long long)known, (unsigned long long)since);
+	return 0;
 }
 
 // phase 1 of a round: next symbols, group heads, tile scans, the rows of the count matrix seen here
@@ -514,6 +520,8 @@ void round_counts(rb2_hip_t *h, BatchState &B, uint64_t r, bool spec = false, bo
 	const TileRecs trs = { (uint32_t*)h->trec.p, (uint32_t)(h->trec.cap & ~(size_t)3) };   // (20 columns of cap words in the 80-byte records' space)
 	tl_slow(h, "start of round_counts");
 	const bool one_launch_tail = B.nst_ub < (unsigned)h->ts_max;  // few tiles (long reads): the counting tail is one launch (k_tscan_setup)
+	// without spec, the k_setup riding on k_tscan_setup / k_tfix runs whatever ctl->overflow says and clears it: never behind an unseen verdict (sticky-void rule)
+	if (!spec && h->spec_rounds > 0) { rb2_fatal("[rb2_hip] internal: counting phase of round %llu queued without spec behind %llu in-place rounds without their verdict\n", (unsigned long long)r, (unsigned long long)h->spec_rounds); }
 	SplitArgs sp; memset(&sp, 0, sizeof(sp));
 	if (with_split) {
 	  sp.ctl = h->ctl; sp.pool = h->pool[h->pside].view(); sp.SPL = h->SPL.p; sp.spl_cap = (uint32_t)std::min<uint64_t>(h->SPL.cap, 0xffffffffu); sp.epoch = h->split_epoch;
@@ -674,6 +682,8 @@ bool round_merge_sparse(rb2_hip_t *h, BatchState &B, uint64_t r, ShardRec *send 
 	if (++h->split_epoch == 0) ++h->split_epoch;
 	if (!(B.setup_round == r && B.setup_sparse && B.setup_epoch == h->layout_epoch))
 	{ Scope sc(h, RB2_K_TSCAN, 0);
+	  // k_setup clears ctl->overflow: behind an in-place round whose verdict the host has not seen, it would wipe out a void round (sticky-void rule)
+	  if (h->spec_rounds > 0) { rb2_fatal("[rb2_hip] internal: k_setup of in-place round %llu queued behind %llu in-place rounds without their verdict\n", (unsigned long long)r, (unsigned long long)h->spec_rounds); }
 	  hipLaunchKernelGGL(k_setup<true>, dim3(1), dim3(64), 0, st, h->ctl, sd, h->gcnt, (int)(r & 1), (uint32_t)r, h->pos32 ? (volatile unsigned long long*)(h->d_flag + 4) : (volatile unsigned long long*)nullptr, (int)(h->push[0] != nullptr)); }
 	const bool lazy = spec && h->lazy_verdict && h->nranks == 1;   // no verdict read here: the caller polls (insert_dev)
 	if (!lazy) h->h_flag[0] = h->h_flag[1] = 0;                // the verdict words k_split writes
@@ -757,6 +767,7 @@ uint32_t verdict_check(rb2_hip_t *h, bool drain)
 	const uint32_t v = ((volatile uint32_t*)h->h_flag)[0];
 	if (((volatile uint32_t*)h->h_flag)[1]) { h->want_respread = true; if (drain) h->h_flag[1] = 0; }
 	if (drain && !v) h->spec_rounds = 0;
+	if (!drain && !h->verdict_poll) return 0;                  // (RB2_VERDICT_POLL=0: a void round waits for the next drain)
 	return v;
 }
 
@@ -905,16 +916,18 @@ void insert_dev(rb2_hip_t *h, int64_t len64, const uint8_t *s, bool lazy = false
 		if (!rv) {
 			if (h->timeline > 1 && (r < 4 || r % 10 == 0)) fprintf(stderr, "[rb2_hip] t = %8.3f ms  queueing round %llu\n", std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count() - h->tl_base, (unsigned long long)r);
 			if (!B.known_ae && r > 0 && ne_all_empty_from(h, r)) B.known_ae = true;
-			maybe_widen(h, B, r);
-			if (!(rv = verdict_check(h, false)) && !choose_layout(h, B, r, B.m)) rv = verdict_check(h, true);
+			if (!(rv = maybe_widen(h, B, r)) && !(rv = verdict_check(h, false)) && !choose_layout(h, B, r, B.m)) rv = verdict_check(h, true);
 		}
 		if (rv) {
 			rv = verdict_check(h, true);                           // (final: everything queued has run -- or returned)
 			const uint64_t r_void = rv - 1;
 			if (r_void >= r || r - r_void > h->spec_rounds) { rb2_fatal("[rb2_hip] internal: void round %llu reported while queueing round %llu (%llu in flight)\n", (unsigned long long)r_void, (unsigned long long)r, (unsigned long long)h->spec_rounds); }
-			if ((r - r_void) & 1) { h->side ^= 1; B.cur ^= 1; }     // every in-place round queued from r_void on flipped the descriptor and array sides once
-			h->n_sparse_rounds -= (int64_t)(r - r_void);
+			const int64_t depth = (int64_t)(r - r_void);
+			if (depth & 1) { h->side ^= 1; B.cur ^= 1; }            // every in-place round queued from r_void on flipped the descriptor and array sides once
+			h->n_sparse_rounds -= depth;
+			++h->n_rewind; h->n_rewound += depth; h->rewind_max = std::max(h->rewind_max, depth); if (!(depth & 1)) ++h->n_rewind_even;
 			h->spec_rounds = 0; h->h_flag[0] = 0;
+			h->h_flag[2] = (uint32_t)r_void;                       // (the progress word: the rounds behind the void one reported themselves done; the run-ahead limit reads it)
 			HIPCHK(hipMemsetAsync(&h->ctl->overflow, 0, 4, h->st));
 			B.counted = (uint64_t)-1; B.setup_round = (uint64_t)-1;
 			// the "every interval is empty from here on" snapshots of the void round and of the rounds behind it are not what those rounds leave
@@ -998,6 +1011,7 @@ rb2_hip_t *rb2_hip_create(int device, int sorting_order)
 	if (getenv("RB2_TS_BLOCKS")) h->ts_blocks = atoi(getenv("RB2_TS_BLOCKS"));
 	if (getenv("RB2_LAZY_VERDICT")) h->lazy_verdict = atoi(getenv("RB2_LAZY_VERDICT"));
 	if (getenv("RB2_RUN_AHEAD")) h->run_ahead = std::max(1, atoi(getenv("RB2_RUN_AHEAD")));
+	if (getenv("RB2_VERDICT_POLL")) h->verdict_poll = atoi(getenv("RB2_VERDICT_POLL"));
 	{ Ctl *hc = (Ctl*)calloc(1, sizeof(Ctl)); for (int b = 0; b < NR; ++b) hc->own[b] = 1; HIPCHK(hipMemcpy(h->ctl, hc, sizeof(Ctl), hipMemcpyHostToDevice)); free(hc); }
 	HIPCHK(hipMemsetAsync(h->d_tmp, 0, 256, h->st));
 	memset(h->h_rope, 0, sizeof(h->h_rope));
@@ -1642,6 +1656,11 @@ void rb2_hip_layout_stats(rb2_hip_t *h, int64_t out[8])
 	HIPCHK(hipStreamSynchronize(h->st));
 	out[0] = h->n_relayout; out[1] = h->n_void; out[2] = h->n_sparse_rounds; out[3] = h->sparse ? 1 : 0;
 	out[4] = h->n_respread; out[5] = (int64_t)ns; out[6] = h->n_grow_in_rounds; out[7] = h->n_plain_handover;
+}
+
+void rb2_hip_rewind_stats(rb2_hip_t *h, int64_t out[4])
+{ finish_pending(h);
+	out[0] = h->n_rewind; out[1] = h->n_rewound; out[2] = h->rewind_max; out[3] = h->n_rewind_even;
 }
 
 void rb2_hip_window_stats(rb2_hip_t *h, int64_t out[6])

@@ -62,6 +62,7 @@ def load_hip_lib():
         "rb2_hip_sync": (None, [vp]),
         "rb2_hip_sparse_stats": (None, [vp, vp]),
         "rb2_hip_layout_stats": (None, [vp, vp]),
+        "rb2_hip_rewind_stats": (None, [vp, vp]),
         "rb2_hip_window_stats": (None, [vp, vp]),
         "rb2_hip_host_register": (C.c_int, [vp, C.c_int64]),
         "rb2_hip_host_unregister": (C.c_int, [vp]),
@@ -114,7 +115,7 @@ ABI_SYMBOLS = [
     "rb2_hip_download_rope", "rb2_hip_stream_rope", "rb2_hip_load_ropes", "rb2_hip_rank1a", "rb2_hip_rank_batch", "rb2_hip_reserve",
     "rb2_hip_backward_search", "rb2_hip_backward_search_dev", "rb2_hip_extend", "rb2_hip_extract", "rb2_hip_dev_alloc",
     "rb2_hip_num_subropes", "rb2_hip_memcpy", "rb2_hip_use_stream",
-    "rb2_hip_dev_free", "rb2_hip_synth_reads", "rb2_hip_synth_reads_cov", "rb2_hip_synth_reads_skew", "rb2_hip_sync", "rb2_hip_sparse_stats", "rb2_hip_layout_stats", "rb2_hip_window_stats", "rb2_hip_host_register", "rb2_hip_host_unregister", "rb2_hip_profile",
+    "rb2_hip_dev_free", "rb2_hip_synth_reads", "rb2_hip_synth_reads_cov", "rb2_hip_synth_reads_skew", "rb2_hip_sync", "rb2_hip_sparse_stats", "rb2_hip_layout_stats", "rb2_hip_rewind_stats", "rb2_hip_window_stats", "rb2_hip_host_register", "rb2_hip_host_unregister", "rb2_hip_profile",
     "rb2_hip_profile_get", "rb2_hip_kernel_name", "rb2_hip_layout",
     "rb2_hip_multi_create", "rb2_hip_multi_unique_id", "rb2_hip_multi_create_rank", "rb2_hip_multi_destroy", "rb2_hip_default_owners",
     "rb2_hip_multi_nranks", "rb2_hip_multi_transport", "rb2_hip_multi_nlocal", "rb2_hip_multi_engine", "rb2_hip_multi_insert_multi", "rb2_hip_multi_insert_multi_dev",
@@ -349,6 +350,12 @@ class HipBwt:
         self.L.rb2_hip_layout_stats(self.h, a.ctypes.data)
         return {"relayouts": int(a[0]), "void_rounds": int(a[1]), "sparse_rounds": int(a[2]), "sparse_now": bool(a[3]),
                 "respreads": int(a[4]), "leaf_splits": int(a[5]), "grown_in_rounds": int(a[6]), "plain_handovers": int(a[7])}
+
+    def rewind_stats(self):
+        """void in-place rounds taken back from behind queued rounds (rb2_hip_rewind_stats)"""
+        a = np.zeros(4, np.int64)
+        self.L.rb2_hip_rewind_stats(self.h, a.ctypes.data)
+        return {"rewinds": int(a[0]), "rounds_taken_back": int(a[1]), "deepest": int(a[2]), "even_depth": int(a[3])}
 
     def window_stats(self):
         a = np.zeros(6, np.int64)
