@@ -374,6 +374,19 @@ void ensure_strings(rb2_hip_t *h, uint64_t m)
 	h->trec.ensure(nst + 8 * XCD_RUN + 8); h->tsc.ensure(nst + 8 * XCD_RUN + 8); h->tfix.ensure(nst + 8 * XCD_RUN + 8); h->cpart.ensure(cdiv(nst, SCHUNK) + 1);
 }
 
+// the string arrays of the round as the round kernels see them: side B.cur this round, side B.cur ^ 1 the next, positions stored as P
+template <class P> StrArrays<P> str_arrays(rb2_hip_t *h, const BatchState &B)
+{
+	const int c = B.cur;
+	return { (P*)h->L[c].p, (P*)h->U[c].p, h->W[c].p, h->A[c].p, (P*)h->L[c ^ 1].p, (P*)h->U[c ^ 1].p, h->W[c ^ 1].p, h->A[c ^ 1].p,
+	         h->tfix.p, (P*)h->SIZE.p, (P*)h->INS_E.p, h->RKREL.p, (P*)h->RKOLD.p, h->INS_A.p };
+}
+// launch F with them, P = the storage type of this batch's positions
+template <class F> inline void with_pos(rb2_hip_t *h, const BatchState &B, F f) { if (h->pos32) f(str_arrays<uint32_t>(h, B)); else f(str_arrays<uint64_t>(h, B)); }
+
+inline volatile unsigned long long *hmax_report(const rb2_hip_t *h) { return h->pos32 ? (volatile unsigned long long*)(h->d_flag + 4) : nullptr; }   // where k_setup reports its (round, largest piece) to maybe_widen
+inline uint32_t split_cap(const rb2_hip_t *h) { return (uint32_t)std::min<uint64_t>(h->SPL.cap, 0xffffffffu); }   // leaves an in-place round may list for splitting (k_part_sparse -> k_split)
+
 // A batch may hold at most this many strings (32-bit slots, tile numbers and work orders).  The reference takes any count
 // (mrope.c:269-277); the single-engine entry points cut a batch that holds more into two and insert them one after the other
 // (insert_dev) -- the BWT does not depend on how a read set is cut into batches, which is what `-m` does to every input anyway.
@@ -438,10 +451,8 @@ bool batch_begin(rb2_hip_t *h, BatchState &B, int64_t len64, const uint8_t *s, b
 	{
 		Scope sc(h, RB2_K_INIT, 0);
 		hipLaunchKernelGGL(k_batch_setup, dim3(1), dim3(1), 0, st, h->ctl, h->side, m, len, is_srt);
-		if (h->pos32) hipLaunchKernelGGL(k_init_strings<uint32_t>, dim3(cdiv(m, 256)), dim3(256), 0, st, h->ctl, is_srt, s, h->START.p,
-				(uint32_t*)h->L[0].p, (uint32_t*)h->U[0].p, h->W[0].p, h->A[0].p);
-		else hipLaunchKernelGGL(k_init_strings<uint64_t>, dim3(cdiv(m, 256)), dim3(256), 0, st, h->ctl, is_srt, s, h->START.p,
-				h->L[0].p, h->U[0].p, h->W[0].p, h->A[0].p);
+		with_pos(h, B, [&](const auto &S) { using P = std::remove_pointer_t<decltype(S.L)>;
+		  hipLaunchKernelGGL(k_init_strings<P>, dim3(cdiv(m, 256)), dim3(256), 0, st, h->ctl, is_srt, s, h->START.p, S); });
 	}
 	HIPCHK(hipMemcpyAsync(&B.max_len, &h->ctl->max_len, 8, hipMemcpyDeviceToHost, st));
 	HIPCHK(hipStreamSynchronize(st));
@@ -468,10 +479,6 @@ bool ne_all_empty_from(rb2_hip_t *h, uint64_t r)               // may round r (a
 	}
 	return false;
 }
-
-// launch F with P = the storage type of this batch's positions; PP(x) = x's array seen as P*
-template <class F> inline void with_pos(rb2_hip_t *h, F f) { if (h->pos32) f((uint32_t*)nullptr); else f((uint64_t*)nullptr); }
-#define RB2_P(x) ((P*)(x))
 
 uint32_t verdict_check(rb2_hip_t *h, bool drain);
 // Leave the narrow storage mode when a piece could reach POS32_LIMIT symbols in round r.  What the host knows: the largest piece as
@@ -514,7 +521,7 @@ static inline void tl_slow(rb2_hip_t *h, const char *what)    // RB2_HIP_TIMELIN
 void round_counts(rb2_hip_t *h, BatchState &B, uint64_t r, bool spec = false, bool with_split = false, bool with_event = true)
 {
 	hipStream_t st = h->st;
-	const int sd = h->side, cur = B.cur;
+	const int sd = h->side;
 	const int64_t units = (int64_t)B.m;
 	h->cur_round = (int)r;
 	const TileRecs trs = { (uint32_t*)h->trec.p, (uint32_t)(h->trec.cap & ~(size_t)3) };   // (20 columns of cap words in the 80-byte records' space)
@@ -524,7 +531,7 @@ void round_counts(rb2_hip_t *h, BatchState &B, uint64_t r, bool spec = false, bo
 	if (!spec && h->spec_rounds > 0) { rb2_fatal("[rb2_hip] internal: counting phase of round %llu queued without spec behind %llu in-place rounds without their verdict\n", (unsigned long long)r, (unsigned long long)h->spec_rounds); }
 	SplitArgs sp; memset(&sp, 0, sizeof(sp));
 	if (with_split) {
-	  sp.ctl = h->ctl; sp.pool = h->pool[h->pside].view(); sp.SPL = h->SPL.p; sp.spl_cap = (uint32_t)std::min<uint64_t>(h->SPL.cap, 0xffffffffu); sp.epoch = h->split_epoch;
+	  sp.ctl = h->ctl; sp.pool = h->pool[h->pside].view(); sp.SPL = h->SPL.p; sp.spl_cap = split_cap(h); sp.epoch = h->split_epoch;
 	  sp.hv = (volatile uint32_t*)h->d_flag; sp.nsplitb = 64;
 	  sp.round1 = (uint32_t)r;                                   // (the splits of round r - 1)
 	  sp.scan2 = (h->dir_ride && !one_launch_tail) ? sp.pool.sbbase : (SbBase*)nullptr;   // the chunk bases of the directory the k_advance launch in front of this one left half-built
@@ -532,19 +539,18 @@ void round_counts(rb2_hip_t *h, BatchState &B, uint64_t r, bool spec = false, bo
 	}
 	SbBase *scan2_tail = (with_split && h->dir_ride && one_launch_tail) ? h->pool[h->pside].view().sbbase : (SbBase*)nullptr;
 	{ Scope sc(h, RB2_K_SYM, units);
-	  with_pos(h, [&](auto *tg_) { using P = std::remove_pointer_t<decltype(tg_)>;
+	  with_pos(h, B, [&](const auto &S) { using P = std::remove_pointer_t<decltype(S.L)>;
 	    if (with_split) {
-	      hipLaunchKernelGGL((k_sym<false, P, true>), dim3((unsigned)rank_share(h, B.nst_ub) + sp.nsplitb + (sp.scan2 ? 1u : 0u)), dim3(256), 0, st, h->ctl, sd, (int)(r & 1), RB2_P(h->L[cur].p), RB2_P(h->U[cur].p), h->A[cur].p, trs, sp, RB2_P(h->INS_E.p), h->INS_A.p);
+	      hipLaunchKernelGGL((k_sym<false, P, true>), dim3((unsigned)rank_share(h, B.nst_ub) + sp.nsplitb + (sp.scan2 ? 1u : 0u)), dim3(256), 0, st, h->ctl, sd, (int)(r & 1), S, trs, sp);
 	    } else
-	    RB2_LAUNCH_STRIDE(h, (k_sym<true, P>), (k_sym<false, P>), dim3(grid8((unsigned)rank_share(h, B.nst_ub))), dim3(256), 0, st, h->ctl, sd, (int)(r & 1), RB2_P(h->L[cur].p), RB2_P(h->U[cur].p), h->A[cur].p, trs, sp, RB2_P(h->INS_E.p), h->INS_A.p); }); }
+	    RB2_LAUNCH_STRIDE(h, (k_sym<true, P>), (k_sym<false, P>), dim3(grid8((unsigned)rank_share(h, B.nst_ub))), dim3(256), 0, st, h->ctl, sd, (int)(r & 1), S, trs, sp); }); }
 	tl_slow(h, "k_sym");
 	if (with_split && with_event) HIPCHK(hipEventRecord(h->ev_flag, st));   // (the splits left the verdict in pinned memory)
 	if (one_launch_tail) {                                      // one launch instead of six, k_setup included (one GPU)
 	  Scope sc(h, RB2_K_TSCAN, units);
 	  const int do_setup = h->nranks == 1;
 	  const unsigned grid = (unsigned)std::max(1, std::min<int>(TSB, h->ts_blocks)) + (scan2_tail ? 7u : 0u);   // (+ one block per column of the chunk bases)
-	  if (h->sparse) hipLaunchKernelGGL(k_tscan_setup<true>, dim3(grid), dim3(SCHUNK), 0, st, h->ctl, sd, (int)(r & 1), trs, h->tfix.p, h->gcnt, do_setup, (int)spec, (uint32_t)r, h->pos32 ? (volatile unsigned long long*)(h->d_flag + 4) : (volatile unsigned long long*)nullptr, scan2_tail);
-	  else hipLaunchKernelGGL(k_tscan_setup<false>, dim3(grid), dim3(SCHUNK), 0, st, h->ctl, sd, (int)(r & 1), trs, h->tfix.p, h->gcnt, do_setup, (int)spec, (uint32_t)r, h->pos32 ? (volatile unsigned long long*)(h->d_flag + 4) : (volatile unsigned long long*)nullptr, scan2_tail);
+	  hipLaunchKernelGGL((h->sparse ? k_tscan_setup<true> : k_tscan_setup<false>), dim3(grid), dim3(SCHUNK), 0, st, h->ctl, sd, (int)(r & 1), trs, h->tfix.p, h->gcnt, do_setup, (int)spec, (uint32_t)r, hmax_report(h), scan2_tail);
 	  if (do_setup) { B.setup_round = r; B.setup_sparse = h->sparse; B.setup_epoch = h->layout_epoch; }
 	} else
 	{ Scope sc(h, RB2_K_TSCAN, units);
@@ -555,10 +561,30 @@ void round_counts(rb2_hip_t *h, BatchState &B, uint64_t r, bool spec = false, bo
 	    hipLaunchKernelGGL(k_tscan3<false>, dim3(B.nsc), dim3(SCHUNK), 0, st, h->ctl, sd, trs, h->cpart.p, h->tsc.p);
 	  }
 	  const int do_setup = h->nranks == 1;                     // one GPU: k_setup of the round rides on block 0 of k_tfix (the local count matrix is the global one)
-	  hipLaunchKernelGGL(k_tfix, dim3(std::max<unsigned>(1u, cdiv(B.nst_ub, 256))), dim3(256), 0, st, h->ctl, sd, (int)(r & 1), trs, h->tsc.p, h->tfix.p, h->gcnt, do_setup, (int)h->sparse, (uint32_t)r,
-	                     h->pos32 ? (volatile unsigned long long*)(h->d_flag + 4) : (volatile unsigned long long*)nullptr, (int)spec);
+	  hipLaunchKernelGGL(k_tfix, dim3(std::max<unsigned>(1u, cdiv(B.nst_ub, 256))), dim3(256), 0, st, h->ctl, sd, (int)(r & 1), trs, h->tsc.p, h->tfix.p, h->gcnt, do_setup, (int)h->sparse, (uint32_t)r, hmax_report(h), (int)spec);
 	  if (do_setup) { B.setup_round = r; B.setup_sparse = h->sparse; B.setup_epoch = h->layout_epoch; } }
 	tl_slow(h, "tile scans");
+}
+
+// the k_prep pair of round r: the variant for non-empty intervals unless the host knows that there are none (B.known_ae), then the all-empty one
+template <bool SPARSE, class P> void launch_prep(rb2_hip_t *h, const BatchState &B, uint64_t r, const PoolView &oldp, const StrArrays<P> &S)
+{
+	Scope sc(h, RB2_K_PREP, (int64_t)B.m);
+	const int sd = h->side, par = (int)(r & 1), is_comp = h->so == RB2_SO_RCLO;
+	const unsigned tg = grid8((unsigned)rank_share(h, B.nst_ub));
+	if (!B.known_ae) RB2_LAUNCH_STRIDE(h, (k_prep<false, SPARSE, true, P>), (k_prep<false, SPARSE, false, P>), dim3(tg), dim3(256), 0, h->st, h->ctl, sd, par, is_comp, oldp, S);
+	RB2_LAUNCH_STRIDE(h, (k_prep<true, SPARSE, true, P>), (k_prep<true, SPARSE, false, P>), dim3(h->nranks > 1 ? tg : grid8(cdiv(tg, PREP_PT))), dim3(256), 0, h->st, h->ctl, sd, par, is_comp, oldp, S);
+}
+
+// the k_advance pair of round r, likewise; the scan blocks of an in-place round (sr) ride on the all-empty variant, which always runs
+template <bool SPARSE, class P> void launch_advance(rb2_hip_t *h, const BatchState &B, uint64_t r, const PoolView &newp, const StrArrays<P> &S, ShardRec *send, ScanRide sr)
+{
+	Scope sc(h, RB2_K_ADVANCE, (int64_t)B.m);
+	const int sd = h->side, is_comp = h->so == RB2_SO_RCLO;
+	const unsigned tg = grid8((unsigned)rank_share(h, B.nst_ub));
+	const PushTab *push = h->push[B.cur ^ 1];
+	if (!B.known_ae) RB2_LAUNCH_STRIDE(h, (k_advance<false, SPARSE, true, P>), (k_advance<false, SPARSE, false, P>), dim3(tg), dim3(256), 0, h->st, h->ctl, sd, is_comp, (uint32_t)r, B.s, newp, S, send, push, ScanRide{ nullptr, 0u });
+	RB2_LAUNCH_STRIDE(h, (k_advance<true, SPARSE, true, P>), (k_advance<true, SPARSE, false, P>), dim3(tg + sr.nscan), dim3(256), 0, h->st, h->ctl, sd, is_comp, (uint32_t)r, B.s, newp, S, send, push, sr);
 }
 
 // phase 2: with the global count matrix in h->gcnt: layout, ranks, merge, directory, new intervals.
@@ -568,40 +594,29 @@ void round_counts(rb2_hip_t *h, BatchState &B, uint64_t r, bool spec = false, bo
 void round_merge(rb2_hip_t *h, BatchState &B, uint64_t r, ShardRec *send, bool compact_out = false)
 {
 	hipStream_t st = h->st;
-	const int sd = h->side, cur = B.cur, is_comp = h->so == RB2_SO_RCLO;
+	const int sd = h->side;
 	const int64_t units = (int64_t)B.m;
 	PoolView oldp = h->pool[h->pside].view(), newp = h->pool[h->pside ^ 1].view();
 	const uint64_t n_new_ub = B.n_tot + std::min<uint64_t>(B.len, (r + 1) * B.m);
 	const unsigned nlf = cdiv(n_new_ub, WIN) + NR;            // output windows, upper bound
-	const unsigned tg = grid8((unsigned)rank_share(h, B.nst_ub));   // string tiles / output windows this handle launches blocks for (rank_share)
-	const unsigned wg = cdiv(B.n_tot + rank_share(h, std::min<uint64_t>(B.len, (r + 1) * B.m)), WIN) + NR;
+	const unsigned wg = cdiv(B.n_tot + rank_share(h, std::min<uint64_t>(B.len, (r + 1) * B.m)), WIN) + NR;   // output windows this handle launches blocks for (rank_share)
 	if ((uint64_t)nlf * 64 >= (1ull << 32)) { rb2_fatal("[rb2_hip] the index is too large for one k_merge launch (%llu symbols: a launch is capped at 2^32 threads)\n", (unsigned long long)n_new_ub); }
 	if (!(B.setup_round == r && !B.setup_sparse && B.setup_epoch == h->layout_epoch))
 	{ Scope sc(h, RB2_K_TSCAN, 0);
-	  hipLaunchKernelGGL(k_setup<false>, dim3(1), dim3(64), 0, st, h->ctl, sd, h->gcnt, (int)(r & 1), (uint32_t)r, h->pos32 ? (volatile unsigned long long*)(h->d_flag + 4) : (volatile unsigned long long*)nullptr, (int)(h->push[0] != nullptr)); }
-	with_pos(h, [&](auto *tg_) { using P = std::remove_pointer_t<decltype(tg_)>;
-	{ Scope sc(h, RB2_K_PREP, units);
-	  if (!B.known_ae) RB2_LAUNCH_STRIDE(h, (k_prep<false, false, true, P>), (k_prep<false, false, false, P>), dim3(tg), dim3(256), 0, st, h->ctl, sd, (int)(r & 1), is_comp, oldp, RB2_P(h->L[cur].p), RB2_P(h->U[cur].p), h->A[cur].p,
-			h->tfix.p, RB2_P(h->INS_E.p), h->INS_A.p, RB2_P(h->SIZE.p));
-	  RB2_LAUNCH_STRIDE(h, (k_prep<true, false, true, P>), (k_prep<true, false, false, P>), dim3(h->nranks > 1 ? tg : grid8(cdiv(tg, PREP_PT))), dim3(256), 0, st, h->ctl, sd, (int)(r & 1), is_comp, oldp, RB2_P(h->L[cur].p), RB2_P(h->U[cur].p), h->A[cur].p,
-			h->tfix.p, RB2_P(h->INS_E.p), h->INS_A.p, RB2_P(h->SIZE.p)); }
+	  hipLaunchKernelGGL(k_setup<false>, dim3(1), dim3(64), 0, st, h->ctl, sd, h->gcnt, (int)(r & 1), (uint32_t)r, hmax_report(h), (int)(h->push[0] != nullptr)); }
+	with_pos(h, B, [&](const auto &S) { using P = std::remove_pointer_t<decltype(S.L)>;
+	launch_prep<false>(h, B, r, oldp, S);
 	tl_slow(h, "k_prep");
 	{ Scope sc(h, RB2_K_PART, units);
-	  RB2_LAUNCH_STRIDE(h, (k_part<true, P>), (k_part<false, P>), dim3(cdiv(wg + NR, 255)), dim3(256), 0, st, h->ctl, sd, RB2_P(h->INS_E.p), h->LD.p, h->pool_compact ? (const uint8_t*)oldp.xh : (const uint8_t*)nullptr); }   // (the formats of the old windows: only a pool side the compact-capable merge wrote has any but plain)
+	  RB2_LAUNCH_STRIDE(h, (k_part<true, P>), (k_part<false, P>), dim3(cdiv(wg + NR, 255)), dim3(256), 0, st, h->ctl, sd, S.INS_E, h->LD.p, h->pool_compact ? (const uint8_t*)oldp.xh : (const uint8_t*)nullptr); }   // (the formats of the old windows: only a pool side the compact-capable merge wrote has any but plain)
 	tl_slow(h, "k_part");
 	{ Scope sc(h, RB2_K_MERGE, units);
-	  RB2_LAUNCH_STRIDE(h, (k_merge<true, P>), (k_merge<false, P>), dim3(grid8(cdiv(wg, MMW))), dim3(64 * MMW), 0, st, h->ctl, h->LD.p, oldp, newp, RB2_P(h->INS_E.p), h->INS_A.p, h->RKREL.p, (int)compact_out | (h->compact_stats ? 2 : 0), (int)(r & 1)); }
-	});
+	  RB2_LAUNCH_STRIDE(h, (k_merge<true, P>), (k_merge<false, P>), dim3(grid8(cdiv(wg, MMW))), dim3(64 * MMW), 0, st, h->ctl, h->LD.p, oldp, newp, S.INS_E, S.INS_A, S.RKREL, (int)compact_out | (h->compact_stats ? 2 : 0), (int)(r & 1)); }
 	tl_slow(h, "k_merge");
 	{ Scope sc(h, RB2_K_META, units);
 	  build_directory(h, sd ^ 1, h->pside ^ 1, std::min<uint64_t>(B.nsb_ub, n_new_ub / (LEAF * SB) + NR + 1), false, false, (uint64_t)wg * WPL / SB + NR + 1); }
-	with_pos(h, [&](auto *tg_) { using P = std::remove_pointer_t<decltype(tg_)>;
 	tl_slow(h, "directory");
-	{ Scope sc(h, RB2_K_ADVANCE, units);
-	  if (!B.known_ae) RB2_LAUNCH_STRIDE(h, (k_advance<false, false, true, P>), (k_advance<false, false, false, P>), dim3(tg), dim3(256), 0, st, h->ctl, sd, is_comp, (uint32_t)r, B.s, newp, h->A[cur ^ 1].p, h->A[cur].p, h->tfix.p,
-			RB2_P(h->SIZE.p), RB2_P(h->INS_E.p), h->RKREL.p, RB2_P(h->L[cur].p), h->W[cur].p, RB2_P(h->L[cur ^ 1].p), RB2_P(h->U[cur ^ 1].p), h->W[cur ^ 1].p, send, (const P*)nullptr, (const PushTab*)h->push[cur ^ 1], ScanRide{ nullptr, 0u });
-	  RB2_LAUNCH_STRIDE(h, (k_advance<true, false, true, P>), (k_advance<true, false, false, P>), dim3(tg), dim3(256), 0, st, h->ctl, sd, is_comp, (uint32_t)r, B.s, newp, h->A[cur ^ 1].p, h->A[cur].p, h->tfix.p,
-			RB2_P(h->SIZE.p), RB2_P(h->INS_E.p), h->RKREL.p, RB2_P(h->L[cur].p), h->W[cur].p, RB2_P(h->L[cur ^ 1].p), RB2_P(h->U[cur ^ 1].p), h->W[cur ^ 1].p, send, (const P*)nullptr, (const PushTab*)h->push[cur ^ 1], ScanRide{ nullptr, 0u }); }
+	launch_advance<false>(h, B, r, newp, S, send, ScanRide{ nullptr, 0u });
 	});
 	tl_slow(h, "k_advance");
 	if (!B.known_ae && !send && h->nranks == 1) ne_snapshot(h, r);
@@ -675,7 +690,7 @@ void relayout(rb2_hip_t *h, bool to_sparse, uint64_t n_ub, uint64_t n_grow)
 bool round_merge_sparse(rb2_hip_t *h, BatchState &B, uint64_t r, ShardRec *send = nullptr, bool spec = true)
 {
 	hipStream_t st = h->st;
-	const int sd = h->side, cur = B.cur, is_comp = h->so == RB2_SO_RCLO;
+	const int sd = h->side;
 	const int64_t units = (int64_t)B.m;
 	PoolView pv = h->pool[h->pside].view();
 	const unsigned tg = grid8((unsigned)rank_share(h, B.nst_ub));
@@ -684,7 +699,7 @@ bool round_merge_sparse(rb2_hip_t *h, BatchState &B, uint64_t r, ShardRec *send 
 	{ Scope sc(h, RB2_K_TSCAN, 0);
 	  // k_setup clears ctl->overflow: behind an in-place round whose verdict the host has not seen, it would wipe out a void round (sticky-void rule)
 	  if (h->spec_rounds > 0) { rb2_fatal("[rb2_hip] internal: k_setup of in-place round %llu queued behind %llu in-place rounds without their verdict\n", (unsigned long long)r, (unsigned long long)h->spec_rounds); }
-	  hipLaunchKernelGGL(k_setup<true>, dim3(1), dim3(64), 0, st, h->ctl, sd, h->gcnt, (int)(r & 1), (uint32_t)r, h->pos32 ? (volatile unsigned long long*)(h->d_flag + 4) : (volatile unsigned long long*)nullptr, (int)(h->push[0] != nullptr)); }
+	  hipLaunchKernelGGL(k_setup<true>, dim3(1), dim3(64), 0, st, h->ctl, sd, h->gcnt, (int)(r & 1), (uint32_t)r, hmax_report(h), (int)(h->push[0] != nullptr)); }
 	const bool lazy = spec && h->lazy_verdict && h->nranks == 1;   // no verdict read here: the caller polls (insert_dev)
 	if (!lazy) h->h_flag[0] = h->h_flag[1] = 0;                // the verdict words k_split writes
 	else if (h->spec_rounds > (uint64_t)h->run_ahead) {          // not too far ahead of the device: it reports the round whose splits it has reached (split_body -> h_flag[2] = round + 1)
@@ -699,38 +714,26 @@ bool round_merge_sparse(rb2_hip_t *h, BatchState &B, uint64_t r, ShardRec *send 
 			__builtin_ia32_pause();
 		}
 	}
-	with_pos(h, [&](auto *tg_) { using P = std::remove_pointer_t<decltype(tg_)>;
-	{ Scope sc(h, RB2_K_PREP, units);
-	  if (!B.known_ae) RB2_LAUNCH_STRIDE(h, (k_prep<false, true, true, P>), (k_prep<false, true, false, P>), dim3(tg), dim3(256), 0, st, h->ctl, sd, (int)(r & 1), is_comp, pv, RB2_P(h->L[cur].p), RB2_P(h->U[cur].p), h->A[cur].p,
-			h->tfix.p, RB2_P(h->INS_E.p), h->INS_A.p, RB2_P(h->SIZE.p));
-	  RB2_LAUNCH_STRIDE(h, (k_prep<true, true, true, P>), (k_prep<true, true, false, P>), dim3(h->nranks > 1 ? tg : grid8(cdiv(tg, PREP_PT))), dim3(256), 0, st, h->ctl, sd, (int)(r & 1), is_comp, pv, RB2_P(h->L[cur].p), RB2_P(h->U[cur].p), h->A[cur].p,
-			h->tfix.p, RB2_P(h->INS_E.p), h->INS_A.p, RB2_P(h->SIZE.p)); }
+	const bool ride = h->dir_ride != 0;
+	with_pos(h, B, [&](const auto &S) { using P = std::remove_pointer_t<decltype(S.L)>;
+	launch_prep<true>(h, B, r, pv, S);
 	{ Scope sc(h, RB2_K_PART, units);
-	  RB2_LAUNCH_STRIDE(h, (k_part_sparse<true, P>), (k_part_sparse<false, P>), dim3(tg), dim3(256), 0, st, h->ctl, sd, pv, (const P*)h->INS_E.p, (const uint8_t*)h->INS_A.p, h->tfix.p, (SpOrd*)h->LD.p, h->SPL.p, (uint32_t)std::min<uint64_t>(h->SPL.cap, 0xffffffffu), RB2_P(h->RKOLD.p), (uint32_t)r); }
+	  RB2_LAUNCH_STRIDE(h, (k_part_sparse<true, P>), (k_part_sparse<false, P>), dim3(tg), dim3(256), 0, st, h->ctl, sd, pv, S.INS_E, S.INS_A, S.tf, (SpOrd*)h->LD.p, h->SPL.p, split_cap(h), S.RKOLD, (uint32_t)r); }
 	{ Scope sc(h, RB2_K_MERGE, units);
 	  const unsigned quads = cdiv(rank_share(h, B.m), MW * LROWS * LQ);   // a wave takes LQ x four work orders per step (one leaf per DPP row) and walks the list with a grid stride
-	  hipLaunchKernelGGL(k_merge_leaf<P>, dim3(std::max<unsigned>(WLC / MW, (h->leaf_pipe > 0 ? std::min<unsigned>(quads, (unsigned)h->leaf_pipe) : quads) / (WLC / MW) * (WLC / MW))), dim3(256), 0, st, (const Ctl*)h->ctl, (const SpOrd*)h->LD.p, pv, (const P*)h->INS_E.p, (const uint8_t*)h->INS_A.p, h->RKREL.p, h->sbtot.p); }
-	});
+	  hipLaunchKernelGGL(k_merge_leaf<P>, dim3(std::max<unsigned>(WLC / MW, (h->leaf_pipe > 0 ? std::min<unsigned>(quads, (unsigned)h->leaf_pipe) : quads) / (WLC / MW) * (WLC / MW))), dim3(256), 0, st, (const Ctl*)h->ctl, (const SpOrd*)h->LD.p, pv, S.INS_E, S.INS_A, S.RKREL, h->sbtot.p); }
 	// the prefix over the superblock totals: in blocks of their own of the k_advance launch and of the launch behind it (rb2_kernels.h "the directory rides along")
-	const bool ride = h->dir_ride != 0;
-	const ScanRide sr = { (const SbTot*)h->sbtot.p, ride ? cdiv(h->sp_nsb, SCHUNK) : 0u };
-	const ScanRide sr0 = { nullptr, 0u };
 	if (!ride)
 	{ Scope sc(h, RB2_K_META, units);
 	  build_directory(h, sd ^ 1, h->pside, h->sp_nsb, true, true); }
-	with_pos(h, [&](auto *tg_) { using P = std::remove_pointer_t<decltype(tg_)>;
-	{ Scope sc(h, RB2_K_ADVANCE, units);
-	  if (!B.known_ae) RB2_LAUNCH_STRIDE(h, (k_advance<false, true, true, P>), (k_advance<false, true, false, P>), dim3(tg), dim3(256), 0, st, h->ctl, sd, is_comp, (uint32_t)r, B.s, pv, h->A[cur ^ 1].p, h->A[cur].p, h->tfix.p,
-			RB2_P(h->SIZE.p), RB2_P(h->INS_E.p), h->RKREL.p, RB2_P(h->L[cur].p), h->W[cur].p, RB2_P(h->L[cur ^ 1].p), RB2_P(h->U[cur ^ 1].p), h->W[cur ^ 1].p, send, (const P*)h->RKOLD.p, (const PushTab*)h->push[cur ^ 1], sr0);
-	  RB2_LAUNCH_STRIDE(h, (k_advance<true, true, true, P>), (k_advance<true, true, false, P>), dim3(tg + sr.nscan), dim3(256), 0, st, h->ctl, sd, is_comp, (uint32_t)r, B.s, pv, h->A[cur ^ 1].p, h->A[cur].p, h->tfix.p,
-			RB2_P(h->SIZE.p), RB2_P(h->INS_E.p), h->RKREL.p, RB2_P(h->L[cur].p), h->W[cur].p, RB2_P(h->L[cur ^ 1].p), RB2_P(h->U[cur ^ 1].p), h->W[cur ^ 1].p, send, (const P*)h->RKOLD.p, (const PushTab*)h->push[cur ^ 1], sr); }   // (this launch always runs: the scan blocks ride here)
+	launch_advance<true>(h, B, r, pv, S, send, ScanRide{ (const SbTot*)h->sbtot.p, ride ? cdiv(h->sp_nsb, SCHUNK) : 0u });
 	});
 	// leaves that came close to full get a second slot of their superblock now: the last kernel of the round (k_split, rb2_kernels.h) --
 	// or, when the counting phase of round r + 1 is queued at once (spec), blocks of their own in its first launch (k_sym<.., SPLIT>)
 	const bool sp = spec && r + 1 <= B.max_len;
 	if (!sp)
 	{ Scope sc(h, RB2_K_SPLIT, 0);
-	  hipLaunchKernelGGL(k_split, dim3(256 + (ride ? 1 : 0)), dim3(256), 0, st, h->ctl, pv, (const uint32_t*)h->SPL.p, (uint32_t)std::min<uint64_t>(h->SPL.cap, 0xffffffffu), h->split_epoch, (volatile uint32_t*)h->d_flag,
+	  hipLaunchKernelGGL(k_split, dim3(256 + (ride ? 1 : 0)), dim3(256), 0, st, h->ctl, pv, (const uint32_t*)h->SPL.p, split_cap(h), h->split_epoch, (volatile uint32_t*)h->d_flag,
 	                     ride ? pv.sbbase : (SbBase*)nullptr, (uint32_t)r + 1u); }
 	// The verdict of the round (did every leaf fit?  did every split find a slot?) travels to pinned host memory behind the last
 	// kernel.  While it is on its way the host already queues the counting phase of round r + 1 -- it only writes per-round scratch,

@@ -195,8 +195,17 @@ __device__ __forceinline__ int cur_sym(uint64_t w) { return (int)(w & 7) - 1; }
 __device__ __forceinline__ uint64_t cur_next(uint64_t w) { return (w & ~CUR_MASK) | ((w & CUR_MASK) >> 3); }   // one symbol consumed
 __device__ __forceinline__ uint64_t cur_refill(const uint8_t *s, uint64_t len, uint64_t w) { const uint64_t p = cur_pos(w); return cur_make(p + CUR_SYMS, pack9(s, len, p)); }
 
-template <typename P = uint64_t> __global__ __launch_bounds__(256) void k_init_strings(Ctl *ctl, int is_srt, const uint8_t *s, const uint64_t *START,
-		P *L, P *U, uint64_t *W, uint8_t *A)
+// The per-string arrays of a round (k_init_strings, k_sym, k_prep, k_advance), positions in the batch's storage width P: this round's side,
+// the next round's (k_advance writes it), the tile table and the round's scratch; built by the host in one place (str_arrays, rb2_engine.hip).
+// (The field order is the kernel argument layout: this one leaves the code of k_prep / k_advance as it was with one parameter per array.)
+template <typename P> struct StrArrays {
+	P *L, *U; uint64_t *W; uint8_t *A;
+	P *L2, *U2; uint64_t *W2; uint8_t *A2;
+	const TileFix *tf;
+	P *SIZE, *INS_E; uint16_t *RKREL; P *RKOLD; uint8_t *INS_A;
+};
+
+template <typename P = uint64_t> __global__ __launch_bounds__(256) void k_init_strings(Ctl *ctl, int is_srt, const uint8_t *s, const uint64_t *START, StrArrays<P> S)
 {
 	__shared__ int s_wm[4];
 	const uint64_t m = ctl->n_strings, k = (uint64_t)blockIdx.x * 256 + threadIdx.x;
@@ -204,12 +213,12 @@ template <typename P = uint64_t> __global__ __launch_bounds__(256) void k_init_s
 	if (k < m) {
 		const uint64_t st = START[k], n0 = ctl->n0;
 		ln = START[k+1] - 1 - st;
-		L[k] = is_srt ? 0 : n0 + k;                 // mrope.c:280-283
-		U[k] = is_srt ? n0 : n0 + k;
+		S.L[k] = is_srt ? 0 : n0 + k;               // mrope.c:280-283
+		S.U[k] = is_srt ? n0 : n0 + k;
 		const uint32_t n1 = 1 + (uint32_t)(k % CUR_SYMS);       // the refills of the batch take turns (see above)
 		const uint32_t c9 = pack9(s, ctl->len, st) & ((1u << 3 * n1) - 1u);
-		W[k] = cur_make(st + n1, c9);
-		A[k] = (uint8_t)cur_sym(c9);
+		S.W[k] = cur_make(st + n1, c9);
+		S.A[k] = (uint8_t)cur_sym(c9);
 	}
 	// block max of the lengths -> ctl->max_len
 	unsigned long long v = ln;
@@ -284,10 +293,9 @@ __device__ __forceinline__ void split_body(Ctl *ctl, const PoolView &pool, const
 // (r04: k_prep<AE> was a second pass over the same strings at 2.3 TB/s: 0.18 ms per round of 42 M strings.)
 constexpr int32_t TILE_DONE = 0x10000;       // in TileRecs::lh (a head index is < STILE)
 constexpr int32_t TILE_SINGLE = 0x20000;     // ... every string of the tile is a group of its own and so is the string behind it (-> TileFix::nexthead bit 2: k_advance asks for its gathers before the barriers only then)
-template <bool STRIDE, typename P = uint64_t, bool SPLIT = false> __global__ __launch_bounds__(256) void k_sym(const Ctl *ctl, int side, int par, const P *L, const P *UU,
-		uint8_t *A /* in: the symbol every string inserts this round (k_init_strings / k_advance); out: + the group-head flag */, TileRecs trec, SplitArgs sp,
-		P *INS_E, uint8_t *INS_A)
+template <bool STRIDE, typename P = uint64_t, bool SPLIT = false> __global__ __launch_bounds__(256) void k_sym(const Ctl *ctl, int side, int par, StrArrays<P> S, TileRecs trec, SplitArgs sp)
 {
+	const P *L = S.L, *UU = S.U; P *INS_E = S.INS_E; uint8_t *INS_A = S.INS_A, *A = S.A;   // A in: the symbol every string inserts this round (k_init_strings / k_advance); out: + the group-head flag
 	__shared__ uint64_t s_bal[8][6], s_head[8];
 	__shared__ __align__(16) uint32_t s_ok[4];                 // per wave: every string of the wave is a group of its own
 	if (SPLIT) {
@@ -898,50 +906,9 @@ __device__ __forceinline__ Member group_member(const GroupLds &G, const TileCtx 
 	return m;
 }
 
-template <bool AE, bool SPARSE, typename P> __device__ __forceinline__ bool prep_tile(const uint32_t tile, const Ctl *ctl, int side, int par, int is_comp, const PoolView &oldp,
-		const P *L, const P *U, uint8_t *A, const TileFix *tf,
-		P *INS_E, uint8_t *INS_A, P *SIZE);                              // false: nothing (more) to do for this block
-constexpr int PREP_PT = 8;                  // string tiles per block of k_prep<AE> on one engine
-
-template <bool AE, bool SPARSE = false, bool STRIDE = false, typename P = uint64_t> __global__ __launch_bounds__(256) void k_prep(const Ctl *ctl, int side, int par, int is_comp, PoolView oldp,
-		const P *L, const P *U, uint8_t *A, const TileFix *tf,
-		P *INS_E, uint8_t *INS_A, P *SIZE)
+template <bool AE, bool SPARSE, typename P> __device__ __forceinline__ bool prep_tile(const uint32_t tile, const Ctl *ctl, int side, int par, int is_comp, const PoolView &oldp, const StrArrays<P> &S)   // false: nothing (more) to do for this block
 {
-	if (AE && !STRIDE) {
-		// all-empty rounds, one engine: k_sym has placed the new symbols of nearly every tile itself (TILE_DONE), and a launch of one block
-		// per tile was 22 us of blocks that read one word and left (82 K of them, 40 turns of the chip).  A block takes PREP_PT consecutive
-		// tiles: one vector load says which of them are still to do (none, as a rule); those go one after the other.
-		const uint32_t t0 = xcd_item() * PREP_PT, nt = ctl->seg[side].tile0[NR];
-		if (ctl->ne[par] != 0) return;
-		if (SPARSE && ctl->overflow) return;                        // (queued behind a void in-place round: its tile records are not this round's -- k_part_sparse, "a void round is sticky")
-		const uint32_t ln = (uint32_t)lane_id();
-		const bool mine = ln < (uint32_t)PREP_PT && t0 + ln < nt;
-		uint32_t nh = 2u;
-		if (mine) nh = tf[t0 + ln].nexthead;
-		uint64_t todo = __ballot(mine && !(nh & 2u));               // (the same in all four waves)
-		while (todo) {
-			const uint32_t k = (uint32_t)__builtin_ctzll(todo);
-			todo &= todo - 1;
-			prep_tile<AE, SPARSE, P>(t0 + k, ctl, side, par, is_comp, oldp, L, U, A, tf, INS_E, INS_A, SIZE);
-			if (todo) __syncthreads();
-		}
-		return;
-	}
-	// the first tile exactly as a one-tile-per-block kernel would run it (its loads are issued before anything is waited for);
-	// further tiles only when the grid is smaller than the number of tiles (grid stride: see k_sym)
-	for (uint32_t tile = STRIDE ? blockIdx.x : xcd_item(); ; ) {
-		if (!prep_tile<AE, SPARSE, P>(tile, ctl, side, par, is_comp, oldp, L, U, A, tf, INS_E, INS_A, SIZE)) return;
-		if (!STRIDE) return;
-		tile += gridDim.x;
-		if (tile >= ctl->seg[side].tile0[NR]) return;
-		__syncthreads();
-	}
-}
-
-template <bool AE, bool SPARSE, typename P> __device__ __forceinline__ bool prep_tile(const uint32_t tile, const Ctl *ctl, int side, int par, int is_comp, const PoolView &oldp,
-		const P *L, const P *U, uint8_t *A, const TileFix *tf,
-		P *INS_E, uint8_t *INS_A, P *SIZE)
-{
+	const P *L = S.L, *U = S.U; uint8_t *A = S.A; const TileFix *tf = S.tf; P *INS_E = S.INS_E; uint8_t *INS_A = S.INS_A; P *SIZE = S.SIZE;
 	__shared__ GroupLds G;
 	const TileFix &tfx = tf[tile];                              // issued together with the mode and tile-count loads
 	const SegDesc &sg = ctl->seg[side];
@@ -1043,6 +1010,41 @@ template <bool AE, bool SPARSE, typename P> __device__ __forceinline__ bool prep
 	return true;
 }
 
+constexpr int PREP_PT = 8;                  // string tiles per block of k_prep<AE> on one engine
+
+template <bool AE, bool SPARSE = false, bool STRIDE = false, typename P = uint64_t> __global__ __launch_bounds__(256) void k_prep(const Ctl *ctl, int side, int par, int is_comp, PoolView oldp, StrArrays<P> S)
+{
+	if (AE && !STRIDE) {
+		// all-empty rounds, one engine: k_sym has placed the new symbols of nearly every tile itself (TILE_DONE), and a launch of one block
+		// per tile was 22 us of blocks that read one word and left (82 K of them, 40 turns of the chip).  A block takes PREP_PT consecutive
+		// tiles: one vector load says which of them are still to do (none, as a rule); those go one after the other.
+		const uint32_t t0 = xcd_item() * PREP_PT, nt = ctl->seg[side].tile0[NR];
+		if (ctl->ne[par] != 0) return;
+		if (SPARSE && ctl->overflow) return;                        // (queued behind a void in-place round: its tile records are not this round's -- k_part_sparse, "a void round is sticky")
+		const uint32_t ln = (uint32_t)lane_id();
+		const bool mine = ln < (uint32_t)PREP_PT && t0 + ln < nt;
+		uint32_t nh = 2u;
+		if (mine) nh = S.tf[t0 + ln].nexthead;
+		uint64_t todo = __ballot(mine && !(nh & 2u));               // (the same in all four waves)
+		while (todo) {
+			const uint32_t k = (uint32_t)__builtin_ctzll(todo);
+			todo &= todo - 1;
+			prep_tile<AE, SPARSE, P>(t0 + k, ctl, side, par, is_comp, oldp, S);
+			if (todo) __syncthreads();
+		}
+		return;
+	}
+	// the first tile exactly as a one-tile-per-block kernel would run it (its loads are issued before anything is waited for);
+	// further tiles only when the grid is smaller than the number of tiles (grid stride: see k_sym)
+	for (uint32_t tile = STRIDE ? blockIdx.x : xcd_item(); ; ) {
+		if (!prep_tile<AE, SPARSE, P>(tile, ctl, side, par, is_comp, oldp, S)) return;
+		if (!STRIDE) return;
+		tile += gridDim.x;
+		if (tile >= ctl->seg[side].tile0[NR]) return;
+		__syncthreads();
+	}
+}
+
 // ---------------------------------------------------------------------------------------------
 // k_part: for every output window boundary o = j*WIN of sub-rope b, the number of inserts that land
 // before it = smallest q with E[q] + q >= o (the final position of insert q is E[q] + q).  Two
@@ -1109,26 +1111,6 @@ template <bool STRIDE, typename P = uint64_t> __global__ __launch_bounds__(256) 
 // (fill + ni > LEAF) voids the round: ctl->overflow, the host falls back to the dense rewrite.
 // One block per string tile (slots and strings of a bucket share the index range).
 // ---------------------------------------------------------------------------------------------
-
-template <typename P> __device__ __forceinline__ bool part_sparse_tile(const uint32_t tile, Ctl *ctl, int side, const PoolView &oldp, const P *__restrict__ INS_E, const uint8_t *__restrict__ INS_A, const TileFix *tf, SpOrd *LD, uint32_t *SPL, uint32_t spl_cap, P *RKOLD, uint32_t round);
-
-// A VOID ROUND IS STICKY.  ctl->overflow = (the round that could not be done in place) + 1 stays set until the HOST has dealt with it: every
-// kernel of an in-place round returns at once while it is set (this one, k_merge_leaf, k_advance<SPARSE>, the leaf splits; the counting
-// phases queued behind it: k_tscan_setup / k_tfix with spec), so the device state stays what it was in front of the void round however
-// many rounds the host has queued behind it.  That is what lets one engine queue in-place rounds WITHOUT reading a verdict per round
-// (rounds 2-5: an event and a host round trip in every round, 14 us of an otherwise 230 us round with nothing on the device): the host
-// polls the verdict word in pinned memory when it queues a round, and finds out at the latest at the end of the batch (insert_dev).
-template <bool STRIDE, typename P = uint64_t> __global__ __launch_bounds__(256) void k_part_sparse(Ctl *ctl, int side, PoolView oldp, const P *__restrict__ INS_E, const uint8_t *__restrict__ INS_A, const TileFix *tf, SpOrd *LD, uint32_t *SPL, uint32_t spl_cap, P *RKOLD, uint32_t round)
-{
-	if (ctl->overflow) return;                                  // (an earlier round is void -- or a block of this launch just found this one to be)
-	for (uint32_t tile = blockIdx.x; ; ) {                      // (first tile as ever, then a grid stride: see k_prep)
-		if (!part_sparse_tile<P>(tile, ctl, side, oldp, INS_E, INS_A, tf, LD, SPL, spl_cap, RKOLD, round)) return;
-		if (!STRIDE) return;
-		tile += gridDim.x;
-		if (tile >= ctl->seg[side].tile0[NR]) return;
-		__syncthreads();
-	}
-}
 
 template <typename P> __device__ __forceinline__ bool part_sparse_tile(const uint32_t tile, Ctl *ctl, int side, const PoolView &oldp, const P *__restrict__ INS_E, const uint8_t *__restrict__ INS_A, const TileFix *tf, SpOrd *LD, uint32_t *SPL, uint32_t spl_cap, P *RKOLD, uint32_t round)
 {
@@ -1332,6 +1314,24 @@ template <typename P> __device__ __forceinline__ bool part_sparse_tile(const uin
 		LD[off++] = d;
 	}
 	return true;
+}
+
+// A VOID ROUND IS STICKY.  ctl->overflow = (the round that could not be done in place) + 1 stays set until the HOST has dealt with it: every
+// kernel of an in-place round returns at once while it is set (this one, k_merge_leaf, k_advance<SPARSE>, the leaf splits; the counting
+// phases queued behind it: k_tscan_setup / k_tfix with spec), so the device state stays what it was in front of the void round however
+// many rounds the host has queued behind it.  That is what lets one engine queue in-place rounds WITHOUT reading a verdict per round
+// (rounds 2-5: an event and a host round trip in every round, 14 us of an otherwise 230 us round with nothing on the device): the host
+// polls the verdict word in pinned memory when it queues a round, and finds out at the latest at the end of the batch (insert_dev).
+template <bool STRIDE, typename P = uint64_t> __global__ __launch_bounds__(256) void k_part_sparse(Ctl *ctl, int side, PoolView oldp, const P *__restrict__ INS_E, const uint8_t *__restrict__ INS_A, const TileFix *tf, SpOrd *LD, uint32_t *SPL, uint32_t spl_cap, P *RKOLD, uint32_t round)
+{
+	if (ctl->overflow) return;                                  // (an earlier round is void -- or a block of this launch just found this one to be)
+	for (uint32_t tile = blockIdx.x; ; ) {                      // (first tile as ever, then a grid stride: see k_prep)
+		if (!part_sparse_tile<P>(tile, ctl, side, oldp, INS_E, INS_A, tf, LD, SPL, spl_cap, RKOLD, round)) return;
+		if (!STRIDE) return;
+		tile += gridDim.x;
+		if (tile >= ctl->seg[side].tile0[NR]) return;
+		__syncthreads();
+	}
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1775,41 +1775,10 @@ __global__ __launch_bounds__(SCHUNK / SBT) void k_sbscan3(const Ctl *ctl, const 
 // ---------------------------------------------------------------------------------------------
 
 template <bool AE, bool SPARSE, typename P> __device__ __forceinline__ bool advance_tile(const uint32_t tile, const Ctl *ctl, int side, int is_comp, uint32_t round, const uint8_t *s, const PoolView &newp,
-		uint8_t *A2, const uint8_t *A, const TileFix *tf,
-		const P *SIZE, const P *INS_E, const uint16_t *RKREL, const P *L, const uint64_t *W,
-		P *L2, P *U2, uint64_t *W2, ShardRec *send, const P *RKOLD, const PushTab *push);
-struct ScanRide { const SbTot *sbtot; uint32_t nscan; };     // in-place rounds: the first nscan blocks of the k_advance launch do k_sbscan3's work (see k_advance)
-
-template <bool AE, bool SPARSE = false, bool STRIDE = false, typename P = uint64_t> __global__ __launch_bounds__(256) void k_advance(const Ctl *ctl, int side, int is_comp, uint32_t round, const uint8_t *s, PoolView newp,
-		uint8_t *A2, const uint8_t *A, const TileFix *tf,
-		const P *SIZE, const P *INS_E, const uint16_t *RKREL, const P *L, const uint64_t *W,
-		P *L2, P *U2, uint64_t *W2, ShardRec *send, const P *RKOLD, const PushTab *push, ScanRide sr)
+		const StrArrays<P> &S, ShardRec *send, const PushTab *push)
 {
-	// THE DIRECTORY RIDES ALONG.  An in-place round leaves the superblock totals current (k_merge_leaf); what is left is the prefix over them
-	// (k_sbscan3 + k_sbscan2: two launches, 12 us per round at 10 G symbols, ~100 us at 90 G -- the one part of the round that reads every
-	// superblock).  Nothing in this kernel reads the directory in an in-place round any more (ranks come from before the merge: RKOLD), and
-	// the next reader is the next round's descent -- so the first sr.nscan blocks of this launch ARE k_sbscan3 (one chunk of superblocks
-	// each), beside the tile blocks, and the chunk bases follow in one block of the next launch (k_sym<.., SPLIT> / k_split: SplitArgs::scan2).
-	// No launch, no event, no second stream; the latency-bound tile blocks leave the memory system to the scan.
-	uint32_t nsc = 0;
-	if (SPARSE) {
-		nsc = sr.nscan;
-		if (blockIdx.x < nsc) { __shared__ uint32_t s_p[6][4]; sbscan3_body(ctl, sr.sbtot, newp, blockIdx.x, s_p); return; }
-	}
-	for (uint32_t tile = (SPARSE && nsc) ? blockIdx.x - nsc : (STRIDE ? blockIdx.x : xcd_item()); ; ) {   // first tile as a one-tile-per-block kernel would run it, then a grid stride (see k_prep)
-		if (!advance_tile<AE, SPARSE, P>(tile, ctl, side, is_comp, round, s, newp, A2, A, tf, SIZE, INS_E, RKREL, L, W, L2, U2, W2, send, RKOLD, push)) return;
-		if (!STRIDE) return;
-		tile += gridDim.x - nsc;
-		if (tile >= ctl->seg[side].tile0[NR]) return;
-		__syncthreads();
-	}
-}
-
-template <bool AE, bool SPARSE, typename P> __device__ __forceinline__ bool advance_tile(const uint32_t tile, const Ctl *ctl, int side, int is_comp, uint32_t round, const uint8_t *s, const PoolView &newp,
-		uint8_t *A2, const uint8_t *A, const TileFix *tf,
-		const P *SIZE, const P *INS_E, const uint16_t *RKREL, const P *L, const uint64_t *W,
-		P *L2, P *U2, uint64_t *W2, ShardRec *send, const P *RKOLD, const PushTab *push)
-{
+	const P *L = S.L, *SIZE = S.SIZE, *INS_E = S.INS_E, *RKOLD = S.RKOLD; const uint64_t *W = S.W; const uint8_t *A = S.A; const TileFix *tf = S.tf; const uint16_t *RKREL = S.RKREL;
+	P *L2 = S.L2, *U2 = S.U2; uint64_t *W2 = S.W2; uint8_t *A2 = S.A2;                      // (the next round's side)
 	__shared__ GroupLds G;
 	const TileFix &tfx = tf[tile];                              // issued together with the mode and tile-count loads
 	const SegDesc &sg = ctl->seg[side];
@@ -1962,6 +1931,31 @@ template <bool AE, bool SPARSE, typename P> __device__ __forceinline__ bool adva
 		if (__any(nz != 0) && lane_id() == 0) ((Ctl*)ctl)->ne[(round & 1) ^ 1] = 1;
 	}
 	return true;
+}
+
+struct ScanRide { const SbTot *sbtot; uint32_t nscan; };     // in-place rounds: the first nscan blocks of the k_advance launch do k_sbscan3's work (see k_advance)
+
+template <bool AE, bool SPARSE = false, bool STRIDE = false, typename P = uint64_t> __global__ __launch_bounds__(256) void k_advance(const Ctl *ctl, int side, int is_comp, uint32_t round, const uint8_t *s, PoolView newp,
+		StrArrays<P> S, ShardRec *send, const PushTab *push, ScanRide sr)
+{
+	// THE DIRECTORY RIDES ALONG.  An in-place round leaves the superblock totals current (k_merge_leaf); what is left is the prefix over them
+	// (k_sbscan3 + k_sbscan2: two launches, 12 us per round at 10 G symbols, ~100 us at 90 G -- the one part of the round that reads every
+	// superblock).  Nothing in this kernel reads the directory in an in-place round any more (ranks come from before the merge: RKOLD), and
+	// the next reader is the next round's descent -- so the first sr.nscan blocks of this launch ARE k_sbscan3 (one chunk of superblocks
+	// each), beside the tile blocks, and the chunk bases follow in one block of the next launch (k_sym<.., SPLIT> / k_split: SplitArgs::scan2).
+	// No launch, no event, no second stream; the latency-bound tile blocks leave the memory system to the scan.
+	uint32_t nsc = 0;
+	if (SPARSE) {
+		nsc = sr.nscan;
+		if (blockIdx.x < nsc) { __shared__ uint32_t s_p[6][4]; sbscan3_body(ctl, sr.sbtot, newp, blockIdx.x, s_p); return; }
+	}
+	for (uint32_t tile = (SPARSE && nsc) ? blockIdx.x - nsc : (STRIDE ? blockIdx.x : xcd_item()); ; ) {   // first tile as a one-tile-per-block kernel would run it, then a grid stride (see k_prep)
+		if (!advance_tile<AE, SPARSE, P>(tile, ctl, side, is_comp, round, s, newp, S, send, push)) return;
+		if (!STRIDE) return;
+		tile += gridDim.x - nsc;
+		if (tile >= ctl->seg[side].tile0[NR]) return;
+		__syncthreads();
+	}
 }
 
 // ---------------------------------------------------------------------------------------------

@@ -349,7 +349,7 @@ void multi_rank_batch(rb2_hip_multi_t *m, int k, int64_t len)
 		}
 		// sum of the count rows (PEER) + exchange plan + k_setup of the round: one launch (k_mround)
 		{
-			volatile unsigned long long *hmax = h->pos32 ? (volatile unsigned long long*)(h->d_flag + 4) : (volatile unsigned long long*)nullptr;
+			volatile unsigned long long *hmax = hmax_report(h);
 			volatile unsigned long long *hne = (volatile unsigned long long*)(h->d_flag + 8);   // (round, any non-empty interval on any rank) as k_mround last saw it
 			if (h->sparse) hipLaunchKernelGGL(k_mround<true>, dim3(1), dim3(256), 0, st, h->ctl, rows, peer ? m->n : 0, h->gcnt, ow, R.grank, (int)peer, sends[r & 1], (const ShardRec*)R.recv, R.tab, h->side, (int)(r & 1), (uint32_t)r, hmax, hne);
 			else hipLaunchKernelGGL(k_mround<false>, dim3(1), dim3(256), 0, st, h->ctl, rows, peer ? m->n : 0, h->gcnt, ow, R.grank, (int)peer, sends[r & 1], (const ShardRec*)R.recv, R.tab, h->side, (int)(r & 1), (uint32_t)r, hmax, hne);
