@@ -30,6 +30,7 @@
 //                 3 bits each, + the text position of the symbols behind them), A (this round's symbol + group-head / non-empty flags).
 #pragma once
 #include <hip/hip_runtime.h>
+#include <stddef.h>
 #include <stdint.h>
 
 namespace rb2 {
@@ -140,6 +141,24 @@ constexpr int GCN = NR * 6 + 2;         // words of the per-round count matrix b
                                         // all-empty kernel variants only, from this round on) + one word of padding
 constexpr int WLC = 16;                 // work lists of a sparse round
 constexpr int WLS = 32;                 // their counters sit 128 bytes apart
+
+// The mailbox: one block of pinned host memory that kernels write straight into and the host reads when it gets there, without
+// synchronising (rb2_engine.hip: the engine holds its host and its device address).  Every word the device writes is volatile.
+constexpr int NE_RING = 32;             // ne snapshots kept, one per round: slot round % NE_RING
+struct Mailbox {
+	volatile uint32_t void_round;       // verdict of the in-place rounds: the void round + 1, 0 = none (split_body: a void round is sticky, ctl->overflow)
+	volatile uint32_t respread;         // ... a superblock ran out of slots: re-spread before the next round (split_body)
+	volatile uint32_t progress;         // the in-place round whose splits the device has reached, + 1 (split_body): how far the host may run ahead
+	uint32_t pad0;
+	volatile unsigned long long hmax;   // (round << 40 | size of the largest piece after it) as k_setup last reported it, 0 = nothing yet (setup_body)
+	uint64_t pad1;
+	volatile unsigned long long hne;    // rank of a sharded index: (round << 32 | some rank holds a non-empty interval) as k_mround last saw it, ~0 = nothing yet
+	uint64_t pad2[3];
+	volatile uint32_t ne[NE_RING][2];   // ctl->ne after each round (ne_snapshot: a copy behind the round), 0xffffffff = not landed yet
+};
+static_assert(offsetof(Mailbox, void_round) == 0 && offsetof(Mailbox, respread) == 4 && offsetof(Mailbox, progress) == 8, "mailbox layout");
+static_assert(offsetof(Mailbox, hmax) == 16 && offsetof(Mailbox, hne) == 32 && offsetof(Mailbox, ne) == 64, "mailbox layout");
+static_assert(sizeof(Mailbox) == 64 + 8 * NE_RING, "mailbox layout");
 
 // one string's state on the wire (24 B): a = l (48 bits) | size[15:0] << 48;  b = id | size[47:16] << 32;  w = the symbol cursor.
 // (Rounds 1-2 sent 16 bytes and rebuilt the cursor on arrival from the batch text every rank holds: a 20-byte random gather per

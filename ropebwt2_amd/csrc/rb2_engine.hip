@@ -196,10 +196,9 @@ struct rb2_hip_s {
 	int sp_maxpen = 6;                  // at most 64 dense rounds between two attempts (a failed attempt costs about four dense rounds)
 	int leaf_pipe = 8192;               // in-place rounds use the software-pipelined k_merge_leaf_pipe with at most this many workgroups (RB2_LEAF_PIPE; 0: one wave per
 	                                    // four work orders, k_merge_leaf).  1 M inserts per round: 232 us with k_merge_leaf, 259 / 228 / 212 / 207 / 212 us with 1024 / 1536 / 4096 / 8192 / 16384
-	uint32_t *h_flag = nullptr;         // pinned: verdict of a sparse round (written by k_split through d_flag); [16..16+2*NE_RING): ring of ctl->ne snapshots, one per round
-	uint32_t *d_flag = nullptr;         // ... its device address
+	Mailbox *mb_h = nullptr;            // pinned: what the kernels report to the host without a synchronisation (rb2_device.h) ...
+	Mailbox *mb_d = nullptr;            // ... its device address
 	uint64_t layout_epoch = 0;          // counts the re-layouts: what k_setup derived from the piece descriptors before one is stale after it
-	static constexpr int NE_RING = 32;
 	hipEvent_t ev_flag = nullptr;
 	// in-place rounds: the prefix over the superblock totals (k_sbscan*) is needed by the NEXT round's descent only (k_advance takes its ranks
 	// from before the merge: RKOLD), so it rides in blocks of their own of the launches that follow the merge anyway (k_advance; k_sym / k_split)
@@ -209,7 +208,7 @@ struct rb2_hip_s {
 	// spec_rounds = in-place rounds queued since the host last looked with the stream drained (verdict_check)
 	int lazy_verdict = 1;               // RB2_LAZY_VERDICT=0: an event and a wait per in-place round, as in rounds 2-5
 	uint64_t spec_rounds = 0;
-	int run_ahead = 3;                  // ... and at most this many in-place rounds ahead of what the device reports done (h_flag[2]): a re-spread asked for by round r takes place this
+	int run_ahead = 3;                  // ... and at most this many in-place rounds ahead of what the device reports done (mb_h->progress): a re-spread asked for by round r takes place this
 	                                    // many rounds late at worst (RB2_RUN_AHEAD)
 	int verdict_poll = 1;               // RB2_VERDICT_POLL=0 (tests): the host does not poll the verdict word while it queues rounds -- it learns of a void round only when it
 	                                    // drains the stream (a re-layout, a widening, the end of the batch), so a void round is taken back from behind every round queued since
@@ -363,6 +362,8 @@ struct BatchState {
 	uint64_t setup_round = (uint64_t)-1;    // round whose k_setup ran inside its counting phase (k_tscan_setup) ...
 	bool setup_sparse = false; uint64_t setup_epoch = 0;   // ... for this layout, at this layout epoch (a re-layout in between: k_setup runs again)
 };
+inline void mark_setup(const rb2_hip_t *h, BatchState &B, uint64_t r) { B.setup_round = r; B.setup_sparse = h->sparse; B.setup_epoch = h->layout_epoch; }   // k_setup of round r is queued
+inline bool setup_done(const rb2_hip_t *h, const BatchState &B, uint64_t r, bool sparse) { return B.setup_round == r && B.setup_sparse == sparse && B.setup_epoch == h->layout_epoch; }   // ... and still stands (no re-layout since)
 
 // per-string arrays + tile tables for batches of up to m strings
 void ensure_strings(rb2_hip_t *h, uint64_t m)
@@ -384,7 +385,7 @@ template <class P> StrArrays<P> str_arrays(rb2_hip_t *h, const BatchState &B)
 // launch F with them, P = the storage type of this batch's positions
 template <class F> inline void with_pos(rb2_hip_t *h, const BatchState &B, F f) { if (h->pos32) f(str_arrays<uint32_t>(h, B)); else f(str_arrays<uint64_t>(h, B)); }
 
-inline volatile unsigned long long *hmax_report(const rb2_hip_t *h) { return h->pos32 ? (volatile unsigned long long*)(h->d_flag + 4) : nullptr; }   // where k_setup reports its (round, largest piece) to maybe_widen
+inline volatile unsigned long long *hmax_report(const rb2_hip_t *h) { return h->pos32 ? &h->mb_d->hmax : nullptr; }   // where k_setup reports its (round, largest piece) to maybe_widen
 inline uint32_t split_cap(const rb2_hip_t *h) { return (uint32_t)std::min<uint64_t>(h->SPL.cap, 0xffffffffu); }   // leaves an in-place round may list for splitting (k_part_sparse -> k_split)
 
 // A batch may hold at most this many strings (32-bit slots, tile numbers and work orders).  The reference takes any count
@@ -445,8 +446,8 @@ bool batch_begin(rb2_hip_t *h, BatchState &B, int64_t len64, const uint8_t *s, b
 		h->pos_m0 = mx;
 		h->pos32 = h->want_pos32 && h->pos_mode != 64 && mx + 2 * m < POS32_LIMIT;
 		h->want_pos32 = false;
-		((volatile unsigned long long*)(h->h_flag + 4))[0] = 0;  // (round, largest piece) as k_setup last reported it: nothing yet
-		((volatile uint32_t*)h->h_flag)[2] = 0;                   // (in-place rounds the device has come through: none of this batch)
+		h->mb_h->hmax = 0;                                       // (round, largest piece) as k_setup last reported it: nothing yet
+		h->mb_h->progress = 0;                                   // (in-place rounds the device has come through: none of this batch)
 	}
 	{
 		Scope sc(h, RB2_K_INIT, 0);
@@ -465,14 +466,14 @@ bool batch_begin(rb2_hip_t *h, BatchState &B, int64_t len64, const uint8_t *s, b
 // (a stale snapshot only delays that).  Before: both variants every round, the wrong one returning at once (2 x ~18 us).
 void ne_snapshot(rb2_hip_t *h, uint64_t r)
 {
-	uint32_t *slot = h->h_flag + 16 + 2 * (r % rb2_hip_s::NE_RING);
-	slot[0] = slot[1] = 0xffffffffu;                           // "not landed yet"
-	HIPCHK(hipMemcpyAsync(slot, &h->ctl->ne[0], 8, hipMemcpyDeviceToHost, h->st));
+	volatile uint32_t *slot = h->mb_h->ne[r % NE_RING];
+	slot[0] = 0xffffffffu; slot[1] = 0xffffffffu;             // "not landed yet"
+	HIPCHK(hipMemcpyAsync((void*)slot, &h->ctl->ne[0], 8, hipMemcpyDeviceToHost, h->st));
 }
 bool ne_all_empty_from(rb2_hip_t *h, uint64_t r)               // may round r (and all later ones) skip the non-AE variants?
 {
-	for (uint64_t q = r; q-- > 0 && r - q < (uint64_t)rb2_hip_s::NE_RING; ) {
-		const volatile uint32_t *slot = h->h_flag + 16 + 2 * (q % rb2_hip_s::NE_RING);
+	for (uint64_t q = r; q-- > 0 && r - q < (uint64_t)NE_RING; ) {
+		const volatile uint32_t *slot = h->mb_h->ne[q % NE_RING];
 		const uint32_t v = slot[(q & 1) ^ 1];                  // after round q: ne[(q&1)^1] is the flag of round q + 1
 		if (v == 0) return true;
 		if (v != 0xffffffffu) return false;                    // the newest snapshot that landed says "still non-empty intervals"
@@ -489,7 +490,7 @@ uint32_t verdict_check(rb2_hip_t *h, bool drain);
 uint32_t maybe_widen(rb2_hip_t *h, BatchState &B, uint64_t r)
 {
 	if (!h->pos32) return 0;
-	const unsigned long long v = ((volatile unsigned long long*)(h->h_flag + 4))[0];
+	const unsigned long long v = h->mb_h->hmax;
 	uint64_t known = h->pos_m0, since = r + 1;                   // rounds the bound must cover
 	if (v != 0) { known = v & ((1ull << 40) - 1); const uint64_t q = v >> 40; since = r >= q ? r - q : r + 1; }   // (the report of round q is the size AFTER round q)
 	const char *e = getenv("RB2_POS_WIDEN_AT");
@@ -508,9 +509,6 @@ uint32_t maybe_widen(rb2_hip_t *h, BatchState &B, uint64_t r)
 	return 0;
 }
 
-// phase 1 of a round: next symbols, group heads, tile scans, the rows of the count matrix seen here
-// spec: queued while the verdict of the in-place round in front of it is still on its way (round_merge_sparse)
-// with_split: the k_sym launch also does the leaf splits of the in-place round in front of it and the verdict event follows it (round_merge_sparse)
 static inline void tl_slow(rb2_hip_t *h, const char *what)    // RB2_HIP_TIMELINE=2: which host call of a round took more than half a millisecond
 {
 	if (h->timeline < 2) return;
@@ -518,7 +516,16 @@ static inline void tl_slow(rb2_hip_t *h, const char *what)    // RB2_HIP_TIMELIN
 	if (h->tl_last != 0 && now - h->tl_last > 0.5) fprintf(stderr, "[rb2_hip] t = %8.3f ms  round %d: %.3f ms on the host up to and including %s\n", now - h->tl_base, h->cur_round, now - h->tl_last, what);
 	h->tl_last = now;
 }
-void round_counts(rb2_hip_t *h, BatchState &B, uint64_t r, bool spec = false, bool with_split = false, bool with_event = true)
+// in-place rounds queued with spec on one engine are not waited for: the host polls their verdict (verdict_check) -- unless RB2_LAZY_VERDICT=0
+inline bool lazy_round(const rb2_hip_t *h, bool spec) { return spec && h->lazy_verdict && h->nranks == 1; }
+// The sticky-void rule: k_setup clears ctl->overflow, so it is never queued behind in-place rounds whose verdict the host has not seen (it would
+// wipe out a void round).  `what` (of round r) may run k_setup.
+void require_verdicts_seen(const rb2_hip_t *h, uint64_t r, const char *what)
+{ if (h->spec_rounds > 0) { rb2_fatal("[rb2_hip] internal: %s %llu queued behind %llu in-place rounds without their verdict\n", what, (unsigned long long)r, (unsigned long long)h->spec_rounds); } }
+// phase 1 of a round: next symbols, group heads, tile scans, the rows of the count matrix seen here
+// spec: follows the in-place round r - 1 while its verdict is still on its way (round_merge_sparse): the k_sym launch also does that round's
+// leaf splits, the verdict event follows it (unless the verdict is polled: lazy_round), and the k_setup riding on the tail returns on a void round
+void round_counts(rb2_hip_t *h, BatchState &B, uint64_t r, bool spec = false)
 {
 	hipStream_t st = h->st;
 	const int sd = h->side;
@@ -527,31 +534,30 @@ void round_counts(rb2_hip_t *h, BatchState &B, uint64_t r, bool spec = false, bo
 	const TileRecs trs = { (uint32_t*)h->trec.p, (uint32_t)(h->trec.cap & ~(size_t)3) };   // (20 columns of cap words in the 80-byte records' space)
 	tl_slow(h, "start of round_counts");
 	const bool one_launch_tail = B.nst_ub < (unsigned)h->ts_max;  // few tiles (long reads): the counting tail is one launch (k_tscan_setup)
-	// without spec, the k_setup riding on k_tscan_setup / k_tfix runs whatever ctl->overflow says and clears it: never behind an unseen verdict (sticky-void rule)
-	if (!spec && h->spec_rounds > 0) { rb2_fatal("[rb2_hip] internal: counting phase of round %llu queued without spec behind %llu in-place rounds without their verdict\n", (unsigned long long)r, (unsigned long long)h->spec_rounds); }
+	if (!spec) require_verdicts_seen(h, r, "counting phase without spec of round");   // (its k_setup runs whatever ctl->overflow says)
 	SplitArgs sp; memset(&sp, 0, sizeof(sp));
-	if (with_split) {
+	if (spec) {
 	  sp.ctl = h->ctl; sp.pool = h->pool[h->pside].view(); sp.SPL = h->SPL.p; sp.spl_cap = split_cap(h); sp.epoch = h->split_epoch;
-	  sp.hv = (volatile uint32_t*)h->d_flag; sp.nsplitb = 64;
+	  sp.mb = h->mb_d; sp.nsplitb = 64;
 	  sp.round1 = (uint32_t)r;                                   // (the splits of round r - 1)
 	  sp.scan2 = (h->dir_ride && !one_launch_tail) ? sp.pool.sbbase : (SbBase*)nullptr;   // the chunk bases of the directory the k_advance launch in front of this one left half-built
 	                                                             // (in a block of this launch -- or, when the counting tail is one launch, of that one: see below)
 	}
-	SbBase *scan2_tail = (with_split && h->dir_ride && one_launch_tail) ? h->pool[h->pside].view().sbbase : (SbBase*)nullptr;
+	SbBase *scan2_tail = (spec && h->dir_ride && one_launch_tail) ? h->pool[h->pside].view().sbbase : (SbBase*)nullptr;
 	{ Scope sc(h, RB2_K_SYM, units);
 	  with_pos(h, B, [&](const auto &S) { using P = std::remove_pointer_t<decltype(S.L)>;
-	    if (with_split) {
+	    if (spec) {
 	      hipLaunchKernelGGL((k_sym<false, P, true>), dim3((unsigned)rank_share(h, B.nst_ub) + sp.nsplitb + (sp.scan2 ? 1u : 0u)), dim3(256), 0, st, h->ctl, sd, (int)(r & 1), S, trs, sp);
 	    } else
 	    RB2_LAUNCH_STRIDE(h, (k_sym<true, P>), (k_sym<false, P>), dim3(grid8((unsigned)rank_share(h, B.nst_ub))), dim3(256), 0, st, h->ctl, sd, (int)(r & 1), S, trs, sp); }); }
 	tl_slow(h, "k_sym");
-	if (with_split && with_event) HIPCHK(hipEventRecord(h->ev_flag, st));   // (the splits left the verdict in pinned memory)
+	if (spec && !lazy_round(h, spec)) HIPCHK(hipEventRecord(h->ev_flag, st));   // (the splits left the verdict in pinned memory)
 	if (one_launch_tail) {                                      // one launch instead of six, k_setup included (one GPU)
 	  Scope sc(h, RB2_K_TSCAN, units);
 	  const int do_setup = h->nranks == 1;
 	  const unsigned grid = (unsigned)std::max(1, std::min<int>(TSB, h->ts_blocks)) + (scan2_tail ? 7u : 0u);   // (+ one block per column of the chunk bases)
 	  hipLaunchKernelGGL((h->sparse ? k_tscan_setup<true> : k_tscan_setup<false>), dim3(grid), dim3(SCHUNK), 0, st, h->ctl, sd, (int)(r & 1), trs, h->tfix.p, h->gcnt, do_setup, (int)spec, (uint32_t)r, hmax_report(h), scan2_tail);
-	  if (do_setup) { B.setup_round = r; B.setup_sparse = h->sparse; B.setup_epoch = h->layout_epoch; }
+	  if (do_setup) mark_setup(h, B, r);
 	} else
 	{ Scope sc(h, RB2_K_TSCAN, units);
 	  hipLaunchKernelGGL(k_tscan1, dim3(B.nsc), dim3(SCHUNK), 0, st, h->ctl, sd, trs, h->cpart.p);
@@ -562,7 +568,7 @@ void round_counts(rb2_hip_t *h, BatchState &B, uint64_t r, bool spec = false, bo
 	  }
 	  const int do_setup = h->nranks == 1;                     // one GPU: k_setup of the round rides on block 0 of k_tfix (the local count matrix is the global one)
 	  hipLaunchKernelGGL(k_tfix, dim3(std::max<unsigned>(1u, cdiv(B.nst_ub, 256))), dim3(256), 0, st, h->ctl, sd, (int)(r & 1), trs, h->tsc.p, h->tfix.p, h->gcnt, do_setup, (int)h->sparse, (uint32_t)r, hmax_report(h), (int)spec);
-	  if (do_setup) { B.setup_round = r; B.setup_sparse = h->sparse; B.setup_epoch = h->layout_epoch; } }
+	  if (do_setup) mark_setup(h, B, r); }
 	tl_slow(h, "tile scans");
 }
 
@@ -601,7 +607,7 @@ void round_merge(rb2_hip_t *h, BatchState &B, uint64_t r, ShardRec *send, bool c
 	const unsigned nlf = cdiv(n_new_ub, WIN) + NR;            // output windows, upper bound
 	const unsigned wg = cdiv(B.n_tot + rank_share(h, std::min<uint64_t>(B.len, (r + 1) * B.m)), WIN) + NR;   // output windows this handle launches blocks for (rank_share)
 	if ((uint64_t)nlf * 64 >= (1ull << 32)) { rb2_fatal("[rb2_hip] the index is too large for one k_merge launch (%llu symbols: a launch is capped at 2^32 threads)\n", (unsigned long long)n_new_ub); }
-	if (!(B.setup_round == r && !B.setup_sparse && B.setup_epoch == h->layout_epoch))
+	if (!setup_done(h, B, r, false))
 	{ Scope sc(h, RB2_K_TSCAN, 0);
 	  hipLaunchKernelGGL(k_setup<false>, dim3(1), dim3(64), 0, st, h->ctl, sd, h->gcnt, (int)(r & 1), (uint32_t)r, hmax_report(h), (int)(h->push[0] != nullptr)); }
 	with_pos(h, B, [&](const auto &S) { using P = std::remove_pointer_t<decltype(S.L)>;
@@ -681,6 +687,40 @@ void relayout(rb2_hip_t *h, bool to_sparse, uint64_t n_ub, uint64_t n_grow)
 	}
 }
 
+// The host queues in-place rounds at most run_ahead rounds ahead of what the device reports done (Mailbox::progress, split_body): before round r
+// it waits until round r - run_ahead - 1 is over, or a void round is reported, or the stream has run dry (nothing more will be reported)
+void wait_progress(rb2_hip_t *h, uint64_t r)
+{
+	const uint32_t want = (uint32_t)r - (uint32_t)h->run_ahead;   // round `want - 1` at least must be over
+	const auto t_spin = std::chrono::steady_clock::now();
+	for (uint32_t spins = 0; (int32_t)(h->mb_h->progress - want) < 0 && !h->mb_h->void_round; ++spins) {
+		if ((spins & 1023u) == 1023u) {
+			if (hipStreamQuery(h->st) == hipSuccess) break;         // (everything queued is done: nothing more will be reported)
+			if (std::chrono::steady_clock::now() - t_spin > std::chrono::seconds(2)) { HIPCHK(hipStreamSynchronize(h->st)); break; }   // (a report that does not come: wait the plain way)
+		}
+#if defined(__x86_64__)
+		__builtin_ia32_pause();
+#else
+		std::this_thread::yield();
+#endif
+	}
+}
+
+// Take back the in-place rounds r_void .. r - 1 (round r is next): every kernel of the void round and of those queued behind it returned (a void
+// round is sticky: rb2_kernels.h k_part_sparse), only the host's bookkeeping rewinds.  A round whose verdict was waited for is the one round in
+// flight.  Returns r - r_void; the caller redoes round r_void densely.
+int64_t take_back(rb2_hip_t *h, BatchState &B, uint64_t r_void, uint64_t r)
+{
+	if (r_void >= r || r - r_void > std::max<uint64_t>(h->spec_rounds, 1)) { rb2_fatal("[rb2_hip] internal: void round %llu reported while queueing round %llu (%llu in flight)\n", (unsigned long long)r_void, (unsigned long long)r, (unsigned long long)h->spec_rounds); }
+	const int64_t depth = (int64_t)(r - r_void);
+	if (depth & 1) { h->side ^= 1; B.cur ^= 1; }                // every in-place round queued from r_void on flipped the descriptor and array sides once
+	HIPCHK(hipMemsetAsync(&h->ctl->overflow, 0, 4, h->st));
+	h->spec_rounds = 0; h->mb_h->void_round = 0;
+	h->mb_h->progress = (uint32_t)r_void;                      // (the rounds behind the void one reported themselves done; wait_progress reads it)
+	B.counted = (uint64_t)-1; B.setup_round = (uint64_t)-1;
+	return depth;
+}
+
 // Sparse round: the strings of the batch touch few leaves, each touched leaf is rewritten where it lies (k_merge_leaf),
 // the rest of the index keeps its bytes.  Returns false when some leaf could not take its inserts: nothing was
 // changed (every kernel behind k_part_sparse saw ctl->overflow and returned) and the caller redoes the round densely.
@@ -695,25 +735,13 @@ bool round_merge_sparse(rb2_hip_t *h, BatchState &B, uint64_t r, ShardRec *send 
 	PoolView pv = h->pool[h->pside].view();
 	const unsigned tg = grid8((unsigned)rank_share(h, B.nst_ub));
 	if (++h->split_epoch == 0) ++h->split_epoch;
-	if (!(B.setup_round == r && B.setup_sparse && B.setup_epoch == h->layout_epoch))
+	if (!setup_done(h, B, r, true))
 	{ Scope sc(h, RB2_K_TSCAN, 0);
-	  // k_setup clears ctl->overflow: behind an in-place round whose verdict the host has not seen, it would wipe out a void round (sticky-void rule)
-	  if (h->spec_rounds > 0) { rb2_fatal("[rb2_hip] internal: k_setup of in-place round %llu queued behind %llu in-place rounds without their verdict\n", (unsigned long long)r, (unsigned long long)h->spec_rounds); }
+	  require_verdicts_seen(h, r, "k_setup of in-place round");
 	  hipLaunchKernelGGL(k_setup<true>, dim3(1), dim3(64), 0, st, h->ctl, sd, h->gcnt, (int)(r & 1), (uint32_t)r, hmax_report(h), (int)(h->push[0] != nullptr)); }
-	const bool lazy = spec && h->lazy_verdict && h->nranks == 1;   // no verdict read here: the caller polls (insert_dev)
-	if (!lazy) h->h_flag[0] = h->h_flag[1] = 0;                // the verdict words k_split writes
-	else if (h->spec_rounds > (uint64_t)h->run_ahead) {          // not too far ahead of the device: it reports the round whose splits it has reached (split_body -> h_flag[2] = round + 1)
-		const volatile uint32_t *prog = (const volatile uint32_t*)h->h_flag + 2;
-		const uint32_t want = (uint32_t)r - (uint32_t)h->run_ahead;   // round `want - 1` at least must be over
-		const auto t_spin = std::chrono::steady_clock::now();
-		for (uint32_t spins = 0; (int32_t)(*prog - want) < 0 && !((const volatile uint32_t*)h->h_flag)[0]; ++spins) {
-			if ((spins & 1023u) == 1023u) {
-				if (hipStreamQuery(st) == hipSuccess) break;         // (everything queued is done: nothing more will be reported)
-				if (std::chrono::steady_clock::now() - t_spin > std::chrono::seconds(2)) { HIPCHK(hipStreamSynchronize(st)); break; }   // (a report that does not come: wait the plain way)
-			}
-			__builtin_ia32_pause();
-		}
-	}
+	const bool lazy = lazy_round(h, spec);                     // no verdict read here: the caller polls (insert_dev)
+	if (!lazy) { h->mb_h->void_round = 0; h->mb_h->respread = 0; }   // the verdict words the splits write
+	else if (h->spec_rounds > (uint64_t)h->run_ahead) wait_progress(h, r);
 	const bool ride = h->dir_ride != 0;
 	with_pos(h, B, [&](const auto &S) { using P = std::remove_pointer_t<decltype(S.L)>;
 	launch_prep<true>(h, B, r, pv, S);
@@ -733,7 +761,7 @@ bool round_merge_sparse(rb2_hip_t *h, BatchState &B, uint64_t r, ShardRec *send 
 	const bool sp = spec && r + 1 <= B.max_len;
 	if (!sp)
 	{ Scope sc(h, RB2_K_SPLIT, 0);
-	  hipLaunchKernelGGL(k_split, dim3(256 + (ride ? 1 : 0)), dim3(256), 0, st, h->ctl, pv, (const uint32_t*)h->SPL.p, split_cap(h), h->split_epoch, (volatile uint32_t*)h->d_flag,
+	  hipLaunchKernelGGL(k_split, dim3(256 + (ride ? 1 : 0)), dim3(256), 0, st, h->ctl, pv, (const uint32_t*)h->SPL.p, split_cap(h), h->split_epoch, h->mb_d,
 	                     ride ? pv.sbbase : (SbBase*)nullptr, (uint32_t)r + 1u); }
 	// The verdict of the round (did every leaf fit?  did every split find a slot?) travels to pinned host memory behind the last
 	// kernel.  While it is on its way the host already queues the counting phase of round r + 1 -- it only writes per-round scratch,
@@ -743,19 +771,15 @@ bool round_merge_sparse(rb2_hip_t *h, BatchState &B, uint64_t r, ShardRec *send 
 	HIPCHK(hipGetLastError());
 	if (!sp && !lazy) HIPCHK(hipEventRecord(h->ev_flag, st));  // (k_split left the verdict in pinned memory)
 	h->side ^= 1; B.cur ^= 1;
-	if (sp) round_counts(h, B, r + 1, true, true, !lazy);      // (records the event behind its first launch)
+	if (sp) round_counts(h, B, r + 1, true);                   // (records the event behind its first launch)
 	if (lazy) {                                                // one engine: nobody waits; a void round makes every kernel queued behind it return (sticky: k_part_sparse)
 		B.counted = sp ? r + 1 : (uint64_t)-1;
 		++h->n_sparse_rounds; ++h->spec_rounds;
 		return true;
 	}
 	HIPCHK(hipEventSynchronize(h->ev_flag));
-	if (h->h_flag[0]) {                                         // void: nothing was changed; the flag comes down here, with nothing queued behind the round
-		h->side ^= 1; B.cur ^= 1; B.counted = (uint64_t)-1;
-		HIPCHK(hipMemsetAsync(&h->ctl->overflow, 0, 4, st));
-		return false;
-	}
-	if (h->h_flag[1]) h->want_respread = true;
+	if (const uint32_t v = h->mb_h->void_round) { take_back(h, B, v - 1, r + 1); return false; }   // void: nothing was changed, nothing is queued behind the round
+	if (h->mb_h->respread) h->want_respread = true;
 	B.counted = sp ? r + 1 : (uint64_t)-1;
 	++h->n_sparse_rounds;
 	return true;
@@ -767,8 +791,8 @@ uint32_t verdict_check(rb2_hip_t *h, bool drain)
 {
 	if (!h->spec_rounds) return 0;
 	if (drain) HIPCHK(hipStreamSynchronize(h->st));
-	const uint32_t v = ((volatile uint32_t*)h->h_flag)[0];
-	if (((volatile uint32_t*)h->h_flag)[1]) { h->want_respread = true; if (drain) h->h_flag[1] = 0; }
+	const uint32_t v = h->mb_h->void_round;
+	if (h->mb_h->respread) { h->want_respread = true; if (drain) h->mb_h->respread = 0; }
 	if (drain && !v) h->spec_rounds = 0;
 	if (!drain && !h->verdict_poll) return 0;                  // (RB2_VERDICT_POLL=0: a void round waits for the next drain)
 	return v;
@@ -924,19 +948,13 @@ void insert_dev(rb2_hip_t *h, int64_t len64, const uint8_t *s, bool lazy = false
 		if (rv) {
 			rv = verdict_check(h, true);                           // (final: everything queued has run -- or returned)
 			const uint64_t r_void = rv - 1;
-			if (r_void >= r || r - r_void > h->spec_rounds) { rb2_fatal("[rb2_hip] internal: void round %llu reported while queueing round %llu (%llu in flight)\n", (unsigned long long)r_void, (unsigned long long)r, (unsigned long long)h->spec_rounds); }
-			const int64_t depth = (int64_t)(r - r_void);
-			if (depth & 1) { h->side ^= 1; B.cur ^= 1; }            // every in-place round queued from r_void on flipped the descriptor and array sides once
+			const int64_t depth = take_back(h, B, r_void, r);
 			h->n_sparse_rounds -= depth;
 			++h->n_rewind; h->n_rewound += depth; h->rewind_max = std::max(h->rewind_max, depth); if (!(depth & 1)) ++h->n_rewind_even;
-			h->spec_rounds = 0; h->h_flag[0] = 0;
-			h->h_flag[2] = (uint32_t)r_void;                       // (the progress word: the rounds behind the void one reported themselves done; the run-ahead limit reads it)
-			HIPCHK(hipMemsetAsync(&h->ctl->overflow, 0, 4, h->st));
-			B.counted = (uint64_t)-1; B.setup_round = (uint64_t)-1;
 			// the "every interval is empty from here on" snapshots of the void round and of the rounds behind it are not what those rounds leave
 			// when they really run (the void round's k_advance never set the flag): forget them, and what the host concluded from them
 			B.known_ae = B.known_ae0;
-			for (int q = 0; q < 2 * rb2_hip_s::NE_RING; ++q) h->h_flag[16 + q] = 0xffffffffu;
+			memset((void*)h->mb_h->ne, 0xff, sizeof(h->mb_h->ne));
 			r = r_void;
 			void_to_dense(h, B, r);
 			round_counts(h, B, r);
@@ -1006,9 +1024,9 @@ rb2_hip_t *rb2_hip_create(int device, int sorting_order)
 	HIPCHK(hipMalloc((void**)&h->ctl, sizeof(Ctl)));
 	HIPCHK(hipMalloc((void**)&h->d_tmp, 256));
 	HIPCHK(hipMalloc((void**)&h->gcnt, GCN * 8));
-	HIPCHK(hipHostMalloc((void**)&h->h_flag, 64 + 8 * rb2_hip_s::NE_RING, hipHostMallocDefault));
-	memset(h->h_flag, 0, 64 + 8 * rb2_hip_s::NE_RING);
-	HIPCHK(hipHostGetDevicePointer((void**)&h->d_flag, h->h_flag, 0));
+	HIPCHK(hipHostMalloc((void**)&h->mb_h, sizeof(Mailbox), hipHostMallocDefault));
+	memset(h->mb_h, 0, sizeof(Mailbox));
+	HIPCHK(hipHostGetDevicePointer((void**)&h->mb_d, h->mb_h, 0));
 	HIPCHK(hipEventCreateWithFlags(&h->ev_flag, hipEventDisableTiming));
 	if (getenv("RB2_DIR_RIDE")) h->dir_ride = atoi(getenv("RB2_DIR_RIDE"));
 	if (getenv("RB2_TS_BLOCKS")) h->ts_blocks = atoi(getenv("RB2_TS_BLOCKS"));
@@ -1035,7 +1053,7 @@ void rb2_hip_destroy(rb2_hip_t *h)
 	if (h->st_copy) HIPCHK(hipStreamDestroy(h->st_copy));
 	h->trec.release(); h->tsc.release(); h->tfix.release(); h->cpart.release(); h->sbtot.release();
 	for (auto e : h->evpool) hipEventDestroy(e);
-	HIPCHK(hipHostFree(h->h_flag)); HIPCHK(hipEventDestroy(h->ev_flag));
+	HIPCHK(hipHostFree(h->mb_h)); HIPCHK(hipEventDestroy(h->ev_flag));
 
 	if (h->pair_d) { HIPCHK(hipFree(h->pair_d)); HIPCHK(hipHostFree(h->pair_h)); }
 	HIPCHK(hipFree(h->ctl)); HIPCHK(hipFree(h->d_tmp)); HIPCHK(hipFree(h->gcnt)); h->xstage.release(); h->xnb.release(); h->xpack.release(); h->xoff.release();

@@ -50,9 +50,9 @@ __device__ __forceinline__ void load64(const uint8_t *s, uint64_t len, uint64_t 
 	}
 }
 
-// also validates the input: *bad_flag is set when a byte is not an nt6 code 0..5 (the reference indexes arrays with
+// also validates the input: *bad_out is set when a byte is not an nt6 code 0..5 (the reference indexes arrays with
 // these bytes unchecked, mrope.c:204; here a stray value would corrupt the bucket bookkeeping silently)
-__global__ __launch_bounds__(256) void k_count_zeros(const uint8_t *s, uint64_t len, uint64_t *blk, uint64_t *bad_flag)
+__global__ __launch_bounds__(256) void k_count_zeros(const uint8_t *s, uint64_t len, uint64_t *blk, uint64_t *bad_out)
 {
 	__shared__ uint32_t s_w[4];
 	uint32_t w[16], c = 0, bad = 0;
@@ -67,7 +67,7 @@ __global__ __launch_bounds__(256) void k_count_zeros(const uint8_t *s, uint64_t 
 	uint32_t tot;
 	block_excl_add<uint32_t>(c, s_w, &tot);
 	if (threadIdx.x == 0) blk[blockIdx.x] = tot;
-	if (bad) *bad_flag = 1;
+	if (bad) *bad_out = 1;
 }
 
 // What a batch adds to the count matrix, known before a single round has run: symbol t[i] of the batch text goes into the rope of
@@ -279,12 +279,12 @@ __device__ __forceinline__ bool tile_ctx(const SegDesc &sg, uint32_t tile, TileC
 // SPLIT: the launch that follows an in-place round on one GPU also does that round's leaf splits (k_split), in nsplitb blocks of its own
 // in front of the tile blocks: k_sym reads string arrays only, the splits touch the pool only -- one launch instead of two, the two running
 // side by side; the verdict of the round reaches the host behind this launch.
-struct SplitArgs { Ctl *ctl; PoolView pool; const uint32_t *SPL; uint32_t spl_cap, epoch; volatile uint32_t *hv; uint32_t nsplitb;
-	uint32_t round1;    // the in-place round whose splits these are, + 1: reported to the host (hv[2]) -- it queues in-place rounds without waiting for them, but only a few ahead
+struct SplitArgs { Ctl *ctl; PoolView pool; const uint32_t *SPL; uint32_t spl_cap, epoch; Mailbox *mb; uint32_t nsplitb;
+	uint32_t round1;    // the in-place round whose splits these are, + 1: reported to the host (Mailbox::progress) -- it queues in-place rounds without waiting for them, but only a few ahead
 	SbBase *scan2; };   // scan2 != null: one more block, behind the split blocks, turns the chunk totals k_advance's scan blocks left into chunk bases (sbscan2_body; "the directory rides along", below)
 template <int NT, int CT> __device__ __forceinline__ void sbscan2_lean(const Ctl *ctl, SbBase *base, uint64_t *s_w /* NT / 64 words */);
 template <int NT, int CT> __device__ __forceinline__ void sbscan2_col(const Ctl *ctl, SbBase *base, uint64_t *s_w, const int col);
-__device__ __forceinline__ void split_body(Ctl *ctl, const PoolView &pool, const uint32_t *SPL, uint32_t spl_cap, uint32_t epoch, volatile uint32_t *hv,
+__device__ __forceinline__ void split_body(Ctl *ctl, const PoolView &pool, const uint32_t *SPL, uint32_t spl_cap, uint32_t epoch, Mailbox *mb,
 		const uint32_t bidx, const uint32_t nblk, uint16_t (*s_row)[7][SB], uint32_t round1);
 // Fused k_prep: in a round whose intervals are all empty (ctl->ne[par] == 0) a tile in which every string is a group of its own -- the
 // rule from round ~14 of a batch on -- needs nothing from the tile scans to place its new symbols: slot = the string's index in its
@@ -302,7 +302,7 @@ template <bool STRIDE, typename P = uint64_t, bool SPLIT = false> __global__ __l
 		__shared__ uint16_t s_row[MW][7][SB];
 		// the FIRST blocks of the grid: the splits' registers (99 VGPRs) cap the launch at five workgroups per CU, the tile blocks take two
 		// turns -- behind them the split blocks started when the first turn was over (16.9 us for the launch; 6.2 + 9.3 apart)
-		if (blockIdx.x < sp.nsplitb) { split_body(sp.ctl, sp.pool, sp.SPL, sp.spl_cap, sp.epoch, sp.hv, blockIdx.x, sp.nsplitb, s_row, sp.round1); return; }
+		if (blockIdx.x < sp.nsplitb) { split_body(sp.ctl, sp.pool, sp.SPL, sp.spl_cap, sp.epoch, sp.mb, blockIdx.x, sp.nsplitb, s_row, sp.round1); return; }
 		if (sp.scan2 && blockIdx.x == sp.nsplitb) { __shared__ uint64_t s_w2[4]; sbscan2_lean<256, 2>(ctl, sp.scan2, s_w2); return; }
 	}
 	const bool ae = ctl->ne[par] == 0;
@@ -569,7 +569,7 @@ __global__ __launch_bounds__(256) void k_tfix(Ctl *ctl, int side, int par, const
 // over ranks when sub-ropes are sharded).  One wave, lane r = sub-rope r; the running sums of the
 // sequential formulation (mrope.c:332-340) are wave scans.
 // SPARSE: the round inserts in place -- every piece keeps its slots (leaf0, nleaves, sb0), only n and the counts move.
-// hmax (pinned host memory, may be null): the round and the size of the largest piece after it -- what the host needs to know
+// hmax (Mailbox::hmax in pinned host memory, may be null): the round and the size of the largest piece after it -- what the host needs to know
 // to keep the per-string positions in 32-bit storage for as long as they fit (rb2_device.h "P"; one 8-byte store, no copy command)
 // keep_ne: the next round's "some interval is non-empty" flag is not cleared here (PEER transport of a sharded index: the other ranks'
 // k_advance set it, and they may run ahead of this rank's k_mround; the host clears it before the round's counting phase instead)
@@ -1453,20 +1453,20 @@ __global__ __launch_bounds__(256) void k_relayout(const Ctl *ctl, int side, Pool
 // rows (fills + own counts) are rewritten to match.  The superblock's total does not change: sbcum / sbpos stay valid.
 // A marked leaf in a superblock without a free slot sets ctl->sbfull: the host re-spreads the index before the next round.
 // ---------------------------------------------------------------------------------------------
-// The verdict of the round -- hv[0]: void round, hv[1]: a superblock ran out of slots -- goes straight into pinned host memory (the host
-// zeroes both words before it queues the round): no copy command behind the last kernel.
+// The verdict of the round -- Mailbox::void_round, Mailbox::respread: a superblock ran out of slots -- goes straight into pinned host memory
+// (the host zeroes both words before it queues the round, or after it took a void round back): no copy command behind the last kernel.
 // (the body: k_split proper, and the last blocks of the k_sym launch that follows an in-place round -- k_sym<.., SPLIT> -- run it: bidx of nblk)
-__device__ __forceinline__ void split_body(Ctl *ctl, const PoolView &pool, const uint32_t *SPL, uint32_t spl_cap, uint32_t epoch /* != 0, never repeats */, volatile uint32_t *hv,
+__device__ __forceinline__ void split_body(Ctl *ctl, const PoolView &pool, const uint32_t *SPL, uint32_t spl_cap, uint32_t epoch /* != 0, never repeats */, Mailbox *mb,
 		const uint32_t bidx, const uint32_t nblk, uint16_t (*s_row)[7][SB], uint32_t round1)
 {
 	const uint32_t tid = threadIdx.x & 255u;                    // (a 1024-thread block of k_tscan_setup is four of these "blocks": bidx says which)
-	if (bidx == 0 && tid == 0) hv[2] = round1;                  // how far the device has come (the host stays a few rounds ahead of this: insert_dev)
-	if (ctl->overflow) { if (bidx == 0 && tid == 0) hv[0] = ctl->overflow; return; }   // void round (this one or one in front of it): nothing was inserted; the host learns which
+	if (bidx == 0 && tid == 0) mb->progress = round1;           // how far the device has come (the host stays a few rounds ahead of this: wait_progress)
+	if (ctl->overflow) { if (bidx == 0 && tid == 0) mb->void_round = ctl->overflow; return; }   // void round (this one or one in front of it): nothing was inserted; the host learns which
 	const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
 	const int ln = lane_id();
 	const uint32_t nsp_raw = ctl->nsplit2[(round1 - 1u) & 1u];  // (the counter of the round whose splits these are)
 	const uint32_t nsp_all = min(nsp_raw, spl_cap);
-	if (nsp_raw > spl_cap && bidx == 0 && tid == 0) { ctl->sbfull = 1; hv[1] = 1; }   // list overflow (never in practice): re-spread
+	if (nsp_raw > spl_cap && bidx == 0 && tid == 0) { ctl->sbfull = 1; mb->respread = 1; }   // list overflow (never in practice): re-spread
 	for (uint32_t e = bidx * MW + wv; e < nsp_all; e += nblk * MW) {
 		const uint64_t gl = SPL[e], sb = gl / SB;
 		uint32_t mine = 0;
@@ -1480,7 +1480,7 @@ __device__ __forceinline__ void split_body(Ctl *ctl, const PoolView &pool, const
 		if (marked == 0) continue;
 		const uint32_t room = SB - used;
 		if ((uint32_t)__popc(marked) > room) {
-			if (ln == 0) { ctl->sbfull = 1; hv[1] = 1; }
+			if (ln == 0) { ctl->sbfull = 1; mb->respread = 1; }
 			while ((uint32_t)__popc(marked) > room) marked &= ~(1u << (31 - __builtin_clz(marked)));   // split the lowest ones that fit
 			if (marked == 0) continue;
 		}
@@ -1549,12 +1549,12 @@ __device__ __forceinline__ void split_body(Ctl *ctl, const PoolView &pool, const
 		__builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront"); __builtin_amdgcn_wave_barrier();   // R is reused by the wave's next entry
 	}
 }
-__global__ __launch_bounds__(256) void k_split(Ctl *ctl, PoolView pool, const uint32_t *SPL, uint32_t spl_cap, uint32_t epoch, volatile uint32_t *hv, SbBase *scan2, uint32_t round1)
+__global__ __launch_bounds__(256) void k_split(Ctl *ctl, PoolView pool, const uint32_t *SPL, uint32_t spl_cap, uint32_t epoch, Mailbox *mb, SbBase *scan2, uint32_t round1)
 {
 	__shared__ uint16_t s_row[MW][7][SB];
 	const uint32_t nb = gridDim.x - (scan2 ? 1u : 0u);         // (the last block: the chunk bases of the directory, see SplitArgs::scan2)
 	if (scan2 && blockIdx.x == nb) { __shared__ uint64_t s_w2[4]; sbscan2_lean<256, 2>(ctl, scan2, s_w2); return; }
-	split_body(ctl, pool, SPL, spl_cap, epoch, hv, blockIdx.x, nb, s_row, round1);
+	split_body(ctl, pool, SPL, spl_cap, epoch, mb, blockIdx.x, nb, s_row, round1);
 }
 
 } // namespace rb2

@@ -323,13 +323,13 @@ void multi_rank_batch(rb2_hip_multi_t *m, int k, int64_t len)
 	memset(&rows, 0, sizeof(rows)); memset(sends, 0, sizeof(sends));
 	if (peer) for (int p = 0; p < m->n; ++p) { rows.p[p] = m->rk[p].gloc; sends[0].p[p] = m->rk[p].send[0]; sends[1].p[p] = m->rk[p].send[1]; }
 	const unsigned grid_m = cdiv(rank_share(h, B.m), 256);
-	((volatile unsigned long long*)(h->h_flag + 8))[0] = ~0ull;   // nothing reported yet
+	h->mb_h->hne = ~0ull;                                       // nothing reported yet
 	for (uint64_t r = 0; r <= B.max_len; ++r) {                 // one round per string position (mrope.c:299-342)
 		// Once NO rank holds a string with a non-empty interval none ever will again: k_mround reports the sum of the ranks' flags of
 		// every round to pinned memory; a report that has landed and reads zero lets this rank launch only the all-empty variants of
 		// k_prep / k_advance from here on (before: both variants every round of every batch on a loaded index, one returning at once)
 		if (!B.known_ae) {
-			const unsigned long long v = ((volatile unsigned long long*)(h->h_flag + 8))[0];
+			const unsigned long long v = h->mb_h->hne;
 			if (v != ~0ull && (v & 1ull) == 0 && (v >> 32) < r) B.known_ae = true;
 		}
 		h->gcnt = R.gloc;
@@ -349,11 +349,10 @@ void multi_rank_batch(rb2_hip_multi_t *m, int k, int64_t len)
 		}
 		// sum of the count rows (PEER) + exchange plan + k_setup of the round: one launch (k_mround)
 		{
-			volatile unsigned long long *hmax = hmax_report(h);
-			volatile unsigned long long *hne = (volatile unsigned long long*)(h->d_flag + 8);   // (round, any non-empty interval on any rank) as k_mround last saw it
+			volatile unsigned long long *hmax = hmax_report(h), *hne = &h->mb_d->hne;
 			if (h->sparse) hipLaunchKernelGGL(k_mround<true>, dim3(1), dim3(256), 0, st, h->ctl, rows, peer ? m->n : 0, h->gcnt, ow, R.grank, (int)peer, sends[r & 1], (const ShardRec*)R.recv, R.tab, h->side, (int)(r & 1), (uint32_t)r, hmax, hne);
 			else hipLaunchKernelGGL(k_mround<false>, dim3(1), dim3(256), 0, st, h->ctl, rows, peer ? m->n : 0, h->gcnt, ow, R.grank, (int)peer, sends[r & 1], (const ShardRec*)R.recv, R.tab, h->side, (int)(r & 1), (uint32_t)r, hmax, hne);
-			B.setup_round = r; B.setup_sparse = h->sparse; B.setup_epoch = h->layout_epoch;
+			mark_setup(h, B, r);
 		}
 		// dense round: the slice is rewritten pool -> pool; in-place round: only the touched leaves, and the host reads a one-word
 		// verdict before the exchange may go ahead (a void round is redone densely: its records do not exist yet)

@@ -26,7 +26,7 @@ import helpers as H
 pytestmark = pytest.mark.gpu
 
 FORCED = dict(RB2_SPARSE_LAMBDA="1e18", RB2_SPARSE_MAXPEN="0")
-NE_RING = 32                                    # rb2_engine.hip rb2_hip_s::NE_RING
+NE_RING = 32                                    # rb2_device.h NE_RING
 
 
 class Env:
