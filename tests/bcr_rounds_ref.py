@@ -75,7 +75,8 @@ class Round:
     x_behind       exceptions of the second old window behind the stage (its groups > g0), counted when `two`
 
     and of the whole array: isnew (one flag per symbol: new this round), start / old_start (first row of every piece after / before the
-    round, NR + 1 entries), old (the array as it was; the model's .bwt is the array as it is)
+    round, NR + 1 entries), old (the array as it was; the model's .bwt is the array as it is), ins (NR entries: the inserts every
+    piece takes this round)
     """
 
     def __init__(self, batch, r, compact, last, **kw):
@@ -220,7 +221,7 @@ class RoundsModel:
         self.xt = np.split(xt, cut)
         rd = Round(self.nbatch, r, compact, last, piece=piece, j=j, nvalid=nvalid, xt=xt, fmt=fmt, ni=ni, new_x=new_x, x_ends=x_ends, i0=i0, g0=g0, sh0=sh0,
                    nwg=nwg, two=two, h0=h0, h1=h1, len0=len0, len1=len1, x_front=x_front, x_tail=x_tail, x_behind=x_behind,
-                   isnew=isnew, start=new_p0, old_start=old_p0, old=old)
+                   isnew=isnew, start=new_p0, old_start=old_p0, old=old, ins=new_sz - old_sz)
         return rd, nxt
 
 
