@@ -161,6 +161,24 @@ void rb2_hip_extend(rb2_hip_t *h, int64_t n, const int64_t *ik, int is_back, int
  * -1 when it is longer than max_len, -2 for a row outside the $ block.  In input order (RB2_SO_IO) row k is the k-th string inserted.
  * Returns the number of rows whose string fitted. */
 int64_t rb2_hip_extract(rb2_hip_t *h, int64_t n, const int64_t *rows, int64_t max_len, uint8_t *out, int64_t *len);
+/* super-maximal exact matches (SMEMs) of n queries against an index that holds both strands of every string (the caller's responsibility,
+ * as for rb2_hip_extend; on any other index the results are unspecified, but the call returns and stays in bounds).  Queries are nt6 codes
+ * in text order, concatenated in qry[off[i] .. off[i+1]): 1..4 can be matched, 5 (N) is legal but belongs to no match, 0 or a code above 5
+ * makes the query malformed.  With occ(s,e) = occurrences of q[s:e) and e(s) = the largest e with occ(s,e) >= min_occ (s if none),
+ * [s, e(s)) is an SMEM when e(s) > s, s == 0 or e(s-1) < e(s), and e(s) - s >= min_len: a match with at least min_occ occurrences that
+ * cannot be extended on either side and lies inside no other such match.  They are reported in increasing s (their ends increase too).
+ * mem[(i*max_mems + k)*5 ..] = start, end, x0, x1, size of the k-th SMEM of query i, (x0, x1, size) its bi-interval in the coordinates of
+ * rb2_hip_extend: x0 = lo of backward_search(q[start:end)), x1 = lo of its reverse complement, size = hi - lo.  cnt[i] = SMEMs found,
+ * which may exceed max_mems (the surplus is counted, not stored), or -1 for a malformed query.  Only the first min(cnt[i], max_mems)
+ * records of a query are meaningful: the host variant returns the others as zeros, the device variant leaves them untouched.
+ * min_len, min_occ and max_mems below 1 are fatal.  Returns the number of records stored (sum of min(cnt[i], max_mems), malformed queries
+ * counting 0).  The host variant lowers its chunk further so that the records staged for one chunk (chunk * max_mems * 40 bytes) stay
+ * under 256 MiB, one query at the least: it never allocates n * max_mems records on the device at once.  Kernel: k_smem. */
+int64_t rb2_hip_smem(rb2_hip_t *h, int64_t n, const uint8_t *qry, const int64_t *off, int64_t min_len, int64_t min_occ, int64_t max_mems,
+                     int64_t *mem, int64_t *cnt);
+/* the same with qry, off, mem and cnt in this device's memory, asynchronous on the handle's stream (no return value: read cnt) */
+void rb2_hip_smem_dev(rb2_hip_t *h, int64_t n, const uint8_t *qry, const int64_t *off, int64_t min_len, int64_t min_occ, int64_t max_mems,
+                      int64_t *mem, int64_t *cnt);
 
 /* 64-bit checksum of rope b computed on the device (position-weighted sum over the packed words of its pieces): equal for
  * equal symbol sequences however the index was built (one engine, N ranks, an .fmr loaded back), sensitive to order.  Lets

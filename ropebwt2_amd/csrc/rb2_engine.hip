@@ -1576,6 +1576,58 @@ int64_t rb2_hip_extract(rb2_hip_t *h, int64_t n, const int64_t *rows, int64_t ma
 	return fit;
 }
 
+static void launch_smem(rb2_hip_t *h, int64_t n, const uint8_t *qry, const int64_t *off, int64_t base, int64_t min_len, int64_t min_occ, int64_t max_mems,
+                        int64_t *mem, int64_t *cnt)
+{
+	const PoolView pv = h->pool[h->pside].view();
+	if (h->sparse) hipLaunchKernelGGL(k_smem<true>, dim3(cdiv((uint64_t)n, QPB)), dim3(256), 0, h->st, (const QTab*)h->qtab.p, pv, qry, off, base, (uint64_t)n, min_len, min_occ, max_mems, mem, cnt);
+	else hipLaunchKernelGGL(k_smem<false>, dim3(cdiv((uint64_t)n, QPB)), dim3(256), 0, h->st, (const QTab*)h->qtab.p, pv, qry, off, base, (uint64_t)n, min_len, min_occ, max_mems, mem, cnt);
+	HIPCHK(hipGetLastError());
+}
+
+static void smem_check(const char *who, int64_t min_len, int64_t min_occ, int64_t max_mems)
+{
+	if (min_len < 1 || min_occ < 1 || max_mems < 1)
+		rb2_fatal("[rb2_hip] %s: min_len, min_occ and max_mems must be at least 1 (got %lld, %lld, %lld)\n", who, (long long)min_len, (long long)min_occ, (long long)max_mems);
+}
+
+/* staged records of one chunk of rb2_hip_smem: the chunk shrinks until chunk * max_mems * 40 bytes fit (one query when a single one does not) */
+static const int64_t SMEM_STAGE_BYTES = (int64_t)256 << 20;
+
+int64_t rb2_hip_smem(rb2_hip_t *h, int64_t n, const uint8_t *qry, const int64_t *off, int64_t min_len, int64_t min_occ, int64_t max_mems, int64_t *mem, int64_t *cnt)
+{
+	query_begin(h, "smem");
+	if (n <= 0) return 0;
+	smem_check("smem", min_len, min_occ, max_mems);
+	for (int64_t i = 0; i < n; ++i)
+		if (off[i + 1] < off[i] || off[0] < 0) { rb2_fatal("[rb2_hip] smem: query offsets must be non-negative and non-decreasing (off[%lld])\n", (long long)i); }
+	const int64_t CH = std::max<int64_t>(1, std::min<int64_t>(query_chunk(h), SMEM_STAGE_BYTES / 40 / max_mems));
+	int64_t stored = 0;
+	for (int64_t i0 = 0; i0 < n; i0 += CH) {
+		const int64_t nc = std::min(CH, n - i0), b0 = off[i0], nb = off[i0 + nc] - b0;
+		h->qin.ensure((size_t)nc * 2 + 1); h->qout.ensure((size_t)(nc * max_mems) * 5); h->qbytes.ensure((size_t)std::max<int64_t>(nb, 1));
+		int64_t *d_off = h->qin.p, *d_cnt = h->qin.p + nc + 1;
+		HIPCHK(hipMemcpyAsync(d_off, off + i0, (size_t)(nc + 1) * 8, hipMemcpyHostToDevice, h->st));
+		if (nb) HIPCHK(hipMemcpyAsync(h->qbytes.p, qry + b0, (size_t)nb, hipMemcpyHostToDevice, h->st));
+		HIPCHK(hipMemsetAsync(h->qout.p, 0, (size_t)(nc * max_mems) * 40, h->st));   // the records no query writes come back as zeros
+		launch_smem(h, nc, h->qbytes.p, d_off, b0, min_len, min_occ, max_mems, h->qout.p, d_cnt);
+		HIPCHK(hipMemcpyAsync(cnt + i0, d_cnt, (size_t)nc * 8, hipMemcpyDeviceToHost, h->st));
+		HIPCHK(hipMemcpyAsync(mem + i0 * max_mems * 5, h->qout.p, (size_t)(nc * max_mems) * 40, hipMemcpyDeviceToHost, h->st));
+		HIPCHK(hipStreamSynchronize(h->st));
+		for (int64_t i = i0; i < i0 + nc; ++i) stored += std::min(std::max<int64_t>(cnt[i], 0), max_mems);
+	}
+	return stored;
+}
+
+void rb2_hip_smem_dev(rb2_hip_t *h, int64_t n, const uint8_t *qry, const int64_t *off, int64_t min_len, int64_t min_occ, int64_t max_mems, int64_t *mem, int64_t *cnt)
+{
+	query_begin(h, "smem_dev");
+	if (n <= 0) return;
+	smem_check("smem_dev", min_len, min_occ, max_mems);
+	const int64_t CH = query_chunk(h);
+	for (int64_t i0 = 0; i0 < n; i0 += CH) launch_smem(h, std::min(CH, n - i0), qry, off + i0, 0, min_len, min_occ, max_mems, mem + i0 * max_mems * 5, cnt + i0);
+}
+
 /* checksum of sub-rope r (k_piece_hash); the handle must hold the piece in the dense layout */
 static uint64_t piece_hash(rb2_hip_t *h, int r)
 {

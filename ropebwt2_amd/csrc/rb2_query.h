@@ -201,4 +201,70 @@ template <bool SPARSE> __global__ __launch_bounds__(256) void k_extract(const QT
 	if (g == 0) len[i] = k;
 }
 
+// super-maximal exact matches of n queries qry[off[i] - base, off[i+1] - base) (codes 1..4 match, 5 belongs to no match, anything else
+// makes the query malformed) against an index that holds both strands: records (start, end, x0, x1, size) in increasing start into
+// mem[(i * max_mems + k) * 5 ..) for k < max_mems, cnt[i] = SMEMs found (the surplus is counted, not stored), -1 for a malformed query.
+//
+// If the previous SMEM ended at p, the next one is the match with the smallest start among those that cover position p: from the
+// bi-interval of q[p] extend backward while size >= min_occ (that gives its start s), then forward from p + 1 (that gives e(s)), and go
+// on from p = e(s).  A start between the previous one and s cannot begin an SMEM: it would cover p with a smaller start.  A position
+// whose symbol alone has fewer than min_occ occurrences is skipped.  p grows by at least 1 per turn, so the loop ends whatever the index
+// holds; steps <= sum of the SMEM lengths + L.  The state is one bi-interval as (xf, xo, sz): xf = the end the next step ranks (x0 going
+// backward, x1 going forward), so turning round is a swap and both directions share one step, the arithmetic of k_extend for one symbol.
+// Left alone the compiler takes 108-114 VGPRs (4 waves per SIMD) to overlap the two ranks of a step; held to 5 waves it needs 90-93 and
+// still no scratch (6 waves would spill).
+template <bool SPARSE> __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(5, 5))) void k_smem(const QTab *Tg, PoolView pv, const uint8_t *qry, const int64_t *off, int64_t base,
+                                                                     uint64_t n, int64_t min_len, int64_t min_occ, int64_t max_mems, int64_t *mem, int64_t *cnt)
+{
+	__shared__ QTab T;
+	qtab_load(Tg, T);
+	const uint64_t i = (uint64_t)blockIdx.x * QPB + (threadIdx.x >> 4);
+	if (i >= n) return;
+	const uint32_t g = (uint32_t)lane_id() & 15u;
+	const int64_t s0 = off[i] - base, L = off[i + 1] - base - s0, N = (int64_t)T.row0[NR];
+	const uint8_t *q = qry + s0;
+	bool bad = L < 0 || s0 < 0;
+	for (int64_t j = 0; !bad && j < L; ++j) { const uint8_t c = q[j]; bad = c == 0 || c > 5; }
+	if (bad) { if (g == 0) cnt[i] = -1; return; }
+	int64_t k = 0, p = 0;
+	while (p < L) {
+		const int c0 = q[p];
+		int64_t xf = (int64_t)qC(T, c0 < 5 ? c0 : 0), xo = (int64_t)qC(T, c0 < 5 ? 5 - c0 : 0), sz = c0 < 5 ? (int64_t)qC(T, c0 + 1) - xf : 0;
+		if (sz < min_occ) { ++p; continue; }                       // N, or a symbol with too few occurrences: no match covers p
+		int64_t s = p, e = p + 1;
+		bool back = true;
+		for (;;) {
+			const int64_t j = back ? s - 1 : e;
+			const int c = j >= 0 && j < L ? q[j] : 0;
+			bool stop = c < 1 || c > 4;
+			if (!stop) {
+				const int a = back ? c : 5 - c;                    // a forward extension by c is the extension of the other strand by its complement
+				uint64_t tk[6], tl[6];
+				qrank<SPARSE>(T, pv, (uint64_t)min(max(xf, (int64_t)0), N), tk);
+				qrank<SPARSE>(T, pv, (uint64_t)min(max(xf + sz, (int64_t)0), N), tl);
+				const int64_t nsz = (int64_t)(tl[a] - tk[a]);
+				if (nsz < min_occ) stop = true;
+				else {
+					xo += (int64_t)(tl[0] - tk[0]);                // the other end in the complement order $ T G C A N
+#pragma unroll
+					for (int b = 4; b >= 2; --b) if (b > a) xo += (int64_t)(tl[b] - tk[b]);
+					xf = (int64_t)(qC(T, a) + tk[a]); sz = nsz;
+					if (back) --s; else ++e;
+				}
+			}
+			if (stop) {
+				if (!back) break;
+				back = false;
+				const int64_t t = xf; xf = xo; xo = t;
+			}
+		}
+		if (e - s >= min_len) {
+			if (k < max_mems && g < 5) mem[(i * (uint64_t)max_mems + (uint64_t)k) * 5 + g] = g == 0 ? s : g == 1 ? e : g == 2 ? xo : g == 3 ? xf : sz;   // five lanes, one 40-byte record
+			++k;
+		}
+		p = e;
+	}
+	if (g == 0) cnt[i] = k;
+}
+
 } // namespace rb2

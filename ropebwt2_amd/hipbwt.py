@@ -50,6 +50,8 @@ def load_hip_lib():
         "rb2_hip_backward_search_dev": (None, [vp, i64, vp, vp, vp]),
         "rb2_hip_extend": (None, [vp, i64, vp, i32, vp]),
         "rb2_hip_extract": (i64, [vp, i64, vp, i64, vp, vp]),
+        "rb2_hip_smem": (i64, [vp, i64, vp, vp, i64, i64, i64, vp, vp]),
+        "rb2_hip_smem_dev": (None, [vp, i64, vp, vp, i64, i64, i64, vp, vp]),
         "rb2_hip_reserve": (None, [vp, i64, i64, i64]),
         "rb2_hip_num_subropes": (i32, []),
         "rb2_hip_memcpy": (None, [vp, vp, vp, i64, i32]),
@@ -113,7 +115,7 @@ ABI_SYMBOLS = [
     "rb2_hip_device_count", "rb2_hip_set_fatal_handler", "rb2_hip_create", "rb2_hip_destroy", "rb2_hip_sorting_order", "rb2_hip_reset",
     "rb2_hip_insert_multi", "rb2_hip_insert_multi_dev", "rb2_hip_set_lazy", "rb2_hip_wait", "rb2_hip_last_batch_counts", "rb2_hip_prefetch", "rb2_hip_mem_info", "rb2_hip_get_counts", "rb2_hip_rope_bytes",
     "rb2_hip_download_rope", "rb2_hip_stream_rope", "rb2_hip_load_ropes", "rb2_hip_rank1a", "rb2_hip_rank_batch", "rb2_hip_reserve",
-    "rb2_hip_backward_search", "rb2_hip_backward_search_dev", "rb2_hip_extend", "rb2_hip_extract", "rb2_hip_dev_alloc",
+    "rb2_hip_backward_search", "rb2_hip_backward_search_dev", "rb2_hip_extend", "rb2_hip_extract", "rb2_hip_smem", "rb2_hip_smem_dev", "rb2_hip_dev_alloc",
     "rb2_hip_num_subropes", "rb2_hip_memcpy", "rb2_hip_use_stream",
     "rb2_hip_dev_free", "rb2_hip_synth_reads", "rb2_hip_synth_reads_cov", "rb2_hip_synth_reads_skew", "rb2_hip_sync", "rb2_hip_sparse_stats", "rb2_hip_layout_stats", "rb2_hip_rewind_stats", "rb2_hip_window_stats", "rb2_hip_host_register", "rb2_hip_host_unregister", "rb2_hip_profile",
     "rb2_hip_profile_get", "rb2_hip_kernel_name", "rb2_hip_layout",
@@ -326,6 +328,29 @@ class HipBwt:
         ln = np.zeros(len(rows), np.int64)
         fit = self.L.rb2_hip_extract(self.h, len(rows), rows.ctypes.data, max_len, out.ctypes.data, ln.ctypes.data) if len(rows) else 0
         return int(fit), out, ln
+
+    def smem_raw(self, queries, min_len=1, min_occ=1, max_mems=64):
+        """rb2_hip_smem as it is: (records stored, mem (n, max_mems, 5) int64 = start, end, x0, x1, size, cnt (n,) int64); only the
+        first min(cnt[i], max_mems) records of query i are meaningful (the others are zeros), cnt[i] = -1 for a malformed query"""
+        qry, off = pack_patterns(queries)
+        n = len(off) - 1
+        mem = np.zeros((n, max(int(max_mems), 0), 5), np.int64)
+        cnt = np.zeros(n, np.int64)
+        stored = self.L.rb2_hip_smem(self.h, n, qry.ctypes.data, off.ctypes.data, min_len, min_occ, max_mems, mem.ctypes.data, cnt.ctypes.data) if n else 0
+        return int(stored), mem, cnt
+
+    def smem(self, queries, min_len=1, min_occ=1, max_mems=64):
+        """super-maximal exact matches of every query (str / bytes over ACGTN, or nt6 arrays) against an index that holds both strands:
+        a list with one (k, 5) int64 array per query, rows = start, end, x0, x1, size in increasing start, k = min(cnt, max_mems), and
+        cnt (n,) = the SMEMs found per query; a malformed query ('$' or a code above 5 inside) raises ValueError"""
+        stored, mem, cnt = self.smem_raw(queries, min_len, min_occ, max_mems)
+        if (cnt < 0).any():
+            raise ValueError("malformed queries (only the codes 1..5 are allowed): %s" % np.flatnonzero(cnt < 0)[:5].tolist())
+        return [mem[i, :min(int(cnt[i]), max_mems)].copy() for i in range(len(cnt))], cnt
+
+    def smem_dev(self, n, qry_dev, off_dev, mem_dev, cnt_dev, min_len=1, min_occ=1, max_mems=64):
+        """rb2_hip_smem_dev: all four pointers in this device's memory; asynchronous on the handle's stream"""
+        self.L.rb2_hip_smem_dev(self.h, n, qry_dev, off_dev, min_len, min_occ, max_mems, mem_dev, cnt_dev)
 
     # -- measurement helpers ----------------------------------------------------------------
     def dev_alloc(self, nbytes):

@@ -5,11 +5,15 @@ tests/test_hip_parity.py::test_full_batch_properties), then times, after a warm-
   - backward_search_dev on P patterns of length 20, 32 and 64: substrings of the reads (hits) and uniform random patterns (mostly misses);
   - extend (host variant) on P bi-intervals;
   - extract (host variant) on R rows;
-  - the baseline: the same backward search composed from rb2_hip_rank_batch calls (what a user could do before), on fewer patterns.
+  - the baseline: the same backward search composed from rb2_hip_rank_batch calls (what a user could do before), on fewer patterns;
+  - smem (--only smem, or after the others): smem_dev on P reads of 101 bp with 2 % substituted bases against an index of the same reads
+    built with BOTH strands, and its baseline, the same algorithm driven from the host with one rb2_hip_extend call per step for a
+    sample of the queries in lock step (composed_smem), reported per query.
 For each case: queries/s, LF steps/s (one step = the ranks at both ends of an interval, or one LF of a walk), the bytes a step touches
 by the layout, and steps/s x bytes against the 8 TB/s HBM peak.  One JSON document on stdout and in --out.
 
-    python tools/query_bench.py --out profiles/query_bench.json [--so 1] [--patterns 4000000] [--rows 1000000]
+    python tools/query_bench.py --out profiles/query_bench.json [--so 1] [--patterns 4000000] [--rows 1000000] [--only smem]
+With --only smem and an --out file that exists, the smem cases replace those of the file and the rest of it stays.
 """
 import argparse
 import json
@@ -87,6 +91,132 @@ def composed_search(g, counts, pats):
     return lo, hi, m
 
 
+def composed_smem(g, counts, qs, min_len=1, min_occ=1):
+    """k_smem's algorithm driven from the host for all the queries qs (n, L) in lock step: per step ONE rb2_hip_extend call for the
+    queries that have a step to take.  The state of a query is (xf, xo, sz) with xf the end the next step ranks, so every step is a
+    backward extension of (xf, xo, sz) whichever way the query is going.  Returns the records per query, the steps and the calls."""
+    n, L = qs.shape
+    C = np.concatenate([[0], np.cumsum(counts.sum(1))]).astype(np.int64)
+    idx = np.arange(n)
+    p = np.zeros(n, np.int64); s = np.zeros(n, np.int64); e = np.zeros(n, np.int64)
+    st = np.zeros((n, 3), np.int64)
+    back = np.zeros(n, bool); walking = np.zeros(n, bool)
+    recs = [[] for _ in range(n)]
+    steps = calls = 0
+    while True:
+        fresh = np.flatnonzero(~walking & (p < L))                    # start from the bi-interval of q[p], or skip p
+        if len(fresh) == 0 and not walking.any():
+            break
+        if len(fresh):
+            c0 = qs[fresh, p[fresh]].astype(np.int64)
+            ok = c0 < 5
+            cc = np.where(ok, c0, 0)
+            sz = np.where(ok, C[cc + 1] - C[cc], 0)
+            go = sz >= min_occ
+            p[fresh[~go]] += 1
+            f = fresh[go]
+            st[f, 0] = C[cc[go]]; st[f, 1] = C[5 - cc[go]]; st[f, 2] = sz[go]
+            s[f] = p[f]; e[f] = p[f] + 1; back[f] = True; walking[f] = True
+        w = np.flatnonzero(walking)
+        if len(w) == 0:
+            continue
+        j = np.where(back[w], s[w] - 1, e[w])
+        inside = (j >= 0) & (j < L)
+        c = np.where(inside, qs[w, np.clip(j, 0, L - 1)], 0).astype(np.int64)
+        stop = (c < 1) | (c > 4)
+        k = np.flatnonzero(~stop)
+        if len(k):
+            a = np.where(back[w[k]], c[k], 5 - c[k])
+            ok6 = g.extend(st[w[k]], 1)
+            calls += 1; steps += len(k)
+            nx = ok6[np.arange(len(k)), a]
+            good = nx[:, 2] >= min_occ
+            stop[k[~good]] = True
+            wk = w[k[good]]
+            st[wk] = nx[good]
+            bk = back[wk]
+            s[wk[bk]] -= 1; e[wk[~bk]] += 1
+        ws = w[stop]
+        turn = ws[back[ws]]
+        st[turn, 0], st[turn, 1] = st[turn, 1].copy(), st[turn, 0].copy()
+        done = ws[~back[ws]]
+        back[turn] = False
+        for i in done:
+            if e[i] - s[i] >= min_len:
+                recs[i].append([s[i], e[i], st[i, 1], st[i, 0], st[i, 2]])
+        p[done] = e[done]; walking[done] = False
+    return recs, steps, calls
+
+
+def smem_steps(qs, mem, cnt):
+    """extension steps k_smem took (min_len = 1, min_occ = 1, no N, every symbol present in the index), from its records: for an SMEM
+    [s, e) found from position p (the end of the one before): p - s backward steps and one that failed unless s == 0, e - p - 1 forward
+    steps and one that failed unless e == L"""
+    n, L = qs.shape
+    k = np.arange(mem.shape[1])[None, :] < cnt[:, None]
+    s, e = mem[:, :, 0], mem[:, :, 1]
+    p = np.concatenate([np.zeros((n, 1), np.int64), e[:, :-1]], 1)
+    return int(((e - s - 1 + (s > 0) + (e < L)) * k).sum()), p
+
+
+def smem_case(a, res):
+    L = 101
+    n = a.reads or -(-(int(4 * 1024 ** 3 * 0.97) + 1) // (L + 1))
+    g = HipBwt(a.so)
+    buf = g.dev_alloc(2 * n * (L + 1))
+    t = time.perf_counter()
+    g.synth_reads(buf, 0, n, L, seed=42, strand=1)                  # every read followed by its reverse complement
+    g.insert_multi_dev(buf, 2 * n * (L + 1))
+    g.sync()
+    counts = g.counts()
+    build_s = time.perf_counter() - t
+    g.dev_free(buf)
+    print("smem: index of %d reads x 2 strands built in %.1f s" % (n, build_s), file=sys.stderr, flush=True)
+    P, M = a.patterns, 16
+    rng = np.random.RandomState(11)
+    qs = hit_patterns(P, L, n, 101)
+    sub = rng.rand(P, L) < 0.02                                     # 2 % substitutions: another base, never the same
+    qs[sub] = 1 + (qs[sub] - 1 + rng.randint(1, 4, size=int(sub.sum()))) % 4
+    flat = np.ascontiguousarray(qs.reshape(-1)); off = np.arange(P + 1, dtype=np.int64) * L
+    dq, do, dm, dc = g.dev_alloc(len(flat)), g.dev_alloc(8 * (P + 1)), g.dev_alloc(40 * M * P), g.dev_alloc(8 * P)
+    g.L.rb2_hip_memcpy(g.h, dq, flat.ctypes.data, len(flat), 0)
+    g.L.rb2_hip_memcpy(g.h, do, off.ctypes.data, 8 * (P + 1), 0)
+    sec = timed(lambda: g.smem_dev(P, dq, do, dm, dc, 1, 1, M), g.sync)
+    mem = np.zeros((P, M, 5), np.int64); cnt = np.zeros(P, np.int64)
+    g.L.rb2_hip_memcpy(g.h, mem.ctypes.data, dm, mem.nbytes, 1)
+    g.L.rb2_hip_memcpy(g.h, cnt.ctypes.data, dc, 8 * P, 1)
+    for q in (dq, do, dm, dc):
+        g.dev_free(q)
+    assert cnt.min() >= 0, int(cnt.min())
+    trunc = int((cnt > M).sum())
+    print("smem: %d queries in %.3f s" % (P, sec), file=sys.stderr, flush=True)
+    # the steps are counted from the records, so they need all of them: a sample of the queries again with room for every SMEM
+    ns, M2 = min(P, a.step_queries), 128
+    st2, mem2, cnt2 = g.smem_raw(list(qs[:ns]), 1, 1, M2)
+    assert np.array_equal(cnt2, cnt[:ns]) and cnt2.max() <= M2, int(cnt2.max())
+    assert all(np.array_equal(mem2[i, :min(cnt2[i], M)], mem[i, :min(cnt2[i], M)]) for i in range(0, ns, 97))
+    steps_s, _ = smem_steps(qs[:ns], mem2, cnt2)
+    steps = int(round(steps_s / ns * P))
+    row = row_case("smem_dev 101 bp reads, 2 %% substitutions, min_len=1 min_occ=1 max_mems=%d (both strands indexed)" % M, P, sec, steps, 2)
+    row.update({"measured": True, "lf_steps_counted_on_queries": ns, "lf_steps_are": "counted on the first %d queries, scaled to %d" % (ns, P),
+                "queries_with_more_than_max_mems": trunc, "smems": int(cnt.sum()), "smems_per_query": float(cnt.mean()),
+                "mean_smem_length": float((mem2[:, :, 1] - mem2[:, :, 0]).sum() / max(cnt2.sum(), 1)),
+                "index": {"reads": n, "strands": 2, "symbols": int(counts.sum()), "build_seconds": build_s, "layout": g.layout_stats()}})
+    nb = min(a.baseline_queries, ns)
+    t = time.perf_counter()
+    recs, bsteps, calls = composed_smem(g, counts, qs[:nb])
+    bsec = time.perf_counter() - t
+    same = all(len(r) == cnt2[i] and np.array_equal(np.array(r, np.int64).reshape(-1, 5), mem2[i, :cnt2[i]]) for i, r in enumerate(recs))
+    fsteps, _ = smem_steps(qs[:nb], mem2[:nb], cnt2[:nb])
+    brow = row_case("baseline: the same SMEM algorithm driven from the host, one rb2_hip_extend call per step, %d queries in lock step" % nb, nb, bsec, bsteps, 2)
+    brow.update({"measured": True, "extend_calls": calls, "equals_fused": bool(same), "steps_equal_fused_count": bool(bsteps == fsteps), "seconds_per_query": bsec / nb})
+    host = timed(lambda: g.smem_raw(list(qs[:nb]), 1, 1, M), lambda: None, reps=1)
+    hrow = row_case("smem (host buffers), the baseline's %d queries" % nb, nb, host, fsteps, 2)
+    hrow["measured"] = True
+    g.close()
+    res["cases"] = [c for c in res["cases"] if "smem" not in c["case"].lower()] + [row, brow, hrow]
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default="")
@@ -95,7 +225,18 @@ def main():
     ap.add_argument("--rows", type=int, default=1_000_000)
     ap.add_argument("--baseline-patterns", type=int, default=200_000)
     ap.add_argument("--reads", type=int, default=0, help="reads in the index (default: the configs[1] batch)")
+    ap.add_argument("--baseline-queries", type=int, default=20_000, help="queries of the host-driven SMEM baseline")
+    ap.add_argument("--step-queries", type=int, default=200_000, help="queries the SMEM extension steps are counted on")
+    ap.add_argument("--only", default="", help="'smem': only the smem cases (added to an existing --out file)")
     a = ap.parse_args()
+    if a.only == "smem":
+        res = {"cases": []}
+        if a.out and os.path.exists(a.out):
+            with open(a.out) as f:
+                res = json.load(f)
+        smem_case(a, res)
+        finish(a, res)
+        return
     L = 101
     n = a.reads or -(-(int(4 * 1024 ** 3 * 0.97) + 1) // (L + 1))
     g = HipBwt(a.so)
@@ -153,6 +294,11 @@ def main():
     res["cases"].append(row_case("extract (host buffers) max_len=101", R, sec, int(ex.ln.sum()) + R, 1))
     res["extract_fitted"] = fit[0]
     g.close()
+    smem_case(a, res)
+    finish(a, res)
+
+
+def finish(a, res):
     js = json.dumps(res, indent=1)
     print(js)
     if a.out:
