@@ -14,6 +14,7 @@
  *   rope_t.c[6] marginal counts  rope.h:19, mrope.h:86   rb2_hip_get_counts()
  *   mr_itr_first/next_block      mrope.c:111-130         rb2_hip_rope_bytes() + rb2_hip_download_rope()
  *   mr_restore / rope_restore    mrope.c:145, rope.c:308 rb2_hip_load_ropes()
+ *   rld_restore                  rld0.c:246-300          rb2_hip_load_fmd[_file]()
  *
  * Run-length byte streams crossing this boundary use ropebwt2's "43+3" codec (rle.h:39-75), so
  * the host can splice them straight into rope leaves.  The device itself only ever emits the
@@ -123,6 +124,20 @@ int64_t rb2_hip_stream_rope(rb2_hip_t *h, int b, rb2_hip_run_cb cb, void *user);
  * width; rle[b] may be NULL when n_bytes[b]==0).  Used to seed the device from an .fmr file /
  * host ropes (mr_restore, mrope.c:145-160; rope_restore, rope.c:308-318). */
 void rb2_hip_load_ropes(rb2_hip_t *h, const uint8_t *const rle[6], const int64_t n_bytes[6]);
+
+/* replace all six ropes by the index an .fmd file holds (fermi's run-length delta BWT, rld0.c:207-244: what `ropebwt2 -d`, this
+ * project's CLI and fermi write).  `fmd` is the whole file image in host memory, borrowed for the call.  Like rb2_hip_load_ropes it
+ * finishes a lazy insert first and leaves the dense layout; the stream is uploaded once and decoded on the device, one lane per 64-byte
+ * block (k_fmd_*, csrc/rb2_fmd_load.h); the rank frames behind the stream are not read.  Returns the number of symbols loaded; a file
+ * whose marginal counts are all zero loads as an empty index.  The file does not record a sorting order: the handle keeps the one it was
+ * created with, and whether later inserts in that order make sense for this index is the caller's business.
+ * Fatal, each with a message of its own: wrong magic; an alphabet other than 6 symbols or blocks other than 8 words; a stream length
+ * that is no multiple of 8, or an image shorter than 80 bytes + the stream; an invalid block header; a block whose decoded symbols
+ * disagree with the counts in the next header; totals that disagree with the file's marginal counts; a symbol code above 5; ropes
+ * that are inconsistent with each other, as for rb2_hip_load_ropes. */
+int64_t rb2_hip_load_fmd(rb2_hip_t *h, const void *fmd, int64_t n_bytes);
+/* the same for a file that is read into memory first; a file that cannot be opened or read is fatal with its name */
+int64_t rb2_hip_load_fmd_file(rb2_hip_t *h, const char *path);
 
 /* optional capacity hint (like the reference sizing its buffers from -m, main.c:136): make room for batches
  * of up to batch_bytes bytes / batch_strings strings and an index of total_symbols symbols, so that
@@ -256,6 +271,8 @@ int64_t rb2_hip_multi_rope_bytes(rb2_hip_multi_t *m, int b);
 int64_t rb2_hip_multi_download_rope(rb2_hip_multi_t *m, int b, uint8_t *dst);
 int64_t rb2_hip_multi_stream_rope(rb2_hip_multi_t *m, int b, rb2_hip_run_cb cb, void *user);
 void rb2_hip_multi_load_ropes(rb2_hip_multi_t *m, const uint8_t *const rle[6], const int64_t n_bytes[6]);
+/* rb2_hip_load_fmd on the sharded index: every rank decodes the stream and keeps its own pieces */
+int64_t rb2_hip_multi_load_fmd(rb2_hip_multi_t *m, const void *fmd, int64_t n_bytes);
 void rb2_hip_multi_reserve(rb2_hip_multi_t *m, int64_t batch_bytes, int64_t batch_strings, int64_t total_symbols);
 void rb2_hip_multi_reset(rb2_hip_multi_t *m);
 void rb2_hip_multi_sync(rb2_hip_multi_t *m);

@@ -17,6 +17,7 @@
 #include "rb2_hip.h"
 #include "rb2_kernels.h"
 #include "rb2_query.h"
+#include "rb2_fmd_load.h"
 
 using namespace rb2;
 
@@ -1284,6 +1285,71 @@ int64_t rb2_hip_download_rope(rb2_hip_t *h, int b, uint8_t *dst)
 	return k;
 }
 
+// What the two loaders (run bytes of six ropes; an .fmd image) share.  tot[b][a] = symbols a in rope b.
+// piece (b,x) of rope b has as many rows as rope x has b's; rope $ is one piece: the RopeDescs, the pieces of every rope in rope
+// order, and the leaves the pool needs
+static uint64_t ld_piece_table(rb2_hip_t *h, const char *who, const uint64_t tot[6][6], RopeDesc rp[NR], LdPieces tab[6])
+{
+	uint64_t leaf = 0;
+	for (int r = 0; r < NR; ++r) memset(&rp[r], 0, sizeof(RopeDesc));
+	for (int b = 0; b < 6; ++b) {
+		LdPieces &t = tab[b];
+		memset(&t, 0, sizeof(t));
+		t.np = b == 0 ? 1 : 6;
+		uint64_t have = 0, want = 0;
+		for (int a = 0; a < 6; ++a) have += tot[b][a];
+		for (int x = 0; x < t.np; ++x) {
+			const int r = b == 0 ? 0 : rope_of(b, x);
+			uint64_t quota = 0;
+			if (b == 0) quota = have; else quota = tot[x][b];
+			const bool keep = h->nranks == 1 || h->owner[r] == h->rank;   // sharded: other ranks' pieces are only counted
+			RopeDesc &d = rp[r];
+			d.leaf0 = leaf; d.sb0 = leaf / SB;
+			d.n = keep ? quota : 0;
+			d.nleaves = keep ? (quota + LEAF - 1) / LEAF : 0;
+			t.q[x] = want; t.word0[x] = leaf * LEAFW; t.keep[x] = keep; t.r[x] = r;
+			want += quota;
+			leaf += (d.nleaves + SB - 1) / SB * SB;
+		}
+		t.q[t.np] = want;
+		if (have < want) { rb2_fatal("[rb2_hip] %s: rope %d is shorter than the symbol counts of the other ropes imply\n", who, b); }
+		if (have > want) { rb2_fatal("[rb2_hip] %s: rope %d is longer than the symbol counts of the other ropes imply (not a BWT of complete strings?)\n", who, b); }
+	}
+	return leaf;
+}
+// the zeroed pool of `leaf` leaves the pieces are ORed into
+static PoolView ld_zero_pool(rb2_hip_t *h, uint64_t leaf)
+{
+	hipStream_t st = h->st;
+	h->sparse = false; h->sp_backoff = h->sp_penalty = 0;      /* what is loaded is the dense layout */
+	h->pool[h->pside].ensure(leaf + SB, false, st);
+	PoolView pv = h->pool[h->pside].view();
+	if (leaf) {
+		HIPCHK(hipMemsetAsync(pv.data, 0, leaf * (uint64_t)LEAFB, st));
+		HIPCHK(hipMemsetAsync(pv.own, 0, leaf * sizeof(LeafMeta), st));
+	}
+	return pv;
+}
+// the pieces are filled and pcnt_dev[NR * 6] holds their symbol counts: own counts of every leaf, control words, directory
+static void ld_finish(rb2_hip_t *h, RopeDesc rp[NR], uint64_t leaf, PoolView pv, const unsigned long long *pcnt_dev)
+{
+	hipStream_t st = h->st;
+	const int sd = h->side, ps = h->pside;
+	unsigned long long pc_h[NR * 6];
+	HIPCHK(hipMemcpyAsync(pc_h, pcnt_dev, sizeof(pc_h), hipMemcpyDeviceToHost, st));
+	for (int r = 0; r < NR; ++r)
+		if (rp[r].nleaves) hipLaunchKernelGGL(k_ld_own, dim3((unsigned)cdiv(rp[r].nleaves, MW)), dim3(256), 0, st, pv, rp[r].leaf0, rp[r].nleaves, rp[r].n);
+	HIPCHK(hipStreamSynchronize(st));
+	for (int r = 0; r < NR; ++r) for (int a = 0; a < 6; ++a) rp[r].cnt[a] = pc_h[r * 6 + a];
+	HIPCHK(hipMemcpyAsync(&h->ctl->rope[sd][0], rp, sizeof(RopeDesc) * NR, hipMemcpyHostToDevice, st));
+	const uint64_t nsb = leaf / SB;
+	HIPCHK(hipMemcpyAsync(&h->ctl->nsb_total, &nsb, 8, hipMemcpyHostToDevice, st));
+	build_directory(h, sd, ps, nsb);
+	HIPCHK(hipGetLastError());
+	HIPCHK(hipStreamSynchronize(st));
+	memcpy(h->h_rope, rp, sizeof(RopeDesc) * NR);
+}
+
 void rb2_hip_load_ropes(rb2_hip_t *h, const uint8_t *const rle[6], const int64_t n_bytes[6])
 { finish_pending(h);
 	HIPCHK(hipSetDevice(h->dev));
@@ -1312,44 +1378,12 @@ void rb2_hip_load_ropes(rb2_hip_t *h, const uint8_t *const rle[6], const int64_t
 	HIPCHK(hipMemcpyAsync(flag_h, flag.p, 8, hipMemcpyDeviceToHost, st));
 	HIPCHK(hipStreamSynchronize(st));
 	if (flag_h[0]) { rb2_fatal("[rb2_hip] load_ropes: not run-length bytes of ropebwt2's codec (bad symbol or truncated run)\n"); }
-	// piece (b,x) of rope b has as many rows as rope x has b's; rope $ is one piece
 	uint64_t tot[6][6];
 	for (int b = 0; b < 6; ++b) for (int a = 0; a < 6; ++a) tot[b][a] = tot_h[b * 6 + a];
 	RopeDesc rp[NR];
 	LdPieces tab[6];
-	uint64_t leaf = 0;
-	for (int r = 0; r < NR; ++r) memset(&rp[r], 0, sizeof(RopeDesc));
-	for (int b = 0; b < 6; ++b) {
-		LdPieces &t = tab[b];
-		memset(&t, 0, sizeof(t));
-		t.np = b == 0 ? 1 : 6;
-		uint64_t have = 0, want = 0;
-		for (int a = 0; a < 6; ++a) have += tot[b][a];
-		for (int x = 0; x < t.np; ++x) {
-			const int r = b == 0 ? 0 : rope_of(b, x);
-			uint64_t quota = 0;
-			if (b == 0) quota = have; else quota = tot[x][b];
-			const bool keep = h->nranks == 1 || h->owner[r] == h->rank;   // sharded: other ranks' pieces are only counted
-			RopeDesc &d = rp[r];
-			d.leaf0 = leaf; d.sb0 = leaf / SB;
-			d.n = keep ? quota : 0;
-			d.nleaves = keep ? (quota + LEAF - 1) / LEAF : 0;
-			t.q[x] = want; t.word0[x] = leaf * LEAFW; t.keep[x] = keep; t.r[x] = r;
-			want += quota;
-			leaf += (d.nleaves + SB - 1) / SB * SB;
-		}
-		t.q[t.np] = want;
-		if (have < want) { rb2_fatal("[rb2_hip] load_ropes: rope %d is shorter than the symbol counts of the other ropes imply\n", b); }
-		if (have > want) { rb2_fatal("[rb2_hip] load_ropes: rope %d is longer than the symbol counts of the other ropes imply (not a BWT of complete strings?)\n", b); }
-	}
-	const int sd = h->side, ps = h->pside;
-	h->sparse = false; h->sp_backoff = h->sp_penalty = 0;      /* what is loaded is the dense layout */
-	h->pool[ps].ensure(leaf + SB, false, st);
-	PoolView pv = h->pool[ps].view();
-	if (leaf) {
-		HIPCHK(hipMemsetAsync(pv.data, 0, leaf * (uint64_t)LEAFB, st));
-		HIPCHK(hipMemsetAsync(pv.own, 0, leaf * sizeof(LeafMeta), st));
-	}
+	const uint64_t leaf = ld_piece_table(h, "load_ropes", tot, rp, tab);
+	PoolView pv = ld_zero_pool(h, leaf);
 	std::vector<uint64_t> off;
 	for (int b = 0; b < 6; ++b) {
 		if (nblk[b] == 0) continue;
@@ -1368,21 +1402,107 @@ void rb2_hip_load_ropes(rb2_hip_t *h, const uint8_t *const rle[6], const int64_t
 		if (flag_h[1] > long_cap) { rb2_fatal("[rb2_hip] load_ropes: more than %u runs longer than %u symbols in rope %d\n", long_cap, LD_LONG, b); }
 		HIPCHK(hipMemsetAsync(flag.p + 1, 0, 4, st));
 	}
-	unsigned long long pc_h[NR * 6];
-	HIPCHK(hipMemcpyAsync(pc_h, cnt.p + 36, sizeof(pc_h), hipMemcpyDeviceToHost, st));
-	for (int r = 0; r < NR; ++r)
-		if (rp[r].nleaves) hipLaunchKernelGGL(k_ld_own, dim3((unsigned)cdiv(rp[r].nleaves, MW)), dim3(256), 0, st, pv, rp[r].leaf0, rp[r].nleaves, rp[r].n);
-	HIPCHK(hipStreamSynchronize(st));
-	for (int r = 0; r < NR; ++r) for (int a = 0; a < 6; ++a) rp[r].cnt[a] = pc_h[r * 6 + a];
-	HIPCHK(hipMemcpyAsync(&h->ctl->rope[sd][0], rp, sizeof(rp), hipMemcpyHostToDevice, st));
-	const uint64_t nsb = leaf / SB;
-	HIPCHK(hipMemcpyAsync(&h->ctl->nsb_total, &nsb, 8, hipMemcpyHostToDevice, st));
-	build_directory(h, sd, ps, nsb);
-	HIPCHK(hipGetLastError());
-	HIPCHK(hipStreamSynchronize(st));
-	memcpy(h->h_rope, rp, sizeof(rp));
+	ld_finish(h, rp, leaf, pv, cnt.p + 36);
 	for (int b = 0; b < 6; ++b) { dr[b].release(); blk[b].release(); }
 	cnt.release(); flag.release(); longs.release();
+}
+
+/* ---- .fmd images (kernels in rb2_fmd_load.h) ------------------------------- */
+
+int64_t rb2_hip_load_fmd(rb2_hip_t *h, const void *fmd, int64_t n_bytes)
+{ finish_pending(h);
+	HIPCHK(hipSetDevice(h->dev));
+	hipStream_t st = h->st;
+	const uint8_t *img = (const uint8_t*)fmd;
+	if (!img || n_bytes < 80) { rb2_fatal("[rb2_hip] load_fmd: %lld bytes are too few for the 80-byte header of an .fmd\n", (long long)(img ? n_bytes : 0)); }
+	if (memcmp(img, "RLD\3", 4) != 0) { rb2_fatal("[rb2_hip] load_fmd: wrong magic (not an .fmd of rld0 version 3)\n"); }
+	uint32_t ab; uint64_t hd[9];                               // reserved, n_bytes, n_frames, mcnt[6]
+	memcpy(&ab, img + 4, 4); memcpy(hd, img + 8, sizeof(hd));
+	if ((ab >> 16) != 6u || (ab & 0xffffu) != 3u) { rb2_fatal("[rb2_hip] load_fmd: alphabet size %u and block bits %u: only 6 and 3 (blocks of 8 words) are supported\n", ab >> 16, ab & 0xffffu); }
+	const uint64_t sbytes = hd[1], nwords = sbytes / 8, nb = nwords / FMD_BW, tail = nwords % FMD_BW;
+	if (sbytes % 8 != 0) { rb2_fatal("[rb2_hip] load_fmd: the stream length %llu is not a multiple of 8\n", (unsigned long long)sbytes); }
+	if (sbytes > (uint64_t)n_bytes - 80) { rb2_fatal("[rb2_hip] load_fmd: the image is truncated: the header announces a stream of %llu bytes, %lld follow it\n", (unsigned long long)sbytes, (long long)(n_bytes - 80)); }
+	if (tail != 2 && tail != 4 && tail != 7) { rb2_fatal("[rb2_hip] load_fmd: a stream of %llu bytes does not end with a block header\n", (unsigned long long)sbytes); }
+	FmdRopes ropes;
+	ropes.R[0] = 0;
+	for (int b = 0; b < 6; ++b) {
+		if (hd[3 + b] >> 48) { rb2_fatal("[rb2_hip] load_fmd: the marginal count of symbol %d is %llu\n", b, (unsigned long long)hd[3 + b]); }
+		ropes.R[b + 1] = ropes.R[b] + hd[3 + b];
+	}
+	ropes.R[7] = ~0ull;
+	const uint64_t rows = ropes.R[6];
+	// one copy of the stream; everything else stays on the device until the 6 x 6 matrix comes back
+	const uint32_t nwg = (uint32_t)cdiv(nb, 256);
+	DevBuf<uint64_t> dw, wg;
+	DevBuf<unsigned long long> cnt;                            // [0, 36): symbol a in rope b; [36, 36 + NR * 6): per piece
+	DevBuf<uint32_t> flag;                                     // [0] FMD_BAD_* bits, [1] long runs
+	const uint32_t long_cap = 1u << 20;
+	DevBuf<LdLong> longs;
+	dw.ensure(nwords + FMD_BW); wg.ensure((uint64_t)nwg + 1); cnt.ensure(36 + NR * 6); flag.ensure(2); longs.ensure(long_cap);
+	HIPCHK(hipMemcpyAsync(dw.p, img + 80, sbytes, hipMemcpyHostToDevice, st));
+	HIPCHK(hipMemsetAsync(cnt.p, 0, (36 + NR * 6) * 8, st));
+	HIPCHK(hipMemsetAsync(flag.p, 0, 8, st));
+	HIPCHK(hipMemsetAsync(wg.p, 0, ((uint64_t)nwg + 1) * 8, st));
+	if (nb) {
+		hipLaunchKernelGGL(k_fmd_sizes, dim3(nwg), dim3(256), 0, st, (const uint64_t*)dw.p, nb, nwords, wg.p, flag.p);
+		hipLaunchKernelGGL(k_fmd_scan, dim3(1), dim3(256), 0, st, wg.p, (uint64_t)nwg);
+		hipLaunchKernelGGL(k_fmd_count, dim3(nwg), dim3(256), 0, st, (const uint64_t*)dw.p, nb, nwords, (const uint64_t*)wg.p, ropes, cnt.p, flag.p);
+	}
+	unsigned long long tot_h[36], rows_dev; uint32_t flag_h[2];
+	HIPCHK(hipMemcpyAsync(tot_h, cnt.p, sizeof(tot_h), hipMemcpyDeviceToHost, st));
+	HIPCHK(hipMemcpyAsync(&rows_dev, wg.p + nwg, 8, hipMemcpyDeviceToHost, st));
+	HIPCHK(hipMemcpyAsync(flag_h, flag.p, 8, hipMemcpyDeviceToHost, st));
+	HIPCHK(hipStreamSynchronize(st));
+	if (flag_h[0] & FMD_BAD_TYPE) { rb2_fatal("[rb2_hip] load_fmd: invalid block header (type 3, or the stream ends inside a header)\n"); }
+	if (flag_h[0] & FMD_BAD_SYM) { rb2_fatal("[rb2_hip] load_fmd: a run has a symbol code above 5\n"); }
+	if (flag_h[0] & FMD_BAD_COUNT) { rb2_fatal("[rb2_hip] load_fmd: a block's decoded symbols disagree with the counts in the next header\n"); }
+	if ((flag_h[0] & FMD_BAD_TOTAL) || rows_dev != rows) {
+		rb2_fatal("[rb2_hip] load_fmd: the blocks hold %llu symbols, the marginal counts of the file %llu\n", (unsigned long long)rows_dev, (unsigned long long)rows);
+	}
+	uint64_t tot[6][6];
+	for (int b = 0; b < 6; ++b) for (int a = 0; a < 6; ++a) tot[b][a] = tot_h[b * 6 + a];
+	for (int a = 0; a < 6; ++a) {
+		uint64_t col = 0;
+		for (int b = 0; b < 6; ++b) col += tot[b][a];
+		if (col != hd[3 + a]) { rb2_fatal("[rb2_hip] load_fmd: the blocks hold %llu symbols %d, the marginal counts of the file %llu\n", (unsigned long long)col, a, (unsigned long long)hd[3 + a]); }
+	}
+	RopeDesc rp[NR];
+	LdPieces tab[6];
+	const uint64_t leaf = ld_piece_table(h, "load_fmd", tot, rp, tab);
+	PoolView pv = ld_zero_pool(h, leaf);
+	FmdPieces gp;
+	memset(&gp, 0, sizeof(gp));
+	for (int b = 0; b < 6; ++b)
+		for (int x = 0; x < tab[b].np; ++x) {
+			const int r = tab[b].r[x];                             // pieces in global row order are sub-ropes 0 .. NR - 1
+			gp.q[r] = ropes.R[b] + tab[b].q[x]; gp.word0[r] = tab[b].word0[x]; gp.keep[r] = tab[b].keep[x];
+		}
+	gp.q[NR] = rows;
+	if (nb) {
+		hipLaunchKernelGGL(k_fmd_expand, dim3(nwg), dim3(256), 0, st, (const uint64_t*)dw.p, nb, nwords, (const uint64_t*)wg.p, gp, (uint64_t*)pv.data,
+				cnt.p + 36, longs.p, flag.p + 1, long_cap, flag.p);
+		hipLaunchKernelGGL(k_ld_long, dim3(1024), dim3(256), 0, st, (const LdLong*)longs.p, (const uint32_t*)(flag.p + 1), long_cap, (uint64_t*)pv.data);
+		HIPCHK(hipMemcpyAsync(flag_h, flag.p, 8, hipMemcpyDeviceToHost, st));
+		HIPCHK(hipStreamSynchronize(st));
+		if (flag_h[0]) { rb2_fatal("[rb2_hip] load_fmd: internal: the second decoding pass disagrees with the first (flags %u)\n", flag_h[0]); }
+		if (flag_h[1] > long_cap) { rb2_fatal("[rb2_hip] load_fmd: more than %u runs longer than %u symbols\n", long_cap, LD_LONG); }
+	}
+	ld_finish(h, rp, leaf, pv, cnt.p + 36);
+	dw.release(); wg.release(); cnt.release(); flag.release(); longs.release();
+	return (int64_t)rows;
+}
+
+int64_t rb2_hip_load_fmd_file(rb2_hip_t *h, const char *path)
+{
+	FILE *fp = path ? fopen(path, "rb") : nullptr;
+	if (!fp) { rb2_fatal("[rb2_hip] load_fmd: cannot open %s\n", path ? path : "(null)"); }
+	std::vector<uint8_t> img;
+	if (fseeko(fp, 0, SEEK_END) == 0) { const off_t n = ftello(fp); if (n > 0) img.resize((size_t)n); }
+	rewind(fp);
+	const size_t got = img.empty() ? 0 : fread(img.data(), 1, img.size(), fp);
+	fclose(fp);
+	if (got != img.size()) { rb2_fatal("[rb2_hip] load_fmd: cannot read %s (%zu of %zu bytes)\n", path, got, img.size()); }
+	return rb2_hip_load_fmd(h, img.data(), (int64_t)img.size());
 }
 
 /* ---- rope sharding across GPUs ------------------------------------------- */

@@ -754,6 +754,13 @@ void rb2_hip_multi_load_ropes(rb2_hip_multi_t *m, const uint8_t *const rle[6], c
 	multi_each(m, [&](int k) { rb2_hip_load_ropes(m->rk[k].h, rle, n_bytes); });   /* every rank decodes the stream, keeps its pieces, counts the others */
 }
 
+int64_t rb2_hip_multi_load_fmd(rb2_hip_multi_t *m, const void *fmd, int64_t n_bytes)
+{
+	std::vector<int64_t> n(m->n, 0);
+	multi_each(m, [&](int k) { n[k] = rb2_hip_load_fmd(m->rk[k].h, fmd, n_bytes); });   /* as above: every rank decodes the whole stream */
+	return n[0];
+}
+
 void rb2_hip_multi_reserve(rb2_hip_multi_t *m, int64_t batch_bytes, int64_t batch_strings, int64_t total_symbols)
 {
 	const int64_t share = total_symbols > 0 ? (int64_t)((double)total_symbols * 1.25 / std::max(1, m->active)) : 0;

@@ -44,6 +44,8 @@ def load_hip_lib():
         "rb2_hip_download_rope": (i64, [vp, i32, vp]),
         "rb2_hip_stream_rope": (i64, [vp, i32, vp, vp]),
         "rb2_hip_load_ropes": (None, [vp, vp, vp]),
+        "rb2_hip_load_fmd": (i64, [vp, vp, i64]),
+        "rb2_hip_load_fmd_file": (i64, [vp, C.c_char_p]),
         "rb2_hip_rank1a": (None, [vp, i32, i64, vp]),
         "rb2_hip_rank_batch": (None, [vp, i32, i64, vp, vp]),
         "rb2_hip_backward_search": (None, [vp, i64, vp, vp, vp]),
@@ -88,6 +90,7 @@ def load_hip_lib():
         "rb2_hip_multi_download_rope": (i64, [vp, i32, vp]),
         "rb2_hip_multi_stream_rope": (i64, [vp, i32, vp, vp]),
         "rb2_hip_multi_load_ropes": (None, [vp, vp, vp]),
+        "rb2_hip_multi_load_fmd": (i64, [vp, vp, i64]),
         "rb2_hip_multi_reserve": (None, [vp, i64, i64, i64]),
         "rb2_hip_multi_reset": (None, [vp]),
         "rb2_hip_multi_sync": (None, [vp]),
@@ -114,7 +117,7 @@ def load_hip_lib():
 ABI_SYMBOLS = [
     "rb2_hip_device_count", "rb2_hip_set_fatal_handler", "rb2_hip_create", "rb2_hip_destroy", "rb2_hip_sorting_order", "rb2_hip_reset",
     "rb2_hip_insert_multi", "rb2_hip_insert_multi_dev", "rb2_hip_set_lazy", "rb2_hip_wait", "rb2_hip_last_batch_counts", "rb2_hip_prefetch", "rb2_hip_mem_info", "rb2_hip_get_counts", "rb2_hip_rope_bytes",
-    "rb2_hip_download_rope", "rb2_hip_stream_rope", "rb2_hip_load_ropes", "rb2_hip_rank1a", "rb2_hip_rank_batch", "rb2_hip_reserve",
+    "rb2_hip_download_rope", "rb2_hip_stream_rope", "rb2_hip_load_ropes", "rb2_hip_load_fmd", "rb2_hip_load_fmd_file", "rb2_hip_rank1a", "rb2_hip_rank_batch", "rb2_hip_reserve",
     "rb2_hip_backward_search", "rb2_hip_backward_search_dev", "rb2_hip_extend", "rb2_hip_extract", "rb2_hip_smem", "rb2_hip_smem_dev", "rb2_hip_dev_alloc",
     "rb2_hip_num_subropes", "rb2_hip_memcpy", "rb2_hip_use_stream",
     "rb2_hip_dev_free", "rb2_hip_synth_reads", "rb2_hip_synth_reads_cov", "rb2_hip_synth_reads_skew", "rb2_hip_sync", "rb2_hip_sparse_stats", "rb2_hip_layout_stats", "rb2_hip_rewind_stats", "rb2_hip_window_stats", "rb2_hip_host_register", "rb2_hip_host_unregister", "rb2_hip_profile",
@@ -122,7 +125,7 @@ ABI_SYMBOLS = [
     "rb2_hip_multi_create", "rb2_hip_multi_unique_id", "rb2_hip_multi_create_rank", "rb2_hip_multi_destroy", "rb2_hip_default_owners",
     "rb2_hip_multi_nranks", "rb2_hip_multi_transport", "rb2_hip_multi_nlocal", "rb2_hip_multi_engine", "rb2_hip_multi_insert_multi", "rb2_hip_multi_insert_multi_dev",
     "rb2_hip_multi_get_counts", "rb2_hip_multi_rope_bytes", "rb2_hip_multi_download_rope", "rb2_hip_multi_stream_rope",
-    "rb2_hip_multi_load_ropes", "rb2_hip_multi_reserve", "rb2_hip_multi_rope_hash", "rb2_hip_rope_hash", "rb2_hip_multi_plan_host", "rb2_hip_multi_reset", "rb2_hip_multi_sync", "rb2_hip_multi_rank1a", "rb2_hip_multi_stats", "rb2_hip_multi_text_bytes",
+    "rb2_hip_multi_load_ropes", "rb2_hip_multi_load_fmd", "rb2_hip_multi_reserve", "rb2_hip_multi_rope_hash", "rb2_hip_rope_hash", "rb2_hip_multi_plan_host", "rb2_hip_multi_reset", "rb2_hip_multi_sync", "rb2_hip_multi_rank1a", "rb2_hip_multi_stats", "rb2_hip_multi_text_bytes",
 ]
 
 
@@ -180,6 +183,15 @@ def encode_runs(symbols):
             out.append({2: 0xC0, 4: 0xE0, 8: 0xF0}[n] | l << 3 | c)
             out.extend(reversed(tail))
     return np.frombuffer(bytes(out), dtype=np.uint8)
+
+
+def _fmd_image(src):
+    """an .fmd as one contiguous uint8 array: the file behind a path, or bytes / a uint8 array as they are"""
+    if isinstance(src, (str, os.PathLike)):
+        return np.fromfile(os.fspath(src), dtype=np.uint8)
+    if isinstance(src, (bytes, bytearray, memoryview)):
+        return np.frombuffer(src, dtype=np.uint8)
+    return np.ascontiguousarray(src, dtype=np.uint8).reshape(-1)
 
 
 class HipBwt:
@@ -258,6 +270,14 @@ class HipBwt:
         ptrs = (C.c_void_p * 6)(*[a.ctypes.data if len(a) else None for a in arrs])
         lens = (C.c_int64 * 6)(*[len(a) for a in arrs])
         self.L.rb2_hip_load_ropes(self.h, ptrs, lens)
+
+    def load_fmd(self, src):
+        """replace the index by the one an .fmd holds (rb2_hip_load_fmd); src: a path, or the file image as bytes / a uint8 array.
+        Returns the number of symbols loaded.  The sorting order stays the one the handle was created with."""
+        if isinstance(src, (str, os.PathLike)):
+            return int(self.L.rb2_hip_load_fmd_file(self.h, os.fsencode(src)))
+        img = _fmd_image(src)
+        return int(self.L.rb2_hip_load_fmd(self.h, img.ctypes.data, len(img)))
 
     def reserve(self, batch_bytes=0, batch_strings=0, total_symbols=0):
         self.L.rb2_hip_reserve(self.h, batch_bytes, batch_strings, total_symbols)
@@ -503,6 +523,11 @@ class MultiBwt:
         ptrs = (C.c_void_p * 6)(*[a.ctypes.data if len(a) else None for a in arrs])
         lens = (C.c_int64 * 6)(*[len(a) for a in arrs])
         self.L.rb2_hip_multi_load_ropes(self.h, ptrs, lens)
+
+    def load_fmd(self, src):
+        """rb2_hip_multi_load_fmd: every rank decodes the image and keeps its own pieces; src as for HipBwt.load_fmd"""
+        img = _fmd_image(src)
+        return int(self.L.rb2_hip_multi_load_fmd(self.h, img.ctypes.data, len(img)))
 
     def reserve(self, batch_bytes=0, batch_strings=0, total_symbols=0):
         self.L.rb2_hip_multi_reserve(self.h, batch_bytes, batch_strings, total_symbols)

@@ -12,7 +12,10 @@ tests/test_hip_parity.py::test_full_batch_properties), then times, after a warm-
 For each case: queries/s, LF steps/s (one step = the ranks at both ends of an interval, or one LF of a walk), the bytes a step touches
 by the layout, and steps/s x bytes against the 8 TB/s HBM peak.  One JSON document on stdout and in --out.
 
-    python tools/query_bench.py --out profiles/query_bench.json [--so 1] [--patterns 4000000] [--rows 1000000] [--only smem]
+    python tools/query_bench.py --out profiles/query_bench.json [--so 1] [--patterns 4000000] [--rows 1000000] [--only smem] [--fmd PATH]
+With --fmd the index is not built but loaded from an .fmd file (rb2_hip_load_fmd, from a file image in host memory): the document then
+records the load -- file bytes, seconds (first load and the median of three more), GB of file per second -- and the smem cases, which
+need an index of their own reads, are left out.  "hits" are then hits only if the file holds the reads of the generator.
 With --only smem and an --out file that exists, the smem cases replace those of the file and the rest of it stays.
 """
 import argparse
@@ -228,6 +231,7 @@ def main():
     ap.add_argument("--baseline-queries", type=int, default=20_000, help="queries of the host-driven SMEM baseline")
     ap.add_argument("--step-queries", type=int, default=200_000, help="queries the SMEM extension steps are counted on")
     ap.add_argument("--only", default="", help="'smem': only the smem cases (added to an existing --out file)")
+    ap.add_argument("--fmd", default="", help="load the index from this .fmd file instead of building it")
     a = ap.parse_args()
     if a.only == "smem":
         res = {"cases": []}
@@ -240,15 +244,26 @@ def main():
     L = 101
     n = a.reads or -(-(int(4 * 1024 ** 3 * 0.97) + 1) // (L + 1))
     g = HipBwt(a.so)
-    p = g.dev_alloc(n * (L + 1))
-    t = time.perf_counter()
-    g.synth_reads(p, 0, n, L, seed=42)
-    g.insert_multi_dev(p, n * (L + 1))
-    g.sync()
-    build_s = time.perf_counter() - t
-    g.dev_free(p)
+    load = None
+    if a.fmd:
+        img = np.fromfile(a.fmd, dtype=np.uint8)
+        t = time.perf_counter()
+        g.load_fmd(img)
+        first = time.perf_counter() - t
+        sec = timed(lambda: g.load_fmd(img), lambda: None)
+        load = {"file": a.fmd, "file_bytes": int(len(img)), "first_load_seconds": first, "seconds": sec, "file_gb_per_s": len(img) / sec / 1e9, "measured": True}
+        build_s = first
+        n = int(g.counts()[:, 0].sum())                  # strings in the index
+    else:
+        p = g.dev_alloc(n * (L + 1))
+        t = time.perf_counter()
+        g.synth_reads(p, 0, n, L, seed=42)
+        g.insert_multi_dev(p, n * (L + 1))
+        g.sync()
+        build_s = time.perf_counter() - t
+        g.dev_free(p)
     counts = g.counts()
-    res = {"index": {"reads": n, "read_len": L, "sorting_order": a.so, "symbols": int(counts.sum()), "build_seconds": build_s,
+    res = {"index": {"reads": n, "read_len": L, "sorting_order": a.so, "symbols": int(counts.sum()), "build_seconds": build_s, "loaded_from_fmd": load,
                      "layout": g.layout_stats()}, "hbm_peak_bytes_per_s": HBM_PEAK,
            "bytes_per_rank": {"leaf_lines": LEAF_BYTES, "leaf_meta": META_BYTES, "sbrec": SB_BYTES}, "cases": []}
     P = a.patterns
@@ -294,7 +309,8 @@ def main():
     res["cases"].append(row_case("extract (host buffers) max_len=101", R, sec, int(ex.ln.sum()) + R, 1))
     res["extract_fitted"] = fit[0]
     g.close()
-    smem_case(a, res)
+    if not a.fmd:
+        smem_case(a, res)
     finish(a, res)
 
 
