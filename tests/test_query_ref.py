@@ -93,6 +93,40 @@ def test_reference_extend_bi_intervals(so):
     assert checked > 20
 
 
+@pytest.mark.parametrize("so", [0, 1, 2])
+@pytest.mark.parametrize("rev", [False, True])
+def test_vectorised_helpers_match_the_scalar_ones(so, rev):
+    """extend_many against extend, walk_all against walk; walk_all reads every row of the BWT exactly once"""
+    fm, strings = _build(so, rev, seed=70 + so)
+    rng = np.random.RandomState(so * 2 + rev)
+    iks = np.array([[x, rng.randint(0, fm.N + 1), 1] for x in range(fm.N)] + [[fm.N, fm.N, 0], [0, 0, fm.N], [0, 3, 0]], np.int64)
+    wide = np.stack([rng.randint(0, fm.N + 1, size=300), rng.randint(0, fm.N + 1, size=300), np.zeros(300, np.int64)], 1)
+    wide[:, 2] = [rng.randint(0, fm.N - x + 1) for x in wide[:, 0]]
+    wide[:, [0, 1]] = np.where((np.arange(300) % 2 == 0)[:, None], wide[:, [0, 1]], wide[:, [1, 0]])   # (so x[1] + x[2] <= N as well, half the time)
+    iks = np.concatenate([iks, wide, [[-3, 2, 5], [fm.N - 1, 0, 4], [2, fm.N + 2, 1]]])                 # out of range: clipped as extend clips
+    for is_back in (0, 1):
+        got = fm.extend_many(iks, is_back)
+        assert got.shape == (len(iks), 6, 3) and got.dtype == np.int64
+        want = np.stack([fm.extend(ik, is_back) for ik in iks])
+        assert np.array_equal(got, want), np.flatnonzero((got != want).reshape(len(iks), -1).any(1))[:5]
+    assert fm.extend_many(np.zeros((0, 3), np.int64), 1).shape == (0, 6, 3)
+    walked, visits = fm.walk_all()
+    assert len(walked) == fm.C[1] == len(strings)
+    for r, w in enumerate(walked):
+        assert w.dtype == np.uint8 and np.array_equal(w, fm.walk(r)), r
+    assert visits.shape == (fm.N,) and (visits == 1).all(), np.flatnonzero(visits != 1)[:5]
+    assert any(len(w) == 0 for w in walked) and max(len(w) for w in walked) == max(len(s) for s in strings)
+
+
+def test_walk_all_on_the_empty_index():
+    fm = Q.FM(np.zeros(0, np.uint8))
+    walked, visits = fm.walk_all()
+    assert walked == [] and len(visits) == 0
+    fm = Q.FM(np.zeros(3, np.uint8))                                # three empty strings
+    walked, visits = fm.walk_all()
+    assert [len(w) for w in walked] == [0, 0, 0] and visits.tolist() == [1, 1, 1]
+
+
 def test_query_symbols_exported():
     from ropebwt2_amd import build_all, load_hip_lib
     build_all()
