@@ -1774,6 +1774,12 @@ __global__ __launch_bounds__(SCHUNK / SBT) void k_sbscan3(const Ctl *ctl, const 
 // the stable 6-way partition into next round's buckets (mrope.c:303-309)
 // ---------------------------------------------------------------------------------------------
 
+// RB2_ADV_STAGE=1: the plain path (one engine, no transport) lays the tile's strings down in LDS run by run -- a tile's 512 strings go to at most
+// five runs, one per symbol that is not the sentinel -- and writes each run with consecutive lanes on consecutive addresses, instead of three
+// scattered stores per string whose wave falls into four or five pieces of ~16 lanes (0: the direct scatter; DESIGN 10, "k_advance's store side")
+#ifndef RB2_ADV_STAGE
+#define RB2_ADV_STAGE 1
+#endif
 template <bool AE, bool SPARSE, typename P> __device__ __forceinline__ bool advance_tile(const uint32_t tile, const Ctl *ctl, int side, int is_comp, uint32_t round, const uint8_t *s, const PoolView &newp,
 		const StrArrays<P> &S, ShardRec *send, const PushTab *push)
 {
@@ -1879,6 +1885,16 @@ template <bool AE, bool SPARSE, typename P> __device__ __forceinline__ bool adva
 	}
 	group_setup(G, t, araw, fixw, sym2, flag2);                 // (its barriers also cover the two tables)
 	uint32_t nz = 0;
+	// staged stores: record j of the tile = the j-th string of the tile in the order of the next round's arrays (symbol, then array order);
+	// the next symbol (A2) is a field of the cursor word and is taken from it on the way out
+	constexpr bool STAGED = RB2_ADV_STAGE != 0 && !SPARSE;     // (the in-place rounds keep the direct scatter: few strings, and their launch shares its blocks with the directory scan)
+	__shared__ uint64_t s_sw[STAGED ? STILE : 1]; __shared__ P s_sl[STAGED ? STILE : 1], s_su[STAGED && !AE ? STILE : 1];
+	const bool stage = STAGED && !send && !push;               // (block-uniform)
+	auto run_starts = [&](uint32_t rs[7]) {                    // rs[a]: first record of the strings that insert a, rs[6]: records in all (G.cpre[8]: the tile's count per symbol)
+		rs[0] = rs[1] = 0;
+#pragma unroll
+		for (int a6 = 1; a6 < 6; ++a6) rs[a6 + 1] = rs[a6] + G.cpre[8][a6];
+	};
 	// The two strings of a thread go through the kernel level by level -- group bookkeeping (LDS), then every gather of both, then the
 	// stores: written string after string, the second one's loads sat behind the first one's stores (the arrays may alias as far as the
 	// compiler knows) and a thread walked two chains of dependent round trips one after the other.
@@ -1906,6 +1922,7 @@ template <bool AE, bool SPARSE, typename P> __device__ __forceinline__ bool adva
 #pragma unroll
 		for (int h = 0; h < 2; ++h) if (act[h] && flag2[h]) sz[h] = (SIZE + t.base)[(uint32_t)(h * 256) + threadIdx.x];
 	}
+	if (STAGED) asm volatile("" ::: "memory");                 // (the run starts are read from LDS where they are used: hoisted to the barrier, they were live across group_member)
 #pragma unroll
 	for (int h = 0; h < 2; ++h) {
 		if (!act[h]) continue;
@@ -1922,9 +1939,34 @@ template <bool AE, bool SPARSE, typename P> __device__ __forceinline__ bool adva
 			if (!AE && u != l) push->ctl[pr]->ne[(round & 1) ^ 1] = 1;   // (the owner's flag: its next round sees a non-empty interval)
 		} else if (send) {                                     // sharded, RCCL transport: the string travels as a record, cursor and all
 			send[ctl->sdest[t.b][a] + m.pa] = shard_pack((uint64_t)l, (uint64_t)(u - l), 0u, wv[h]);
+		} else if (stage) {
+			uint32_t rs[7], r = 0;
+			run_starts(rs);
+#pragma unroll
+			for (int a6 = 2; a6 < 6; ++a6) r = a == a6 ? rs[a6] : r;
+			const uint32_t j = r + (m.pa - G.fix.tpre[a]);      // (m.pa - tpre: the tile's strings with a in front of mine)
+			s_sl[j] = l; s_sw[j] = wv[h];
+			if (!AE) { s_su[j] = u; nz += (u != l); }
 		} else {
 			L2[d] = l; W2[d] = wv[h]; A2[d] = (uint8_t)cur_sym(wv[h]);
 			if (!AE) { U2[d] = u; nz += (u != l); }            // AE: u == l for every string of the batch from here on; U is dead
+		}
+	}
+	if (stage) {
+		__syncthreads();
+		uint32_t rs[7];
+		run_starts(rs);
+#pragma unroll
+		for (int h = 0; h < 2; ++h) {
+			const uint32_t j = (uint32_t)(h * 256) + threadIdx.x;
+			if (j >= rs[6]) continue;
+			int a = 1; uint32_t r = 0;                           // the run record j lies in: the last one that starts at or in front of it (empty runs start where the next one does)
+#pragma unroll
+			for (int a6 = 2; a6 < 6; ++a6) if (j >= rs[a6]) { a = a6; r = rs[a6]; }
+			const uint32_t d = s_dst[a] + G.fix.tpre[a] + (j - r);   // = s_dst[a] + m.pa of the string that staged it
+			const uint64_t wj = s_sw[j];
+			L2[d] = s_sl[j]; W2[d] = wj; A2[d] = (uint8_t)cur_sym(wj);
+			if (!AE) U2[d] = s_su[j];
 		}
 	}
 	if (!AE && !send && !push) {                               // does the next round see a non-empty interval?  (a flag: plain store, no atomic)

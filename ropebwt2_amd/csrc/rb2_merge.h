@@ -274,7 +274,7 @@ template <bool FULL, int GPL_, typename P> __device__ __forceinline__ void merge
 		uint32_t p = p_first, a = a_first, lo = g_first;
 		if (jj != ln32) { a = A0[jj]; p = (uint32_t)E0[jj] - i0lo + jj; lo = p >> 6; }   // more than 64 new symbols in the window: read them again
 		uint32_t r = LP[8 * lo + a];                               // equal symbols in the groups of its leaf in front of its group
-		// all-ones where its code in the planes ($ <-> T) has the bit set: bit a of the set of symbols whose code has it (plane 0: A T N, plane 1: C T... as
+		// all-ones where its code in the planes ($ <-> T) has the bit set: bit a of the set of symbols whose code has it (plane 0: A G N, plane 1: C T... as
 		// numbers: 1 3 5 / 2 3 / 0 5) -- one signed bit-field extract per plane; then, per half, three three-input bit operations (v_bitop3_b32)
 		// AND together "plane bit equals code bit" and "below my position": 18 VALU per new symbol (r05: 34)
 		const uint32_t n0 = (uint32_t)__builtin_amdgcn_sbfe(0x2a, a, 1), n1 = (uint32_t)__builtin_amdgcn_sbfe(0x0c, a, 1), n2 = (uint32_t)__builtin_amdgcn_sbfe(0x21, a, 1);
