@@ -195,6 +195,31 @@ int64_t rb2_hip_smem(rb2_hip_t *h, int64_t n, const uint8_t *qry, const int64_t 
 void rb2_hip_smem_dev(rb2_hip_t *h, int64_t n, const uint8_t *qry, const int64_t *off, int64_t min_len, int64_t min_occ, int64_t max_mems,
                       int64_t *mem, int64_t *cnt);
 
+/* ---- sampled suffix array: from rows back to places in the strings ----
+ * String id k = the row of the $ block rb2_hip_extract takes (in input order the k-th string inserted); n = C[1] strings.  The walk of k
+ * starts at row k and takes LF steps until the BWT symbol is `$`; the row after j steps is the suffix of string k that starts j symbols
+ * before its end.  Every row lies on exactly one walk, and SA(row) = (k, len[k] - j): the string and the 0-based position in text order
+ * where the row's suffix starts; for the rows of the $ block that is (k, len[k]), the place of the sentinel.
+ * rb2_hip_ssa_build walks every string once (k_ssa_build) and keeps (k, j) of every row x with x % 2^log2_step == 0, the length of every
+ * string, and the string behind every whole-string row: 16 bytes per sample and 16 per string of device memory.  It returns the samples
+ * stored, ceil(N / 2^log2_step); an empty index gives 0.  log2_step outside 0 .. 30 is fatal.  The array describes the rows as they are
+ * now: an insert, rb2_hip_load_ropes, rb2_hip_load_fmd* and rb2_hip_reset drop it (rb2_hip_ssa_drop does so on request and frees its
+ * memory, rb2_hip_destroy too); a change between the dense and the sparse layout does not.  Building again replaces it.
+ * rb2_hip_ssa_info: out[0] 1 when an array is valid, out[1] its log2_step, out[2] its samples, out[3] the bytes of device memory held. */
+int64_t rb2_hip_ssa_build(rb2_hip_t *h, int log2_step);
+void    rb2_hip_ssa_drop(rb2_hip_t *h);
+void    rb2_hip_ssa_info(rb2_hip_t *h, int64_t out[4]);
+/* n intervals of rows iv[2*i], iv[2*i+1] = lo, hi (what backward_search, extend and smem return): hit[(i*max_hits + k)*2 ..] = string id,
+ * position of row lo + k for k < min(hi - lo, max_hits), in row order; cnt[i] = hi - lo, which may exceed max_hits (the surplus is counted,
+ * not stored), or -1 for lo < 0, hi > N or lo > hi (not an error).  Each row walks LF to the nearest sample or string end (k_locate): at
+ * most the length of its string, about 2^log2_step steps in a BWT of many strings.  Only the first min(cnt[i], max_hits) records of an
+ * interval are meaningful: the host variant returns the others as zeros, the device variant leaves them untouched.  Without a valid array
+ * the call is fatal (the message names rb2_hip_ssa_build); max_hits < 1 is fatal.  Returns the number of records stored.  The host variant
+ * stages chunks whose records (chunk * max_hits * 16 bytes) stay under 256 MiB, one interval at the least. */
+int64_t rb2_hip_locate(rb2_hip_t *h, int64_t n, const int64_t *iv, int64_t max_hits, int64_t *hit, int64_t *cnt);
+/* the same with iv, hit and cnt in this device's memory, asynchronous on the handle's stream (no return value: read cnt) */
+void    rb2_hip_locate_dev(rb2_hip_t *h, int64_t n, const int64_t *iv, int64_t max_hits, int64_t *hit, int64_t *cnt);
+
 /* 64-bit checksum of rope b computed on the device (position-weighted sum over the packed words of its pieces): equal for
  * equal symbol sequences however the index was built (one engine, N ranks, an .fmr loaded back), sensitive to order.  Lets
  * tests compare indexes of 10^11 symbols without moving them off the device (the reference has no counterpart; its ropes are

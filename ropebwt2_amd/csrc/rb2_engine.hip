@@ -238,6 +238,9 @@ struct rb2_hip_s {
 	DevBuf<uint64_t> qbuf;              // rank queries and their answers
 	DevBuf<QTab> qtab;                  // FM-index queries (rb2_query.h): the piece table of the launch ...
 	DevBuf<uint8_t> qbytes; DevBuf<int64_t> qin, qout;   // ... and the staging buffers of the host variants
+	// sampled suffix array (rb2_hip_ssa_build): it describes the rows as they were when it was built (index_rows_change)
+	DevBuf<uint64_t> ssa_smp, ssa_len, ssa_head;   // (string, step) of every row x with x % 2^ssa_s == 0; length of every string; string of the q-th whole-string row
+	bool ssa_valid = false; int ssa_s = 0; int64_t ssa_n = 0; uint64_t ssa_nstr = 0;   // ssa_n samples, ssa_nstr strings
 	uint64_t sp_nsb = 0;                // superblocks of the sparse pool (upper bound)
 	DevBuf<LeafDesc> LD;
 	DevBuf<uint8_t> A[2], INS_A, sbuf;   // A: symbol (+ flags) of every string this round; the other side receives next round's from k_advance
@@ -401,6 +404,17 @@ static uint64_t max_batch_strings()
 	return v;
 }
 
+/* The sampled suffix array belongs to one state of the rows.  Whatever is about to change the rows -- a batch (batch_begin: both inserts,
+ * one engine or a rank), a loader (ld_zero_pool), rb2_hip_reset -- calls this first; rb2_hip_ssa_drop and rb2_hip_destroy free it the same
+ * way.  A re-layout moves leaves, not rows, and does not come here. */
+static void index_rows_change(rb2_hip_t *h, bool drained = false)
+{
+	h->ssa_valid = false; h->ssa_s = 0; h->ssa_n = 0; h->ssa_nstr = 0;
+	if (!h->ssa_smp.p && !h->ssa_len.p && !h->ssa_head.p) return;
+	if (!drained) HIPCHK(hipStreamSynchronize(h->st));         // a rb2_hip_locate_dev may still be reading it
+	h->ssa_smp.release(); h->ssa_len.release(); h->ssa_head.release();
+}
+
 // split into strings (mrope.c:269-277), size the buffers, initial state (mrope.c:279-284).  false: more strings than a batch may
 // hold (B.m says how many) -- nothing was changed, the caller cuts the batch (may_split) or gives up.
 bool batch_begin(rb2_hip_t *h, BatchState &B, int64_t len64, const uint8_t *s, bool may_split = false)
@@ -423,6 +437,7 @@ bool batch_begin(rb2_hip_t *h, BatchState &B, int64_t len64, const uint8_t *s, b
 		if (res[1]) { rb2_fatal("[rb2_hip] the batch contains bytes that are not nt6 codes 0..5 ($ACGTN)\n"); }
 		if (m >= max_batch_strings() && may_split) { B.m = m; return false; }
 		if (m == 0 || m >= max_batch_strings()) { rb2_fatal("[rb2_hip] unsupported number of strings in one batch: %llu\n", (unsigned long long)m); }
+		index_rows_change(h);
 		h->START.ensure(m + 1);
 		hipLaunchKernelGGL(k_write_starts, dim3(nzb), dim3(256), 0, st, s, len, h->zblk.p, h->START.p);
 	}
@@ -1048,6 +1063,7 @@ void rb2_hip_destroy(rb2_hip_t *h)
 	if (!h) return;
 	HIPCHK(hipSetDevice(h->dev));
 	if (h->own_stream) HIPCHK(hipStreamSynchronize(h->st)); else HIPCHK(hipDeviceSynchronize());   /* a caller's stream (rb2_hip_use_stream) may be gone already */
+	index_rows_change(h, true);
 	for (int i = 0; i < 2; ++i) { h->pool[i].release(); h->L[i].release(); h->U[i].release(); h->W[i].release(); }
 	h->START.release(); h->SIZE.release(); h->INS_E.release(); h->RKREL.release(); h->RKOLD.release(); h->SPL.release(); h->qbuf.release(); h->zblk.release(); h->qtab.release(); h->qbytes.release(); h->qin.release(); h->qout.release();
 	h->LD.release(); h->A[0].release(); h->A[1].release(); h->INS_A.release(); h->sbuf.release(); h->sbuf2.release();
@@ -1069,6 +1085,7 @@ int rb2_hip_sorting_order(const rb2_hip_t *h) { return h->so; }
 void rb2_hip_reset(rb2_hip_t *h)
 { finish_pending(h);
 	HIPCHK(hipSetDevice(h->dev));
+	index_rows_change(h);
 	memset(h->h_rope, 0, sizeof(h->h_rope));
 	h->sparse = false; h->sp_backoff = h->sp_penalty = 0;
 	HIPCHK(hipMemsetAsync(&h->ctl->rope[0][0], 0, sizeof(RopeDesc) * 2 * NR, h->st));
@@ -1321,6 +1338,7 @@ static uint64_t ld_piece_table(rb2_hip_t *h, const char *who, const uint64_t tot
 static PoolView ld_zero_pool(rb2_hip_t *h, uint64_t leaf)
 {
 	hipStream_t st = h->st;
+	index_rows_change(h);
 	h->sparse = false; h->sp_backoff = h->sp_penalty = 0;      /* what is loaded is the dense layout */
 	h->pool[h->pside].ensure(leaf + SB, false, st);
 	PoolView pv = h->pool[h->pside].view();
@@ -1746,6 +1764,102 @@ void rb2_hip_smem_dev(rb2_hip_t *h, int64_t n, const uint8_t *qry, const int64_t
 	smem_check("smem_dev", min_len, min_occ, max_mems);
 	const int64_t CH = query_chunk(h);
 	for (int64_t i0 = 0; i0 < n; i0 += CH) launch_smem(h, std::min(CH, n - i0), qry, off + i0, 0, min_len, min_occ, max_mems, mem + i0 * max_mems * 5, cnt + i0);
+}
+
+/* ---- sampled suffix array: rows back to (string, position) (k_ssa_build, k_locate) ---- */
+
+static const int64_t SSA_LAUNCH = 1 << 24;                     /* DPP rows (strings, hit slots) per launch: 2^28 threads */
+
+int64_t rb2_hip_ssa_build(rb2_hip_t *h, int log2_step)
+{
+	query_begin(h, "ssa_build");
+	if (log2_step < 0 || log2_step > 30) { rb2_fatal("[rb2_hip] ssa_build: log2_step must be 0 .. 30 (got %d)\n", log2_step); }
+	index_rows_change(h);                                      // (an array that is there is freed first: the new one is sized exactly)
+	uint64_t N = 0;
+	for (int r = 0; r < NR; ++r) N += h->h_rope[r].n;
+	const uint64_t n = h->h_rope[0].n;                          // C[1]: rope $ is one piece
+	const uint64_t ns = (N + (1ull << log2_step) - 1) >> log2_step;
+	if (n) {
+		h->ssa_smp.ensure((size_t)ns * 2); h->ssa_len.ensure((size_t)n); h->ssa_head.ensure((size_t)n);
+		const PoolView pv = h->pool[h->pside].view();
+		for (uint64_t k0 = 0; k0 < n; k0 += (uint64_t)SSA_LAUNCH) {
+			const unsigned nb = (unsigned)cdiv(std::min<uint64_t>((uint64_t)SSA_LAUNCH, n - k0), QPB);
+			if (h->sparse) hipLaunchKernelGGL(k_ssa_build<true>, dim3(nb), dim3(256), 0, h->st, (const QTab*)h->qtab.p, pv, k0, n, log2_step, h->ssa_smp.p, h->ssa_len.p, h->ssa_head.p);
+			else hipLaunchKernelGGL(k_ssa_build<false>, dim3(nb), dim3(256), 0, h->st, (const QTab*)h->qtab.p, pv, k0, n, log2_step, h->ssa_smp.p, h->ssa_len.p, h->ssa_head.p);
+			HIPCHK(hipGetLastError());
+		}
+		HIPCHK(hipStreamSynchronize(h->st));
+	}
+	h->ssa_valid = true; h->ssa_s = log2_step; h->ssa_n = (int64_t)ns; h->ssa_nstr = n;
+	return (int64_t)ns;
+}
+
+void rb2_hip_ssa_drop(rb2_hip_t *h)
+{ finish_pending(h);
+	HIPCHK(hipSetDevice(h->dev));
+	index_rows_change(h);
+}
+
+void rb2_hip_ssa_info(rb2_hip_t *h, int64_t out[4])
+{
+	out[0] = h->ssa_valid ? 1 : 0; out[1] = h->ssa_s; out[2] = h->ssa_n;
+	out[3] = (int64_t)((h->ssa_smp.cap + h->ssa_len.cap + h->ssa_head.cap) * sizeof(uint64_t));
+}
+
+static void locate_check(rb2_hip_t *h, const char *who, int64_t max_hits)
+{
+	if (!h->ssa_valid) { rb2_fatal("[rb2_hip] %s: the index has no sampled suffix array (none was built, or the index changed since): call rb2_hip_ssa_build first\n", who); }
+	if (max_hits < 1) { rb2_fatal("[rb2_hip] %s: max_hits must be at least 1 (got %lld)\n", who, (long long)max_hits); }
+}
+
+/* n intervals, all device pointers; hit and cnt belong to interval 0 of iv.  One launch takes SSA_LAUNCH slots: whole intervals, or a part
+ * of the hits of one interval when max_hits alone is larger */
+static void launch_locate(rb2_hip_t *h, int64_t n, const int64_t *iv, int64_t max_hits, int64_t *hit, int64_t *cnt)
+{
+	const PoolView pv = h->pool[h->pside].view();
+	const int64_t kn = std::min(max_hits, SSA_LAUNCH), per = std::max<int64_t>(1, SSA_LAUNCH / kn);
+	for (int64_t i0 = 0; i0 < n; i0 += per) {
+		const int64_t nc = std::min(per, n - i0);
+		for (int64_t k0 = 0; k0 < max_hits; k0 += kn) {
+			const int64_t kc = std::min(kn, max_hits - k0);
+			const unsigned nb = (unsigned)cdiv((uint64_t)(nc * kc), QPB);
+			if (h->sparse) hipLaunchKernelGGL(k_locate<true>, dim3(nb), dim3(256), 0, h->st, (const QTab*)h->qtab.p, pv, iv + 2 * i0, (uint64_t)nc, max_hits, k0, kc, h->ssa_s,
+					(const uint64_t*)h->ssa_smp.p, (const uint64_t*)h->ssa_len.p, (const uint64_t*)h->ssa_head.p, h->ssa_nstr, hit + i0 * max_hits * 2, cnt + i0);
+			else hipLaunchKernelGGL(k_locate<false>, dim3(nb), dim3(256), 0, h->st, (const QTab*)h->qtab.p, pv, iv + 2 * i0, (uint64_t)nc, max_hits, k0, kc, h->ssa_s,
+					(const uint64_t*)h->ssa_smp.p, (const uint64_t*)h->ssa_len.p, (const uint64_t*)h->ssa_head.p, h->ssa_nstr, hit + i0 * max_hits * 2, cnt + i0);
+			HIPCHK(hipGetLastError());
+		}
+	}
+}
+
+int64_t rb2_hip_locate(rb2_hip_t *h, int64_t n, const int64_t *iv, int64_t max_hits, int64_t *hit, int64_t *cnt)
+{
+	query_begin(h, "locate");
+	locate_check(h, "locate", max_hits);
+	if (n <= 0) return 0;
+	const int64_t CH = std::max<int64_t>(1, std::min<int64_t>(query_chunk(h), SMEM_STAGE_BYTES / 16 / max_hits));   // the records of a chunk: under 256 MiB, one interval at the least
+	int64_t stored = 0;
+	for (int64_t i0 = 0; i0 < n; i0 += CH) {
+		const int64_t nc = std::min(CH, n - i0);
+		h->qin.ensure((size_t)nc * 3); h->qout.ensure((size_t)(nc * max_hits) * 2);
+		int64_t *d_iv = h->qin.p, *d_cnt = h->qin.p + 2 * nc;
+		HIPCHK(hipMemcpyAsync(d_iv, iv + 2 * i0, (size_t)nc * 16, hipMemcpyHostToDevice, h->st));
+		HIPCHK(hipMemsetAsync(h->qout.p, 0, (size_t)(nc * max_hits) * 16, h->st));   // the records no slot writes come back as zeros
+		launch_locate(h, nc, d_iv, max_hits, h->qout.p, d_cnt);
+		HIPCHK(hipMemcpyAsync(cnt + i0, d_cnt, (size_t)nc * 8, hipMemcpyDeviceToHost, h->st));
+		HIPCHK(hipMemcpyAsync(hit + i0 * max_hits * 2, h->qout.p, (size_t)(nc * max_hits) * 16, hipMemcpyDeviceToHost, h->st));
+		HIPCHK(hipStreamSynchronize(h->st));
+		for (int64_t i = i0; i < i0 + nc; ++i) stored += std::min(std::max<int64_t>(cnt[i], 0), max_hits);
+	}
+	return stored;
+}
+
+void rb2_hip_locate_dev(rb2_hip_t *h, int64_t n, const int64_t *iv, int64_t max_hits, int64_t *hit, int64_t *cnt)
+{
+	query_begin(h, "locate_dev");
+	locate_check(h, "locate_dev", max_hits);
+	if (n <= 0) return;
+	launch_locate(h, n, iv, max_hits, hit, cnt);
 }
 
 /* checksum of sub-rope r (k_piece_hash); the handle must hold the piece in the dense layout */

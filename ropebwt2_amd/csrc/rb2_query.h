@@ -267,4 +267,73 @@ template <bool SPARSE> __global__ __launch_bounds__(256) __attribute__((amdgpu_w
 	if (g == 0) cnt[i] = k;
 }
 
+// ---- sampled suffix array ----
+// String k = row k of the $ block; its walk x_0 = k, x_{j+1} = LF(x_j) ends at the first row whose symbol is `$`, after len[k] steps.
+// Row x_j is the suffix of string k that starts j symbols before its end: SA(x_j) = (k, len[k] - j).  The walks are the cycles of LF cut
+// at the `$`s, so every row lies on exactly one walk and every slot below is written by exactly one string: no atomics.
+//   smp[2 * (x >> s) ..] = k, j    for the rows x with x % 2^s == 0 (two 64-bit words: ids go up to n, distances up to 2^48)
+//   slen[k] = len[k]               head[q] = k for the q-th whole-string row (q = the `$`s in front of the row where the walk of k ends)
+// A walk is cut off after N steps and an index out of range is not stored: an index that is no BWT of complete strings (load_ropes takes
+// any six streams with consistent totals) then gives a wrong array, never a write out of bounds or a kernel that does not end.
+
+// the walks of strings k0 .. n - 1 (n = C[1]) as far as the launch reaches, one string per DPP row
+template <bool SPARSE> __global__ __launch_bounds__(256) void k_ssa_build(const QTab *Tg, PoolView pv, uint64_t k0, uint64_t n, int s, uint64_t *smp, uint64_t *slen, uint64_t *head)
+{
+	__shared__ QTab T;
+	qtab_load(Tg, T);
+	const uint64_t k = k0 + (uint64_t)blockIdx.x * QPB + (threadIdx.x >> 4);
+	if (k >= n) return;
+	const uint32_t g = (uint32_t)lane_id() & 15u;
+	const uint64_t N = T.row0[NR], mask = (1ull << s) - 1;
+	uint64_t x = k, j = 0, c6[6];
+	for (;;) {
+		uint32_t c;
+		qrank<SPARSE>(T, pv, x, c6, &c);
+		if ((x & mask) == 0 && g < 2) smp[2 * (x >> s) + g] = g ? j : k;   // two lanes, one 16-byte sample
+		if (c == 0 || j >= N) break;
+		++j;
+		x = qC(T, (int)c) + c6[c];                             // LF
+		if (x >= N) break;
+	}
+	if (g == 0) { slen[k] = j; if (c6[0] < n) head[c6[0]] = k; }
+}
+
+// rows to places: slot q of the launch is hit kk = k0 + q % kn of interval i = q / kn (kn hits of every interval per launch, from k0 on:
+// kn = max_hits and k0 = 0 unless one interval alone has more slots than a launch takes).  The row lo_i + kk walks LF, counting its
+// steps t, to the first row that is a sample (sid, j): (sid, len[sid] - j + t) -- or whose symbol is `$`: (head[`$`s in front], t).  The
+// sample is tested first, so the rows of the $ block need no case of their own: row k < n is step 0 of the walk of string k, and what the
+// walk from it meets -- a sample of string k at step j (t = j) or the end of string k (t = len[k]) -- gives (k, len[k]) either way.
+// hit[(i * max_hits + kk) * 2 ..] = string, position; cnt[i] = hi - lo, -1 for a malformed interval (written by the slot of hit 0).
+template <bool SPARSE> __global__ __launch_bounds__(256) void k_locate(const QTab *Tg, PoolView pv, const int64_t *iv, uint64_t n, int64_t max_hits, int64_t k0, int64_t kn,
+                                                                       int s, const uint64_t *smp, const uint64_t *slen, const uint64_t *head, uint64_t nstr,
+                                                                       int64_t *hit, int64_t *cnt)
+{
+	__shared__ QTab T;
+	qtab_load(Tg, T);
+	const uint64_t q = (uint64_t)blockIdx.x * QPB + (threadIdx.x >> 4);
+	if (q >= n * (uint64_t)kn) return;
+	const uint64_t i = q / (uint64_t)kn;
+	const int64_t kk = k0 + (int64_t)(q % (uint64_t)kn);
+	const uint32_t g = (uint32_t)lane_id() & 15u;
+	const int64_t lo = iv[2 * i], hi = iv[2 * i + 1], N = (int64_t)T.row0[NR];
+	const bool bad = lo < 0 || hi > N || lo > hi;
+	if (kk == 0 && g == 0) cnt[i] = bad ? -1 : hi - lo;
+	if (bad || kk >= hi - lo) return;
+	const uint64_t mask = (1ull << s) - 1;
+	uint64_t x = (uint64_t)(lo + kk), t = 0, sid = 0, pos = 0;
+	for (;;) {
+		if ((x & mask) == 0) {
+			sid = smp[2 * (x >> s)];
+			pos = (sid < nstr ? slen[sid] : 0) - smp[2 * (x >> s) + 1] + t;
+			break;
+		}
+		uint64_t c6[6]; uint32_t c;
+		qrank<SPARSE>(T, pv, x, c6, &c);
+		if (c == 0) { sid = c6[0] < nstr ? head[c6[0]] : 0; pos = t; break; }
+		x = qC(T, (int)c) + c6[c];                             // LF
+		if (++t > (uint64_t)N || x >= (uint64_t)N) break;      // (no BWT of complete strings)
+	}
+	if (g < 2) hit[(i * (uint64_t)max_hits + (uint64_t)kk) * 2 + g] = (int64_t)(g ? pos : sid);
+}
+
 } // namespace rb2

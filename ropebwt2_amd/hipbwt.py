@@ -54,6 +54,11 @@ def load_hip_lib():
         "rb2_hip_extract": (i64, [vp, i64, vp, i64, vp, vp]),
         "rb2_hip_smem": (i64, [vp, i64, vp, vp, i64, i64, i64, vp, vp]),
         "rb2_hip_smem_dev": (None, [vp, i64, vp, vp, i64, i64, i64, vp, vp]),
+        "rb2_hip_ssa_build": (i64, [vp, i32]),
+        "rb2_hip_ssa_drop": (None, [vp]),
+        "rb2_hip_ssa_info": (None, [vp, vp]),
+        "rb2_hip_locate": (i64, [vp, i64, vp, i64, vp, vp]),
+        "rb2_hip_locate_dev": (None, [vp, i64, vp, i64, vp, vp]),
         "rb2_hip_reserve": (None, [vp, i64, i64, i64]),
         "rb2_hip_num_subropes": (i32, []),
         "rb2_hip_memcpy": (None, [vp, vp, vp, i64, i32]),
@@ -119,6 +124,7 @@ ABI_SYMBOLS = [
     "rb2_hip_insert_multi", "rb2_hip_insert_multi_dev", "rb2_hip_set_lazy", "rb2_hip_wait", "rb2_hip_last_batch_counts", "rb2_hip_prefetch", "rb2_hip_mem_info", "rb2_hip_get_counts", "rb2_hip_rope_bytes",
     "rb2_hip_download_rope", "rb2_hip_stream_rope", "rb2_hip_load_ropes", "rb2_hip_load_fmd", "rb2_hip_load_fmd_file", "rb2_hip_rank1a", "rb2_hip_rank_batch", "rb2_hip_reserve",
     "rb2_hip_backward_search", "rb2_hip_backward_search_dev", "rb2_hip_extend", "rb2_hip_extract", "rb2_hip_smem", "rb2_hip_smem_dev", "rb2_hip_dev_alloc",
+    "rb2_hip_ssa_build", "rb2_hip_ssa_drop", "rb2_hip_ssa_info", "rb2_hip_locate", "rb2_hip_locate_dev",
     "rb2_hip_num_subropes", "rb2_hip_memcpy", "rb2_hip_use_stream",
     "rb2_hip_dev_free", "rb2_hip_synth_reads", "rb2_hip_synth_reads_cov", "rb2_hip_synth_reads_skew", "rb2_hip_sync", "rb2_hip_sparse_stats", "rb2_hip_layout_stats", "rb2_hip_rewind_stats", "rb2_hip_window_stats", "rb2_hip_host_register", "rb2_hip_host_unregister", "rb2_hip_profile",
     "rb2_hip_profile_get", "rb2_hip_kernel_name", "rb2_hip_layout",
@@ -371,6 +377,55 @@ class HipBwt:
     def smem_dev(self, n, qry_dev, off_dev, mem_dev, cnt_dev, min_len=1, min_occ=1, max_mems=64):
         """rb2_hip_smem_dev: all four pointers in this device's memory; asynchronous on the handle's stream"""
         self.L.rb2_hip_smem_dev(self.h, n, qry_dev, off_dev, min_len, min_occ, max_mems, mem_dev, cnt_dev)
+
+    # -- sampled suffix array: rows back to (string id, position) (include/rb2_hip.h) ----------------------------------------
+    def build_ssa(self, log2_step=5):
+        """rb2_hip_ssa_build: sample every row that is a multiple of 2**log2_step; returns the samples stored.  Valid until the
+        index changes (an insert, a load, reset)"""
+        return int(self.L.rb2_hip_ssa_build(self.h, int(log2_step)))
+
+    def drop_ssa(self):
+        self.L.rb2_hip_ssa_drop(self.h)
+
+    def ssa_info(self):
+        a = np.zeros(4, np.int64)
+        self.L.rb2_hip_ssa_info(self.h, a.ctypes.data)
+        return {"valid": bool(a[0]), "log2_step": int(a[1]), "samples": int(a[2]), "device_bytes": int(a[3])}
+
+    def locate_raw(self, intervals, max_hits):
+        """rb2_hip_locate as it is: (records stored, hit (n, max_hits, 2) int64 = string id, position, cnt (n,) int64); only the first
+        min(cnt[i], max_hits) records of interval i are meaningful (the others are zeros), cnt[i] = -1 for a malformed interval"""
+        iv = np.ascontiguousarray(np.asarray(intervals, dtype=np.int64).reshape(-1, 2))
+        n = len(iv)
+        hit = np.zeros((n, max(int(max_hits), 0), 2), np.int64)
+        cnt = np.zeros(n, np.int64)
+        stored = self.L.rb2_hip_locate(self.h, n, iv.ctypes.data, max_hits, hit.ctypes.data, cnt.ctypes.data)
+        return int(stored), hit, cnt
+
+    def locate(self, intervals, max_hits=64):
+        """the places of the rows of every interval (lo, hi): a list with one (m, 2) int64 array per interval, rows = string id,
+        position (0-based, text order) in row order, m = min(hi - lo, max_hits); a malformed interval raises ValueError"""
+        stored, hit, cnt = self.locate_raw(intervals, max_hits)
+        if (cnt < 0).any():
+            raise ValueError("malformed intervals (0 <= lo <= hi <= rows): %s" % np.flatnonzero(cnt < 0)[:5].tolist())
+        return [hit[i, :min(int(cnt[i]), max_hits)].copy() for i in range(len(cnt))]
+
+    def locate_dev(self, n, iv_dev, hit_dev, cnt_dev, max_hits=64):
+        """rb2_hip_locate_dev: all three pointers in this device's memory; asynchronous on the handle's stream"""
+        self.L.rb2_hip_locate_dev(self.h, n, iv_dev, max_hits, hit_dev, cnt_dev)
+
+    def find(self, patterns, max_hits=64):
+        """where every pattern (str / bytes over $ACGTN, or nt6 arrays) occurs: backward search, then locate for the patterns that
+        matched in full.  One (m, 2) int64 array per pattern, rows = string id, position of the pattern's first symbol, at most
+        max_hits of them; empty for a pattern that does not occur"""
+        lens = np.array([len(encode_pattern(p)) for p in patterns], np.int64)
+        lo, hi, m = self.backward_search(patterns)
+        full = np.flatnonzero(m == lens)
+        out = [np.zeros((0, 2), np.int64) for _ in patterns]
+        if len(full):
+            for i, h in zip(full, self.locate(np.stack([lo[full], hi[full]], 1), max_hits)):
+                out[i] = h
+        return out
 
     # -- measurement helpers ----------------------------------------------------------------
     def dev_alloc(self, nbytes):

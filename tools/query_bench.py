@@ -17,6 +17,10 @@ With --fmd the index is not built but loaded from an .fmd file (rb2_hip_load_fmd
 records the load -- file bytes, seconds (first load and the median of three more), GB of file per second -- and the smem cases, which
 need an index of their own reads, are left out.  "hits" are then hits only if the file holds the reads of the generator.
 With --only smem and an --out file that exists, the smem cases replace those of the file and the rest of it stays.
+With --locate only the sampled suffix array is measured, on the index of the first cases (single strand), and stored under "locate" in
+the --out file, whose other entries stay: rb2_hip_ssa_build at log2_step 3, 5 and 7 (seconds, LF steps per second -- one step per row of
+the index --, bytes held), and at each step locate_dev for the intervals of P substring patterns of length 20 and 64 with max_hits 16
+(hits per second).
 """
 import argparse
 import json
@@ -220,6 +224,56 @@ def smem_case(a, res):
     res["cases"] = [c for c in res["cases"] if "smem" not in c["case"].lower()] + [row, brow, hrow]
 
 
+def locate_case(a, res):
+    L = 101
+    n = a.reads or -(-(int(4 * 1024 ** 3 * 0.97) + 1) // (L + 1))
+    g = HipBwt(a.so)
+    p = g.dev_alloc(n * (L + 1))
+    g.synth_reads(p, 0, n, L, seed=42)
+    g.insert_multi_dev(p, n * (L + 1))
+    g.sync()
+    g.dev_free(p)
+    N = int(g.counts().sum())
+    P, M = a.patterns, 16
+    ivs = {}
+    for Lp in (20, 64):                                              # the intervals of substrings of the reads, kept on the device
+        pats = hit_patterns(P, Lp, n, Lp)
+        flat = np.ascontiguousarray(pats.reshape(-1)); off = np.arange(P + 1, dtype=np.int64) * Lp
+        dp, do, dq = g.dev_alloc(len(flat)), g.dev_alloc(8 * (P + 1)), g.dev_alloc(24 * P)
+        g.L.rb2_hip_memcpy(g.h, dp, flat.ctypes.data, len(flat), 0)
+        g.L.rb2_hip_memcpy(g.h, do, off.ctypes.data, 8 * (P + 1), 0)
+        g.backward_search_dev(P, dp, do, dq)
+        out = np.zeros((P, 3), np.int64)
+        g.L.rb2_hip_memcpy(g.h, out.ctypes.data, dq, 24 * P, 1)
+        for q in (dp, do, dq):
+            g.dev_free(q)
+        assert (out[:, 2] == Lp).all()
+        ivs[Lp] = np.ascontiguousarray(out[:, :2])
+    d_iv, d_hit, d_cnt = g.dev_alloc(16 * P), g.dev_alloc(16 * M * P), g.dev_alloc(8 * P)
+    rows = []
+    for s in (3, 5, 7):
+        sec = timed(lambda: g.build_ssa(s), lambda: None)           # (rb2_hip_ssa_build synchronises before it returns)
+        inf = g.ssa_info()
+        row = {"case": "ssa_build log2_step=%d" % s, "seconds": sec, "lf_steps": N, "lf_steps_per_s": N / sec, "samples": inf["samples"],
+               "device_bytes": inf["device_bytes"], "bytes_per_row": inf["device_bytes"] / N, "measured": True, "locate": []}
+        print("locate: built step %d in %.3f s" % (s, sec), file=sys.stderr, flush=True)
+        for Lp in (20, 64):
+            g.L.rb2_hip_memcpy(g.h, d_iv, ivs[Lp].ctypes.data, 16 * P, 0)
+            lsec = timed(lambda: g.locate_dev(P, d_iv, d_hit, d_cnt, M), g.sync)
+            cnt = np.zeros(P, np.int64)
+            g.L.rb2_hip_memcpy(g.h, cnt.ctypes.data, d_cnt, 8 * P, 1)
+            assert np.array_equal(cnt, ivs[Lp][:, 1] - ivs[Lp][:, 0])
+            hits = int(np.minimum(cnt, M).sum())
+            row["locate"].append({"case": "locate_dev, intervals of %d substrings of length %d, max_hits=%d" % (P, Lp, M), "intervals": P, "slots": P * M,
+                                  "hits": hits, "intervals_with_more_than_max_hits": int((cnt > M).sum()), "seconds": lsec, "hits_per_s": hits / lsec,
+                                  "intervals_per_s": P / lsec, "measured": True})
+        rows.append(row)
+    for q in (d_iv, d_hit, d_cnt):
+        g.dev_free(q)
+    res["locate"] = {"index": {"reads": n, "read_len": L, "sorting_order": a.so, "symbols": N, "strands": 1, "layout": g.layout_stats()}, "cases": rows}
+    g.close()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default="")
@@ -232,7 +286,16 @@ def main():
     ap.add_argument("--step-queries", type=int, default=200_000, help="queries the SMEM extension steps are counted on")
     ap.add_argument("--only", default="", help="'smem': only the smem cases (added to an existing --out file)")
     ap.add_argument("--fmd", default="", help="load the index from this .fmd file instead of building it")
+    ap.add_argument("--locate", action="store_true", help="only the sampled suffix array: build and locate rates (added to an existing --out file)")
     a = ap.parse_args()
+    if a.locate:
+        res = {"cases": []}
+        if a.out and os.path.exists(a.out):
+            with open(a.out) as f:
+                res = json.load(f)
+        locate_case(a, res)
+        finish(a, res)
+        return
     if a.only == "smem":
         res = {"cases": []}
         if a.out and os.path.exists(a.out):
