@@ -220,6 +220,35 @@ int64_t rb2_hip_locate(rb2_hip_t *h, int64_t n, const int64_t *iv, int64_t max_h
 /* the same with iv, hit and cnt in this device's memory, asynchronous on the handle's stream (no return value: read cnt) */
 void    rb2_hip_locate_dev(rb2_hip_t *h, int64_t n, const int64_t *iv, int64_t max_hits, int64_t *hit, int64_t *cnt);
 
+/* ---- suffix-prefix overlaps: which strings of the index begin with a suffix of a query ----
+ * A row of the interval [lo, hi) of a non-empty pattern P whose BWT symbol is `$` is the row of a whole string that starts with P: the
+ * index holds occ($,hi) - occ($,lo) strings with the prefix P, and the `$` ranks q in [occ($,lo), occ($,hi)) name them.
+ * rb2_hip_overlap: n queries as for rb2_hip_smem (nt6 codes in text order, concatenated in qry[off[i] .. off[i+1]); 1..4 match; 5 (N) is
+ * legal but belongs to no overlap: the search of a query stops at the first N met from the query's end; 0 or a code above 5 makes the query
+ * malformed).  For every length l, min_ovlp <= l <= len, whose suffix q[len-l ..) occurs and is the prefix of at least one string there is
+ * one record rec[(i*max_recs + k)*3 ..] = l, zlo, zhi, in increasing l: [zlo, zhi) is the range of `$` ranks of those strings (zhi - zlo
+ * of them; rb2_hip_string_ids names them).  l == len is reported too: the query itself when it is in the index, its copies, and the strings
+ * it is a proper prefix of.  cnt[i] = records found, which may exceed max_recs (the surplus is counted, not stored; len - min_ovlp + 1
+ * always suffices), 0 for the empty query, -1 for a malformed one.  Only the first min(cnt[i], max_recs) records of a query are meaningful:
+ * the host variant returns the others as zeros, the device variant leaves them untouched.  min_ovlp and max_recs below 1 are fatal.
+ * Returns the number of records stored.  No suffix array is needed.  The index may hold one strand or both: the reverse-complement overlaps
+ * of a query are the overlaps of its reverse complement on an index of both strands.  One backward search per query whose every step reads
+ * the `$` counts along with the step's own (k_overlap): at most len rank pairs.  The host variant stages chunks whose records (chunk *
+ * max_recs * 24 bytes) stay under 256 MiB, one query at the least. */
+int64_t rb2_hip_overlap(rb2_hip_t *h, int64_t n, const uint8_t *qry, const int64_t *off, int64_t min_ovlp, int64_t max_recs, int64_t *rec, int64_t *cnt);
+/* the same with qry, off, rec and cnt in this device's memory, asynchronous on the handle's stream (no return value: read cnt) */
+void    rb2_hip_overlap_dev(rb2_hip_t *h, int64_t n, const uint8_t *qry, const int64_t *off, int64_t min_ovlp, int64_t max_recs, int64_t *rec, int64_t *cnt);
+/* n ranges of `$` ranks zv[2*i], zv[2*i+1] = zlo, zhi (what rb2_hip_overlap returns): ids[i*max_hits + k] = the string behind the
+ * (zlo + k)-th `$` of the BWT for k < min(zhi - zlo, max_hits), ids as in rb2_hip_extract and rb2_hip_locate; cnt[i] = zhi - zlo, which may
+ * exceed max_hits (the surplus is counted, not stored), or -1 for zlo < 0, zhi > the number of strings or zlo > zhi (not an error).  Only
+ * the first min(cnt[i], max_hits) ids of a range are meaningful: the host variant returns the others as zeros, the device variant leaves
+ * them untouched.  A gather from the suffix array's table of whole-string rows (k_string_ids), so it needs a valid array of any log2_step:
+ * without one the call is fatal (the message names rb2_hip_ssa_build); max_hits < 1 is fatal.  Returns the number of ids stored.  The host
+ * variant stages chunks whose ids (chunk * max_hits * 8 bytes) stay under 256 MiB, one range at the least. */
+int64_t rb2_hip_string_ids(rb2_hip_t *h, int64_t n, const int64_t *zv, int64_t max_hits, int64_t *ids, int64_t *cnt);
+/* the same with zv, ids and cnt in this device's memory, asynchronous on the handle's stream (no return value: read cnt) */
+void    rb2_hip_string_ids_dev(rb2_hip_t *h, int64_t n, const int64_t *zv, int64_t max_hits, int64_t *ids, int64_t *cnt);
+
 /* 64-bit checksum of rope b computed on the device (position-weighted sum over the packed words of its pieces): equal for
  * equal symbol sequences however the index was built (one engine, N ranks, an .fmr loaded back), sensitive to order.  Lets
  * tests compare indexes of 10^11 symbols without moving them off the device (the reference has no counterpart; its ropes are

@@ -1862,6 +1862,104 @@ void rb2_hip_locate_dev(rb2_hip_t *h, int64_t n, const int64_t *iv, int64_t max_
 	launch_locate(h, n, iv, max_hits, hit, cnt);
 }
 
+/* ---- suffix-prefix overlaps: the strings that begin with a suffix of a query (k_overlap, k_string_ids) ---- */
+
+static void launch_overlap(rb2_hip_t *h, int64_t n, const uint8_t *qry, const int64_t *off, int64_t base, int64_t min_ovlp, int64_t max_recs, int64_t *rec, int64_t *cnt)
+{
+	const PoolView pv = h->pool[h->pside].view();
+	if (h->sparse) hipLaunchKernelGGL(k_overlap<true>, dim3(cdiv((uint64_t)n, QPB)), dim3(256), 0, h->st, (const QTab*)h->qtab.p, pv, qry, off, base, (uint64_t)n, min_ovlp, max_recs, rec, cnt);
+	else hipLaunchKernelGGL(k_overlap<false>, dim3(cdiv((uint64_t)n, QPB)), dim3(256), 0, h->st, (const QTab*)h->qtab.p, pv, qry, off, base, (uint64_t)n, min_ovlp, max_recs, rec, cnt);
+	HIPCHK(hipGetLastError());
+}
+
+static void overlap_check(const char *who, int64_t min_ovlp, int64_t max_recs)
+{
+	if (min_ovlp < 1 || max_recs < 1)
+		rb2_fatal("[rb2_hip] %s: min_ovlp and max_recs must be at least 1 (got %lld, %lld)\n", who, (long long)min_ovlp, (long long)max_recs);
+}
+
+int64_t rb2_hip_overlap(rb2_hip_t *h, int64_t n, const uint8_t *qry, const int64_t *off, int64_t min_ovlp, int64_t max_recs, int64_t *rec, int64_t *cnt)
+{
+	query_begin(h, "overlap");
+	if (n <= 0) return 0;
+	overlap_check("overlap", min_ovlp, max_recs);
+	for (int64_t i = 0; i < n; ++i)
+		if (off[i + 1] < off[i] || off[0] < 0) { rb2_fatal("[rb2_hip] overlap: query offsets must be non-negative and non-decreasing (off[%lld])\n", (long long)i); }
+	const int64_t CH = std::max<int64_t>(1, std::min<int64_t>(query_chunk(h), SMEM_STAGE_BYTES / 24 / max_recs));   // the records of a chunk: under 256 MiB, one query at the least
+	int64_t stored = 0;
+	for (int64_t i0 = 0; i0 < n; i0 += CH) {
+		const int64_t nc = std::min(CH, n - i0), b0 = off[i0], nb = off[i0 + nc] - b0;
+		h->qin.ensure((size_t)nc * 2 + 1); h->qout.ensure((size_t)(nc * max_recs) * 3); h->qbytes.ensure((size_t)std::max<int64_t>(nb, 1));
+		int64_t *d_off = h->qin.p, *d_cnt = h->qin.p + nc + 1;
+		HIPCHK(hipMemcpyAsync(d_off, off + i0, (size_t)(nc + 1) * 8, hipMemcpyHostToDevice, h->st));
+		if (nb) HIPCHK(hipMemcpyAsync(h->qbytes.p, qry + b0, (size_t)nb, hipMemcpyHostToDevice, h->st));
+		HIPCHK(hipMemsetAsync(h->qout.p, 0, (size_t)(nc * max_recs) * 24, h->st));   // the records no query writes come back as zeros
+		launch_overlap(h, nc, h->qbytes.p, d_off, b0, min_ovlp, max_recs, h->qout.p, d_cnt);
+		HIPCHK(hipMemcpyAsync(cnt + i0, d_cnt, (size_t)nc * 8, hipMemcpyDeviceToHost, h->st));
+		HIPCHK(hipMemcpyAsync(rec + i0 * max_recs * 3, h->qout.p, (size_t)(nc * max_recs) * 24, hipMemcpyDeviceToHost, h->st));
+		HIPCHK(hipStreamSynchronize(h->st));
+		for (int64_t i = i0; i < i0 + nc; ++i) stored += std::min(std::max<int64_t>(cnt[i], 0), max_recs);
+	}
+	return stored;
+}
+
+void rb2_hip_overlap_dev(rb2_hip_t *h, int64_t n, const uint8_t *qry, const int64_t *off, int64_t min_ovlp, int64_t max_recs, int64_t *rec, int64_t *cnt)
+{
+	query_begin(h, "overlap_dev");
+	if (n <= 0) return;
+	overlap_check("overlap_dev", min_ovlp, max_recs);
+	const int64_t CH = query_chunk(h);
+	for (int64_t i0 = 0; i0 < n; i0 += CH) launch_overlap(h, std::min(CH, n - i0), qry, off + i0, 0, min_ovlp, max_recs, rec + i0 * max_recs * 3, cnt + i0);
+}
+
+static const int64_t IDS_LAUNCH = 1 << 28;                     /* hit slots (threads) per launch of k_string_ids */
+
+/* n ranges, all device pointers; ids and cnt belong to range 0 of zv.  One launch takes IDS_LAUNCH slots: whole ranges, or a part of the
+ * hits of one range when max_hits alone is larger (as launch_locate) */
+static void launch_string_ids(rb2_hip_t *h, int64_t n, const int64_t *zv, int64_t max_hits, int64_t *ids, int64_t *cnt)
+{
+	const int64_t kn = std::min(max_hits, IDS_LAUNCH), per = std::max<int64_t>(1, IDS_LAUNCH / kn);
+	for (int64_t i0 = 0; i0 < n; i0 += per) {
+		const int64_t nc = std::min(per, n - i0);
+		for (int64_t k0 = 0; k0 < max_hits; k0 += kn) {
+			const int64_t kc = std::min(kn, max_hits - k0);
+			hipLaunchKernelGGL(k_string_ids, dim3((unsigned)cdiv((uint64_t)(nc * kc), 256)), dim3(256), 0, h->st, zv + 2 * i0, (uint64_t)nc, max_hits, k0, kc,
+					(const uint64_t*)h->ssa_head.p, h->ssa_nstr, ids + i0 * max_hits, cnt + i0);
+			HIPCHK(hipGetLastError());
+		}
+	}
+}
+
+int64_t rb2_hip_string_ids(rb2_hip_t *h, int64_t n, const int64_t *zv, int64_t max_hits, int64_t *ids, int64_t *cnt)
+{
+	query_begin(h, "string_ids");
+	locate_check(h, "string_ids", max_hits);
+	if (n <= 0) return 0;
+	const int64_t CH = std::max<int64_t>(1, std::min<int64_t>(query_chunk(h), SMEM_STAGE_BYTES / 8 / max_hits));   // the ids of a chunk: under 256 MiB, one range at the least
+	int64_t stored = 0;
+	for (int64_t i0 = 0; i0 < n; i0 += CH) {
+		const int64_t nc = std::min(CH, n - i0);
+		h->qin.ensure((size_t)nc * 3); h->qout.ensure((size_t)(nc * max_hits));
+		int64_t *d_zv = h->qin.p, *d_cnt = h->qin.p + 2 * nc;
+		HIPCHK(hipMemcpyAsync(d_zv, zv + 2 * i0, (size_t)nc * 16, hipMemcpyHostToDevice, h->st));
+		HIPCHK(hipMemsetAsync(h->qout.p, 0, (size_t)(nc * max_hits) * 8, h->st));   // the ids no slot writes come back as zeros
+		launch_string_ids(h, nc, d_zv, max_hits, h->qout.p, d_cnt);
+		HIPCHK(hipMemcpyAsync(cnt + i0, d_cnt, (size_t)nc * 8, hipMemcpyDeviceToHost, h->st));
+		HIPCHK(hipMemcpyAsync(ids + i0 * max_hits, h->qout.p, (size_t)(nc * max_hits) * 8, hipMemcpyDeviceToHost, h->st));
+		HIPCHK(hipStreamSynchronize(h->st));
+		for (int64_t i = i0; i < i0 + nc; ++i) stored += std::min(std::max<int64_t>(cnt[i], 0), max_hits);
+	}
+	return stored;
+}
+
+void rb2_hip_string_ids_dev(rb2_hip_t *h, int64_t n, const int64_t *zv, int64_t max_hits, int64_t *ids, int64_t *cnt)
+{
+	query_begin(h, "string_ids_dev");
+	locate_check(h, "string_ids_dev", max_hits);
+	if (n <= 0) return;
+	launch_string_ids(h, n, zv, max_hits, ids, cnt);
+}
+
 /* checksum of sub-rope r (k_piece_hash); the handle must hold the piece in the dense layout */
 static uint64_t piece_hash(rb2_hip_t *h, int r)
 {

@@ -336,4 +336,63 @@ template <bool SPARSE> __global__ __launch_bounds__(256) void k_locate(const QTa
 	if (g < 2) hit[(i * (uint64_t)max_hits + (uint64_t)kk) * 2 + g] = (int64_t)(g ? pos : sid);
 }
 
+// ---- suffix-prefix overlaps ----
+// A row of the interval [lo, hi) of a pattern P, |P| >= 1, whose BWT symbol is `$` is the row of a whole string that starts with P.  So
+// occ($, hi) - occ($, lo) strings have the prefix P, and they are head[q] (the array k_ssa_build writes) for q in [occ($, lo), occ($, hi)).
+
+// backward search of n queries qry[off[i] - base, off[i+1] - base) (codes 1..4 match, 5 ends the search, anything else makes the query
+// malformed) that reports on its way every suffix some string of the index starts with: records (l, zlo, zhi) in increasing l into
+// rec[(i * max_recs + k) * 3 ..) for k < max_recs, cnt[i] = records found (the surplus is counted, not stored), -1 for a malformed query.
+// The pair of ranks at the two ends of the interval of the last m symbols serves twice: the `$` counts are the record of length m, the
+// counts of the next symbol are the step.  The search starts at the interval of the last symbol (C[c], C[c + 1]: no rank) and ends
+// behind the ranks of the whole query, at an N, or when the interval empties: at most len rank pairs.
+template <bool SPARSE> __global__ __launch_bounds__(256) void k_overlap(const QTab *Tg, PoolView pv, const uint8_t *qry, const int64_t *off, int64_t base,
+                                                                        uint64_t n, int64_t min_ovlp, int64_t max_recs, int64_t *rec, int64_t *cnt)
+{
+	__shared__ QTab T;
+	qtab_load(Tg, T);
+	const uint64_t i = (uint64_t)blockIdx.x * QPB + (threadIdx.x >> 4);
+	if (i >= n) return;
+	const uint32_t g = (uint32_t)lane_id() & 15u;
+	const int64_t s0 = off[i] - base, L = off[i + 1] - base - s0;
+	const uint8_t *q = qry + s0;
+	bool bad = L < 0 || s0 < 0;
+	for (int64_t j = 0; !bad && j < L; ++j) { const uint8_t c = q[j]; bad = c == 0 || c > 5; }
+	if (bad) { if (g == 0) cnt[i] = -1; return; }
+	const int c0 = L > 0 ? q[L - 1] : 5;
+	int64_t lo = (int64_t)qC(T, c0 < 5 ? c0 : 0), hi = c0 < 5 ? (int64_t)qC(T, c0 + 1) : lo, m = 1, k = 0;
+	while (lo < hi) {
+		uint64_t cl[6], ch[6];
+		qrank<SPARSE>(T, pv, (uint64_t)lo, cl);
+		qrank<SPARSE>(T, pv, (uint64_t)hi, ch);
+		if (m >= min_ovlp && ch[0] > cl[0]) {
+			if (k < max_recs && g < 3) rec[(i * (uint64_t)max_recs + (uint64_t)k) * 3 + g] = g == 0 ? m : (int64_t)(g == 1 ? cl[0] : ch[0]);   // three lanes, one 24-byte record
+			++k;
+		}
+		if (m == L) break;
+		const int c = q[L - 1 - m];
+		if (c == 5) break;
+		const uint64_t C = qC(T, c);
+		lo = (int64_t)(C + cl[c]); hi = (int64_t)(C + ch[c]); ++m;
+	}
+	if (g == 0) cnt[i] = k;
+}
+
+// `$` ranks to string ids: slot q of the launch is hit kk = k0 + q % kn of range i = q / kn (covered in parts as k_locate is), one thread
+// per slot, so a range reads head[] and writes ids[] in whole lines.  ids[i * max_hits + kk] = head[zlo_i + kk]; cnt[i] = zhi - zlo, -1
+// for a malformed range (written by the slot of hit 0).
+__global__ __launch_bounds__(256) void k_string_ids(const int64_t *zv, uint64_t n, int64_t max_hits, int64_t k0, int64_t kn, const uint64_t *head, uint64_t nstr,
+                                                    int64_t *ids, int64_t *cnt)
+{
+	const uint64_t q = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+	if (q >= n * (uint64_t)kn) return;
+	const uint64_t i = q / (uint64_t)kn;
+	const int64_t kk = k0 + (int64_t)(q % (uint64_t)kn);
+	const int64_t zlo = zv[2 * i], zhi = zv[2 * i + 1];
+	const bool bad = zlo < 0 || zhi > (int64_t)nstr || zlo > zhi;
+	if (kk == 0) cnt[i] = bad ? -1 : zhi - zlo;
+	if (bad || kk >= zhi - zlo) return;
+	ids[i * (uint64_t)max_hits + (uint64_t)kk] = (int64_t)head[zlo + kk];
+}
+
 } // namespace rb2

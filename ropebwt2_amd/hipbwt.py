@@ -59,6 +59,10 @@ def load_hip_lib():
         "rb2_hip_ssa_info": (None, [vp, vp]),
         "rb2_hip_locate": (i64, [vp, i64, vp, i64, vp, vp]),
         "rb2_hip_locate_dev": (None, [vp, i64, vp, i64, vp, vp]),
+        "rb2_hip_overlap": (i64, [vp, i64, vp, vp, i64, i64, vp, vp]),
+        "rb2_hip_overlap_dev": (None, [vp, i64, vp, vp, i64, i64, vp, vp]),
+        "rb2_hip_string_ids": (i64, [vp, i64, vp, i64, vp, vp]),
+        "rb2_hip_string_ids_dev": (None, [vp, i64, vp, i64, vp, vp]),
         "rb2_hip_reserve": (None, [vp, i64, i64, i64]),
         "rb2_hip_num_subropes": (i32, []),
         "rb2_hip_memcpy": (None, [vp, vp, vp, i64, i32]),
@@ -125,6 +129,7 @@ ABI_SYMBOLS = [
     "rb2_hip_download_rope", "rb2_hip_stream_rope", "rb2_hip_load_ropes", "rb2_hip_load_fmd", "rb2_hip_load_fmd_file", "rb2_hip_rank1a", "rb2_hip_rank_batch", "rb2_hip_reserve",
     "rb2_hip_backward_search", "rb2_hip_backward_search_dev", "rb2_hip_extend", "rb2_hip_extract", "rb2_hip_smem", "rb2_hip_smem_dev", "rb2_hip_dev_alloc",
     "rb2_hip_ssa_build", "rb2_hip_ssa_drop", "rb2_hip_ssa_info", "rb2_hip_locate", "rb2_hip_locate_dev",
+    "rb2_hip_overlap", "rb2_hip_overlap_dev", "rb2_hip_string_ids", "rb2_hip_string_ids_dev",
     "rb2_hip_num_subropes", "rb2_hip_memcpy", "rb2_hip_use_stream",
     "rb2_hip_dev_free", "rb2_hip_synth_reads", "rb2_hip_synth_reads_cov", "rb2_hip_synth_reads_skew", "rb2_hip_sync", "rb2_hip_sparse_stats", "rb2_hip_layout_stats", "rb2_hip_rewind_stats", "rb2_hip_window_stats", "rb2_hip_host_register", "rb2_hip_host_unregister", "rb2_hip_profile",
     "rb2_hip_profile_get", "rb2_hip_kernel_name", "rb2_hip_layout",
@@ -426,6 +431,55 @@ class HipBwt:
             for i, h in zip(full, self.locate(np.stack([lo[full], hi[full]], 1), max_hits)):
                 out[i] = h
         return out
+
+    # -- suffix-prefix overlaps: the strings that begin with a suffix of a query (include/rb2_hip.h) -------------------------
+    def overlap_raw(self, queries, min_ovlp, max_recs):
+        """rb2_hip_overlap as it is: (records stored, rec (n, max_recs, 3) int64 = length, zlo, zhi, cnt (n,) int64); only the first
+        min(cnt[i], max_recs) records of query i are meaningful (the others are zeros), cnt[i] = -1 for a malformed query"""
+        qry, off = pack_patterns(queries)
+        n = len(off) - 1
+        rec = np.zeros((n, max(int(max_recs), 0), 3), np.int64)
+        cnt = np.zeros(n, np.int64)
+        stored = self.L.rb2_hip_overlap(self.h, n, qry.ctypes.data, off.ctypes.data, min_ovlp, max_recs, rec.ctypes.data, cnt.ctypes.data) if n else 0
+        return int(stored), rec, cnt
+
+    def overlap_dev(self, n, qry_dev, off_dev, rec_dev, cnt_dev, min_ovlp, max_recs):
+        """rb2_hip_overlap_dev: all four pointers in this device's memory; asynchronous on the handle's stream"""
+        self.L.rb2_hip_overlap_dev(self.h, n, qry_dev, off_dev, min_ovlp, max_recs, rec_dev, cnt_dev)
+
+    def string_ids_raw(self, ranges, max_hits):
+        """rb2_hip_string_ids as it is: (ids stored, ids (n, max_hits) int64, cnt (n,) int64); only the first min(cnt[i], max_hits) ids
+        of range i are meaningful (the others are zeros), cnt[i] = -1 for a malformed range.  Needs build_ssa()"""
+        zv = np.ascontiguousarray(np.asarray(ranges, dtype=np.int64).reshape(-1, 2))
+        n = len(zv)
+        ids = np.zeros((n, max(int(max_hits), 0)), np.int64)
+        cnt = np.zeros(n, np.int64)
+        stored = self.L.rb2_hip_string_ids(self.h, n, zv.ctypes.data, max_hits, ids.ctypes.data, cnt.ctypes.data)
+        return int(stored), ids, cnt
+
+    def string_ids_dev(self, n, zv_dev, ids_dev, cnt_dev, max_hits=64):
+        """rb2_hip_string_ids_dev: all three pointers in this device's memory; asynchronous on the handle's stream"""
+        self.L.rb2_hip_string_ids_dev(self.h, n, zv_dev, max_hits, ids_dev, cnt_dev)
+
+    def overlaps(self, queries, min_ovlp, max_hits=64):
+        """the strings of the index that begin with a suffix of at least min_ovlp symbols of each query (str / bytes over ACGTN, or nt6
+        arrays): per query the list of (string id, overlap length), longest overlap first, at most max_hits strings per length.  The
+        whole query counts as a suffix of itself, so a query that is in the index finds itself, its copies and the strings it is a proper
+        prefix of.  Needs build_ssa() (none is built here); a malformed query ('$' or a code above 5 inside) raises ValueError"""
+        lens = [len(encode_pattern(q)) for q in queries]
+        max_recs = max(max(lens, default=0) - int(min_ovlp) + 1, 1)                  # one record per length at the most: nothing is cut
+        _, rec, cnt = self.overlap_raw(queries, min_ovlp, max_recs)
+        if (cnt < 0).any():
+            raise ValueError("malformed queries (only the codes 1..5 are allowed): %s" % np.flatnonzero(cnt < 0)[:5].tolist())
+        live = np.arange(max_recs)[None, :] < cnt[:, None]
+        who = np.nonzero(live)[0]
+        recs = rec[live]
+        max_hits = max(min(int(max_hits), int((recs[:, 2] - recs[:, 1]).max(initial=1))), 1)    # no wider than the widest range
+        _, ids, n_ids = self.string_ids_raw(recs[:, 1:], max_hits)
+        out = [[] for _ in queries]
+        for i, l, k, row in zip(who.tolist(), recs[:, 0].tolist(), np.minimum(n_ids, max_hits).tolist(), ids.tolist()):
+            out[i].append([(s, l) for s in row[:k]])
+        return [[p for grp in reversed(o) for p in grp] for o in out]
 
     # -- measurement helpers ----------------------------------------------------------------
     def dev_alloc(self, nbytes):

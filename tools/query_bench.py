@@ -21,6 +21,11 @@ With --locate only the sampled suffix array is measured, on the index of the fir
 the --out file, whose other entries stay: rb2_hip_ssa_build at log2_step 3, 5 and 7 (seconds, LF steps per second -- one step per row of
 the index --, bytes held), and at each step locate_dev for the intervals of P substring patterns of length 20 and 64 with max_hits 16
 (hits per second).
+With --overlap only the suffix-prefix overlap query is measured and stored under "overlap" in the --out file, whose other entries stay:
+on the index of the first cases (single strand), overlap_dev on P whole reads of the index at min_ovlp 1 and 20 (queries, LF steps --
+one per rank pair -- and records per second, with the fastest and slowest of the three runs) and backward_search_dev on the same reads
+in the same run; then, on an index of both strands, the baseline a user could compose before: every suffix of a read a pattern of its
+own, count(revcomp(suffix) + $) through rb2_hip_backward_search, against rb2_hip_overlap on the same few thousand reads.
 """
 import argparse
 import json
@@ -274,6 +279,93 @@ def locate_case(a, res):
     g.close()
 
 
+def spread(fn, sync, reps=3):
+    """timed(), with the fastest and the slowest run beside the median"""
+    fn(); sync()
+    ts = []
+    for _ in range(reps):
+        t = time.perf_counter(); fn(); sync(); ts.append(time.perf_counter() - t)
+    return float(np.median(ts)), float(min(ts)), float(max(ts))
+
+
+def overlap_case(a, res):
+    L, M = 101, 24
+    n = a.reads or -(-(int(4 * 1024 ** 3 * 0.97) + 1) // (L + 1))
+    P = a.patterns
+    qs = hit_patterns(P, L, n, 101)                                 # whole reads of the index
+    flat = np.ascontiguousarray(qs.reshape(-1)); off = np.arange(P + 1, dtype=np.int64) * L
+    g = HipBwt(a.so)
+    p = g.dev_alloc(n * (L + 1))
+    g.synth_reads(p, 0, n, L, seed=42)
+    g.insert_multi_dev(p, n * (L + 1))
+    g.sync()
+    g.dev_free(p)
+    N = int(g.counts().sum())
+    dq, do, dr, dc, db = g.dev_alloc(len(flat)), g.dev_alloc(8 * (P + 1)), g.dev_alloc(24 * M * P), g.dev_alloc(8 * P), g.dev_alloc(24 * P)
+    g.L.rb2_hip_memcpy(g.h, dq, flat.ctypes.data, len(flat), 0)
+    g.L.rb2_hip_memcpy(g.h, do, off.ctypes.data, 8 * (P + 1), 0)
+    rows = []
+
+    def bsearch():
+        sec, lo, hi = spread(lambda: g.backward_search_dev(P, dq, do, db), g.sync)
+        out = np.zeros((P, 3), np.int64)
+        g.L.rb2_hip_memcpy(g.h, out.ctypes.data, db, 24 * P, 1)
+        assert (out[:, 2] == L).all()                               # reads of the index: every step succeeds, L rank pairs each
+        row = row_case("backward_search_dev on the same %d reads" % P, P, sec, P * L, 2)
+        row.update({"measured": True, "lf_steps_per_s_slowest": P * L / hi, "lf_steps_per_s_fastest": P * L / lo})
+        return row
+    rows.append(bsearch())
+    for min_ovlp in (1, 20):
+        sec, lo, hi = spread(lambda: g.overlap_dev(P, dq, do, dr, dc, min_ovlp, M), g.sync)
+        cnt = np.zeros(P, np.int64)
+        g.L.rb2_hip_memcpy(g.h, cnt.ctypes.data, dc, 8 * P, 1)
+        assert cnt.min() >= 1                                       # a read of the index finds itself
+        recs = int(cnt.sum())
+        row = row_case("overlap_dev, %d reads of the index (101 bp), min_ovlp=%d max_recs=%d" % (P, min_ovlp, M), P, sec, P * L, 2)
+        row.update({"measured": True, "lf_steps_are": "rank pairs: one per symbol of a read, every suffix of which occurs", "lf_steps_per_s_slowest": P * L / hi,
+                    "lf_steps_per_s_fastest": P * L / lo, "records": recs, "records_per_s": recs / sec, "records_per_query": recs / P,
+                    "queries_with_more_than_max_recs": int((cnt > M).sum())})
+        rows.append(row)
+        print("overlap: min_ovlp %d: %d queries in %.3f s" % (min_ovlp, P, sec), file=sys.stderr, flush=True)
+    rows.append(bsearch())                                          # once more behind the overlap runs: the drift of the run itself
+    rows[-1]["case"] += " (again, after the overlap runs)"
+    for q in (dq, do, dr, dc, db):
+        g.dev_free(q)
+    index = {"reads": n, "read_len": L, "sorting_order": a.so, "symbols": N, "strands": 1, "layout": g.layout_stats()}
+    g.close()
+    # the baseline needs the strings that END in a pattern: on an index of both strands those are the strings that start with its reverse complement
+    g = HipBwt(a.so)
+    buf = g.dev_alloc(2 * n * (L + 1))
+    g.synth_reads(buf, 0, n, L, seed=42, strand=1)
+    g.insert_multi_dev(buf, 2 * n * (L + 1))
+    g.sync()
+    g.dev_free(buf)
+    nb, min_ovlp = min(a.baseline_queries // 5, P), 20                # (4000 reads by default: 82 patterns each)
+    comp = np.array([0, 4, 3, 2, 1, 5], np.uint8)
+    pats = [np.concatenate([comp[q[L - l:][::-1]], [0]]).astype(np.uint8) for q in qs[:nb] for l in range(min_ovlp, L + 1)]
+    pat, poff = pack_patterns(pats)
+    out = np.zeros((len(pats), 3), np.int64)
+    bsec = timed(lambda: g.L.rb2_hip_backward_search(g.h, len(pats), pat.ctypes.data, poff.ctypes.data, out.ctypes.data), lambda: None)
+    lens = np.diff(poff)
+    ends = np.where(out[:, 2] == lens, out[:, 1] - out[:, 0], 0).reshape(nb, L - min_ovlp + 1)
+    got = [None]
+
+    def fused():
+        got[0] = g.overlap_raw(list(qs[:nb]), min_ovlp, L - min_ovlp + 1)
+    fsec = timed(fused, lambda: None)
+    _, rec, cnt = got[0]
+    mine = np.zeros_like(ends)
+    k = np.arange(rec.shape[1])[None, :] < cnt[:, None]
+    mine[np.nonzero(k)[0], rec[:, :, 0][k] - min_ovlp] = (rec[:, :, 2] - rec[:, :, 1])[k]
+    brow = row_case("baseline: one pattern per suffix, count(revcomp(suffix) + $) through rb2_hip_backward_search (host buffers), %d reads, min_ovlp=%d, both strands indexed"
+                    % (nb, min_ovlp), nb, bsec, int(np.minimum(out[:, 2] + 1, lens).sum()), 2)
+    brow.update({"measured": True, "patterns": len(pats), "pattern_bytes": int(len(pat)), "equals_fused": bool(np.array_equal(ends, mine)), "seconds_per_query": bsec / nb})
+    frow = row_case("overlap (host buffers), the baseline's %d reads, min_ovlp=%d" % (nb, min_ovlp), nb, fsec, nb * L, 2)
+    frow.update({"measured": True, "records": int(cnt.sum()), "seconds_per_query": fsec / nb})
+    g.close()
+    res["overlap"] = {"index": index, "cases": rows + [brow, frow]}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default="")
@@ -287,7 +379,16 @@ def main():
     ap.add_argument("--only", default="", help="'smem': only the smem cases (added to an existing --out file)")
     ap.add_argument("--fmd", default="", help="load the index from this .fmd file instead of building it")
     ap.add_argument("--locate", action="store_true", help="only the sampled suffix array: build and locate rates (added to an existing --out file)")
+    ap.add_argument("--overlap", action="store_true", help="only the suffix-prefix overlap query (added to an existing --out file)")
     a = ap.parse_args()
+    if a.overlap:
+        res = {"cases": []}
+        if a.out and os.path.exists(a.out):
+            with open(a.out) as f:
+                res = json.load(f)
+        overlap_case(a, res)
+        finish(a, res)
+        return
     if a.locate:
         res = {"cases": []}
         if a.out and os.path.exists(a.out):
