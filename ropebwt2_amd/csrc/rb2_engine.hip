@@ -1612,353 +1612,9 @@ void rb2_hip_rank1a(rb2_hip_t *h, int b, int64_t x, int64_t cx[6])
 	rb2_hip_rank_batch(h, b, 1, &x, cx);
 }
 
-/* ---- FM-index queries (rb2_query.h): one DPP row of 16 lanes per query ---- */
-
-/* queries per launch: 16 threads each, so 2^24 stay far below the 2^32 threads of one launch; RB2_QUERY_CHUNK lowers it (tests of the chunking) */
-static int64_t query_chunk(rb2_hip_t *h)
-{
-	(void)h;
-	const int64_t CH = 1 << 24;
-	const char *e = getenv("RB2_QUERY_CHUNK");
-	const int64_t v = e ? atoll(e) : 0;
-	return v > 0 ? std::min(v, CH) : CH;
-}
-
-/* what every query does first: wait for a lazy insert, refuse a shard, build the piece table of the index as it is now */
-static void query_begin(rb2_hip_t *h, const char *who)
-{
-	finish_pending(h);
-	HIPCHK(hipSetDevice(h->dev));
-	if (h->nranks > 1) rb2_fatal("[rb2_hip] %s: this handle holds only its own sub-ropes of a sharded index; queries need the whole index on one engine\n", who);
-	require_plain(h, who);
-	h->qtab.ensure(1);
-	hipLaunchKernelGGL(k_qtab, dim3(1), dim3(64), 0, h->st, (const Ctl*)h->ctl, h->side, h->pool[h->pside].view(), h->qtab.p);
-	HIPCHK(hipGetLastError());
-}
-
-static void launch_bsearch(rb2_hip_t *h, int64_t n, const uint8_t *pat, const int64_t *off, int64_t base, int64_t *out)
-{
-	const PoolView pv = h->pool[h->pside].view();
-	if (h->sparse) hipLaunchKernelGGL(k_bsearch<true>, dim3(cdiv((uint64_t)n, QPB)), dim3(256), 0, h->st, (const QTab*)h->qtab.p, pv, pat, off, base, (uint64_t)n, out);
-	else hipLaunchKernelGGL(k_bsearch<false>, dim3(cdiv((uint64_t)n, QPB)), dim3(256), 0, h->st, (const QTab*)h->qtab.p, pv, pat, off, base, (uint64_t)n, out);
-	HIPCHK(hipGetLastError());
-}
-
-void rb2_hip_backward_search(rb2_hip_t *h, int64_t n, const uint8_t *pat, const int64_t *off, int64_t *out)
-{
-	query_begin(h, "backward_search");
-	if (n <= 0) return;
-	for (int64_t i = 0; i < n; ++i)
-		if (off[i + 1] < off[i] || off[0] < 0) { rb2_fatal("[rb2_hip] backward_search: pattern offsets must be non-negative and non-decreasing (off[%lld])\n", (long long)i); }
-	const int64_t CH = query_chunk(h);
-	for (int64_t i0 = 0; i0 < n; i0 += CH) {
-		const int64_t nc = std::min(CH, n - i0), b0 = off[i0], nb = off[i0 + nc] - b0;
-		h->qin.ensure((size_t)nc + 1); h->qout.ensure((size_t)nc * 3); h->qbytes.ensure((size_t)std::max<int64_t>(nb, 1));
-		HIPCHK(hipMemcpyAsync(h->qin.p, off + i0, (size_t)(nc + 1) * 8, hipMemcpyHostToDevice, h->st));
-		if (nb) HIPCHK(hipMemcpyAsync(h->qbytes.p, pat + b0, (size_t)nb, hipMemcpyHostToDevice, h->st));
-		launch_bsearch(h, nc, h->qbytes.p, h->qin.p, b0, h->qout.p);
-		HIPCHK(hipMemcpyAsync(out + 3 * i0, h->qout.p, (size_t)nc * 24, hipMemcpyDeviceToHost, h->st));
-		HIPCHK(hipStreamSynchronize(h->st));
-	}
-}
-
-void rb2_hip_backward_search_dev(rb2_hip_t *h, int64_t n, const uint8_t *pat, const int64_t *off, int64_t *out)
-{
-	query_begin(h, "backward_search_dev");
-	const int64_t CH = query_chunk(h);
-	for (int64_t i0 = 0; i0 < n; i0 += CH) launch_bsearch(h, std::min(CH, n - i0), pat, off + i0, 0, out + 3 * i0);
-}
-
-void rb2_hip_extend(rb2_hip_t *h, int64_t n, const int64_t *ik, int is_back, int64_t *ok)
-{
-	query_begin(h, "extend");
-	if (n <= 0) return;
-	is_back = is_back ? 1 : 0;
-	const int64_t CH = query_chunk(h);
-	const PoolView pv = h->pool[h->pside].view();
-	h->qin.ensure((size_t)std::min(CH, n) * 3); h->qout.ensure((size_t)std::min(CH, n) * 18);
-	for (int64_t i0 = 0; i0 < n; i0 += CH) {
-		const int64_t nc = std::min(CH, n - i0);
-		HIPCHK(hipMemcpyAsync(h->qin.p, ik + 3 * i0, (size_t)nc * 24, hipMemcpyHostToDevice, h->st));
-		if (h->sparse) hipLaunchKernelGGL(k_extend<true>, dim3(cdiv((uint64_t)nc, QPB)), dim3(256), 0, h->st, (const QTab*)h->qtab.p, pv, (const int64_t*)h->qin.p, is_back, (uint64_t)nc, h->qout.p);
-		else hipLaunchKernelGGL(k_extend<false>, dim3(cdiv((uint64_t)nc, QPB)), dim3(256), 0, h->st, (const QTab*)h->qtab.p, pv, (const int64_t*)h->qin.p, is_back, (uint64_t)nc, h->qout.p);
-		HIPCHK(hipGetLastError());
-		HIPCHK(hipMemcpyAsync(ok + 18 * i0, h->qout.p, (size_t)nc * 144, hipMemcpyDeviceToHost, h->st));
-		HIPCHK(hipStreamSynchronize(h->st));
-	}
-}
-
-int64_t rb2_hip_extract(rb2_hip_t *h, int64_t n, const int64_t *rows, int64_t max_len, uint8_t *out, int64_t *len)
-{
-	query_begin(h, "extract");
-	if (n <= 0) return 0;
-	if (max_len < 0) max_len = 0;
-	int64_t CH = query_chunk(h);
-	if (max_len > 0) CH = std::max<int64_t>(1, std::min<int64_t>(CH, (int64_t)(256u << 20) / max_len));   // at most 256 MiB of strings staged per launch
-	const PoolView pv = h->pool[h->pside].view();
-	h->qin.ensure((size_t)std::min(CH, n) * 2); h->qbytes.ensure((size_t)std::max<int64_t>(std::min(CH, n) * max_len, 1));
-	int64_t fit = 0;
-	for (int64_t i0 = 0; i0 < n; i0 += CH) {
-		const int64_t nc = std::min(CH, n - i0);
-		int64_t *d_rows = h->qin.p, *d_len = h->qin.p + nc;
-		HIPCHK(hipMemcpyAsync(d_rows, rows + i0, (size_t)nc * 8, hipMemcpyHostToDevice, h->st));
-		if (h->sparse) hipLaunchKernelGGL(k_extract<true>, dim3(cdiv((uint64_t)nc, QPB)), dim3(256), 0, h->st, (const QTab*)h->qtab.p, pv, (const int64_t*)d_rows, (uint64_t)nc, max_len, h->qbytes.p, d_len);
-		else hipLaunchKernelGGL(k_extract<false>, dim3(cdiv((uint64_t)nc, QPB)), dim3(256), 0, h->st, (const QTab*)h->qtab.p, pv, (const int64_t*)d_rows, (uint64_t)nc, max_len, h->qbytes.p, d_len);
-		HIPCHK(hipGetLastError());
-		HIPCHK(hipMemcpyAsync(len + i0, d_len, (size_t)nc * 8, hipMemcpyDeviceToHost, h->st));
-		if (nc * max_len) HIPCHK(hipMemcpyAsync(out + i0 * max_len, h->qbytes.p, (size_t)(nc * max_len), hipMemcpyDeviceToHost, h->st));
-		HIPCHK(hipStreamSynchronize(h->st));
-		for (int64_t i = i0; i < i0 + nc; ++i)                  // the walk spells a string from its last symbol: text order is the reverse
-			if (len[i] >= 0) { std::reverse(out + i * max_len, out + i * max_len + len[i]); ++fit; }
-	}
-	return fit;
-}
-
-static void launch_smem(rb2_hip_t *h, int64_t n, const uint8_t *qry, const int64_t *off, int64_t base, int64_t min_len, int64_t min_occ, int64_t max_mems,
-                        int64_t *mem, int64_t *cnt)
-{
-	const PoolView pv = h->pool[h->pside].view();
-	if (h->sparse) hipLaunchKernelGGL(k_smem<true>, dim3(cdiv((uint64_t)n, QPB)), dim3(256), 0, h->st, (const QTab*)h->qtab.p, pv, qry, off, base, (uint64_t)n, min_len, min_occ, max_mems, mem, cnt);
-	else hipLaunchKernelGGL(k_smem<false>, dim3(cdiv((uint64_t)n, QPB)), dim3(256), 0, h->st, (const QTab*)h->qtab.p, pv, qry, off, base, (uint64_t)n, min_len, min_occ, max_mems, mem, cnt);
-	HIPCHK(hipGetLastError());
-}
-
-static void smem_check(const char *who, int64_t min_len, int64_t min_occ, int64_t max_mems)
-{
-	if (min_len < 1 || min_occ < 1 || max_mems < 1)
-		rb2_fatal("[rb2_hip] %s: min_len, min_occ and max_mems must be at least 1 (got %lld, %lld, %lld)\n", who, (long long)min_len, (long long)min_occ, (long long)max_mems);
-}
-
-/* staged records of one chunk of rb2_hip_smem: the chunk shrinks until chunk * max_mems * 40 bytes fit (one query when a single one does not) */
-static const int64_t SMEM_STAGE_BYTES = (int64_t)256 << 20;
-
-int64_t rb2_hip_smem(rb2_hip_t *h, int64_t n, const uint8_t *qry, const int64_t *off, int64_t min_len, int64_t min_occ, int64_t max_mems, int64_t *mem, int64_t *cnt)
-{
-	query_begin(h, "smem");
-	if (n <= 0) return 0;
-	smem_check("smem", min_len, min_occ, max_mems);
-	for (int64_t i = 0; i < n; ++i)
-		if (off[i + 1] < off[i] || off[0] < 0) { rb2_fatal("[rb2_hip] smem: query offsets must be non-negative and non-decreasing (off[%lld])\n", (long long)i); }
-	const int64_t CH = std::max<int64_t>(1, std::min<int64_t>(query_chunk(h), SMEM_STAGE_BYTES / 40 / max_mems));
-	int64_t stored = 0;
-	for (int64_t i0 = 0; i0 < n; i0 += CH) {
-		const int64_t nc = std::min(CH, n - i0), b0 = off[i0], nb = off[i0 + nc] - b0;
-		h->qin.ensure((size_t)nc * 2 + 1); h->qout.ensure((size_t)(nc * max_mems) * 5); h->qbytes.ensure((size_t)std::max<int64_t>(nb, 1));
-		int64_t *d_off = h->qin.p, *d_cnt = h->qin.p + nc + 1;
-		HIPCHK(hipMemcpyAsync(d_off, off + i0, (size_t)(nc + 1) * 8, hipMemcpyHostToDevice, h->st));
-		if (nb) HIPCHK(hipMemcpyAsync(h->qbytes.p, qry + b0, (size_t)nb, hipMemcpyHostToDevice, h->st));
-		HIPCHK(hipMemsetAsync(h->qout.p, 0, (size_t)(nc * max_mems) * 40, h->st));   // the records no query writes come back as zeros
-		launch_smem(h, nc, h->qbytes.p, d_off, b0, min_len, min_occ, max_mems, h->qout.p, d_cnt);
-		HIPCHK(hipMemcpyAsync(cnt + i0, d_cnt, (size_t)nc * 8, hipMemcpyDeviceToHost, h->st));
-		HIPCHK(hipMemcpyAsync(mem + i0 * max_mems * 5, h->qout.p, (size_t)(nc * max_mems) * 40, hipMemcpyDeviceToHost, h->st));
-		HIPCHK(hipStreamSynchronize(h->st));
-		for (int64_t i = i0; i < i0 + nc; ++i) stored += std::min(std::max<int64_t>(cnt[i], 0), max_mems);
-	}
-	return stored;
-}
-
-void rb2_hip_smem_dev(rb2_hip_t *h, int64_t n, const uint8_t *qry, const int64_t *off, int64_t min_len, int64_t min_occ, int64_t max_mems, int64_t *mem, int64_t *cnt)
-{
-	query_begin(h, "smem_dev");
-	if (n <= 0) return;
-	smem_check("smem_dev", min_len, min_occ, max_mems);
-	const int64_t CH = query_chunk(h);
-	for (int64_t i0 = 0; i0 < n; i0 += CH) launch_smem(h, std::min(CH, n - i0), qry, off + i0, 0, min_len, min_occ, max_mems, mem + i0 * max_mems * 5, cnt + i0);
-}
-
-/* ---- sampled suffix array: rows back to (string, position) (k_ssa_build, k_locate) ---- */
-
-static const int64_t SSA_LAUNCH = 1 << 24;                     /* DPP rows (strings, hit slots) per launch: 2^28 threads */
-
-int64_t rb2_hip_ssa_build(rb2_hip_t *h, int log2_step)
-{
-	query_begin(h, "ssa_build");
-	if (log2_step < 0 || log2_step > 30) { rb2_fatal("[rb2_hip] ssa_build: log2_step must be 0 .. 30 (got %d)\n", log2_step); }
-	index_rows_change(h);                                      // (an array that is there is freed first: the new one is sized exactly)
-	uint64_t N = 0;
-	for (int r = 0; r < NR; ++r) N += h->h_rope[r].n;
-	const uint64_t n = h->h_rope[0].n;                          // C[1]: rope $ is one piece
-	const uint64_t ns = (N + (1ull << log2_step) - 1) >> log2_step;
-	if (n) {
-		h->ssa_smp.ensure((size_t)ns * 2); h->ssa_len.ensure((size_t)n); h->ssa_head.ensure((size_t)n);
-		const PoolView pv = h->pool[h->pside].view();
-		for (uint64_t k0 = 0; k0 < n; k0 += (uint64_t)SSA_LAUNCH) {
-			const unsigned nb = (unsigned)cdiv(std::min<uint64_t>((uint64_t)SSA_LAUNCH, n - k0), QPB);
-			if (h->sparse) hipLaunchKernelGGL(k_ssa_build<true>, dim3(nb), dim3(256), 0, h->st, (const QTab*)h->qtab.p, pv, k0, n, log2_step, h->ssa_smp.p, h->ssa_len.p, h->ssa_head.p);
-			else hipLaunchKernelGGL(k_ssa_build<false>, dim3(nb), dim3(256), 0, h->st, (const QTab*)h->qtab.p, pv, k0, n, log2_step, h->ssa_smp.p, h->ssa_len.p, h->ssa_head.p);
-			HIPCHK(hipGetLastError());
-		}
-		HIPCHK(hipStreamSynchronize(h->st));
-	}
-	h->ssa_valid = true; h->ssa_s = log2_step; h->ssa_n = (int64_t)ns; h->ssa_nstr = n;
-	return (int64_t)ns;
-}
-
-void rb2_hip_ssa_drop(rb2_hip_t *h)
-{ finish_pending(h);
-	HIPCHK(hipSetDevice(h->dev));
-	index_rows_change(h);
-}
-
-void rb2_hip_ssa_info(rb2_hip_t *h, int64_t out[4])
-{
-	out[0] = h->ssa_valid ? 1 : 0; out[1] = h->ssa_s; out[2] = h->ssa_n;
-	out[3] = (int64_t)((h->ssa_smp.cap + h->ssa_len.cap + h->ssa_head.cap) * sizeof(uint64_t));
-}
-
-static void locate_check(rb2_hip_t *h, const char *who, int64_t max_hits)
-{
-	if (!h->ssa_valid) { rb2_fatal("[rb2_hip] %s: the index has no sampled suffix array (none was built, or the index changed since): call rb2_hip_ssa_build first\n", who); }
-	if (max_hits < 1) { rb2_fatal("[rb2_hip] %s: max_hits must be at least 1 (got %lld)\n", who, (long long)max_hits); }
-}
-
-/* n intervals, all device pointers; hit and cnt belong to interval 0 of iv.  One launch takes SSA_LAUNCH slots: whole intervals, or a part
- * of the hits of one interval when max_hits alone is larger */
-static void launch_locate(rb2_hip_t *h, int64_t n, const int64_t *iv, int64_t max_hits, int64_t *hit, int64_t *cnt)
-{
-	const PoolView pv = h->pool[h->pside].view();
-	const int64_t kn = std::min(max_hits, SSA_LAUNCH), per = std::max<int64_t>(1, SSA_LAUNCH / kn);
-	for (int64_t i0 = 0; i0 < n; i0 += per) {
-		const int64_t nc = std::min(per, n - i0);
-		for (int64_t k0 = 0; k0 < max_hits; k0 += kn) {
-			const int64_t kc = std::min(kn, max_hits - k0);
-			const unsigned nb = (unsigned)cdiv((uint64_t)(nc * kc), QPB);
-			if (h->sparse) hipLaunchKernelGGL(k_locate<true>, dim3(nb), dim3(256), 0, h->st, (const QTab*)h->qtab.p, pv, iv + 2 * i0, (uint64_t)nc, max_hits, k0, kc, h->ssa_s,
-					(const uint64_t*)h->ssa_smp.p, (const uint64_t*)h->ssa_len.p, (const uint64_t*)h->ssa_head.p, h->ssa_nstr, hit + i0 * max_hits * 2, cnt + i0);
-			else hipLaunchKernelGGL(k_locate<false>, dim3(nb), dim3(256), 0, h->st, (const QTab*)h->qtab.p, pv, iv + 2 * i0, (uint64_t)nc, max_hits, k0, kc, h->ssa_s,
-					(const uint64_t*)h->ssa_smp.p, (const uint64_t*)h->ssa_len.p, (const uint64_t*)h->ssa_head.p, h->ssa_nstr, hit + i0 * max_hits * 2, cnt + i0);
-			HIPCHK(hipGetLastError());
-		}
-	}
-}
-
-int64_t rb2_hip_locate(rb2_hip_t *h, int64_t n, const int64_t *iv, int64_t max_hits, int64_t *hit, int64_t *cnt)
-{
-	query_begin(h, "locate");
-	locate_check(h, "locate", max_hits);
-	if (n <= 0) return 0;
-	const int64_t CH = std::max<int64_t>(1, std::min<int64_t>(query_chunk(h), SMEM_STAGE_BYTES / 16 / max_hits));   // the records of a chunk: under 256 MiB, one interval at the least
-	int64_t stored = 0;
-	for (int64_t i0 = 0; i0 < n; i0 += CH) {
-		const int64_t nc = std::min(CH, n - i0);
-		h->qin.ensure((size_t)nc * 3); h->qout.ensure((size_t)(nc * max_hits) * 2);
-		int64_t *d_iv = h->qin.p, *d_cnt = h->qin.p + 2 * nc;
-		HIPCHK(hipMemcpyAsync(d_iv, iv + 2 * i0, (size_t)nc * 16, hipMemcpyHostToDevice, h->st));
-		HIPCHK(hipMemsetAsync(h->qout.p, 0, (size_t)(nc * max_hits) * 16, h->st));   // the records no slot writes come back as zeros
-		launch_locate(h, nc, d_iv, max_hits, h->qout.p, d_cnt);
-		HIPCHK(hipMemcpyAsync(cnt + i0, d_cnt, (size_t)nc * 8, hipMemcpyDeviceToHost, h->st));
-		HIPCHK(hipMemcpyAsync(hit + i0 * max_hits * 2, h->qout.p, (size_t)(nc * max_hits) * 16, hipMemcpyDeviceToHost, h->st));
-		HIPCHK(hipStreamSynchronize(h->st));
-		for (int64_t i = i0; i < i0 + nc; ++i) stored += std::min(std::max<int64_t>(cnt[i], 0), max_hits);
-	}
-	return stored;
-}
-
-void rb2_hip_locate_dev(rb2_hip_t *h, int64_t n, const int64_t *iv, int64_t max_hits, int64_t *hit, int64_t *cnt)
-{
-	query_begin(h, "locate_dev");
-	locate_check(h, "locate_dev", max_hits);
-	if (n <= 0) return;
-	launch_locate(h, n, iv, max_hits, hit, cnt);
-}
-
-/* ---- suffix-prefix overlaps: the strings that begin with a suffix of a query (k_overlap, k_string_ids) ---- */
-
-static void launch_overlap(rb2_hip_t *h, int64_t n, const uint8_t *qry, const int64_t *off, int64_t base, int64_t min_ovlp, int64_t max_recs, int64_t *rec, int64_t *cnt)
-{
-	const PoolView pv = h->pool[h->pside].view();
-	if (h->sparse) hipLaunchKernelGGL(k_overlap<true>, dim3(cdiv((uint64_t)n, QPB)), dim3(256), 0, h->st, (const QTab*)h->qtab.p, pv, qry, off, base, (uint64_t)n, min_ovlp, max_recs, rec, cnt);
-	else hipLaunchKernelGGL(k_overlap<false>, dim3(cdiv((uint64_t)n, QPB)), dim3(256), 0, h->st, (const QTab*)h->qtab.p, pv, qry, off, base, (uint64_t)n, min_ovlp, max_recs, rec, cnt);
-	HIPCHK(hipGetLastError());
-}
-
-static void overlap_check(const char *who, int64_t min_ovlp, int64_t max_recs)
-{
-	if (min_ovlp < 1 || max_recs < 1)
-		rb2_fatal("[rb2_hip] %s: min_ovlp and max_recs must be at least 1 (got %lld, %lld)\n", who, (long long)min_ovlp, (long long)max_recs);
-}
-
-int64_t rb2_hip_overlap(rb2_hip_t *h, int64_t n, const uint8_t *qry, const int64_t *off, int64_t min_ovlp, int64_t max_recs, int64_t *rec, int64_t *cnt)
-{
-	query_begin(h, "overlap");
-	if (n <= 0) return 0;
-	overlap_check("overlap", min_ovlp, max_recs);
-	for (int64_t i = 0; i < n; ++i)
-		if (off[i + 1] < off[i] || off[0] < 0) { rb2_fatal("[rb2_hip] overlap: query offsets must be non-negative and non-decreasing (off[%lld])\n", (long long)i); }
-	const int64_t CH = std::max<int64_t>(1, std::min<int64_t>(query_chunk(h), SMEM_STAGE_BYTES / 24 / max_recs));   // the records of a chunk: under 256 MiB, one query at the least
-	int64_t stored = 0;
-	for (int64_t i0 = 0; i0 < n; i0 += CH) {
-		const int64_t nc = std::min(CH, n - i0), b0 = off[i0], nb = off[i0 + nc] - b0;
-		h->qin.ensure((size_t)nc * 2 + 1); h->qout.ensure((size_t)(nc * max_recs) * 3); h->qbytes.ensure((size_t)std::max<int64_t>(nb, 1));
-		int64_t *d_off = h->qin.p, *d_cnt = h->qin.p + nc + 1;
-		HIPCHK(hipMemcpyAsync(d_off, off + i0, (size_t)(nc + 1) * 8, hipMemcpyHostToDevice, h->st));
-		if (nb) HIPCHK(hipMemcpyAsync(h->qbytes.p, qry + b0, (size_t)nb, hipMemcpyHostToDevice, h->st));
-		HIPCHK(hipMemsetAsync(h->qout.p, 0, (size_t)(nc * max_recs) * 24, h->st));   // the records no query writes come back as zeros
-		launch_overlap(h, nc, h->qbytes.p, d_off, b0, min_ovlp, max_recs, h->qout.p, d_cnt);
-		HIPCHK(hipMemcpyAsync(cnt + i0, d_cnt, (size_t)nc * 8, hipMemcpyDeviceToHost, h->st));
-		HIPCHK(hipMemcpyAsync(rec + i0 * max_recs * 3, h->qout.p, (size_t)(nc * max_recs) * 24, hipMemcpyDeviceToHost, h->st));
-		HIPCHK(hipStreamSynchronize(h->st));
-		for (int64_t i = i0; i < i0 + nc; ++i) stored += std::min(std::max<int64_t>(cnt[i], 0), max_recs);
-	}
-	return stored;
-}
-
-void rb2_hip_overlap_dev(rb2_hip_t *h, int64_t n, const uint8_t *qry, const int64_t *off, int64_t min_ovlp, int64_t max_recs, int64_t *rec, int64_t *cnt)
-{
-	query_begin(h, "overlap_dev");
-	if (n <= 0) return;
-	overlap_check("overlap_dev", min_ovlp, max_recs);
-	const int64_t CH = query_chunk(h);
-	for (int64_t i0 = 0; i0 < n; i0 += CH) launch_overlap(h, std::min(CH, n - i0), qry, off + i0, 0, min_ovlp, max_recs, rec + i0 * max_recs * 3, cnt + i0);
-}
-
-static const int64_t IDS_LAUNCH = 1 << 28;                     /* hit slots (threads) per launch of k_string_ids */
-
-/* n ranges, all device pointers; ids and cnt belong to range 0 of zv.  One launch takes IDS_LAUNCH slots: whole ranges, or a part of the
- * hits of one range when max_hits alone is larger (as launch_locate) */
-static void launch_string_ids(rb2_hip_t *h, int64_t n, const int64_t *zv, int64_t max_hits, int64_t *ids, int64_t *cnt)
-{
-	const int64_t kn = std::min(max_hits, IDS_LAUNCH), per = std::max<int64_t>(1, IDS_LAUNCH / kn);
-	for (int64_t i0 = 0; i0 < n; i0 += per) {
-		const int64_t nc = std::min(per, n - i0);
-		for (int64_t k0 = 0; k0 < max_hits; k0 += kn) {
-			const int64_t kc = std::min(kn, max_hits - k0);
-			hipLaunchKernelGGL(k_string_ids, dim3((unsigned)cdiv((uint64_t)(nc * kc), 256)), dim3(256), 0, h->st, zv + 2 * i0, (uint64_t)nc, max_hits, k0, kc,
-					(const uint64_t*)h->ssa_head.p, h->ssa_nstr, ids + i0 * max_hits, cnt + i0);
-			HIPCHK(hipGetLastError());
-		}
-	}
-}
-
-int64_t rb2_hip_string_ids(rb2_hip_t *h, int64_t n, const int64_t *zv, int64_t max_hits, int64_t *ids, int64_t *cnt)
-{
-	query_begin(h, "string_ids");
-	locate_check(h, "string_ids", max_hits);
-	if (n <= 0) return 0;
-	const int64_t CH = std::max<int64_t>(1, std::min<int64_t>(query_chunk(h), SMEM_STAGE_BYTES / 8 / max_hits));   // the ids of a chunk: under 256 MiB, one range at the least
-	int64_t stored = 0;
-	for (int64_t i0 = 0; i0 < n; i0 += CH) {
-		const int64_t nc = std::min(CH, n - i0);
-		h->qin.ensure((size_t)nc * 3); h->qout.ensure((size_t)(nc * max_hits));
-		int64_t *d_zv = h->qin.p, *d_cnt = h->qin.p + 2 * nc;
-		HIPCHK(hipMemcpyAsync(d_zv, zv + 2 * i0, (size_t)nc * 16, hipMemcpyHostToDevice, h->st));
-		HIPCHK(hipMemsetAsync(h->qout.p, 0, (size_t)(nc * max_hits) * 8, h->st));   // the ids no slot writes come back as zeros
-		launch_string_ids(h, nc, d_zv, max_hits, h->qout.p, d_cnt);
-		HIPCHK(hipMemcpyAsync(cnt + i0, d_cnt, (size_t)nc * 8, hipMemcpyDeviceToHost, h->st));
-		HIPCHK(hipMemcpyAsync(ids + i0 * max_hits, h->qout.p, (size_t)(nc * max_hits) * 8, hipMemcpyDeviceToHost, h->st));
-		HIPCHK(hipStreamSynchronize(h->st));
-		for (int64_t i = i0; i < i0 + nc; ++i) stored += std::min(std::max<int64_t>(cnt[i], 0), max_hits);
-	}
-	return stored;
-}
-
-void rb2_hip_string_ids_dev(rb2_hip_t *h, int64_t n, const int64_t *zv, int64_t max_hits, int64_t *ids, int64_t *cnt)
-{
-	query_begin(h, "string_ids_dev");
-	locate_check(h, "string_ids_dev", max_hits);
-	if (n <= 0) return;
-	launch_string_ids(h, n, zv, max_hits, ids, cnt);
-}
+} // extern "C"
+#include "rb2_query_host.h"                                  /* the FM-index queries: their host side (templates: C++ linkage) */
+extern "C" {
 
 /* checksum of sub-rope r (k_piece_hash); the handle must hold the piece in the dense layout */
 static uint64_t piece_hash(rb2_hip_t *h, int r)

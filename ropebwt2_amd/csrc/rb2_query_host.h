@@ -1,0 +1,315 @@
+// Host side of the FM-index queries (kernels: rb2_query.h; the launch arithmetic: rb2_query_plan.h).  Included from rb2_engine.hip, whose
+// handle, buffers and checks it uses.  Three helpers carry every query: qlaunch (one launch of a kernel in the layout of the index),
+// stage_inputs (a chunk's inputs to the device) and staged_records (the chunked loop of the host variants that return records).
+#pragma once
+#include "rb2_query_plan.h"
+
+/* queries per launch: 16 threads each, so 2^24 stay far below the 2^32 threads of one launch; RB2_QUERY_CHUNK lowers it (tests of the chunking) */
+static int64_t query_chunk()
+{
+	const int64_t CH = 1 << 24;
+	const char *e = getenv("RB2_QUERY_CHUNK");
+	const int64_t v = e ? atoll(e) : 0;
+	return v > 0 ? std::min(v, CH) : CH;
+}
+
+/* what every query does first: wait for a lazy insert, refuse a shard, build the piece table of the index as it is now */
+static void query_begin(rb2_hip_t *h, const char *who)
+{
+	finish_pending(h);
+	HIPCHK(hipSetDevice(h->dev));
+	if (h->nranks > 1) rb2_fatal("[rb2_hip] %s: this handle holds only its own sub-ropes of a sharded index; queries need the whole index on one engine\n", who);
+	require_plain(h, who);
+	h->qtab.ensure(1);
+	hipLaunchKernelGGL(k_qtab, dim3(1), dim3(64), 0, h->st, (const Ctl*)h->ctl, h->side, h->pool[h->pside].view(), h->qtab.p);
+	HIPCHK(hipGetLastError());
+}
+
+/* one launch of a query kernel, one DPP row (16 lanes) for each of rows: the instantiation for the layout of the index, on the handle's
+ * stream, the piece table and the pool in front of the kernel's own arguments a */
+template <typename... P, typename... A>
+static void qlaunch(rb2_hip_t *h, void (*sparse)(const QTab*, PoolView, P...), void (*dense)(const QTab*, PoolView, P...), uint64_t rows, A... a)
+{
+	const auto k = h->sparse ? sparse : dense;
+	hipLaunchKernelGGL(k, dim3((unsigned)cdiv(rows, QPB)), dim3(256), 0, h->st, (const QTab*)h->qtab.p, h->pool[h->pside].view(), static_cast<P>(a)...);
+	HIPCHK(hipGetLastError());
+}
+
+/* the inputs of a host variant, in host memory: n packed strings (w == 0: bytes, and v = their n + 1 offsets) or n tuples of w int64 (v) */
+struct QInput { const uint8_t *bytes; const int64_t *v; int w; };
+/* a chunk of them on the device: v as it was cut from the host's (offsets still count from the first byte of the whole input, base of them
+ * in front of bytes), and tail, room behind v for what the kernel writes per item beside its records */
+struct QStaged { const uint8_t *bytes; const int64_t *v; int64_t base; int64_t *tail; };
+
+static void check_offsets(const char *who, const char *what, int64_t n, const int64_t *off)
+{
+	for (int64_t i = 0; i < n; ++i)
+		if (off[i + 1] < off[i] || off[0] < 0) { rb2_fatal("[rb2_hip] %s: %s offsets must be non-negative and non-decreasing (off[%lld])\n", who, what, (long long)i); }
+}
+
+/* the items [i0, i0 + nc) of in into qin (and qbytes), with tail more int64 behind them; asynchronous on the handle's stream */
+static QStaged stage_inputs(rb2_hip_t *h, const QInput &in, int64_t i0, int64_t nc, int64_t tail)
+{
+	const int64_t nw = in.w ? nc * in.w : nc + 1, first = in.w ? i0 * in.w : i0;
+	int64_t base = 0;
+	h->qin.ensure((size_t)(nw + tail));
+	HIPCHK(hipMemcpyAsync(h->qin.p, in.v + first, (size_t)nw * 8, hipMemcpyHostToDevice, h->st));
+	if (!in.w) {
+		base = in.v[i0];
+		const int64_t nb = in.v[i0 + nc] - base;
+		h->qbytes.ensure((size_t)std::max<int64_t>(nb, 1));
+		if (nb) HIPCHK(hipMemcpyAsync(h->qbytes.p, in.bytes + base, (size_t)nb, hipMemcpyHostToDevice, h->st));
+	}
+	return {h->qbytes.p, h->qin.p, base, h->qin.p + nw};
+}
+
+/* the host variants with one fixed result of words int64 per item: launch(nc, staged inputs, results) per chunk, one synchronise each */
+template <typename F>
+static void staged_results(rb2_hip_t *h, int64_t n, const QInput &in, int words, int64_t *out, F launch)
+{
+	const int64_t CH = query_chunk();
+	for (int64_t i0 = 0; i0 < n; i0 += CH) {
+		const int64_t nc = std::min(CH, n - i0);
+		const QStaged s = stage_inputs(h, in, i0, nc, 0);
+		h->qout.ensure((size_t)nc * words);
+		launch(nc, s, h->qout.p);
+		HIPCHK(hipMemcpyAsync(out + i0 * words, h->qout.p, (size_t)nc * words * 8, hipMemcpyDeviceToHost, h->st));
+		HIPCHK(hipStreamSynchronize(h->st));
+	}
+}
+
+/* the host variants with up to cap (>= 1) records of words int64 per item and a count: launch(nc, staged inputs, records, counts) per chunk of
+ * at most QUERY_STAGE_BYTES of records (one item when a single one has more), one synchronise each.  The records no item writes come
+ * back as zeros; returns the records stored, min(max(cnt, 0), cap) over the items */
+template <typename F>
+static int64_t staged_records(rb2_hip_t *h, int64_t n, const QInput &in, int words, int64_t cap, int64_t *rec, int64_t *cnt, F launch)
+{
+	const int64_t CH = record_chunk(query_chunk(), 8 * words * cap);
+	int64_t stored = 0;
+	for (int64_t i0 = 0; i0 < n; i0 += CH) {
+		const int64_t nc = std::min(CH, n - i0);
+		const size_t bytes = (size_t)(nc * cap) * words * 8;
+		const QStaged s = stage_inputs(h, in, i0, nc, nc);
+		h->qout.ensure(bytes / 8);
+		HIPCHK(hipMemsetAsync(h->qout.p, 0, bytes, h->st));
+		launch(nc, s, h->qout.p, s.tail);
+		HIPCHK(hipMemcpyAsync(cnt + i0, s.tail, (size_t)nc * 8, hipMemcpyDeviceToHost, h->st));
+		HIPCHK(hipMemcpyAsync(rec + i0 * cap * words, h->qout.p, bytes, hipMemcpyDeviceToHost, h->st));
+		HIPCHK(hipStreamSynchronize(h->st));
+		for (int64_t i = i0; i < i0 + nc; ++i) stored += std::min(std::max<int64_t>(cnt[i], 0), cap);
+	}
+	return stored;
+}
+
+/* ---- backward search, extend, extract: one DPP row of 16 lanes per query ---- */
+
+static void launch_bsearch(rb2_hip_t *h, int64_t n, const uint8_t *pat, const int64_t *off, int64_t base, int64_t *out)
+{
+	qlaunch(h, k_bsearch<true>, k_bsearch<false>, (uint64_t)n, pat, off, base, n, out);
+}
+
+void rb2_hip_backward_search(rb2_hip_t *h, int64_t n, const uint8_t *pat, const int64_t *off, int64_t *out)
+{
+	query_begin(h, "backward_search");
+	if (n <= 0) return;
+	check_offsets("backward_search", "pattern", n, off);
+	staged_results(h, n, {pat, off, 0}, 3, out, [&](int64_t nc, const QStaged &s, int64_t *d_out) { launch_bsearch(h, nc, s.bytes, s.v, s.base, d_out); });
+}
+
+void rb2_hip_backward_search_dev(rb2_hip_t *h, int64_t n, const uint8_t *pat, const int64_t *off, int64_t *out)
+{
+	query_begin(h, "backward_search_dev");
+	const int64_t CH = query_chunk();
+	for (int64_t i0 = 0; i0 < n; i0 += CH) launch_bsearch(h, std::min(CH, n - i0), pat, off + i0, 0, out + 3 * i0);
+}
+
+void rb2_hip_extend(rb2_hip_t *h, int64_t n, const int64_t *ik, int is_back, int64_t *ok)
+{
+	query_begin(h, "extend");
+	if (n <= 0) return;
+	is_back = is_back ? 1 : 0;
+	staged_results(h, n, {nullptr, ik, 3}, 18, ok, [&](int64_t nc, const QStaged &s, int64_t *d_ok) {
+		qlaunch(h, k_extend<true>, k_extend<false>, (uint64_t)nc, s.v, is_back, nc, d_ok); });
+}
+
+int64_t rb2_hip_extract(rb2_hip_t *h, int64_t n, const int64_t *rows, int64_t max_len, uint8_t *out, int64_t *len)
+{
+	query_begin(h, "extract");
+	if (n <= 0) return 0;
+	if (max_len < 0) max_len = 0;
+	int64_t CH = query_chunk();
+	if (max_len > 0) CH = record_chunk(CH, max_len);
+	h->qbytes.ensure((size_t)std::max<int64_t>(std::min(CH, n) * max_len, 1));
+	int64_t fit = 0;
+	for (int64_t i0 = 0; i0 < n; i0 += CH) {
+		const int64_t nc = std::min(CH, n - i0);
+		const QStaged s = stage_inputs(h, {nullptr, rows, 1}, i0, nc, nc);
+		qlaunch(h, k_extract<true>, k_extract<false>, (uint64_t)nc, s.v, nc, max_len, h->qbytes.p, s.tail);
+		HIPCHK(hipMemcpyAsync(len + i0, s.tail, (size_t)nc * 8, hipMemcpyDeviceToHost, h->st));
+		if (nc * max_len) HIPCHK(hipMemcpyAsync(out + i0 * max_len, h->qbytes.p, (size_t)(nc * max_len), hipMemcpyDeviceToHost, h->st));
+		HIPCHK(hipStreamSynchronize(h->st));
+		for (int64_t i = i0; i < i0 + nc; ++i)                  // the walk spells a string from its last symbol: text order is the reverse
+			if (len[i] >= 0) { std::reverse(out + i * max_len, out + i * max_len + len[i]); ++fit; }
+	}
+	return fit;
+}
+
+/* ---- super-maximal exact matches (k_smem) ---- */
+
+static void launch_smem(rb2_hip_t *h, int64_t n, const uint8_t *qry, const int64_t *off, int64_t base, int64_t min_len, int64_t min_occ, int64_t max_mems,
+                        int64_t *mem, int64_t *cnt)
+{
+	qlaunch(h, k_smem<true>, k_smem<false>, (uint64_t)n, qry, off, base, n, min_len, min_occ, max_mems, mem, cnt);
+}
+
+static void smem_check(const char *who, int64_t min_len, int64_t min_occ, int64_t max_mems)
+{
+	if (min_len < 1 || min_occ < 1 || max_mems < 1)
+		rb2_fatal("[rb2_hip] %s: min_len, min_occ and max_mems must be at least 1 (got %lld, %lld, %lld)\n", who, (long long)min_len, (long long)min_occ, (long long)max_mems);
+}
+
+int64_t rb2_hip_smem(rb2_hip_t *h, int64_t n, const uint8_t *qry, const int64_t *off, int64_t min_len, int64_t min_occ, int64_t max_mems, int64_t *mem, int64_t *cnt)
+{
+	query_begin(h, "smem");
+	if (n <= 0) return 0;
+	smem_check("smem", min_len, min_occ, max_mems);
+	check_offsets("smem", "query", n, off);
+	return staged_records(h, n, {qry, off, 0}, 5, max_mems, mem, cnt, [&](int64_t nc, const QStaged &s, int64_t *d_mem, int64_t *d_cnt) {
+		launch_smem(h, nc, s.bytes, s.v, s.base, min_len, min_occ, max_mems, d_mem, d_cnt); });
+}
+
+void rb2_hip_smem_dev(rb2_hip_t *h, int64_t n, const uint8_t *qry, const int64_t *off, int64_t min_len, int64_t min_occ, int64_t max_mems, int64_t *mem, int64_t *cnt)
+{
+	query_begin(h, "smem_dev");
+	if (n <= 0) return;
+	smem_check("smem_dev", min_len, min_occ, max_mems);
+	const int64_t CH = query_chunk();
+	for (int64_t i0 = 0; i0 < n; i0 += CH) launch_smem(h, std::min(CH, n - i0), qry, off + i0, 0, min_len, min_occ, max_mems, mem + i0 * max_mems * 5, cnt + i0);
+}
+
+/* ---- sampled suffix array: rows back to (string, position) (k_ssa_build, k_locate) ---- */
+
+static const int64_t SSA_LAUNCH = 1 << 24;                     /* DPP rows (strings, hit slots) per launch: 2^28 threads */
+
+int64_t rb2_hip_ssa_build(rb2_hip_t *h, int log2_step)
+{
+	query_begin(h, "ssa_build");
+	if (log2_step < 0 || log2_step > 30) { rb2_fatal("[rb2_hip] ssa_build: log2_step must be 0 .. 30 (got %d)\n", log2_step); }
+	index_rows_change(h);                                      // (an array that is there is freed first: the new one is sized exactly)
+	uint64_t N = 0;
+	for (int r = 0; r < NR; ++r) N += h->h_rope[r].n;
+	const uint64_t n = h->h_rope[0].n;                          // C[1]: rope $ is one piece
+	const uint64_t ns = (N + (1ull << log2_step) - 1) >> log2_step;
+	if (n) {
+		h->ssa_smp.ensure((size_t)ns * 2); h->ssa_len.ensure((size_t)n); h->ssa_head.ensure((size_t)n);
+		for (uint64_t k0 = 0; k0 < n; k0 += (uint64_t)SSA_LAUNCH)
+			qlaunch(h, k_ssa_build<true>, k_ssa_build<false>, std::min<uint64_t>((uint64_t)SSA_LAUNCH, n - k0), k0, n, log2_step, h->ssa_smp.p, h->ssa_len.p, h->ssa_head.p);
+		HIPCHK(hipStreamSynchronize(h->st));
+	}
+	h->ssa_valid = true; h->ssa_s = log2_step; h->ssa_n = (int64_t)ns; h->ssa_nstr = n;
+	return (int64_t)ns;
+}
+
+void rb2_hip_ssa_drop(rb2_hip_t *h)
+{ finish_pending(h);
+	HIPCHK(hipSetDevice(h->dev));
+	index_rows_change(h);
+}
+
+void rb2_hip_ssa_info(rb2_hip_t *h, int64_t out[4])
+{
+	out[0] = h->ssa_valid ? 1 : 0; out[1] = h->ssa_s; out[2] = h->ssa_n;
+	out[3] = (int64_t)((h->ssa_smp.cap + h->ssa_len.cap + h->ssa_head.cap) * sizeof(uint64_t));
+}
+
+static void locate_check(rb2_hip_t *h, const char *who, int64_t max_hits)
+{
+	if (!h->ssa_valid) { rb2_fatal("[rb2_hip] %s: the index has no sampled suffix array (none was built, or the index changed since): call rb2_hip_ssa_build first\n", who); }
+	if (max_hits < 1) { rb2_fatal("[rb2_hip] %s: max_hits must be at least 1 (got %lld)\n", who, (long long)max_hits); }
+}
+
+/* n intervals, all device pointers; hit and cnt belong to interval 0 of iv.  One launch takes SSA_LAUNCH slots (split_slots) */
+static void launch_locate(rb2_hip_t *h, int64_t n, const int64_t *iv, int64_t max_hits, int64_t *hit, int64_t *cnt)
+{
+	split_slots(n, max_hits, SSA_LAUNCH, [&](int64_t i0, int64_t nc, int64_t k0, int64_t kc) {
+		qlaunch(h, k_locate<true>, k_locate<false>, (uint64_t)(nc * kc), iv + 2 * i0, nc, max_hits, k0, kc, h->ssa_s,
+				h->ssa_smp.p, h->ssa_len.p, h->ssa_head.p, h->ssa_nstr, hit + i0 * max_hits * 2, cnt + i0); });
+}
+
+int64_t rb2_hip_locate(rb2_hip_t *h, int64_t n, const int64_t *iv, int64_t max_hits, int64_t *hit, int64_t *cnt)
+{
+	query_begin(h, "locate");
+	locate_check(h, "locate", max_hits);
+	if (n <= 0) return 0;
+	return staged_records(h, n, {nullptr, iv, 2}, 2, max_hits, hit, cnt, [&](int64_t nc, const QStaged &s, int64_t *d_hit, int64_t *d_cnt) {
+		launch_locate(h, nc, s.v, max_hits, d_hit, d_cnt); });
+}
+
+void rb2_hip_locate_dev(rb2_hip_t *h, int64_t n, const int64_t *iv, int64_t max_hits, int64_t *hit, int64_t *cnt)
+{
+	query_begin(h, "locate_dev");
+	locate_check(h, "locate_dev", max_hits);
+	if (n <= 0) return;
+	launch_locate(h, n, iv, max_hits, hit, cnt);
+}
+
+/* ---- suffix-prefix overlaps: the strings that begin with a suffix of a query (k_overlap, k_string_ids) ---- */
+
+static void launch_overlap(rb2_hip_t *h, int64_t n, const uint8_t *qry, const int64_t *off, int64_t base, int64_t min_ovlp, int64_t max_recs, int64_t *rec, int64_t *cnt)
+{
+	qlaunch(h, k_overlap<true>, k_overlap<false>, (uint64_t)n, qry, off, base, n, min_ovlp, max_recs, rec, cnt);
+}
+
+static void overlap_check(const char *who, int64_t min_ovlp, int64_t max_recs)
+{
+	if (min_ovlp < 1 || max_recs < 1)
+		rb2_fatal("[rb2_hip] %s: min_ovlp and max_recs must be at least 1 (got %lld, %lld)\n", who, (long long)min_ovlp, (long long)max_recs);
+}
+
+int64_t rb2_hip_overlap(rb2_hip_t *h, int64_t n, const uint8_t *qry, const int64_t *off, int64_t min_ovlp, int64_t max_recs, int64_t *rec, int64_t *cnt)
+{
+	query_begin(h, "overlap");
+	if (n <= 0) return 0;
+	overlap_check("overlap", min_ovlp, max_recs);
+	check_offsets("overlap", "query", n, off);
+	return staged_records(h, n, {qry, off, 0}, 3, max_recs, rec, cnt, [&](int64_t nc, const QStaged &s, int64_t *d_rec, int64_t *d_cnt) {
+		launch_overlap(h, nc, s.bytes, s.v, s.base, min_ovlp, max_recs, d_rec, d_cnt); });
+}
+
+void rb2_hip_overlap_dev(rb2_hip_t *h, int64_t n, const uint8_t *qry, const int64_t *off, int64_t min_ovlp, int64_t max_recs, int64_t *rec, int64_t *cnt)
+{
+	query_begin(h, "overlap_dev");
+	if (n <= 0) return;
+	overlap_check("overlap_dev", min_ovlp, max_recs);
+	const int64_t CH = query_chunk();
+	for (int64_t i0 = 0; i0 < n; i0 += CH) launch_overlap(h, std::min(CH, n - i0), qry, off + i0, 0, min_ovlp, max_recs, rec + i0 * max_recs * 3, cnt + i0);
+}
+
+static const int64_t IDS_LAUNCH = 1 << 28;                     /* hit slots (threads) per launch of k_string_ids */
+
+/* n ranges, all device pointers; ids and cnt belong to range 0 of zv.  One launch takes IDS_LAUNCH slots (split_slots), one thread each:
+ * k_string_ids reads no rope, so it has no layout and no piece table */
+static void launch_string_ids(rb2_hip_t *h, int64_t n, const int64_t *zv, int64_t max_hits, int64_t *ids, int64_t *cnt)
+{
+	split_slots(n, max_hits, IDS_LAUNCH, [&](int64_t i0, int64_t nc, int64_t k0, int64_t kc) {
+		hipLaunchKernelGGL(k_string_ids, dim3((unsigned)cdiv((uint64_t)(nc * kc), 256)), dim3(256), 0, h->st, zv + 2 * i0, (uint64_t)nc, max_hits, k0, kc,
+				(const uint64_t*)h->ssa_head.p, h->ssa_nstr, ids + i0 * max_hits, cnt + i0);
+		HIPCHK(hipGetLastError()); });
+}
+
+int64_t rb2_hip_string_ids(rb2_hip_t *h, int64_t n, const int64_t *zv, int64_t max_hits, int64_t *ids, int64_t *cnt)
+{
+	query_begin(h, "string_ids");
+	locate_check(h, "string_ids", max_hits);
+	if (n <= 0) return 0;
+	return staged_records(h, n, {nullptr, zv, 2}, 1, max_hits, ids, cnt, [&](int64_t nc, const QStaged &s, int64_t *d_ids, int64_t *d_cnt) {
+		launch_string_ids(h, nc, s.v, max_hits, d_ids, d_cnt); });
+}
+
+void rb2_hip_string_ids_dev(rb2_hip_t *h, int64_t n, const int64_t *zv, int64_t max_hits, int64_t *ids, int64_t *cnt)
+{
+	query_begin(h, "string_ids_dev");
+	locate_check(h, "string_ids_dev", max_hits);
+	if (n <= 0) return;
+	launch_string_ids(h, n, zv, max_hits, ids, cnt);
+}

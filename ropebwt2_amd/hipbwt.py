@@ -205,6 +205,14 @@ def _fmd_image(src):
     return np.ascontiguousarray(src, dtype=np.uint8).reshape(-1)
 
 
+def _stored(cnt, cap, what):
+    """how many of its records every item of a *_raw result holds, min(cnt, cap); an item with cnt < 0 raises ValueError: what, and
+    the first five of them"""
+    if (cnt < 0).any():
+        raise ValueError("%s: %s" % (what, np.flatnonzero(cnt < 0)[:5].tolist()))
+    return np.minimum(cnt, cap)
+
+
 class HipBwt:
     """Six-rope BWT resident in the HBM of one MI355X."""
 
@@ -360,24 +368,26 @@ class HipBwt:
         fit = self.L.rb2_hip_extract(self.h, len(rows), rows.ctypes.data, max_len, out.ctypes.data, ln.ctypes.data) if len(rows) else 0
         return int(fit), out, ln
 
+    def _records(self, fn, n, args, cap, words, call_empty):
+        """(records stored, rec (n, cap, words) int64, cnt (n,) int64) of fn(h, n, *args, rec, cnt), one of the host variants that return
+        records; rec and cnt start as zeros, and without items fn is called only if call_empty (its checks still run then)"""
+        rec = np.zeros((n, max(int(cap), 0), words), np.int64)
+        cnt = np.zeros(n, np.int64)
+        stored = fn(self.h, n, *args, rec.ctypes.data, cnt.ctypes.data) if n or call_empty else 0
+        return int(stored), rec, cnt
+
     def smem_raw(self, queries, min_len=1, min_occ=1, max_mems=64):
         """rb2_hip_smem as it is: (records stored, mem (n, max_mems, 5) int64 = start, end, x0, x1, size, cnt (n,) int64); only the
         first min(cnt[i], max_mems) records of query i are meaningful (the others are zeros), cnt[i] = -1 for a malformed query"""
         qry, off = pack_patterns(queries)
-        n = len(off) - 1
-        mem = np.zeros((n, max(int(max_mems), 0), 5), np.int64)
-        cnt = np.zeros(n, np.int64)
-        stored = self.L.rb2_hip_smem(self.h, n, qry.ctypes.data, off.ctypes.data, min_len, min_occ, max_mems, mem.ctypes.data, cnt.ctypes.data) if n else 0
-        return int(stored), mem, cnt
+        return self._records(self.L.rb2_hip_smem, len(off) - 1, (qry.ctypes.data, off.ctypes.data, min_len, min_occ, max_mems), max_mems, 5, False)
 
     def smem(self, queries, min_len=1, min_occ=1, max_mems=64):
         """super-maximal exact matches of every query (str / bytes over ACGTN, or nt6 arrays) against an index that holds both strands:
         a list with one (k, 5) int64 array per query, rows = start, end, x0, x1, size in increasing start, k = min(cnt, max_mems), and
         cnt (n,) = the SMEMs found per query; a malformed query ('$' or a code above 5 inside) raises ValueError"""
         stored, mem, cnt = self.smem_raw(queries, min_len, min_occ, max_mems)
-        if (cnt < 0).any():
-            raise ValueError("malformed queries (only the codes 1..5 are allowed): %s" % np.flatnonzero(cnt < 0)[:5].tolist())
-        return [mem[i, :min(int(cnt[i]), max_mems)].copy() for i in range(len(cnt))], cnt
+        return [m[:k].copy() for m, k in zip(mem, _stored(cnt, max_mems, "malformed queries (only the codes 1..5 are allowed)"))], cnt
 
     def smem_dev(self, n, qry_dev, off_dev, mem_dev, cnt_dev, min_len=1, min_occ=1, max_mems=64):
         """rb2_hip_smem_dev: all four pointers in this device's memory; asynchronous on the handle's stream"""
@@ -401,19 +411,13 @@ class HipBwt:
         """rb2_hip_locate as it is: (records stored, hit (n, max_hits, 2) int64 = string id, position, cnt (n,) int64); only the first
         min(cnt[i], max_hits) records of interval i are meaningful (the others are zeros), cnt[i] = -1 for a malformed interval"""
         iv = np.ascontiguousarray(np.asarray(intervals, dtype=np.int64).reshape(-1, 2))
-        n = len(iv)
-        hit = np.zeros((n, max(int(max_hits), 0), 2), np.int64)
-        cnt = np.zeros(n, np.int64)
-        stored = self.L.rb2_hip_locate(self.h, n, iv.ctypes.data, max_hits, hit.ctypes.data, cnt.ctypes.data)
-        return int(stored), hit, cnt
+        return self._records(self.L.rb2_hip_locate, len(iv), (iv.ctypes.data, max_hits), max_hits, 2, True)
 
     def locate(self, intervals, max_hits=64):
         """the places of the rows of every interval (lo, hi): a list with one (m, 2) int64 array per interval, rows = string id,
         position (0-based, text order) in row order, m = min(hi - lo, max_hits); a malformed interval raises ValueError"""
         stored, hit, cnt = self.locate_raw(intervals, max_hits)
-        if (cnt < 0).any():
-            raise ValueError("malformed intervals (0 <= lo <= hi <= rows): %s" % np.flatnonzero(cnt < 0)[:5].tolist())
-        return [hit[i, :min(int(cnt[i]), max_hits)].copy() for i in range(len(cnt))]
+        return [m[:k].copy() for m, k in zip(hit, _stored(cnt, max_hits, "malformed intervals (0 <= lo <= hi <= rows)"))]
 
     def locate_dev(self, n, iv_dev, hit_dev, cnt_dev, max_hits=64):
         """rb2_hip_locate_dev: all three pointers in this device's memory; asynchronous on the handle's stream"""
@@ -437,11 +441,7 @@ class HipBwt:
         """rb2_hip_overlap as it is: (records stored, rec (n, max_recs, 3) int64 = length, zlo, zhi, cnt (n,) int64); only the first
         min(cnt[i], max_recs) records of query i are meaningful (the others are zeros), cnt[i] = -1 for a malformed query"""
         qry, off = pack_patterns(queries)
-        n = len(off) - 1
-        rec = np.zeros((n, max(int(max_recs), 0), 3), np.int64)
-        cnt = np.zeros(n, np.int64)
-        stored = self.L.rb2_hip_overlap(self.h, n, qry.ctypes.data, off.ctypes.data, min_ovlp, max_recs, rec.ctypes.data, cnt.ctypes.data) if n else 0
-        return int(stored), rec, cnt
+        return self._records(self.L.rb2_hip_overlap, len(off) - 1, (qry.ctypes.data, off.ctypes.data, min_ovlp, max_recs), max_recs, 3, False)
 
     def overlap_dev(self, n, qry_dev, off_dev, rec_dev, cnt_dev, min_ovlp, max_recs):
         """rb2_hip_overlap_dev: all four pointers in this device's memory; asynchronous on the handle's stream"""
@@ -451,11 +451,8 @@ class HipBwt:
         """rb2_hip_string_ids as it is: (ids stored, ids (n, max_hits) int64, cnt (n,) int64); only the first min(cnt[i], max_hits) ids
         of range i are meaningful (the others are zeros), cnt[i] = -1 for a malformed range.  Needs build_ssa()"""
         zv = np.ascontiguousarray(np.asarray(ranges, dtype=np.int64).reshape(-1, 2))
-        n = len(zv)
-        ids = np.zeros((n, max(int(max_hits), 0)), np.int64)
-        cnt = np.zeros(n, np.int64)
-        stored = self.L.rb2_hip_string_ids(self.h, n, zv.ctypes.data, max_hits, ids.ctypes.data, cnt.ctypes.data)
-        return int(stored), ids, cnt
+        stored, ids, cnt = self._records(self.L.rb2_hip_string_ids, len(zv), (zv.ctypes.data, max_hits), max_hits, 1, True)
+        return stored, ids[:, :, 0], cnt
 
     def string_ids_dev(self, n, zv_dev, ids_dev, cnt_dev, max_hits=64):
         """rb2_hip_string_ids_dev: all three pointers in this device's memory; asynchronous on the handle's stream"""
@@ -469,9 +466,7 @@ class HipBwt:
         lens = [len(encode_pattern(q)) for q in queries]
         max_recs = max(max(lens, default=0) - int(min_ovlp) + 1, 1)                  # one record per length at the most: nothing is cut
         _, rec, cnt = self.overlap_raw(queries, min_ovlp, max_recs)
-        if (cnt < 0).any():
-            raise ValueError("malformed queries (only the codes 1..5 are allowed): %s" % np.flatnonzero(cnt < 0)[:5].tolist())
-        live = np.arange(max_recs)[None, :] < cnt[:, None]
+        live = np.arange(max_recs)[None, :] < _stored(cnt, max_recs, "malformed queries (only the codes 1..5 are allowed)")[:, None]
         who = np.nonzero(live)[0]
         recs = rec[live]
         max_hits = max(min(int(max_hits), int((recs[:, 2] - recs[:, 1]).max(initial=1))), 1)    # no wider than the widest range
