@@ -249,6 +249,32 @@ int64_t rb2_hip_string_ids(rb2_hip_t *h, int64_t n, const int64_t *zv, int64_t m
 /* the same with zv, ids and cnt in this device's memory, asynchronous on the handle's stream (no return value: read cnt) */
 void    rb2_hip_string_ids_dev(rb2_hip_t *h, int64_t n, const int64_t *zv, int64_t max_hits, int64_t *ids, int64_t *cnt);
 
+/* ---- k-mer enumeration: which k-mers the indexed strings contain, and how often ----
+ * A k-mer is k consecutive symbols of one indexed string, all of them A C G T (nt6 codes 1 .. 4): a window that holds an N, or that would
+ * run over the end of its string, is none.  Its count is hi - lo of rb2_hip_backward_search on it, so an index of both strands counts both
+ * strands.  rb2_hip_kmers reports every distinct k-mer with at least min_occ occurrences (what `fermi2 count` lists; the k-mer spectrum).
+ * rec[3*j ..] = code, lo, hi for j < min(return value, max_recs): code packs the k-mer two bits per symbol, A = 0 C = 1 G = 2 T = 3, the
+ * symbol at text position p at bits 2 * (k - 1 - p), so that the numeric order of the codes (taken as unsigned) is the lexicographic order
+ * of the k-mers, which is also the order of their lo; [lo, hi) is the k-mer's interval in the global rows of the other queries and can be
+ * handed to rb2_hip_locate as it is.  The order of the records is unspecified.  Returns the number of k-mers found, which may exceed
+ * max_recs (the surplus is counted, not stored): exactly max_recs records are stored then, every one a true record, none twice; which ones
+ * is unspecified, and rec beyond the records stored is left untouched.
+ * hist[c], c < hist_len - 1 = the reported k-mers with exactly c occurrences, hist[hist_len - 1] = those with hist_len - 1 or more:
+ * complete whatever max_recs is (max_recs = 0 gives the spectrum alone); the bins below min_occ are zero.
+ * canonical != 0: a k-mer is reported only if its code <= the code of its reverse complement (a palindrome once); the count stays that of
+ * the k-mer itself.  Meaningful on an index of both strands, where the two counts agree: the caller's responsibility, as for rb2_hip_extend.
+ * info (may be NULL): [0] expand launches, [1] the largest number of items in a frontier segment, [2] the largest number of segments alive
+ * at once, [3] the k-mers that met min_occ before the canonical filter.
+ * rec may be NULL when max_recs == 0, hist when hist_len == 0.  Fatal: k outside 1 .. 32, min_occ < 1, max_recs < 0 or hist_len < 0, a NULL
+ * pointer with a size that is not 0.  An empty index gives 0 and a histogram of zeros.  Like every query the call reads the index and
+ * nothing else: a sampled suffix array stays valid across it.
+ * The enumeration is level-wise (k_kmer_expand: the two ranks of an l-mer's interval give the intervals of its four left extensions; an
+ * extension below min_occ is dropped for good) and walks the levels depth-first over segments of at most F items, so it holds k * F * 24
+ * bytes of device memory at the most whatever the index (F = RB2_KMER_FRONTIER in the environment, at least 4, 2^22 by default); the
+ * records are staged on the device and copied out in pieces of at most 256 MiB.  There is no _dev variant: the host sizes every launch
+ * from the count the one before it wrote, so the call cannot be asynchronous. */
+int64_t rb2_hip_kmers(rb2_hip_t *h, int k, int64_t min_occ, int canonical, int64_t max_recs, int64_t *rec, int64_t hist_len, int64_t *hist, int64_t info[4]);
+
 /* 64-bit checksum of rope b computed on the device (position-weighted sum over the packed words of its pieces): equal for
  * equal symbol sequences however the index was built (one engine, N ranks, an .fmr loaded back), sensitive to order.  Lets
  * tests compare indexes of 10^11 symbols without moving them off the device (the reference has no counterpart; its ropes are

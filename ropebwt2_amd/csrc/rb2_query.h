@@ -15,6 +15,7 @@
 // Queries read the pool, the directory and ctl->rope only: they never write the index, the Ctl or a buffer an insert reads.
 #pragma once
 #include "rb2_device.h"
+#include "rb2_kmer_plan.h"
 
 namespace rb2 {
 
@@ -393,6 +394,81 @@ __global__ __launch_bounds__(256) void k_string_ids(const int64_t *zv, uint64_t 
 	if (kk == 0) cnt[i] = bad ? -1 : zhi - zlo;
 	if (bad || kk >= zhi - zlo) return;
 	ids[i * (uint64_t)max_hits + (uint64_t)kk] = (int64_t)head[zlo + kk];
+}
+
+// ---- k-mer enumeration ----
+// The two ranks of an interval [lo, hi) give the intervals of all four one-symbol left extensions at once: the child of the l-mer P by a
+// is aP = [C[a] + occ(a, lo), C[a] + occ(a, hi)), and aP cannot occur more often than P, so a child smaller than min_occ is dropped for
+// good.  From the single item (0, 0, N) -- the empty word -- k levels of that give every k-mer with at least min_occ occurrences, each once.
+
+constexpr int KMER_HL = 256;               // histogram bins below this are counted in LDS and added to global memory once per block
+constexpr int KMER_ROWS = 16 * 2048;       // DPP rows of a launch at the most (2048 blocks: eight per CU); a row takes items a launch apart
+
+// one level of the enumeration: item i of in[3i ..] = code, lo, hi is an l-mer; its live children are (l+1)-mers.  ctr[0], ctr[1], ctr[2]:
+// the cursor of the next segment, the k-mers found, the k-mers that met min_occ before the canonical filter.
+//   l + 1 < k   a live child draws a number j from ctr[0] and goes to out[3j ..], the segment of the next level (j < out_cap always holds
+//               for the slices the host cuts; a number beyond it is not stored)
+//   l + 1 == k  a live child that passes the canonical filter is a k-mer of the result: it draws j from ctr[1], is stored in
+//               out[3 * (j - out_base) ..] when j < out_max (max_recs) and the slot lies inside the staging buffer (out_base <= j <
+//               out_base + out_cap), and is counted in hist[min(hi - lo, hist_len - 1)]
+// One DPP row per item, both ranks by all 16 lanes; lane a - 1 of the row then owns child a.  Numbers are drawn once per wave: a ballot
+// of the live children, one atomic by lane 0, the position of a child = the live children in the lanes below it.  Every row of a block
+// makes the same number of turns, so the ballots see whole waves.
+template <bool SPARSE> __global__ __launch_bounds__(256) void k_kmer_expand(const QTab *Tg, PoolView pv, const int64_t *in, uint64_t n, int l, int k, int64_t min_occ, int canonical,
+                                                                            int64_t *out, uint64_t out_cap, uint64_t out_base, uint64_t out_max,
+                                                                            unsigned long long *ctr, unsigned long long *hist, int64_t hist_len)
+{
+	__shared__ QTab T;
+	__shared__ uint32_t s_hist[KMER_HL];
+	__shared__ uint32_t s_pre;
+	static_assert(KMER_HL == 256, "one thread per bin");
+	s_hist[threadIdx.x] = 0;
+	if (threadIdx.x == 0) s_pre = 0;
+	qtab_load(Tg, T);
+	const int lane = lane_id();
+	const uint32_t g = (uint32_t)lane & 15u;
+	const bool last = l + 1 == k;
+	for (uint64_t i0 = (uint64_t)blockIdx.x * QPB; i0 < n; i0 += (uint64_t)gridDim.x * QPB) {
+		const uint64_t i = i0 + (threadIdx.x >> 4);
+		bool live = false;
+		uint64_t code = 0, nlo = 0, nhi = 0;
+		if (i < n) {
+			const uint64_t pc = (uint64_t)in[3 * i], lo = (uint64_t)in[3 * i + 1], hi = (uint64_t)in[3 * i + 2];
+			uint64_t cl[6], ch[6];
+			qrank<SPARSE>(T, pv, lo, cl);
+			qrank<SPARSE>(T, pv, hi, ch);
+#pragma unroll
+			for (int a = 1; a <= 4; ++a)
+				if (g == (uint32_t)(a - 1)) { const uint64_t C = qC(T, a); nlo = C + cl[a]; nhi = C + ch[a]; }
+			code = kmer_prepend(pc, l, (int)g + 1);
+			live = g < 4 && nhi - nlo >= (uint64_t)min_occ;
+		}
+		if (last) {
+			const uint64_t pre = ballot64(live);
+			if (lane == 0 && pre) atomicAdd(&s_pre, (uint32_t)__popcll(pre));
+			if (canonical) live = live && kmer_canonical(code, k);
+		}
+		const uint64_t mask = ballot64(live);
+		unsigned long long base = 0;
+		if (lane == 0 && mask) base = atomicAdd(&ctr[last ? 1 : 0], (unsigned long long)__popcll(mask));
+		const uint64_t j = uniform64(base) + (uint64_t)__popcll(mask & lt_mask(lane));
+		if (live) {
+			if (j < out_max && j >= out_base && j - out_base < out_cap) {
+				int64_t *o = out + 3 * (j - out_base);
+				o[0] = (int64_t)code; o[1] = (int64_t)nlo; o[2] = (int64_t)nhi;
+			}
+			if (last && hist_len > 0) {
+				const uint64_t bin = min(nhi - nlo, (uint64_t)hist_len - 1);
+				if (bin < (uint64_t)KMER_HL) atomicAdd(&s_hist[bin], 1u);
+				else atomicAdd(&hist[bin], 1ull);
+			}
+		}
+	}
+	if (!last) return;                                              // (the same in the whole block)
+	__syncthreads();
+	const uint32_t v = s_hist[threadIdx.x];
+	if (v) atomicAdd(&hist[threadIdx.x], (unsigned long long)v);     // (a bin that was counted lies below hist_len)
+	if (threadIdx.x == 0 && s_pre) atomicAdd(&ctr[2], (unsigned long long)s_pre);
 }
 
 } // namespace rb2

@@ -1,8 +1,9 @@
-// Host side of the FM-index queries (kernels: rb2_query.h; the launch arithmetic: rb2_query_plan.h).  Included from rb2_engine.hip, whose
+// Host side of the FM-index queries (kernels: rb2_query.h; the launch arithmetic: rb2_query_plan.h, rb2_kmer_plan.h).  Included from rb2_engine.hip, whose
 // handle, buffers and checks it uses.  Three helpers carry every query: qlaunch (one launch of a kernel in the layout of the index),
 // stage_inputs (a chunk's inputs to the device) and staged_records (the chunked loop of the host variants that return records).
 #pragma once
 #include "rb2_query_plan.h"
+#include "rb2_kmer_plan.h"
 
 /* queries per launch: 16 threads each, so 2^24 stay far below the 2^32 threads of one launch; RB2_QUERY_CHUNK lowers it (tests of the chunking) */
 static int64_t query_chunk()
@@ -312,4 +313,99 @@ void rb2_hip_string_ids_dev(rb2_hip_t *h, int64_t n, const int64_t *zv, int64_t 
 	locate_check(h, "string_ids_dev", max_hits);
 	if (n <= 0) return;
 	launch_string_ids(h, n, zv, max_hits, ids, cnt);
+}
+
+/* ---- k-mer enumeration: every k-mer of the indexed strings with its count (k_kmer_expand) ---- */
+
+/* items a frontier segment holds at the most: RB2_KMER_FRONTIER in the environment, read on every call; 2^22 (96 MiB a level, at most
+ * 3 GiB at k = 32; a slice of 2^20 items is some hundreds of microseconds of ranks, far above what a launch and its read-back cost) */
+static int64_t kmer_frontier()
+{
+	const char *e = getenv("RB2_KMER_FRONTIER");
+	const int64_t v = e ? atoll(e) : 0;
+	return v > 0 ? std::max(v, KMER_FRONTIER_MIN) : (int64_t)1 << 22;
+}
+
+/* records the staging buffer holds at the most: QUERY_STAGE_BYTES of them; RB2_KMER_STAGE lowers it (tests of the flushes) */
+static int64_t kmer_stage_limit()
+{
+	const int64_t lim = QUERY_STAGE_BYTES / 24;
+	const char *e = getenv("RB2_KMER_STAGE");
+	const int64_t v = e ? atoll(e) : 0;
+	return v > 0 ? std::min(std::max<int64_t>(v, 4), lim) : lim;
+}
+
+int64_t rb2_hip_kmers(rb2_hip_t *h, int k, int64_t min_occ, int canonical, int64_t max_recs, int64_t *rec, int64_t hist_len, int64_t *hist, int64_t info[4])
+{
+	query_begin(h, "kmers");
+	if (k < 1 || k > KMER_MAX_K) { rb2_fatal("[rb2_hip] kmers: k must be 1 .. %d (got %d)\n", KMER_MAX_K, k); }
+	if (min_occ < 1) { rb2_fatal("[rb2_hip] kmers: min_occ must be at least 1 (got %lld)\n", (long long)min_occ); }
+	if (max_recs < 0 || hist_len < 0) { rb2_fatal("[rb2_hip] kmers: max_recs and hist_len must not be negative (got %lld, %lld)\n", (long long)max_recs, (long long)hist_len); }
+	if ((max_recs > 0 && !rec) || (hist_len > 0 && !hist)) { rb2_fatal("[rb2_hip] kmers: %s is NULL but its size is not 0\n", max_recs > 0 && !rec ? "rec" : "hist"); }
+	int64_t inf[4] = {0, 0, 0, 0};
+	for (int64_t c = 0; c < hist_len; ++c) hist[c] = 0;
+	if (info) memcpy(info, inf, sizeof(inf));
+	int64_t N = 0;
+	for (int r = 0; r < NR; ++r) N += (int64_t)h->h_rope[r].n;
+	if (N < min_occ) return 0;                                     // (an empty index: nothing occurs)
+	const int64_t F = kmer_frontier(), stage = kmer_stage_recs(max_recs, kmer_stage_limit());
+	/* the segments of levels 0 .. k - 1 behind each other in qin, the record staging in qout, three counters and the histogram in qbytes */
+	int64_t seg0[KMER_MAX_K + 1], have[KMER_MAX_K] = {0};
+	seg0[0] = 0;
+	for (int l = 0; l < k; ++l) seg0[l + 1] = seg0[l] + kmer_segment_cap(l, F, N);
+	h->qin.ensure((size_t)seg0[k] * 3);
+	h->qout.ensure((size_t)std::max<int64_t>(stage, 1) * 3);
+	h->qbytes.ensure((size_t)(8 + hist_len) * 8);
+	unsigned long long *ctr = (unsigned long long*)h->qbytes.p, *d_hist = ctr + 8;
+	HIPCHK(hipMemsetAsync(ctr, 0, (size_t)(8 + hist_len) * 8, h->st));
+	const int64_t root[3] = {0, 0, N};
+	HIPCHK(hipMemcpyAsync(h->qin.p, root, sizeof(root), hipMemcpyHostToDevice, h->st));
+	have[0] = 1; inf[1] = inf[2] = 1;
+	int64_t found = 0, flushed = 0;
+	auto flush = [&]() {                                           // (the stream is idle: every launch is followed by a synchronise)
+		const int64_t m = kmer_staged(found, flushed, max_recs);
+		if (m > 0) HIPCHK(hipMemcpyAsync(rec + 3 * flushed, h->qout.p, (size_t)m * 24, hipMemcpyDeviceToHost, h->st));
+		flushed += std::max<int64_t>(m, 0);
+	};
+	int top = 0;
+	while (top >= 0) {
+		if (have[top] == 0) { --top; continue; }
+		const int l = top;
+		const bool last = l + 1 == k;
+		const int64_t take = last ? kmer_final_slice(have[l], F, stage, max_recs) : kmer_slice(have[l], F);
+		have[l] -= take;
+		const int64_t *src = h->qin.p + 3 * (seg0[l] + have[l]);      // the slice comes off the end of its segment
+		unsigned long long got = 0;
+		if (last) {
+			if (kmer_must_flush(found, flushed, take, stage, max_recs)) { flush(); HIPCHK(hipStreamSynchronize(h->st)); }
+			qlaunch(h, k_kmer_expand<true>, k_kmer_expand<false>, (uint64_t)std::min<int64_t>(take, KMER_ROWS), src, take, l, k, min_occ, canonical ? 1 : 0,
+					h->qout.p, stage, flushed, max_recs, ctr, d_hist, hist_len);
+			HIPCHK(hipMemcpyAsync(&got, ctr + 1, 8, hipMemcpyDeviceToHost, h->st));
+			HIPCHK(hipStreamSynchronize(h->st));
+			found = (int64_t)got;
+		} else {
+			const int64_t cap = seg0[l + 2] - seg0[l + 1];
+			HIPCHK(hipMemsetAsync(ctr, 0, 8, h->st));
+			qlaunch(h, k_kmer_expand<true>, k_kmer_expand<false>, (uint64_t)std::min<int64_t>(take, KMER_ROWS), src, take, l, k, min_occ, 0,
+					h->qin.p + 3 * seg0[l + 1], cap, 0, cap, ctr, d_hist, (int64_t)0);
+			HIPCHK(hipMemcpyAsync(&got, ctr, 8, hipMemcpyDeviceToHost, h->st));
+			HIPCHK(hipStreamSynchronize(h->st));
+			if ((int64_t)got > cap) { rb2_fatal("[rb2_hip] kmers: %llu items for a segment of %lld at level %d (the index is no BWT of strings?)\n", got, (long long)cap, l + 1); }
+			have[l + 1] = (int64_t)got;
+			inf[1] = std::max(inf[1], have[l + 1]);
+			top = l + 1;
+			int64_t alive = 0;
+			for (int q = 0; q <= top; ++q) alive += have[q] > 0;
+			inf[2] = std::max(inf[2], alive);
+		}
+		++inf[0];
+	}
+	flush();
+	unsigned long long pre = 0;
+	HIPCHK(hipMemcpyAsync(&pre, ctr + 2, 8, hipMemcpyDeviceToHost, h->st));
+	if (hist_len) HIPCHK(hipMemcpyAsync(hist, d_hist, (size_t)hist_len * 8, hipMemcpyDeviceToHost, h->st));
+	HIPCHK(hipStreamSynchronize(h->st));
+	inf[3] = (int64_t)pre;
+	if (info) memcpy(info, inf, sizeof(inf));
+	return found;
 }

@@ -63,6 +63,7 @@ def load_hip_lib():
         "rb2_hip_overlap_dev": (None, [vp, i64, vp, vp, i64, i64, vp, vp]),
         "rb2_hip_string_ids": (i64, [vp, i64, vp, i64, vp, vp]),
         "rb2_hip_string_ids_dev": (None, [vp, i64, vp, i64, vp, vp]),
+        "rb2_hip_kmers": (i64, [vp, i32, i64, i32, i64, vp, i64, vp, vp]),
         "rb2_hip_reserve": (None, [vp, i64, i64, i64]),
         "rb2_hip_num_subropes": (i32, []),
         "rb2_hip_memcpy": (None, [vp, vp, vp, i64, i32]),
@@ -129,7 +130,7 @@ ABI_SYMBOLS = [
     "rb2_hip_download_rope", "rb2_hip_stream_rope", "rb2_hip_load_ropes", "rb2_hip_load_fmd", "rb2_hip_load_fmd_file", "rb2_hip_rank1a", "rb2_hip_rank_batch", "rb2_hip_reserve",
     "rb2_hip_backward_search", "rb2_hip_backward_search_dev", "rb2_hip_extend", "rb2_hip_extract", "rb2_hip_smem", "rb2_hip_smem_dev", "rb2_hip_dev_alloc",
     "rb2_hip_ssa_build", "rb2_hip_ssa_drop", "rb2_hip_ssa_info", "rb2_hip_locate", "rb2_hip_locate_dev",
-    "rb2_hip_overlap", "rb2_hip_overlap_dev", "rb2_hip_string_ids", "rb2_hip_string_ids_dev",
+    "rb2_hip_overlap", "rb2_hip_overlap_dev", "rb2_hip_string_ids", "rb2_hip_string_ids_dev", "rb2_hip_kmers",
     "rb2_hip_num_subropes", "rb2_hip_memcpy", "rb2_hip_use_stream",
     "rb2_hip_dev_free", "rb2_hip_synth_reads", "rb2_hip_synth_reads_cov", "rb2_hip_synth_reads_skew", "rb2_hip_sync", "rb2_hip_sparse_stats", "rb2_hip_layout_stats", "rb2_hip_rewind_stats", "rb2_hip_window_stats", "rb2_hip_host_register", "rb2_hip_host_unregister", "rb2_hip_profile",
     "rb2_hip_profile_get", "rb2_hip_kernel_name", "rb2_hip_layout",
@@ -165,6 +166,22 @@ def pack_patterns(patterns):
         off[1:] = np.cumsum([len(e) for e in enc])
     pat = np.concatenate(enc) if enc and off[-1] else np.zeros(1, np.uint8)
     return np.ascontiguousarray(pat, dtype=np.uint8), off
+
+
+def pack_kmer(seq):
+    """the code of a k-mer (str / bytes over ACGT, or nt6 codes 1..4; k = 1 .. 32) as rb2_hip_kmers reports it: two bits per symbol,
+    A C G T = 0 1 2 3, the first symbol in the highest bits, so that codes of one k sort as the k-mers do"""
+    a = encode_pattern(seq).astype(np.uint64)
+    if not 1 <= len(a) <= 32 or (a < 1).any() or (a > 4).any():
+        raise ValueError("k-mer %r: 1 .. 32 symbols out of ACGT" % (seq,))
+    return np.uint64(((a - np.uint64(1)) << (np.uint64(2) * np.arange(len(a) - 1, -1, -1, dtype=np.uint64))).sum())
+
+
+def unpack_kmers(codes, k):
+    """codes of k-mers (rb2_hip_kmers) -> an (n, k) uint8 array of nt6 codes 1..4 in text order"""
+    codes = np.asarray(codes, dtype=np.uint64).reshape(-1)
+    sh = np.uint64(2) * np.arange(k - 1, -1, -1, dtype=np.uint64)
+    return ((codes[:, None] >> sh[None, :]) & np.uint64(3)).astype(np.uint8) + np.uint8(1)
 
 
 def expand_runs(rle):
@@ -475,6 +492,34 @@ class HipBwt:
         for i, l, k, row in zip(who.tolist(), recs[:, 0].tolist(), np.minimum(n_ids, max_hits).tolist(), ids.tolist()):
             out[i].append([(s, l) for s in row[:k]])
         return [[p for grp in reversed(o) for p in grp] for o in out]
+
+    # -- k-mer enumeration: the k-mers of the indexed strings and their counts (include/rb2_hip.h) ------------------------------
+    def kmers_raw(self, k, min_occ=1, canonical=False, max_recs=1 << 16, hist_len=0):
+        """rb2_hip_kmers as it is: (k-mers found, rec (max_recs, 3) int64 = code, lo, hi, hist (hist_len,) int64, info (4,) int64); only
+        the first min(found, max_recs) records are meaningful (the others are zeros), in no particular order"""
+        rec = np.zeros((max(int(max_recs), 0), 3), np.int64)
+        hist = np.zeros(max(int(hist_len), 0), np.int64)
+        info = np.zeros(4, np.int64)
+        found = self.L.rb2_hip_kmers(self.h, int(k), int(min_occ), int(bool(canonical)), int(max_recs), rec.ctypes.data if len(rec) else None,
+                                     int(hist_len), hist.ctypes.data if len(hist) else None, info.ctypes.data)
+        return int(found), rec, hist, info
+
+    def kmers(self, k, min_occ=1, canonical=False):
+        """every distinct k-mer of the indexed strings with at least min_occ occurrences: (codes uint64, lo, hi), sorted by lo, which
+        is the order of the codes and of the k-mers; hi - lo = occurrences, [lo, hi) goes to locate() as it is.  canonical: only the
+        smaller of a k-mer and its reverse complement (an index of both strands).  One call when the k-mers fit the first guess, else one
+        to count and one to fetch"""
+        found, rec, _, _ = self.kmers_raw(k, min_occ, canonical)
+        if found > len(rec):
+            found, rec, _, _ = self.kmers_raw(k, min_occ, canonical, max_recs=found)
+        rec = rec[:found]
+        rec = rec[np.argsort(rec[:, 1], kind="stable")]
+        return rec[:, 0].astype(np.uint64), rec[:, 1].copy(), rec[:, 2].copy()
+
+    def kmer_spectrum(self, k, hist_len=256, min_occ=1, canonical=False):
+        """the k-mer spectrum: hist[c] = distinct k-mers with exactly c occurrences, hist[hist_len - 1] = those with that many or more
+        (no records are fetched)"""
+        return self.kmers_raw(k, min_occ, canonical, max_recs=0, hist_len=hist_len)[2]
 
     # -- measurement helpers ----------------------------------------------------------------
     def dev_alloc(self, nbytes):

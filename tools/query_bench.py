@@ -366,6 +366,92 @@ def overlap_case(a, res):
     res["overlap"] = {"index": index, "cases": rows + [brow, frow]}
 
 
+def composed_kmers(g, lo, hi, code, l0, k, min_occ):
+    """the k-mers that end in the l0-mer `code` with interval [lo, hi), level by level from the host: one extend call per level"""
+    code = np.array([code], np.uint64); ik = np.array([[lo, 0, hi - lo]], np.int64)
+    calls = items = 0
+    for l in range(l0, k):
+        ok = g.extend(ik, 1)[:, 1:5]                                 # (n, 4, 3): the left extensions by A C G T
+        calls += 1; items += len(ik)
+        live = ok[:, :, 2] >= min_occ
+        code = (code[:, None] | (np.arange(4, dtype=np.uint64)[None, :] << np.uint64(2 * l)))[live]
+        ik = np.ascontiguousarray(ok[live])
+        ik[:, 1] = 0
+    return code, ik[:, 0], ik[:, 0] + ik[:, 2], calls, items
+
+
+def kmers_case(a, res):
+    L = 101
+    n = a.reads or -(-(int(4 * 1024 ** 3 * 0.97) + 1) // (L + 1))
+    g = HipBwt(a.so)
+    p = g.dev_alloc(n * (L + 1))
+    g.synth_reads(p, 0, n, L, seed=42)
+    g.insert_multi_dev(p, n * (L + 1))
+    g.sync()
+    g.dev_free(p)
+    N = int(g.counts().sum())
+    P, Lp = a.patterns, 32
+    pats = hit_patterns(P, Lp, n, Lp)
+    flat = np.ascontiguousarray(pats.reshape(-1)); off = np.arange(P + 1, dtype=np.int64) * Lp
+    dp, do, dq = g.dev_alloc(len(flat)), g.dev_alloc(8 * (P + 1)), g.dev_alloc(24 * P)
+    g.L.rb2_hip_memcpy(g.h, dp, flat.ctypes.data, len(flat), 0)
+    g.L.rb2_hip_memcpy(g.h, do, off.ctypes.data, 8 * (P + 1), 0)
+
+    def bsearch(tag):
+        sec, lo, hi = spread(lambda: g.backward_search_dev(P, dp, do, dq), g.sync)
+        row = row_case("backward_search_dev L=%d hits, %d patterns%s" % (Lp, P, tag), P, sec, P * Lp, 2)
+        row.update({"measured": True, "lf_steps_per_s_slowest": P * Lp / hi, "lf_steps_per_s_fastest": P * Lp / lo})
+        return row
+    rows = [bsearch("")]
+    for k in (21, 31):
+        for min_occ in (1, 2):
+            items = 1 + sum(g.kmers_raw(l, min_occ, False, 0, 0)[0] for l in range(1, k))          # the l-mers the walk ranks, l < k
+            got = [None]
+
+            def spectrum():
+                got[0] = g.kmers_raw(k, min_occ, False, 0, 256)
+            sec, lo, hi = spread(spectrum, lambda: None)
+            found, _, hist, info = got[0]
+            base = {"k": k, "min_occ": min_occ, "kmers": found, "expanded_items": items, "launches": int(info[0]), "largest_segment": int(info[1]),
+                    "segments_alive": int(info[2]), "measured": True}
+            row = dict(base, case="kmers k=%d min_occ=%d, spectrum only (256 bins)" % (k, min_occ), seconds=sec, kmers_per_s=found / sec,
+                       expanded_items_per_s=items / sec, expanded_items_per_s_slowest=items / hi, expanded_items_per_s_fastest=items / lo, spectrum_head=hist[:8].tolist())
+            rows.append(row)
+            print("kmers: k %d min_occ %d: %d k-mers, %d items, spectrum in %.3f s" % (k, min_occ, found, items, sec), file=sys.stderr, flush=True)
+            cap = min(found, a.kmer_recs)
+
+            def records():
+                got[0] = g.kmers_raw(k, min_occ, False, cap, 0)
+            sec, lo, hi = spread(records, lambda: None)
+            assert got[0][0] == found
+            rows.append(dict(base, case="kmers k=%d min_occ=%d, records to host (max_recs %d)" % (k, min_occ, cap), seconds=sec, records=cap, kmers_per_s=found / sec,
+                             records_per_s=cap / sec, expanded_items_per_s=items / sec, expanded_items_per_s_slowest=items / hi, expanded_items_per_s_fastest=items / lo))
+    rows.append(bsearch(" (again, after the k-mer runs)"))
+    # the baseline: the k-mers that end in one 8-mer, from the host level by level, against the fused records with that ending
+    k, min_occ, l0 = 21, 2, 8
+    tail = pats[0, :l0]
+    tcode = int(sum((int(c) - 1) << (2 * (l0 - 1 - i)) for i, c in enumerate(tail)))
+    blo, bhi, bm = g.backward_search([tail])
+    assert bm[0] == l0
+    t = time.perf_counter()
+    ccode, clo, chi, calls, citems = composed_kmers(g, int(blo[0]), int(bhi[0]), tcode, l0, k, min_occ)
+    bsec = time.perf_counter() - t
+    found = g.kmers_raw(k, min_occ, False, 0, 0)[0]
+    same = None
+    if found <= a.kmer_recs:
+        _, rec, _, _ = g.kmers_raw(k, min_occ, False, found, 0)
+        mine = rec[(rec[:, 0].astype(np.uint64) & np.uint64(4 ** l0 - 1)) == np.uint64(tcode)]
+        mine = mine[np.argsort(mine[:, 1])]
+        o = np.argsort(clo)
+        same = bool(len(mine) == len(ccode) and np.array_equal(mine[:, 0].astype(np.uint64), ccode[o]) and np.array_equal(mine[:, 1], clo[o]) and np.array_equal(mine[:, 2], chi[o]))
+    rows.append({"case": "baseline: the k-mers ending in one %d-mer (k=%d, min_occ=%d) from the host, one rb2_hip_extend call per level" % (l0, k, min_occ), "seconds": bsec,
+                 "extend_calls": calls, "expanded_items": citems, "expanded_items_per_s": citems / bsec, "kmers": int(len(ccode)), "equals_fused": same, "measured": True})
+    for q in (dp, do, dq):
+        g.dev_free(q)
+    res["kmers"] = {"index": {"reads": n, "read_len": L, "sorting_order": a.so, "symbols": N, "strands": 1, "layout": g.layout_stats()}, "cases": rows}
+    g.close()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default="")
@@ -380,7 +466,17 @@ def main():
     ap.add_argument("--fmd", default="", help="load the index from this .fmd file instead of building it")
     ap.add_argument("--locate", action="store_true", help="only the sampled suffix array: build and locate rates (added to an existing --out file)")
     ap.add_argument("--overlap", action="store_true", help="only the suffix-prefix overlap query (added to an existing --out file)")
+    ap.add_argument("--kmers", action="store_true", help="only the k-mer enumeration (added to an existing --out file)")
+    ap.add_argument("--kmer-recs", type=int, default=1 << 26, help="records fetched to host memory at the most (24 bytes each)")
     a = ap.parse_args()
+    if a.kmers:
+        res = {"cases": []}
+        if a.out and os.path.exists(a.out):
+            with open(a.out) as f:
+                res = json.load(f)
+        kmers_case(a, res)
+        finish(a, res)
+        return
     if a.overlap:
         res = {"cases": []}
         if a.out and os.path.exists(a.out):
