@@ -275,6 +275,37 @@ void    rb2_hip_string_ids_dev(rb2_hip_t *h, int64_t n, const int64_t *zv, int64
  * from the count the one before it wrote, so the call cannot be asynchronous. */
 int64_t rb2_hip_kmers(rb2_hip_t *h, int k, int64_t min_occ, int canonical, int64_t max_recs, int64_t *rec, int64_t hist_len, int64_t *hist, int64_t info[4]);
 
+/* ---- approximate search: the matches of a query within a bounded number of substitutions ----
+ * rb2_hip_approx: n queries as for rb2_hip_smem (nt6 codes in text order, concatenated in qry[off[i] .. off[i+1]); 1..4 can match; 5 (N) is
+ * legal and matches nothing: an N position is always a substitution, by any of A C G T; 0, a code above 5 or a length above 8192 makes the
+ * query malformed).  A match of a query of L symbols is a word S of L symbols out of A C G T with at most max_mm positions where
+ * S[p] != q[p] and at least min_occ occurrences, occurrences = hi - lo of rb2_hip_backward_search on S.  Every match is reported exactly
+ * once, as one record rec[(i*max_recs + k)*4 ..] = lo, hi, n_mm, subs: [lo, hi) is the interval of S in global rows and can be handed to
+ * rb2_hip_locate as it is; n_mm is the number of substitutions; subs packs them 16 bits each as pos << 3 | sym -- the text position and the
+ * nt6 code S has there -- in decreasing pos (the order a backward search meets them), the first in bits 0 .. 15.  Unused fields are 0, a
+ * used one never is (sym >= 1).  The order of a query's records is unspecified.
+ * cnt[i] >= 0: the matches found, which may exceed max_recs: exactly max_recs records are stored then, every one a true record, none
+ * twice; which ones is unspecified.  0 for the empty query, -1 for a malformed one.  cnt[i] <= -2: the query used up max_steps before its
+ * search ended -- a step is one pair of ranks --; -2 - cnt[i] matches had been found by then and min(-2 - cnt[i], max_recs) of them are
+ * stored, every one a true record, none twice.  max_steps is what keeps one query (a homopolymer against a repetitive index at max_mm = 4
+ * has millions of nodes) from occupying the device: a call ends after n * max_steps rank pairs whatever the index holds.
+ * Only the records stored are meaningful: the host variant returns the others as zeros, the device variant leaves them untouched.
+ * Returns the number of records stored.  Fatal: max_mm outside 0 .. 4; min_occ, max_steps or max_recs below 1 (n <= 0 returns first).
+ * The index may hold one strand or both: the reverse-complement hits of a query are the hits of its reverse complement on an index of both
+ * strands.  No suffix array is needed, and one that is there stays valid: like every query the call reads the index and nothing else.
+ * Depth-first backtracking over the positions L-1 .. 0 (k_approx), one query per 16 lanes: the two ranks of a node's interval give its four
+ * children; a child is dropped when it has fewer than min_occ rows or when the substitutions so far, its own and a lower bound for the
+ * positions in front of it exceed max_mm.  The bound comes from one plain backward search over the query (at most L steps, counted like
+ * the others): the query is cut into disjoint pieces that each occur fewer than min_occ times, and every match must change every piece.
+ * The stacks live in device memory, 66 bytes per symbol of the longest query and row of the launch, 256 MiB at the most
+ * (RB2_APPROX_SCRATCH in the environment lowers that; rows take further queries a launch apart); when the queries are many and the
+ * longest is long, those of up to 248 symbols run in a launch of their own on many rows.  The host variant stages chunks whose records
+ * (chunk * max_recs * 32 bytes) stay under 256 MiB, one query at the least. */
+int64_t rb2_hip_approx(rb2_hip_t *h, int64_t n, const uint8_t *qry, const int64_t *off, int max_mm, int64_t min_occ, int64_t max_steps, int64_t max_recs, int64_t *rec, int64_t *cnt);
+/* the same with qry, off, rec and cnt in this device's memory, asynchronous on the handle's stream (no return value: read cnt).  The host
+ * does not see the lengths, so the stacks are sized for 8192 symbols: always 256 MiB once there are more than some 500 queries */
+void    rb2_hip_approx_dev(rb2_hip_t *h, int64_t n, const uint8_t *qry, const int64_t *off, int max_mm, int64_t min_occ, int64_t max_steps, int64_t max_recs, int64_t *rec, int64_t *cnt);
+
 /* 64-bit checksum of rope b computed on the device (position-weighted sum over the packed words of its pieces): equal for
  * equal symbol sequences however the index was built (one engine, N ranks, an .fmr loaded back), sensitive to order.  Lets
  * tests compare indexes of 10^11 symbols without moving them off the device (the reference has no counterpart; its ropes are

@@ -238,6 +238,7 @@ struct rb2_hip_s {
 	DevBuf<uint64_t> qbuf;              // rank queries and their answers
 	DevBuf<QTab> qtab;                  // FM-index queries (rb2_query.h): the piece table of the launch ...
 	DevBuf<uint8_t> qbytes; DevBuf<int64_t> qin, qout;   // ... and the staging buffers of the host variants
+	DevBuf<uint8_t> qscr;                // ... and the stacks of k_approx's rows
 	// sampled suffix array (rb2_hip_ssa_build): it describes the rows as they were when it was built (index_rows_change)
 	DevBuf<uint64_t> ssa_smp, ssa_len, ssa_head;   // (string, step) of every row x with x % 2^ssa_s == 0; length of every string; string of the q-th whole-string row
 	bool ssa_valid = false; int ssa_s = 0; int64_t ssa_n = 0; uint64_t ssa_nstr = 0;   // ssa_n samples, ssa_nstr strings
@@ -1065,7 +1066,7 @@ void rb2_hip_destroy(rb2_hip_t *h)
 	if (h->own_stream) HIPCHK(hipStreamSynchronize(h->st)); else HIPCHK(hipDeviceSynchronize());   /* a caller's stream (rb2_hip_use_stream) may be gone already */
 	index_rows_change(h, true);
 	for (int i = 0; i < 2; ++i) { h->pool[i].release(); h->L[i].release(); h->U[i].release(); h->W[i].release(); }
-	h->START.release(); h->SIZE.release(); h->INS_E.release(); h->RKREL.release(); h->RKOLD.release(); h->SPL.release(); h->qbuf.release(); h->zblk.release(); h->qtab.release(); h->qbytes.release(); h->qin.release(); h->qout.release();
+	h->START.release(); h->SIZE.release(); h->INS_E.release(); h->RKREL.release(); h->RKOLD.release(); h->SPL.release(); h->qbuf.release(); h->zblk.release(); h->qtab.release(); h->qbytes.release(); h->qin.release(); h->qout.release(); h->qscr.release();
 	h->LD.release(); h->A[0].release(); h->A[1].release(); h->INS_A.release(); h->sbuf.release(); h->sbuf2.release();
 	if (h->st_copy) HIPCHK(hipStreamDestroy(h->st_copy));
 	h->trec.release(); h->tsc.release(); h->tfix.release(); h->cpart.release(); h->sbtot.release();

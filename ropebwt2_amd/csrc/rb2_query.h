@@ -16,6 +16,7 @@
 #pragma once
 #include "rb2_device.h"
 #include "rb2_kmer_plan.h"
+#include "rb2_query_plan.h"
 
 namespace rb2 {
 
@@ -469,6 +470,110 @@ template <bool SPARSE> __global__ __launch_bounds__(256) void k_kmer_expand(cons
 	const uint32_t v = s_hist[threadIdx.x];
 	if (v) atomicAdd(&hist[threadIdx.x], (unsigned long long)v);     // (a bin that was counted lies below hist_len)
 	if (threadIdx.x == 0 && s_pre) atomicAdd(&ctr[2], (unsigned long long)s_pre);
+}
+
+// ---- approximate search: the matches of a query within max_mm substitutions ----
+// A match of the query q (L symbols) is a word S of L symbols A C G T that differs from q at no more than max_mm positions and has at
+// least min_occ occurrences.  Backtracking over the positions L - 1 .. 0: a node is (p, the interval of S[p + 1 ..), the m substitutions so
+// far), and one pair of ranks of its interval gives the intervals of its four children, as in k_kmer_expand; the child of q[p] costs
+// nothing, the three others one substitution each, an N costs one whatever stands for it.  A child is dropped when its interval is
+// smaller than min_occ, or when m + cost + D[p - 1] > max_mm, D being the piece bound of approx_bound (rb2_query_plan.h), which one plain
+// backward search over the query computes first.  A live child at position 0 is a match.
+//
+// One query per DPP row, control uniform within the row; a row takes the queries i = row, row + rows, ... with lmin < L <= lcap (the host
+// sorts the lengths into launches that way: approx_passes).  The stack is the path, in the row's part of scr (approx_row_bytes(lrow) bytes):
+//   kid[8 p + 2 (a - 1) ..] = lo, hi of child a of the node at position p      (lanes 0 .. 7 store one word each: one 64-byte line)
+//   G[p]                      approx_bound's count                             tk[p] = the child taken at p | the next one to try << 3
+// so that coming back to a position costs two loads and no rank.  The children are tried in the order q[p], A, C, G, T.  kid is written by
+// eight lanes and read by all sixteen: the vector memory operations of one wave are performed in order, the two fences keep the compiler
+// from moving them.  G and tk are written by every lane with the same value, each lane reads its own.
+// Every pair of ranks, those of the bound included, is a step: at max_steps the query ends with cnt = -2 - (matches found so far).  Between
+// two steps a row does a bounded amount of other work (four children, and one pop per push), so a launch ends after n * max_steps steps.
+// rec[(i * max_recs + k) * 4 ..] = lo, hi, n_mm, subs (approx_push) for k < max_recs, by lanes 0 .. 3; cnt[i] as in include/rb2_hip.h.
+template <bool SPARSE> __global__ __launch_bounds__(256) void k_approx(const QTab *Tg, PoolView pv, const uint8_t *qry, const int64_t *off, int64_t base, uint64_t n,
+                                                                       int max_mm, int64_t min_occ, int64_t max_steps, int64_t max_recs, int64_t lmin, int64_t lcap,
+                                                                       uint64_t rows, int64_t lrow, uint8_t *scr, int64_t *rec, int64_t *cnt)
+{
+	__shared__ QTab T;
+	qtab_load(Tg, T);
+	const uint64_t row = (uint64_t)blockIdx.x * QPB + (threadIdx.x >> 4);
+	if (row >= rows) return;
+	const uint32_t g = (uint32_t)lane_id() & 15u;
+	const int64_t N = (int64_t)T.row0[NR];
+	uint64_t *kid = (uint64_t*)(scr + row * (uint64_t)approx_row_bytes(lrow));
+	uint8_t *G = (uint8_t*)(kid + 8 * lrow), *tk = G + approx_pad(lrow);
+	for (uint64_t i = row; i < n; i += rows) {
+		const int64_t s0 = off[i] - base, L = off[i + 1] - base - s0;
+		if (L <= lmin || L > lcap) continue;                       // another launch takes it
+		const uint8_t *q = qry + s0;
+		bool bad = L < 0 || s0 < 0 || L > min(lrow, APPROX_MAX_LEN);
+		for (int64_t j = 0; !bad && j < L; ++j) { const uint8_t c = q[j]; bad = c == 0 || c > 5; }
+		if (bad || L == 0) { if (g == 0) cnt[i] = bad ? -1 : 0; continue; }
+		int64_t steps = 0, k = 0;
+		const int pieces = approx_bound(q, L, N, min_occ, max_mm, max_steps, [&](int64_t lo, int64_t hi, int c, int64_t &nlo, int64_t &nhi) {
+			uint64_t cl[6], ch[6];
+			qrank<SPARSE>(T, pv, (uint64_t)lo, cl);
+			qrank<SPARSE>(T, pv, (uint64_t)hi, ch);
+			const uint64_t C = qC(T, c);
+			nlo = (int64_t)(C + cl[c]); nhi = (int64_t)(C + ch[c]); }, G, &steps);
+		if (pieces < 0 || pieces > max_mm) { if (g == 0) cnt[i] = pieces < 0 ? -2 : 0; continue; }
+		int64_t p = L - 1;
+		uint64_t lo = 0, hi = (uint64_t)N, subs = 0;
+		int m = 0;
+		bool over = false;
+		for (;;) {                                                 // the node (p, [lo, hi), m, subs): its children, then the next node in depth-first order
+			if (steps >= max_steps) { over = true; break; }
+			++steps;
+			uint64_t klo[4], khi[4];
+			{
+				uint64_t cl[6], ch[6], v = 0;
+				qrank<SPARSE>(T, pv, lo, cl);
+				qrank<SPARSE>(T, pv, hi, ch);
+#pragma unroll
+				for (int a = 1; a <= 4; ++a) { const uint64_t C = qC(T, a); klo[a - 1] = C + cl[a]; khi[a - 1] = C + ch[a]; }
+#pragma unroll
+				for (int w = 0; w < 8; ++w) if (g == (uint32_t)w) v = w & 1 ? khi[w >> 1] : klo[w >> 1];
+				if (g < 8) kid[8 * p + g] = v;
+				__builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+			}
+			bool fresh = true, down = false;
+			int t = 0;
+			for (;;) {                                             // the children of the node at p from try t on; with none left, back to the node behind
+				const int c = q[p], need = approx_need(G, pieces, p);
+				while (t < 5) {
+					const int tt = t++, a = tt == 0 ? c : tt, cost = tt != 0;
+					if (tt == 0 ? c == 5 : a == c) continue;           // (N has no child of its own; q[p] was try 0)
+					if (m + cost + need > max_mm) { if (cost) t = 5; continue; }
+					uint64_t xlo = 0, xhi = 0;
+					if (fresh) {
+#pragma unroll
+						for (int b = 0; b < 4; ++b) if (a == b + 1) { xlo = klo[b]; xhi = khi[b]; }
+					} else { xlo = kid[8 * p + 2 * (a - 1)]; xhi = kid[8 * p + 2 * (a - 1) + 1]; }
+					if ((int64_t)(xhi - xlo) < min_occ) continue;
+					if (p == 0) {                                      // a match
+						if (k < max_recs && g < 4) {
+							const uint64_t sb = cost ? approx_push(subs, m, 0, a) : subs;
+							rec[(i * (uint64_t)max_recs + (uint64_t)k) * 4 + g] = (int64_t)(g == 0 ? xlo : g == 1 ? xhi : g == 2 ? (uint64_t)(m + cost) : sb);   // four lanes, one 32-byte record
+						}
+						++k;
+						continue;
+					}
+					if (cost) { subs = approx_push(subs, m, p, a); ++m; }
+					tk[p] = (uint8_t)(a | t << 3);
+					lo = xlo; hi = xhi; --p; down = true;
+					break;
+				}
+				if (down || ++p == L) break;
+				const int b = tk[p];
+				t = b >> 3;
+				if ((b & 7) != q[p]) { subs = approx_pop(subs, m); --m; }
+				fresh = false;
+				__builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+			}
+			if (!down) break;                                      // back behind the last position: the search is complete
+		}
+		if (g == 0) cnt[i] = over ? -2 - k : k;
+	}
 }
 
 } // namespace rb2

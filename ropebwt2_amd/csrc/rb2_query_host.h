@@ -81,9 +81,9 @@ static void staged_results(rb2_hip_t *h, int64_t n, const QInput &in, int words,
 
 /* the host variants with up to cap (>= 1) records of words int64 per item and a count: launch(nc, staged inputs, records, counts) per chunk of
  * at most QUERY_STAGE_BYTES of records (one item when a single one has more), one synchronise each.  The records no item writes come
- * back as zeros; returns the records stored, min(max(cnt, 0), cap) over the items */
-template <typename F>
-static int64_t staged_records(rb2_hip_t *h, int64_t n, const QInput &in, int words, int64_t cap, int64_t *rec, int64_t *cnt, F launch)
+ * back as zeros; returns the records stored, min(stored_of(cnt), cap) over the items (stored_of: max(cnt, 0) unless the family says otherwise) */
+template <typename F, typename S>
+static int64_t staged_records(rb2_hip_t *h, int64_t n, const QInput &in, int words, int64_t cap, int64_t *rec, int64_t *cnt, F launch, S stored_of)
 {
 	const int64_t CH = record_chunk(query_chunk(), 8 * words * cap);
 	int64_t stored = 0;
@@ -97,9 +97,15 @@ static int64_t staged_records(rb2_hip_t *h, int64_t n, const QInput &in, int wor
 		HIPCHK(hipMemcpyAsync(cnt + i0, s.tail, (size_t)nc * 8, hipMemcpyDeviceToHost, h->st));
 		HIPCHK(hipMemcpyAsync(rec + i0 * cap * words, h->qout.p, bytes, hipMemcpyDeviceToHost, h->st));
 		HIPCHK(hipStreamSynchronize(h->st));
-		for (int64_t i = i0; i < i0 + nc; ++i) stored += std::min(std::max<int64_t>(cnt[i], 0), cap);
+		for (int64_t i = i0; i < i0 + nc; ++i) stored += std::min(stored_of(cnt[i]), cap);
 	}
 	return stored;
+}
+
+template <typename F>
+static int64_t staged_records(rb2_hip_t *h, int64_t n, const QInput &in, int words, int64_t cap, int64_t *rec, int64_t *cnt, F launch)
+{
+	return staged_records(h, n, in, words, cap, rec, cnt, launch, [](int64_t c) { return std::max<int64_t>(c, 0); });
 }
 
 /* ---- backward search, extend, extract: one DPP row of 16 lanes per query ---- */
@@ -408,4 +414,59 @@ int64_t rb2_hip_kmers(rb2_hip_t *h, int k, int64_t min_occ, int canonical, int64
 	inf[3] = (int64_t)pre;
 	if (info) memcpy(info, inf, sizeof(inf));
 	return found;
+}
+
+/* ---- approximate search: the matches of a query within max_mm substitutions (k_approx) ---- */
+
+/* scratch for the stacks of a launch: APPROX_SCRATCH_BYTES; RB2_APPROX_SCRATCH in the environment lowers it (tests of the row cap) */
+static int64_t approx_scratch()
+{
+	const char *e = getenv("RB2_APPROX_SCRATCH");
+	const int64_t v = e ? atoll(e) : 0;
+	return v > 0 ? std::min(v, APPROX_SCRATCH_BYTES) : APPROX_SCRATCH_BYTES;
+}
+
+/* n queries, all device pointers, the longest of lmax symbols (APPROX_MAX_LEN when only the device knows): one launch, or one for the
+ * short queries and one for the long ones (approx_passes), the stacks sized before the first */
+static void launch_approx(rb2_hip_t *h, int64_t n, const uint8_t *qry, const int64_t *off, int64_t base, int64_t lmax, int max_mm, int64_t min_occ, int64_t max_steps,
+                          int64_t max_recs, int64_t *rec, int64_t *cnt)
+{
+	int64_t pass[2][4], bytes = 0;
+	const int np = approx_passes(n, std::min(std::max<int64_t>(lmax, 1), APPROX_MAX_LEN), approx_scratch(), pass);
+	for (int k = 0; k < np; ++k) bytes = std::max(bytes, pass[k][3] * approx_row_bytes(pass[k][2]));
+	h->qscr.ensure((size_t)bytes);
+	for (int k = 0; k < np; ++k)
+		qlaunch(h, k_approx<true>, k_approx<false>, (uint64_t)pass[k][3], qry, off, base, n, max_mm, min_occ, max_steps, max_recs, pass[k][0], pass[k][1],
+				pass[k][3], pass[k][2], h->qscr.p, rec, cnt);
+}
+
+static void approx_check(const char *who, int max_mm, int64_t min_occ, int64_t max_steps, int64_t max_recs)
+{
+	if (max_mm < 0 || max_mm > APPROX_MAX_MM) { rb2_fatal("[rb2_hip] %s: max_mm must be 0 .. %d (got %d)\n", who, APPROX_MAX_MM, max_mm); }
+	if (min_occ < 1) { rb2_fatal("[rb2_hip] %s: min_occ must be at least 1 (got %lld)\n", who, (long long)min_occ); }
+	if (max_steps < 1) { rb2_fatal("[rb2_hip] %s: max_steps must be at least 1 (got %lld)\n", who, (long long)max_steps); }
+	if (max_recs < 1) { rb2_fatal("[rb2_hip] %s: max_recs must be at least 1 (got %lld)\n", who, (long long)max_recs); }
+}
+
+int64_t rb2_hip_approx(rb2_hip_t *h, int64_t n, const uint8_t *qry, const int64_t *off, int max_mm, int64_t min_occ, int64_t max_steps, int64_t max_recs, int64_t *rec, int64_t *cnt)
+{
+	query_begin(h, "approx");
+	if (n <= 0) return 0;
+	approx_check("approx", max_mm, min_occ, max_steps, max_recs);
+	check_offsets("approx", "query", n, off);
+	int64_t lmax = 1;                                              // the longest query that is not malformed by its length alone
+	for (int64_t i = 0; i < n; ++i) if (off[i + 1] - off[i] <= APPROX_MAX_LEN) lmax = std::max(lmax, off[i + 1] - off[i]);
+	return staged_records(h, n, {qry, off, 0}, 4, max_recs, rec, cnt, [&](int64_t nc, const QStaged &s, int64_t *d_rec, int64_t *d_cnt) {
+		launch_approx(h, nc, s.bytes, s.v, s.base, lmax, max_mm, min_occ, max_steps, max_recs, d_rec, d_cnt); },
+		[](int64_t c) { return c >= 0 ? c : c <= -2 ? -2 - c : 0; });     // a query that ran out of steps keeps what it had found
+}
+
+void rb2_hip_approx_dev(rb2_hip_t *h, int64_t n, const uint8_t *qry, const int64_t *off, int max_mm, int64_t min_occ, int64_t max_steps, int64_t max_recs, int64_t *rec, int64_t *cnt)
+{
+	query_begin(h, "approx_dev");
+	if (n <= 0) return;
+	approx_check("approx_dev", max_mm, min_occ, max_steps, max_recs);
+	const int64_t CH = query_chunk();
+	for (int64_t i0 = 0; i0 < n; i0 += CH)
+		launch_approx(h, std::min(CH, n - i0), qry, off + i0, 0, APPROX_MAX_LEN, max_mm, min_occ, max_steps, max_recs, rec + i0 * max_recs * 4, cnt + i0);
 }

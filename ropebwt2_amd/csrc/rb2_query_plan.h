@@ -22,3 +22,101 @@ template <typename F> static inline void split_slots(int64_t n, int64_t max_hits
 	for (int64_t i0 = 0; i0 < n; i0 += per)
 		for (int64_t k0 = 0; k0 < max_hits; k0 += kn) f(i0, std::min(per, n - i0), k0, std::min(kn, max_hits - k0));
 }
+
+/* ---- approximate search (rb2_hip_approx: kernel k_approx in rb2_query.h, host side in rb2_query_host.h) ----
+ * What follows is also compiled into the kernel: the functions are constexpr, or marked for both sides when a HIP compiler reads them. */
+#ifdef __HIPCC__
+#define RB2_PLAN_HD __host__ __device__
+#else
+#define RB2_PLAN_HD
+#endif
+
+static const int APPROX_MAX_MM = 4;                            /* substitutions of a match at the most: four 16-bit fields of subs */
+static const int64_t APPROX_MAX_LEN = 8192;                    /* symbols of a query at the most: a position has 13 bits of a field */
+static const int64_t APPROX_ROWS = 16 * 2048;                  /* DPP rows of a launch at the most (2048 blocks: eight per CU); a row takes queries a launch apart */
+static const int64_t APPROX_SCRATCH_BYTES = (int64_t)256 << 20;   /* the stacks of all rows of a launch stay under this */
+static const int64_t APPROX_SHORT_ROWS = 16 * 1024;            /* rows of the launch that takes the short queries when the lengths are mixed or unknown */
+
+/* subs: the substitutions of a match, 16 bits each as pos << 3 | sym, in the order a backward search meets them (decreasing pos), the
+ * first in bits 0 .. 15; sym >= 1, so a used field is never 0 */
+constexpr uint64_t approx_push(uint64_t subs, int m, int64_t pos, int sym) { return subs | ((uint64_t)pos << 3 | (uint64_t)sym) << (16 * m); }   /* field m (m fields used) */
+constexpr uint64_t approx_pop(uint64_t subs, int m) { return subs & ~(0xffffull << (16 * (m - 1))); }                                               /* drops field m - 1 */
+constexpr int64_t approx_sub_pos(uint64_t subs, int k) { return (int64_t)(subs >> (16 * k) & 0xffff) >> 3; }
+constexpr int approx_sub_sym(uint64_t subs, int k) { return (int)(subs >> (16 * k) & 7); }
+
+/* the stack of one row for queries of up to L (>= 1) symbols: per position the intervals of the four children (64 bytes), then two
+ * bytes per position -- the piece count G of approx_bound, and the child taken with the next one to try -- each array padded to 8 bytes */
+constexpr int64_t approx_pad(int64_t L) { return (L + 7) & ~(int64_t)7; }
+constexpr int64_t approx_row_bytes(int64_t L) { return 64 * L + 2 * approx_pad(L); }
+
+/* rows of a launch over n (>= 1) queries of up to L symbols with `bytes` of scratch: at most n and APPROX_ROWS, one at the least */
+constexpr int64_t approx_rows(int64_t n, int64_t L, int64_t bytes)
+{
+	int64_t r = bytes / approx_row_bytes(L);
+	if (r > APPROX_ROWS) r = APPROX_ROWS;
+	if (r > n) r = n;
+	return r < 1 ? 1 : r;
+}
+
+/* the longest query the stacks of `rows` rows hold in `bytes` of scratch (0: none), APPROX_MAX_LEN at the most */
+constexpr int64_t approx_len_cap(int64_t rows, int64_t bytes)
+{
+	int64_t L = bytes / rows / 66;                             /* 64 L + 2 pad(L) <= 66 L + 14 */
+	while (L > 0 && approx_row_bytes(L) * rows > bytes) --L;
+	return L > APPROX_MAX_LEN ? APPROX_MAX_LEN : L;
+}
+
+/* A call is one launch when every query is short enough for APPROX_SHORT_ROWS rows (or there are no more queries than rows anyway);
+ * else two: the first takes the queries of up to `cut` symbols on many rows, the second the longer ones on the rows that lmax allows.
+ * lmax = the longest query (APPROX_MAX_LEN when the lengths are not known to the host, as in the _dev variant), at least 1.
+ * pass[k] = {lmin, lcap, lrow, rows}: the launch takes the queries with lmin < length <= lcap on `rows` rows with stacks for lrow symbols;
+ * returns the number of launches.  Every length, negative and oversized ones included, belongs to exactly one launch. */
+static inline int approx_passes(int64_t n, int64_t lmax, int64_t bytes, int64_t pass[2][4])
+{
+	const int64_t all = approx_rows(n, lmax, bytes), cut = approx_len_cap(APPROX_SHORT_ROWS, bytes);
+	if (all >= n || all >= APPROX_SHORT_ROWS || lmax <= cut || cut < 1) {
+		pass[0][0] = INT64_MIN; pass[0][1] = INT64_MAX; pass[0][2] = lmax; pass[0][3] = all;
+		return 1;
+	}
+	pass[0][0] = INT64_MIN; pass[0][1] = cut; pass[0][2] = cut; pass[0][3] = approx_rows(n, cut, bytes);
+	pass[1][0] = cut; pass[1][1] = INT64_MAX; pass[1][2] = lmax; pass[1][3] = all;
+	return 2;
+}
+
+/* The piece bound.  One backward search over q[0 .. L) (nt6 codes 1 .. 5) from its last symbol: when the interval of q[s .. e] holds
+ * fewer than min_occ rows, [s, e] is a piece and the search starts again at s - 1 from the whole index [0, N); an N (5) is a piece by
+ * itself (the symbols behind it that still matched are no piece).  No string with min_occ occurrences contains a piece unchanged and the
+ * pieces are disjoint, so a match of q needs at least D[p] = (pieces that lie wholly in [0, p]) substitutions in q[0 .. p].
+ * step(lo, hi, c, nlo, nhi) must set [nlo, nhi) to the interval of c followed by the word of [lo, hi): one pair of ranks, counted in *steps.
+ * G[p] = the pieces whose last position lies behind p, so that D[p] = pieces - G[p].  Returns the number of pieces; stops early with
+ * max_mm + 1 once there are more than max_mm (G is then incomplete: no match exists), and with -1 when *steps reached max_steps. */
+template <typename F>
+RB2_PLAN_HD inline int approx_bound(const uint8_t *q, int64_t L, int64_t N, int64_t min_occ, int max_mm, int64_t max_steps, F step, uint8_t *G, int64_t *steps)
+{
+	int pieces = 0;
+	int64_t lo = 0, hi = N, e = L - 1;                         /* the interval of q[j + 1 .. e]: the run that may become a piece */
+	for (int64_t j = L - 1; j >= 0; --j) {
+		const int c = q[j];
+		bool cut = c == 5, piece = false;
+		if (!cut) {
+			if (*steps >= max_steps) return -1;
+			++*steps;
+			int64_t nlo = 0, nhi = 0;
+			step(lo, hi, c, nlo, nhi);
+			if (nhi - nlo < min_occ) cut = piece = true;
+			else { lo = nlo; hi = nhi; }
+		}
+		if (!cut && j > 0) continue;
+		/* the run ends here, as the piece [j, e], in front of an N, or at the first symbol: only now is G known for its positions.
+		 * The pieces found so far all end behind e; the piece [j, e] itself ends behind every position of the run but e */
+		for (int64_t x = j; x <= e; ++x) G[x] = (uint8_t)(pieces + (piece && x < e));
+		if (cut) {
+			if (++pieces > max_mm) return pieces;
+			lo = 0; hi = N; e = j - 1;
+		}
+	}
+	return pieces;
+}
+
+/* D[p - 1] from what approx_bound left: the substitutions every match needs in front of position p */
+RB2_PLAN_HD inline int approx_need(const uint8_t *G, int pieces, int64_t p) { return p > 0 ? pieces - (int)G[p - 1] : 0; }

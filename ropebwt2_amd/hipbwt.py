@@ -64,6 +64,8 @@ def load_hip_lib():
         "rb2_hip_string_ids": (i64, [vp, i64, vp, i64, vp, vp]),
         "rb2_hip_string_ids_dev": (None, [vp, i64, vp, i64, vp, vp]),
         "rb2_hip_kmers": (i64, [vp, i32, i64, i32, i64, vp, i64, vp, vp]),
+        "rb2_hip_approx": (i64, [vp, i64, vp, vp, i32, i64, i64, i64, vp, vp]),
+        "rb2_hip_approx_dev": (None, [vp, i64, vp, vp, i32, i64, i64, i64, vp, vp]),
         "rb2_hip_reserve": (None, [vp, i64, i64, i64]),
         "rb2_hip_num_subropes": (i32, []),
         "rb2_hip_memcpy": (None, [vp, vp, vp, i64, i32]),
@@ -131,6 +133,7 @@ ABI_SYMBOLS = [
     "rb2_hip_backward_search", "rb2_hip_backward_search_dev", "rb2_hip_extend", "rb2_hip_extract", "rb2_hip_smem", "rb2_hip_smem_dev", "rb2_hip_dev_alloc",
     "rb2_hip_ssa_build", "rb2_hip_ssa_drop", "rb2_hip_ssa_info", "rb2_hip_locate", "rb2_hip_locate_dev",
     "rb2_hip_overlap", "rb2_hip_overlap_dev", "rb2_hip_string_ids", "rb2_hip_string_ids_dev", "rb2_hip_kmers",
+    "rb2_hip_approx", "rb2_hip_approx_dev",
     "rb2_hip_num_subropes", "rb2_hip_memcpy", "rb2_hip_use_stream",
     "rb2_hip_dev_free", "rb2_hip_synth_reads", "rb2_hip_synth_reads_cov", "rb2_hip_synth_reads_skew", "rb2_hip_sync", "rb2_hip_sparse_stats", "rb2_hip_layout_stats", "rb2_hip_rewind_stats", "rb2_hip_window_stats", "rb2_hip_host_register", "rb2_hip_host_unregister", "rb2_hip_profile",
     "rb2_hip_profile_get", "rb2_hip_kernel_name", "rb2_hip_layout",
@@ -182,6 +185,33 @@ def unpack_kmers(codes, k):
     codes = np.asarray(codes, dtype=np.uint64).reshape(-1)
     sh = np.uint64(2) * np.arange(k - 1, -1, -1, dtype=np.uint64)
     return ((codes[:, None] >> sh[None, :]) & np.uint64(3)).astype(np.uint8) + np.uint8(1)
+
+
+def pack_subs(subs):
+    """substitutions [(pos, sym), ...] of a match (at most four, positions below 8192, nt6 codes 1..4) -> the subs word of rb2_hip_approx:
+    16 bits each as pos << 3 | sym, in decreasing pos, the first in bits 0..15"""
+    subs = sorted(((int(p), int(c)) for p, c in subs), reverse=True)
+    if len(subs) > 4 or any(not (0 <= p < 8192 and 1 <= c <= 4) for p, c in subs) or len({p for p, _ in subs}) != len(subs):
+        raise ValueError("substitutions %r: at most four (pos, sym) with distinct pos < 8192 and sym in 1..4" % (subs,))
+    return sum((p << 3 | c) << (16 * k) for k, (p, c) in enumerate(subs))
+
+
+def unpack_subs(subs):
+    """the subs word of a record of rb2_hip_approx -> [(pos, sym), ...] in decreasing pos: text position, nt6 code the match has there"""
+    subs = int(subs) & 0xFFFFFFFFFFFFFFFF
+    out = []
+    while subs & 0xFFFF:
+        out.append(((subs & 0xFFFF) >> 3, subs & 7))
+        subs >>= 16
+    return out
+
+
+class StepBudgetExceeded(RuntimeError):
+    """HipBwt.approx: some queries used up max_steps before their search ended; .queries lists them, .results holds what approx() would
+    have returned, with the matches those queries had found so far"""
+    def __init__(self, queries, results):
+        RuntimeError.__init__(self, "approx: %d queries ran out of steps (the first: %s); raise max_steps or lower max_mm" % (len(queries), queries[:5]))
+        self.queries, self.results = queries, results
 
 
 def expand_runs(rle):
@@ -520,6 +550,31 @@ class HipBwt:
         """the k-mer spectrum: hist[c] = distinct k-mers with exactly c occurrences, hist[hist_len - 1] = those with that many or more
         (no records are fetched)"""
         return self.kmers_raw(k, min_occ, canonical, max_recs=0, hist_len=hist_len)[2]
+
+    # -- approximate search: the matches of a query within max_mm substitutions (include/rb2_hip.h) ---------------------------------
+    def approx_raw(self, queries, max_mm, min_occ=1, max_steps=1 << 16, max_recs=64):
+        """rb2_hip_approx as it is: (records stored, rec (n, max_recs, 4) int64 = lo, hi, n_mm, subs, cnt (n,) int64).  cnt[i] >= 0: the
+        matches found, min(cnt[i], max_recs) of them stored; -1: a malformed query; <= -2: the query ran out of steps with -2 - cnt[i]
+        matches found, min(that, max_recs) stored.  The records not stored are zeros, the order of a query's records is unspecified"""
+        qry, off = pack_patterns(queries)
+        return self._records(self.L.rb2_hip_approx, len(off) - 1, (qry.ctypes.data, off.ctypes.data, int(max_mm), min_occ, max_steps, max_recs), max_recs, 4, False)
+
+    def approx(self, queries, max_mm, min_occ=1, max_steps=1 << 16, max_recs=64):
+        """the words within max_mm substitutions of every query (str / bytes over ACGTN, or nt6 arrays) that occur at least min_occ times:
+        per query a list of (lo, hi, n_mm, [(pos, sym), ...]) sorted by lo -- [lo, hi) goes to locate() as it is, the match has the nt6 code
+        sym at text position pos and the query's symbols elsewhere --, at most max_recs of them, or None for a malformed query ('$' or a code
+        above 5 inside, more than 8192 symbols).  Raises StepBudgetExceeded when a query used up max_steps: the exception names the queries
+        and carries the results, partial for those"""
+        _, rec, cnt = self.approx_raw(queries, max_mm, min_occ, max_steps, max_recs)
+        have = np.minimum(np.where(cnt <= -2, -2 - cnt, np.maximum(cnt, 0)), max_recs)
+        out = [None if c == -1 else sorted((int(lo), int(hi), int(mm), unpack_subs(sb)) for lo, hi, mm, sb in r[:k].tolist()) for r, k, c in zip(rec, have, cnt)]
+        if (cnt <= -2).any():
+            raise StepBudgetExceeded(np.flatnonzero(cnt <= -2).tolist(), out)
+        return out
+
+    def approx_dev(self, n, qry_dev, off_dev, rec_dev, cnt_dev, max_mm, min_occ=1, max_steps=1 << 16, max_recs=64):
+        """rb2_hip_approx_dev: all four pointers in this device's memory; asynchronous on the handle's stream"""
+        self.L.rb2_hip_approx_dev(self.h, n, qry_dev, off_dev, int(max_mm), min_occ, max_steps, max_recs, rec_dev, cnt_dev)
 
     # -- measurement helpers ----------------------------------------------------------------
     def dev_alloc(self, nbytes):

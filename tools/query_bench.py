@@ -366,6 +366,51 @@ def overlap_case(a, res):
     res["overlap"] = {"index": index, "cases": rows + [brow, frow]}
 
 
+def approx_case(a, res):
+    """reads of the index with 0 .. max_mm planted substitutions through approx_dev: queries per second, and rank pairs per second from a
+    lower bound of the steps (the call does not report the steps a query took: a query that finds its read again ranks every position
+    once for the piece bound and once along the path of the match, 2 L pairs, and whatever it backtracks through on top)"""
+    L, M = 101, 16
+    n = a.reads or -(-(int(4 * 1024 ** 3 * 0.97) + 1) // (L + 1))
+    P = a.approx_queries
+    g = HipBwt(a.so)
+    p = g.dev_alloc(n * (L + 1))
+    g.synth_reads(p, 0, n, L, seed=42)
+    g.insert_multi_dev(p, n * (L + 1))
+    g.sync()
+    g.dev_free(p)
+    index = {"reads": n, "read_len": L, "sorting_order": a.so, "symbols": int(g.counts().sum()), "strands": 1, "layout": g.layout_stats()}
+    rng = np.random.RandomState(11)
+    rows = []
+    do, dr, dc = g.dev_alloc(8 * (P + 1)), g.dev_alloc(32 * M * P), g.dev_alloc(8 * P)
+    off = np.arange(P + 1, dtype=np.int64) * L
+    g.L.rb2_hip_memcpy(g.h, do, off.ctypes.data, 8 * (P + 1), 0)
+    for max_mm, planted in ((0, 0), (1, 1), (2, 2), (2, 0), (3, 3)):
+        qs = hit_patterns(P, L, n, 101).copy()
+        for _ in range(planted):                                    # (two may fall on one position: then fewer are planted)
+            at = rng.randint(L, size=P)
+            qs[np.arange(P), at] = 1 + (qs[np.arange(P), at] + rng.randint(3, size=P)) % 4
+        flat = np.ascontiguousarray(qs.reshape(-1))
+        dq = g.dev_alloc(len(flat))
+        g.L.rb2_hip_memcpy(g.h, dq, flat.ctypes.data, len(flat), 0)
+        sec, lo, hi = spread(lambda: g.approx_dev(P, dq, do, dr, dc, max_mm, 1, a.approx_steps, M), g.sync)
+        cnt = np.zeros(P, np.int64)
+        g.L.rb2_hip_memcpy(g.h, cnt.ctypes.data, dc, 8 * P, 1)
+        g.dev_free(dq)
+        assert (cnt != -1).all() and (planted > max_mm or ((cnt >= 1) | (cnt <= -2)).all())      # the read itself is within reach, unless the steps ran out
+        least = int(2 * L * ((cnt >= 1) | (cnt <= -3)).sum() + (cnt == 0).sum())
+        row = {"case": "approx_dev, %d reads of the index (%d bp) with %d planted substitutions, max_mm=%d min_occ=1 max_steps=%d max_recs=%d" % (P, L, planted, max_mm, a.approx_steps, M),
+               "measured": True, "queries": P, "seconds": sec, "seconds_fastest": lo, "seconds_slowest": hi, "queries_per_s": P / sec,
+               "rank_pairs_at_least": least, "rank_pairs_per_s_at_least": least / sec, "matches": int(np.maximum(cnt, 0).sum()),
+               "queries_with_a_match": int((cnt >= 1).sum()), "queries_out_of_steps": int((cnt <= -2).sum()), "queries_with_more_than_max_recs": int((cnt > M).sum())}
+        rows.append(row)
+        print("approx: max_mm %d, %d planted: %d queries in %.3f s" % (max_mm, planted, P, sec), file=sys.stderr, flush=True)
+    for q in (do, dr, dc):
+        g.dev_free(q)
+    g.close()
+    res["approx"] = {"index": index, "cases": rows}
+
+
 def composed_kmers(g, lo, hi, code, l0, k, min_occ):
     """the k-mers that end in the l0-mer `code` with interval [lo, hi), level by level from the host: one extend call per level"""
     code = np.array([code], np.uint64); ik = np.array([[lo, 0, hi - lo]], np.int64)
@@ -468,7 +513,18 @@ def main():
     ap.add_argument("--overlap", action="store_true", help="only the suffix-prefix overlap query (added to an existing --out file)")
     ap.add_argument("--kmers", action="store_true", help="only the k-mer enumeration (added to an existing --out file)")
     ap.add_argument("--kmer-recs", type=int, default=1 << 26, help="records fetched to host memory at the most (24 bytes each)")
+    ap.add_argument("--approx", action="store_true", help="only the approximate search (added to an existing --out file)")
+    ap.add_argument("--approx-queries", type=int, default=1_000_000)
+    ap.add_argument("--approx-steps", type=int, default=1 << 16, help="max_steps of the approximate search")
     a = ap.parse_args()
+    if a.approx:
+        res = {"cases": []}
+        if a.out and os.path.exists(a.out):
+            with open(a.out) as f:
+                res = json.load(f)
+        approx_case(a, res)
+        finish(a, res)
+        return
     if a.kmers:
         res = {"cases": []}
         if a.out and os.path.exists(a.out):
