@@ -118,32 +118,103 @@ __device__ __forceinline__ uint64_t qC(const QTab &T, int a) { return T.row0[rop
 
 constexpr int QPB = 256 / 16;              // queries per block of 256 threads
 
+// ---- what the row kernels are made of: each kernel below is these helpers plus its own loop ----
+
+// the DPP row of this thread: i = its number in the launch (the item it takes), b = the number of the block's first row (the same in the
+// whole block), g = the lane inside the row
+struct QRow { uint64_t b, i; uint32_t g; };
+__device__ __forceinline__ QRow qrow()
+{
+	const uint64_t b = (uint64_t)blockIdx.x * QPB;
+	return {b, b + (threadIdx.x >> 4), (uint32_t)lane_id() & 15u};
+}
+
+// the ranks at the two ends of an interval [lo, hi) (lo <= hi <= N): cl[a] = occ(a, lo), ch[a] = occ(a, hi).  size(a) = the rows of the
+// interval whose symbol is a (size(0): the whole strings among them, in front of which stand cl[0] others); child(c) = the interval of c
+// followed by the word of [lo, hi), empty (nlo >= nhi) when that word does not occur
+template <bool SPARSE> struct QPair {
+	uint64_t cl[6], ch[6];
+	__device__ __forceinline__ QPair() {}
+	__device__ __forceinline__ QPair(const QTab &T, const PoolView &pv, uint64_t lo, uint64_t hi) { qrank<SPARSE>(T, pv, lo, cl); qrank<SPARSE>(T, pv, hi, ch); }
+	static __device__ __forceinline__ uint64_t at(const uint64_t (&v)[6], int a)   // v[a] by selects: an index into a member the compiler does not know puts the pair into scratch
+	{
+		const uint64_t v0 = v[0], v1 = v[1], v2 = v[2], v3 = v[3], v4 = v[4], v5 = v[5];
+		return a == 0 ? v0 : a == 1 ? v1 : a == 2 ? v2 : a == 3 ? v3 : a == 4 ? v4 : v5;
+	}
+	__device__ __forceinline__ uint64_t size(int a) const { return at(ch, a) - at(cl, a); }
+	template <typename I> __device__ __forceinline__ void child(const QTab &T, int c, I &nlo, I &nhi) const { const uint64_t C = qC(T, c); nlo = (I)(C + at(cl, c)); nhi = (I)(C + at(ch, c)); }
+};
+
+// one LF step from row x (x < N): returns the symbol c of the row and, unless it is `$`, moves x to the row of the suffix one longer;
+// c6 = the counts in front of the row x was (c6[0]: the `$`s in front of it, which names the string when c is `$`).  On an index that
+// is no BWT of complete strings the new x can be N or more and a walk need not end: the guard is the caller's, because the three differ.
+// k_ssa_build and k_locate count their steps against N and test x < N after every step, so they never rank a row outside the index;
+// k_extract has no guard and relies on max_len to end (for a row that is not there qrank reads no memory and leaves the symbol unset).
+template <bool SPARSE> __device__ __forceinline__ uint32_t qlf(const QTab &T, const PoolView &pv, uint64_t &x, uint64_t c6[6])
+{
+	uint32_t c;
+	qrank<SPARSE>(T, pv, x, c6, &c);
+	if (c != 0) x = qC(T, (int)c) + c6[c];
+	return c;
+}
+
+// query i of a packed batch: q[0 .. L) = qry[off[i] - base, off[i + 1] - base).  bad: the offsets are no slice (or the caller says so:
+// bad0), or a symbol is no code 1 .. 5; with END0 a 0 (`$`) may stand as the last symbol.  The symbols of a bad slice are not all read.
+struct QSlice { const uint8_t *q; int64_t L; bool bad; };
+template <bool END0> __device__ __forceinline__ QSlice qslice(const uint8_t *qry, const int64_t *off, int64_t base, uint64_t i, bool bad0 = false)
+{
+	const int64_t s0 = off[i] - base, L = off[i + 1] - base - s0;
+	QSlice S = {qry + s0, L, bad0 || L < 0 || s0 < 0};
+	for (int64_t j = 0; !S.bad && j < L; ++j) { const uint8_t c = S.q[j]; S.bad = c > 5 || (c == 0 && !(END0 && j == L - 1)); }
+	return S;
+}
+
+// record k of item i, the W words v... at rec[(i * cap + k) * W ..], stored by the lanes g < W of the row (lane g stores the g-th word:
+// one store of 8 W bytes) when k < cap; a record beyond cap is the caller's to count
+template <typename... V> __device__ __forceinline__ void qstore(int64_t *rec, uint64_t i, int64_t cap, int64_t k, uint32_t g, V... v)
+{
+	constexpr uint32_t W = sizeof...(V);
+	if (k >= cap || g >= W) return;
+	int64_t x = 0;
+	uint32_t w = 0;
+	((x = g == w++ ? (int64_t)v : x), ...);
+	rec[(i * (uint64_t)cap + (uint64_t)k) * W + g] = x;
+}
+
+// slot q of a launch that takes kn hits of each of n ranges, from hit k0 on (kn = max_hits and k0 = 0 unless one range alone has more
+// slots than a launch takes: split_slots): hit kk = k0 + q % kn of range i = q / kn, [lo, hi) = rv[2i ..] inside [0, top].  The slot of
+// hit 0 writes cnt[i] = hi - lo, -1 for a malformed range (if it is the `writer`: one lane of a row).  live: the slot has a hit, x = lo + kk
+struct QSlot { uint64_t i; int64_t kk, x; bool live; };
+__device__ __forceinline__ QSlot qslot(uint64_t q, uint64_t n, int64_t k0, int64_t kn, const int64_t *rv, int64_t top, bool writer, int64_t *cnt)
+{
+	if (q >= n * (uint64_t)kn) return {0, 0, 0, false};
+	const uint64_t i = q / (uint64_t)kn;
+	const int64_t kk = k0 + (int64_t)(q % (uint64_t)kn), lo = rv[2 * i], hi = rv[2 * i + 1];
+	const bool bad = lo < 0 || hi > top || lo > hi;
+	if (kk == 0 && writer) cnt[i] = bad ? -1 : hi - lo;
+	return {i, kk, lo + kk, !bad && kk < hi - lo};
+}
+
 // backward search: n patterns pat[off[i] - base, off[i+1] - base), out[3i..] = lo, hi, m (include/rb2_hip.h)
 template <bool SPARSE> __global__ __launch_bounds__(256) void k_bsearch(const QTab *Tg, PoolView pv, const uint8_t *pat, const int64_t *off, int64_t base,
                                                                         uint64_t n, int64_t *out)
 {
 	__shared__ QTab T;
 	qtab_load(Tg, T);
-	const uint64_t i = (uint64_t)blockIdx.x * QPB + (threadIdx.x >> 4);
-	if (i >= n) return;
-	const int64_t s0 = off[i] - base, s1 = off[i + 1] - base;
+	const QRow R = qrow();
+	if (R.i >= n) return;
+	const QSlice S = qslice<true>(pat, off, base, R.i);
 	int64_t lo = 0, hi = (int64_t)T.row0[NR], m = 0;
-	bool bad = s1 < s0 || s0 < 0;
-	for (int64_t j = s0; !bad && j < s1; ++j) { const uint8_t c = pat[j]; bad = c > 5 || (c == 0 && j != s1 - 1); }
-	if (bad) lo = hi = m = -1;
+	if (S.bad) lo = hi = m = -1;
 	else {
-		for (int64_t j = s1 - 1; j >= s0; --j) {
-			const int c = pat[j];
-			uint64_t cl[6], ch[6];
-			qrank<SPARSE>(T, pv, (uint64_t)lo, cl);
-			qrank<SPARSE>(T, pv, (uint64_t)hi, ch);
-			const uint64_t C = qC(T, c), nl = C + cl[c], nh = C + ch[c];
+		for (int64_t j = S.L - 1; j >= 0; --j) {
+			uint64_t nl, nh;
+			QPair<SPARSE>(T, pv, (uint64_t)lo, (uint64_t)hi).child(T, S.q[j], nl, nh);
 			if (nl >= nh) break;                               // the suffix one longer does not occur: stop early
 			lo = (int64_t)nl; hi = (int64_t)nh; ++m;
 		}
 	}
-	const uint32_t g = (uint32_t)lane_id() & 15u;
-	if (g < 3) out[3 * i + g] = g == 0 ? lo : g == 1 ? hi : m;
+	qstore(out, R.i, 1, 0, R.g, lo, hi, m);
 }
 
 // rld_extend (rld0.c:474-490) on n bi-intervals: ok[18i + 3a + j]
@@ -151,27 +222,26 @@ template <bool SPARSE> __global__ __launch_bounds__(256) void k_extend(const QTa
 {
 	__shared__ QTab T;
 	qtab_load(Tg, T);
-	const uint64_t i = (uint64_t)blockIdx.x * QPB + (threadIdx.x >> 4);
-	if (i >= n) return;
+	const QRow R = qrow();
+	if (R.i >= n) return;
 	const int fb = !is_back;
-	const uint64_t x0 = (uint64_t)ik[3 * i + fb], sz = (uint64_t)ik[3 * i + 2], xb = (uint64_t)ik[3 * i + is_back];
-	uint64_t tk[6], tl[6];
-	qrank<SPARSE>(T, pv, x0, tk);
-	if (sz) qrank<SPARSE>(T, pv, x0 + sz, tl);
-	else for (int a = 0; a < 6; ++a) tl[a] = tk[a];
+	const uint64_t x0 = (uint64_t)ik[3 * R.i + fb], sz = (uint64_t)ik[3 * R.i + 2], xb = (uint64_t)ik[3 * R.i + is_back];
+	QPair<SPARSE> P;                                                 // (an empty interval needs one rank only)
+	qrank<SPARSE>(T, pv, x0, P.cl);
+	if (sz) qrank<SPARSE>(T, pv, x0 + sz, P.ch);
+	else for (int a = 0; a < 6; ++a) P.ch[a] = P.cl[a];
 	int64_t xf[6], sz6[6], xo[6];                              // x[!is_back], x[2], x[is_back] of the six extensions
 #pragma unroll
-	for (int a = 0; a < 6; ++a) { xf[a] = (int64_t)(qC(T, a) + tk[a]); sz6[a] = (int64_t)(tl[a] - tk[a]); }
+	for (int a = 0; a < 6; ++a) { int64_t xh; P.child(T, a, xf[a], xh); sz6[a] = (int64_t)P.size(a); }
 	xo[0] = (int64_t)xb;                                       // the other end in the complement order $ T G C A N
 	xo[4] = xo[0] + sz6[0];
 	xo[3] = xo[4] + sz6[4];
 	xo[2] = xo[3] + sz6[3];
 	xo[1] = xo[2] + sz6[2];
 	xo[5] = xo[1] + sz6[1];
-	const uint32_t g = (uint32_t)lane_id() & 15u;               // 18 words: lanes 0..15, then lanes 0..1 again
 #pragma unroll
-	for (int k = 0; k < 18; ++k)
-		if ((uint32_t)(k & 15) == g) ok[18 * i + k] = k % 3 == 2 ? sz6[k / 3] : k % 3 == fb ? xf[k / 3] : xo[k / 3];
+	for (int k = 0; k < 18; ++k)                               // 18 words: lanes 0..15, then lanes 0..1 again
+		if ((uint32_t)(k & 15) == R.g) ok[18 * R.i + k] = k % 3 == 2 ? sz6[k / 3] : k % 3 == fb ? xf[k / 3] : xo[k / 3];
 }
 
 // inverse BWT from rows of the $ block: the string of row rows[i], LAST symbol first, into out[i * max_len ..) (the host reverses it);
@@ -181,26 +251,24 @@ template <bool SPARSE> __global__ __launch_bounds__(256) void k_extract(const QT
 {
 	__shared__ QTab T;
 	qtab_load(Tg, T);
-	const uint64_t i = (uint64_t)blockIdx.x * QPB + (threadIdx.x >> 4);
-	if (i >= n) return;
-	const uint32_t g = (uint32_t)lane_id() & 15u;
-	const int64_t row = rows[i];
+	const QRow R = qrow();
+	if (R.i >= n) return;
+	const int64_t row = rows[R.i];
 	int64_t k = 0;
 	if (row < 0 || (uint64_t)row >= qC(T, 1)) k = -2;
 	else {
 		uint64_t x = (uint64_t)row;
-		uint8_t *o = out + i * (uint64_t)max_len;
+		uint8_t *o = out + R.i * (uint64_t)max_len;
 		for (;;) {
-			uint64_t c6[6]; uint32_t c;
-			qrank<SPARSE>(T, pv, x, c6, &c);
+			uint64_t c6[6];
+			const uint32_t c = qlf<SPARSE>(T, pv, x, c6);
 			if (c == 0) break;                                 // back at the string's own '$' row
 			if (k == max_len) { k = -1; break; }
-			if (g == 0) o[k] = (uint8_t)c;
+			if (R.g == 0) o[k] = (uint8_t)c;
 			++k;
-			x = qC(T, (int)c) + c6[c];                         // LF
 		}
 	}
-	if (g == 0) len[i] = k;
+	if (R.g == 0) len[R.i] = k;
 }
 
 // super-maximal exact matches of n queries qry[off[i] - base, off[i+1] - base) (codes 1..4 match, 5 belongs to no match, anything else
@@ -220,37 +288,33 @@ template <bool SPARSE> __global__ __launch_bounds__(256) __attribute__((amdgpu_w
 {
 	__shared__ QTab T;
 	qtab_load(Tg, T);
-	const uint64_t i = (uint64_t)blockIdx.x * QPB + (threadIdx.x >> 4);
-	if (i >= n) return;
-	const uint32_t g = (uint32_t)lane_id() & 15u;
-	const int64_t s0 = off[i] - base, L = off[i + 1] - base - s0, N = (int64_t)T.row0[NR];
-	const uint8_t *q = qry + s0;
-	bool bad = L < 0 || s0 < 0;
-	for (int64_t j = 0; !bad && j < L; ++j) { const uint8_t c = q[j]; bad = c == 0 || c > 5; }
-	if (bad) { if (g == 0) cnt[i] = -1; return; }
+	const QRow R = qrow();
+	if (R.i >= n) return;
+	const QSlice S = qslice<false>(qry, off, base, R.i);
+	if (S.bad) { if (R.g == 0) cnt[R.i] = -1; return; }
+	const int64_t L = S.L, N = (int64_t)T.row0[NR];
 	int64_t k = 0, p = 0;
 	while (p < L) {
-		const int c0 = q[p];
+		const int c0 = S.q[p];
 		int64_t xf = (int64_t)qC(T, c0 < 5 ? c0 : 0), xo = (int64_t)qC(T, c0 < 5 ? 5 - c0 : 0), sz = c0 < 5 ? (int64_t)qC(T, c0 + 1) - xf : 0;
 		if (sz < min_occ) { ++p; continue; }                       // N, or a symbol with too few occurrences: no match covers p
 		int64_t s = p, e = p + 1;
 		bool back = true;
 		for (;;) {
 			const int64_t j = back ? s - 1 : e;
-			const int c = j >= 0 && j < L ? q[j] : 0;
+			const int c = j >= 0 && j < L ? S.q[j] : 0;
 			bool stop = c < 1 || c > 4;
 			if (!stop) {
 				const int a = back ? c : 5 - c;                    // a forward extension by c is the extension of the other strand by its complement
-				uint64_t tk[6], tl[6];
-				qrank<SPARSE>(T, pv, (uint64_t)min(max(xf, (int64_t)0), N), tk);
-				qrank<SPARSE>(T, pv, (uint64_t)min(max(xf + sz, (int64_t)0), N), tl);
-				const int64_t nsz = (int64_t)(tl[a] - tk[a]);
+				const QPair<SPARSE> P(T, pv, (uint64_t)min(max(xf, (int64_t)0), N), (uint64_t)min(max(xf + sz, (int64_t)0), N));
+				const int64_t nsz = (int64_t)P.size(a);
 				if (nsz < min_occ) stop = true;
 				else {
-					xo += (int64_t)(tl[0] - tk[0]);                // the other end in the complement order $ T G C A N
+					xo += (int64_t)P.size(0);                      // the other end in the complement order $ T G C A N
 #pragma unroll
-					for (int b = 4; b >= 2; --b) if (b > a) xo += (int64_t)(tl[b] - tk[b]);
-					xf = (int64_t)(qC(T, a) + tk[a]); sz = nsz;
+					for (int b = 4; b >= 2; --b) if (b > a) xo += (int64_t)P.size(b);
+					int64_t xh;
+					P.child(T, a, xf, xh); sz = nsz;
 					if (back) --s; else ++e;
 				}
 			}
@@ -260,13 +324,10 @@ template <bool SPARSE> __global__ __launch_bounds__(256) __attribute__((amdgpu_w
 				const int64_t t = xf; xf = xo; xo = t;
 			}
 		}
-		if (e - s >= min_len) {
-			if (k < max_mems && g < 5) mem[(i * (uint64_t)max_mems + (uint64_t)k) * 5 + g] = g == 0 ? s : g == 1 ? e : g == 2 ? xo : g == 3 ? xf : sz;   // five lanes, one 40-byte record
-			++k;
-		}
+		if (e - s >= min_len) { qstore(mem, R.i, max_mems, k, R.g, s, e, xo, xf, sz); ++k; }
 		p = e;
 	}
-	if (g == 0) cnt[i] = k;
+	if (R.g == 0) cnt[R.i] = k;
 }
 
 // ---- sampled suffix array ----
@@ -283,59 +344,47 @@ template <bool SPARSE> __global__ __launch_bounds__(256) void k_ssa_build(const 
 {
 	__shared__ QTab T;
 	qtab_load(Tg, T);
-	const uint64_t k = k0 + (uint64_t)blockIdx.x * QPB + (threadIdx.x >> 4);
+	const QRow R = qrow();
+	const uint64_t k = k0 + R.i;
 	if (k >= n) return;
-	const uint32_t g = (uint32_t)lane_id() & 15u;
 	const uint64_t N = T.row0[NR], mask = (1ull << s) - 1;
 	uint64_t x = k, j = 0, c6[6];
 	for (;;) {
-		uint32_t c;
-		qrank<SPARSE>(T, pv, x, c6, &c);
-		if ((x & mask) == 0 && g < 2) smp[2 * (x >> s) + g] = g ? j : k;   // two lanes, one 16-byte sample
-		if (c == 0 || j >= N) break;
+		if ((x & mask) == 0) qstore((int64_t*)smp, x >> s, 1, 0, R.g, k, j);   // (one sample is one record)
+		if (qlf<SPARSE>(T, pv, x, c6) == 0 || j >= N) break;
 		++j;
-		x = qC(T, (int)c) + c6[c];                             // LF
 		if (x >= N) break;
 	}
-	if (g == 0) { slen[k] = j; if (c6[0] < n) head[c6[0]] = k; }
+	if (R.g == 0) { slen[k] = j; if (c6[0] < n) head[c6[0]] = k; }
 }
 
-// rows to places: slot q of the launch is hit kk = k0 + q % kn of interval i = q / kn (kn hits of every interval per launch, from k0 on:
-// kn = max_hits and k0 = 0 unless one interval alone has more slots than a launch takes).  The row lo_i + kk walks LF, counting its
+// rows to places: slot q of the launch is hit kk of interval i (qslot).  The row lo_i + kk walks LF, counting its
 // steps t, to the first row that is a sample (sid, j): (sid, len[sid] - j + t) -- or whose symbol is `$`: (head[`$`s in front], t).  The
 // sample is tested first, so the rows of the $ block need no case of their own: row k < n is step 0 of the walk of string k, and what the
 // walk from it meets -- a sample of string k at step j (t = j) or the end of string k (t = len[k]) -- gives (k, len[k]) either way.
-// hit[(i * max_hits + kk) * 2 ..] = string, position; cnt[i] = hi - lo, -1 for a malformed interval (written by the slot of hit 0).
+// hit[(i * max_hits + kk) * 2 ..] = string, position; cnt[i] = hi - lo, -1 for a malformed interval.
 template <bool SPARSE> __global__ __launch_bounds__(256) void k_locate(const QTab *Tg, PoolView pv, const int64_t *iv, uint64_t n, int64_t max_hits, int64_t k0, int64_t kn,
                                                                        int s, const uint64_t *smp, const uint64_t *slen, const uint64_t *head, uint64_t nstr,
                                                                        int64_t *hit, int64_t *cnt)
 {
 	__shared__ QTab T;
 	qtab_load(Tg, T);
-	const uint64_t q = (uint64_t)blockIdx.x * QPB + (threadIdx.x >> 4);
-	if (q >= n * (uint64_t)kn) return;
-	const uint64_t i = q / (uint64_t)kn;
-	const int64_t kk = k0 + (int64_t)(q % (uint64_t)kn);
-	const uint32_t g = (uint32_t)lane_id() & 15u;
-	const int64_t lo = iv[2 * i], hi = iv[2 * i + 1], N = (int64_t)T.row0[NR];
-	const bool bad = lo < 0 || hi > N || lo > hi;
-	if (kk == 0 && g == 0) cnt[i] = bad ? -1 : hi - lo;
-	if (bad || kk >= hi - lo) return;
-	const uint64_t mask = (1ull << s) - 1;
-	uint64_t x = (uint64_t)(lo + kk), t = 0, sid = 0, pos = 0;
+	const QRow R = qrow();
+	const uint64_t N = T.row0[NR], mask = (1ull << s) - 1;
+	const QSlot S = qslot(R.i, n, k0, kn, iv, (int64_t)N, R.g == 0, cnt);
+	if (!S.live) return;
+	uint64_t x = (uint64_t)S.x, t = 0, sid = 0, pos = 0;
 	for (;;) {
 		if ((x & mask) == 0) {
 			sid = smp[2 * (x >> s)];
 			pos = (sid < nstr ? slen[sid] : 0) - smp[2 * (x >> s) + 1] + t;
 			break;
 		}
-		uint64_t c6[6]; uint32_t c;
-		qrank<SPARSE>(T, pv, x, c6, &c);
-		if (c == 0) { sid = c6[0] < nstr ? head[c6[0]] : 0; pos = t; break; }
-		x = qC(T, (int)c) + c6[c];                             // LF
-		if (++t > (uint64_t)N || x >= (uint64_t)N) break;      // (no BWT of complete strings)
+		uint64_t c6[6];
+		if (qlf<SPARSE>(T, pv, x, c6) == 0) { sid = c6[0] < nstr ? head[c6[0]] : 0; pos = t; break; }
+		if (++t > N || x >= N) break;                              // (no BWT of complete strings)
 	}
-	if (g < 2) hit[(i * (uint64_t)max_hits + (uint64_t)kk) * 2 + g] = (int64_t)(g ? pos : sid);
+	qstore(hit, S.i, max_hits, S.kk, R.g, sid, pos);
 }
 
 // ---- suffix-prefix overlaps ----
@@ -353,48 +402,31 @@ template <bool SPARSE> __global__ __launch_bounds__(256) void k_overlap(const QT
 {
 	__shared__ QTab T;
 	qtab_load(Tg, T);
-	const uint64_t i = (uint64_t)blockIdx.x * QPB + (threadIdx.x >> 4);
-	if (i >= n) return;
-	const uint32_t g = (uint32_t)lane_id() & 15u;
-	const int64_t s0 = off[i] - base, L = off[i + 1] - base - s0;
-	const uint8_t *q = qry + s0;
-	bool bad = L < 0 || s0 < 0;
-	for (int64_t j = 0; !bad && j < L; ++j) { const uint8_t c = q[j]; bad = c == 0 || c > 5; }
-	if (bad) { if (g == 0) cnt[i] = -1; return; }
-	const int c0 = L > 0 ? q[L - 1] : 5;
+	const QRow R = qrow();
+	if (R.i >= n) return;
+	const QSlice S = qslice<false>(qry, off, base, R.i);
+	if (S.bad) { if (R.g == 0) cnt[R.i] = -1; return; }
+	const int c0 = S.L > 0 ? S.q[S.L - 1] : 5;
 	int64_t lo = (int64_t)qC(T, c0 < 5 ? c0 : 0), hi = c0 < 5 ? (int64_t)qC(T, c0 + 1) : lo, m = 1, k = 0;
 	while (lo < hi) {
-		uint64_t cl[6], ch[6];
-		qrank<SPARSE>(T, pv, (uint64_t)lo, cl);
-		qrank<SPARSE>(T, pv, (uint64_t)hi, ch);
-		if (m >= min_ovlp && ch[0] > cl[0]) {
-			if (k < max_recs && g < 3) rec[(i * (uint64_t)max_recs + (uint64_t)k) * 3 + g] = g == 0 ? m : (int64_t)(g == 1 ? cl[0] : ch[0]);   // three lanes, one 24-byte record
-			++k;
-		}
-		if (m == L) break;
-		const int c = q[L - 1 - m];
+		const QPair<SPARSE> P(T, pv, (uint64_t)lo, (uint64_t)hi);
+		if (m >= min_ovlp && P.ch[0] > P.cl[0]) { qstore(rec, R.i, max_recs, k, R.g, m, P.cl[0], P.ch[0]); ++k; }
+		if (m == S.L) break;
+		const int c = S.q[S.L - 1 - m];
 		if (c == 5) break;
-		const uint64_t C = qC(T, c);
-		lo = (int64_t)(C + cl[c]); hi = (int64_t)(C + ch[c]); ++m;
+		P.child(T, c, lo, hi); ++m;
 	}
-	if (g == 0) cnt[i] = k;
+	if (R.g == 0) cnt[R.i] = k;
 }
 
-// `$` ranks to string ids: slot q of the launch is hit kk = k0 + q % kn of range i = q / kn (covered in parts as k_locate is), one thread
+// `$` ranks to string ids: slot q of the launch is hit kk of range i (qslot; covered in parts as k_locate is), one thread
 // per slot, so a range reads head[] and writes ids[] in whole lines.  ids[i * max_hits + kk] = head[zlo_i + kk]; cnt[i] = zhi - zlo, -1
-// for a malformed range (written by the slot of hit 0).
+// for a malformed range.
 __global__ __launch_bounds__(256) void k_string_ids(const int64_t *zv, uint64_t n, int64_t max_hits, int64_t k0, int64_t kn, const uint64_t *head, uint64_t nstr,
                                                     int64_t *ids, int64_t *cnt)
 {
-	const uint64_t q = (uint64_t)blockIdx.x * 256 + threadIdx.x;
-	if (q >= n * (uint64_t)kn) return;
-	const uint64_t i = q / (uint64_t)kn;
-	const int64_t kk = k0 + (int64_t)(q % (uint64_t)kn);
-	const int64_t zlo = zv[2 * i], zhi = zv[2 * i + 1];
-	const bool bad = zlo < 0 || zhi > (int64_t)nstr || zlo > zhi;
-	if (kk == 0) cnt[i] = bad ? -1 : zhi - zlo;
-	if (bad || kk >= zhi - zlo) return;
-	ids[i * (uint64_t)max_hits + (uint64_t)kk] = (int64_t)head[zlo + kk];
+	const QSlot S = qslot((uint64_t)blockIdx.x * 256 + threadIdx.x, n, k0, kn, zv, (int64_t)nstr, true, cnt);
+	if (S.live) ids[S.i * (uint64_t)max_hits + (uint64_t)S.kk] = (int64_t)head[S.x];
 }
 
 // ---- k-mer enumeration ----
@@ -427,22 +459,20 @@ template <bool SPARSE> __global__ __launch_bounds__(256) void k_kmer_expand(cons
 	if (threadIdx.x == 0) s_pre = 0;
 	qtab_load(Tg, T);
 	const int lane = lane_id();
-	const uint32_t g = (uint32_t)lane & 15u;
+	const QRow R = qrow();
 	const bool last = l + 1 == k;
-	for (uint64_t i0 = (uint64_t)blockIdx.x * QPB; i0 < n; i0 += (uint64_t)gridDim.x * QPB) {
-		const uint64_t i = i0 + (threadIdx.x >> 4);
+	for (uint64_t d = 0; R.b + d < n; d += (uint64_t)gridDim.x * QPB) {   // (by the block's first row: the same turns in the whole block)
+		const uint64_t i = R.i + d;
 		bool live = false;
 		uint64_t code = 0, nlo = 0, nhi = 0;
 		if (i < n) {
 			const uint64_t pc = (uint64_t)in[3 * i], lo = (uint64_t)in[3 * i + 1], hi = (uint64_t)in[3 * i + 2];
-			uint64_t cl[6], ch[6];
-			qrank<SPARSE>(T, pv, lo, cl);
-			qrank<SPARSE>(T, pv, hi, ch);
+			const QPair<SPARSE> P(T, pv, lo, hi);
 #pragma unroll
 			for (int a = 1; a <= 4; ++a)
-				if (g == (uint32_t)(a - 1)) { const uint64_t C = qC(T, a); nlo = C + cl[a]; nhi = C + ch[a]; }
-			code = kmer_prepend(pc, l, (int)g + 1);
-			live = g < 4 && nhi - nlo >= (uint64_t)min_occ;
+				if (R.g == (uint32_t)(a - 1)) P.child(T, a, nlo, nhi);
+			code = kmer_prepend(pc, l, (int)R.g + 1);
+			live = R.g < 4 && nhi - nlo >= (uint64_t)min_occ;
 		}
 		if (last) {
 			const uint64_t pre = ballot64(live);
@@ -496,27 +526,20 @@ template <bool SPARSE> __global__ __launch_bounds__(256) void k_approx(const QTa
 {
 	__shared__ QTab T;
 	qtab_load(Tg, T);
-	const uint64_t row = (uint64_t)blockIdx.x * QPB + (threadIdx.x >> 4);
-	if (row >= rows) return;
-	const uint32_t g = (uint32_t)lane_id() & 15u;
+	const QRow R = qrow();
+	if (R.i >= rows) return;
 	const int64_t N = (int64_t)T.row0[NR];
-	uint64_t *kid = (uint64_t*)(scr + row * (uint64_t)approx_row_bytes(lrow));
+	uint64_t *kid = (uint64_t*)(scr + R.i * (uint64_t)approx_row_bytes(lrow));
 	uint8_t *G = (uint8_t*)(kid + 8 * lrow), *tk = G + approx_pad(lrow);
-	for (uint64_t i = row; i < n; i += rows) {
-		const int64_t s0 = off[i] - base, L = off[i + 1] - base - s0;
+	for (uint64_t i = R.i; i < n; i += rows) {
+		const int64_t L = off[i + 1] - off[i];
 		if (L <= lmin || L > lcap) continue;                       // another launch takes it
-		const uint8_t *q = qry + s0;
-		bool bad = L < 0 || s0 < 0 || L > min(lrow, APPROX_MAX_LEN);
-		for (int64_t j = 0; !bad && j < L; ++j) { const uint8_t c = q[j]; bad = c == 0 || c > 5; }
-		if (bad || L == 0) { if (g == 0) cnt[i] = bad ? -1 : 0; continue; }
+		const QSlice S = qslice<false>(qry, off, base, i, L > min(lrow, APPROX_MAX_LEN));   // (longer than the stack: malformed, and not read)
+		if (S.bad || L == 0) { if (R.g == 0) cnt[i] = S.bad ? -1 : 0; continue; }
 		int64_t steps = 0, k = 0;
-		const int pieces = approx_bound(q, L, N, min_occ, max_mm, max_steps, [&](int64_t lo, int64_t hi, int c, int64_t &nlo, int64_t &nhi) {
-			uint64_t cl[6], ch[6];
-			qrank<SPARSE>(T, pv, (uint64_t)lo, cl);
-			qrank<SPARSE>(T, pv, (uint64_t)hi, ch);
-			const uint64_t C = qC(T, c);
-			nlo = (int64_t)(C + cl[c]); nhi = (int64_t)(C + ch[c]); }, G, &steps);
-		if (pieces < 0 || pieces > max_mm) { if (g == 0) cnt[i] = pieces < 0 ? -2 : 0; continue; }
+		const int pieces = approx_bound(S.q, L, N, min_occ, max_mm, max_steps, [&](int64_t lo, int64_t hi, int c, int64_t &nlo, int64_t &nhi) {
+			QPair<SPARSE>(T, pv, (uint64_t)lo, (uint64_t)hi).child(T, c, nlo, nhi); }, G, &steps);
+		if (pieces < 0 || pieces > max_mm) { if (R.g == 0) cnt[i] = pieces < 0 ? -2 : 0; continue; }
 		int64_t p = L - 1;
 		uint64_t lo = 0, hi = (uint64_t)N, subs = 0;
 		int m = 0;
@@ -526,20 +549,19 @@ template <bool SPARSE> __global__ __launch_bounds__(256) void k_approx(const QTa
 			++steps;
 			uint64_t klo[4], khi[4];
 			{
-				uint64_t cl[6], ch[6], v = 0;
-				qrank<SPARSE>(T, pv, lo, cl);
-				qrank<SPARSE>(T, pv, hi, ch);
+				const QPair<SPARSE> P(T, pv, lo, hi);
+				uint64_t v = 0;
 #pragma unroll
-				for (int a = 1; a <= 4; ++a) { const uint64_t C = qC(T, a); klo[a - 1] = C + cl[a]; khi[a - 1] = C + ch[a]; }
+				for (int a = 1; a <= 4; ++a) P.child(T, a, klo[a - 1], khi[a - 1]);
 #pragma unroll
-				for (int w = 0; w < 8; ++w) if (g == (uint32_t)w) v = w & 1 ? khi[w >> 1] : klo[w >> 1];
-				if (g < 8) kid[8 * p + g] = v;
+				for (int w = 0; w < 8; ++w) if (R.g == (uint32_t)w) v = w & 1 ? khi[w >> 1] : klo[w >> 1];
+				if (R.g < 8) kid[8 * p + R.g] = v;
 				__builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
 			}
 			bool fresh = true, down = false;
 			int t = 0;
 			for (;;) {                                             // the children of the node at p from try t on; with none left, back to the node behind
-				const int c = q[p], need = approx_need(G, pieces, p);
+				const int c = S.q[p], need = approx_need(G, pieces, p);
 				while (t < 5) {
 					const int tt = t++, a = tt == 0 ? c : tt, cost = tt != 0;
 					if (tt == 0 ? c == 5 : a == c) continue;           // (N has no child of its own; q[p] was try 0)
@@ -551,10 +573,7 @@ template <bool SPARSE> __global__ __launch_bounds__(256) void k_approx(const QTa
 					} else { xlo = kid[8 * p + 2 * (a - 1)]; xhi = kid[8 * p + 2 * (a - 1) + 1]; }
 					if ((int64_t)(xhi - xlo) < min_occ) continue;
 					if (p == 0) {                                      // a match
-						if (k < max_recs && g < 4) {
-							const uint64_t sb = cost ? approx_push(subs, m, 0, a) : subs;
-							rec[(i * (uint64_t)max_recs + (uint64_t)k) * 4 + g] = (int64_t)(g == 0 ? xlo : g == 1 ? xhi : g == 2 ? (uint64_t)(m + cost) : sb);   // four lanes, one 32-byte record
-						}
+						qstore(rec, i, max_recs, k, R.g, xlo, xhi, m + cost, cost ? approx_push(subs, m, 0, a) : subs);
 						++k;
 						continue;
 					}
@@ -566,13 +585,13 @@ template <bool SPARSE> __global__ __launch_bounds__(256) void k_approx(const QTa
 				if (down || ++p == L) break;
 				const int b = tk[p];
 				t = b >> 3;
-				if ((b & 7) != q[p]) { subs = approx_pop(subs, m); --m; }
+				if ((b & 7) != S.q[p]) { subs = approx_pop(subs, m); --m; }
 				fresh = false;
 				__builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 			}
 			if (!down) break;                                      // back behind the last position: the search is complete
 		}
-		if (g == 0) cnt[i] = over ? -2 - k : k;
+		if (R.g == 0) cnt[i] = over ? -2 - k : k;
 	}
 }
 

@@ -1,6 +1,7 @@
 // Host side of the FM-index queries (kernels: rb2_query.h; the launch arithmetic: rb2_query_plan.h, rb2_kmer_plan.h).  Included from rb2_engine.hip, whose
-// handle, buffers and checks it uses.  Three helpers carry every query: qlaunch (one launch of a kernel in the layout of the index),
-// stage_inputs (a chunk's inputs to the device) and staged_records (the chunked loop of the host variants that return records).
+// handle, buffers and checks it uses.  Four helpers carry every query: qlaunch (one launch of a kernel in the layout of the index),
+// stage_inputs (a chunk's inputs to the device), staged_records (the chunked loop of the host variants that return records) and
+// dev_chunks (the chunked loop of the device-pointer variants).
 #pragma once
 #include "rb2_query_plan.h"
 #include "rb2_kmer_plan.h"
@@ -34,6 +35,14 @@ static void qlaunch(rb2_hip_t *h, void (*sparse)(const QTab*, PoolView, P...), v
 	const auto k = h->sparse ? sparse : dense;
 	hipLaunchKernelGGL(k, dim3((unsigned)cdiv(rows, QPB)), dim3(256), 0, h->st, (const QTab*)h->qtab.p, h->pool[h->pside].view(), static_cast<P>(a)...);
 	HIPCHK(hipGetLastError());
+}
+
+/* the _dev variants that take packed strings: launch(i0, nc) for the items [i0, i0 + nc) of every chunk, nothing staged and no synchronise */
+template <typename F>
+static void dev_chunks(int64_t n, F launch)
+{
+	const int64_t CH = query_chunk();
+	for (int64_t i0 = 0; i0 < n; i0 += CH) launch(i0, std::min(CH, n - i0));
 }
 
 /* the inputs of a host variant, in host memory: n packed strings (w == 0: bytes, and v = their n + 1 offsets) or n tuples of w int64 (v) */
@@ -126,8 +135,7 @@ void rb2_hip_backward_search(rb2_hip_t *h, int64_t n, const uint8_t *pat, const 
 void rb2_hip_backward_search_dev(rb2_hip_t *h, int64_t n, const uint8_t *pat, const int64_t *off, int64_t *out)
 {
 	query_begin(h, "backward_search_dev");
-	const int64_t CH = query_chunk();
-	for (int64_t i0 = 0; i0 < n; i0 += CH) launch_bsearch(h, std::min(CH, n - i0), pat, off + i0, 0, out + 3 * i0);
+	dev_chunks(n, [&](int64_t i0, int64_t nc) { launch_bsearch(h, nc, pat, off + i0, 0, out + 3 * i0); });
 }
 
 void rb2_hip_extend(rb2_hip_t *h, int64_t n, const int64_t *ik, int is_back, int64_t *ok)
@@ -190,8 +198,7 @@ void rb2_hip_smem_dev(rb2_hip_t *h, int64_t n, const uint8_t *qry, const int64_t
 	query_begin(h, "smem_dev");
 	if (n <= 0) return;
 	smem_check("smem_dev", min_len, min_occ, max_mems);
-	const int64_t CH = query_chunk();
-	for (int64_t i0 = 0; i0 < n; i0 += CH) launch_smem(h, std::min(CH, n - i0), qry, off + i0, 0, min_len, min_occ, max_mems, mem + i0 * max_mems * 5, cnt + i0);
+	dev_chunks(n, [&](int64_t i0, int64_t nc) { launch_smem(h, nc, qry, off + i0, 0, min_len, min_occ, max_mems, mem + i0 * max_mems * 5, cnt + i0); });
 }
 
 /* ---- sampled suffix array: rows back to (string, position) (k_ssa_build, k_locate) ---- */
@@ -288,8 +295,7 @@ void rb2_hip_overlap_dev(rb2_hip_t *h, int64_t n, const uint8_t *qry, const int6
 	query_begin(h, "overlap_dev");
 	if (n <= 0) return;
 	overlap_check("overlap_dev", min_ovlp, max_recs);
-	const int64_t CH = query_chunk();
-	for (int64_t i0 = 0; i0 < n; i0 += CH) launch_overlap(h, std::min(CH, n - i0), qry, off + i0, 0, min_ovlp, max_recs, rec + i0 * max_recs * 3, cnt + i0);
+	dev_chunks(n, [&](int64_t i0, int64_t nc) { launch_overlap(h, nc, qry, off + i0, 0, min_ovlp, max_recs, rec + i0 * max_recs * 3, cnt + i0); });
 }
 
 static const int64_t IDS_LAUNCH = 1 << 28;                     /* hit slots (threads) per launch of k_string_ids */
@@ -466,7 +472,6 @@ void rb2_hip_approx_dev(rb2_hip_t *h, int64_t n, const uint8_t *qry, const int64
 	query_begin(h, "approx_dev");
 	if (n <= 0) return;
 	approx_check("approx_dev", max_mm, min_occ, max_steps, max_recs);
-	const int64_t CH = query_chunk();
-	for (int64_t i0 = 0; i0 < n; i0 += CH)
-		launch_approx(h, std::min(CH, n - i0), qry, off + i0, 0, APPROX_MAX_LEN, max_mm, min_occ, max_steps, max_recs, rec + i0 * max_recs * 4, cnt + i0);
+	dev_chunks(n, [&](int64_t i0, int64_t nc) {
+		launch_approx(h, nc, qry, off + i0, 0, APPROX_MAX_LEN, max_mm, min_occ, max_steps, max_recs, rec + i0 * max_recs * 4, cnt + i0); });
 }
