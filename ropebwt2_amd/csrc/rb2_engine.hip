@@ -566,7 +566,8 @@ void round_counts(rb2_hip_t *h, BatchState &B, uint64_t r, bool spec = false)
 	    if (spec) {
 	      hipLaunchKernelGGL((k_sym<false, P, true>), dim3((unsigned)rank_share(h, B.nst_ub) + sp.nsplitb + (sp.scan2 ? 1u : 0u)), dim3(256), 0, st, h->ctl, sd, (int)(r & 1), S, trs, sp);
 	    } else
-	    RB2_LAUNCH_STRIDE(h, (k_sym<true, P>), (k_sym<false, P>), dim3(grid8((unsigned)rank_share(h, B.nst_ub))), dim3(256), 0, st, h->ctl, sd, (int)(r & 1), S, trs, sp); }); }
+	    if (h->nranks > 1) hipLaunchKernelGGL((k_sym<true, P>), dim3(grid8((unsigned)rank_share(h, B.nst_ub))), dim3(256), 0, st, h->ctl, sd, (int)(r & 1), S, trs, sp);
+	    else hipLaunchKernelGGL((k_sym<false, P>), dim3(grid8(cdiv(B.nst_ub, (unsigned)SYM_PAIR))), dim3(256), 0, st, h->ctl, sd, (int)(r & 1), S, trs, sp); }); }   // (one engine: a block takes SYM_PAIR tiles)
 	tl_slow(h, "k_sym");
 	if (spec && !lazy_round(h, spec)) HIPCHK(hipEventRecord(h->ev_flag, st));   // (the splits left the verdict in pinned memory)
 	if (one_launch_tail) {                                      // one launch instead of six, k_setup included (one GPU)
@@ -716,7 +717,9 @@ void wait_progress(rb2_hip_t *h, uint64_t r)
 			if (std::chrono::steady_clock::now() - t_spin > std::chrono::seconds(2)) { HIPCHK(hipStreamSynchronize(h->st)); break; }   // (a report that does not come: wait the plain way)
 		}
 #if defined(__x86_64__)
+#if defined(__x86_64__) || defined(__i386__)
 		__builtin_ia32_pause();
+#endif
 #else
 		std::this_thread::yield();
 #endif

@@ -293,11 +293,24 @@ __device__ __forceinline__ void split_body(Ctl *ctl, const PoolView &pool, const
 // (r04: k_prep<AE> was a second pass over the same strings at 2.3 TB/s: 0.18 ms per round of 42 M strings.)
 constexpr int32_t TILE_DONE = 0x10000;       // in TileRecs::lh (a head index is < STILE)
 constexpr int32_t TILE_SINGLE = 0x20000;     // ... every string of the tile is a group of its own and so is the string behind it (-> TileFix::nexthead bit 2: k_advance asks for its gathers before the barriers only then)
+// Two tiles per block (round 8, RB2_SYM_PAIR): the one-engine dense instantiation k_sym<false, P, false> takes tiles 2i and 2i + 1 (i = xcd_item()):
+// tile_ctx for both, then ALL loads of both tiles straight-line (A, U / L, the predecessor, the string behind the tile -- nothing loaded is looked at
+// before they are all issued, the rule of k_merge_leaf), then the flag stores and the ballots into LDS tables with a tile index, ONE barrier, and per
+// tile its own all-single / fused decision, summary (twelve threads, six per tile) and fused stores.  A one-tile block lived for one memory round
+// trip and a barrier / summary / store tail with nothing in flight; the pair pays round trip, barrier and tail once per 1024 strings.  The two
+// tiles may lie in different buckets and the second may not exist: all per-tile state (first_tile, segend, slot0, nval) is per tile.
+// The STRIDE (rank of a sharded index) and SPLIT (behind an in-place round) instantiations keep ONE tile per trip.  -DRB2_SYM_PAIR=0: one tile per
+// block everywhere, the kernel of round 7.
+#ifndef RB2_SYM_PAIR
+#define RB2_SYM_PAIR 1
+#endif
+constexpr int SYM_PAIR = RB2_SYM_PAIR != 0 ? 2 : 1;   // tiles per block of k_sym<false, P, false> (the host sizes its grid by it)
 template <bool STRIDE, typename P = uint64_t, bool SPLIT = false> __global__ __launch_bounds__(256) void k_sym(const Ctl *ctl, int side, int par, StrArrays<P> S, TileRecs trec, SplitArgs sp)
 {
+	constexpr int NT = (STRIDE || SPLIT) ? 1 : SYM_PAIR;       // tiles per trip
 	const P *L = S.L, *UU = S.U; P *INS_E = S.INS_E; uint8_t *INS_A = S.INS_A, *A = S.A;   // A in: the symbol every string inserts this round (k_init_strings / k_advance); out: + the group-head flag
-	__shared__ uint64_t s_bal[8][6], s_head[8];
-	__shared__ __align__(16) uint32_t s_ok[4];                 // per wave: every string of the wave is a group of its own
+	__shared__ uint64_t s_bal[NT][8][6], s_head[NT][8];
+	__shared__ __align__(16) uint32_t s_ok[NT][4];             // per tile and wave: every string of the wave is a group of its own
 	if (SPLIT) {
 		__shared__ uint16_t s_row[MW][7][SB];
 		// the FIRST blocks of the grid: the splits' registers (99 VGPRs) cap the launch at five workgroups per CU, the tile blocks take two
@@ -307,82 +320,98 @@ template <bool STRIDE, typename P = uint64_t, bool SPLIT = false> __global__ __l
 	}
 	const bool ae = ctl->ne[par] == 0;
 	const P *U = ae ? L : UU;
-	for (uint32_t tile = (STRIDE || SPLIT) ? blockIdx.x - (SPLIT ? sp.nsplitb + (sp.scan2 ? 1u : 0u) : 0u) : xcd_item(); ; tile += gridDim.x) {     // the first tile as ever (its loads issue at once); the bound ends the walk
+	for (uint32_t tile = (STRIDE || SPLIT) ? blockIdx.x - (SPLIT ? sp.nsplitb + (sp.scan2 ? 1u : 0u) : 0u) : xcd_item() * (uint32_t)NT; ; tile += gridDim.x) {     // the first tile as ever (its loads issue at once); the bound ends the walk
 	if (STRIDE && tile != blockIdx.x) __syncthreads();          // the LDS tables of the previous tile are done with (STRIDE and SPLIT never come together)
-	TileCtx t;
-	if (!tile_ctx(ctl->seg[side], tile, t)) return;
+	TileCtx t[NT];
+	if (!tile_ctx(ctl->seg[side], tile, t[0])) return;
+	bool have[NT]; have[0] = true;                             // (block-uniform)
+	if (NT > 1) { have[1] = tile_ctx(ctl->seg[side], tile + 1, t[1]); if (!have[1]) t[1] = t[0]; }   // (no second tile: nval = 0 below, nothing of it is read or written)
 	const int ln = lane_id(), w = wave_id();
-	// all loads of the thread's two strings first: A is a byte array (it may alias anything as far as the compiler knows), so a load
+	// all loads of the thread's strings first: A is a byte array (it may alias anything as far as the compiler knows), so a load
 	// written behind the store of the first string's flag would wait for it
-	// every access of the tile is a wave-uniform base + a 32-bit offset (string x of the tile = string t.base + x of the arrays; its slot in the
+	// every access of a tile is a wave-uniform base + a 32-bit offset (string x of the tile = string t.base + x of the arrays; its slot in the
 	// bucket's insert list, lt * STILE + x, is the same place in INS_E / INS_A): no 64-bit address arithmetic per lane
-	const uint32_t nval = (uint32_t)min((uint64_t)STILE, t.segend - t.base);   // strings in this tile
-	const uint8_t *Ab = A + t.base; const P *Ub = U + t.base;
-	const bool first_tile = t.base == t.segstart;
-	uint32_t av[2]; P uv[2], up[2], un = 0;
-#pragma unroll
-	for (int h = 0; h < 2; ++h) {
-		const uint32_t x = (uint32_t)(h * 256) + threadIdx.x;
-		RB2_UNDEFV(av[h]); RB2_UNDEFV(uv[h]); RB2_UNDEFV(up[h]);   // (only looked at where x < nval)
-		if (x < nval) { av[h] = Ab[x]; uv[h] = Ub[x]; up[h] = (x > 0 || !first_tile) ? Ub[(int32_t)x - 1] : (P)0; }
-	}
+	uint32_t nval[NT]; bool first_tile[NT], has_next[NT];
+	uint32_t av[NT][2]; P uv[NT][2], up[NT][2], un[NT];
 	const bool last_thread = threadIdx.x == 255;
-	const bool has_next = last_thread && t.base + STILE < t.segend;   // the string behind the tile (same bucket): does it start a group?
-	if (has_next) un = Ub[STILE];
-	bool single = true;                                       // my strings are groups of their own (and, last thread: so is the tile's end)
-	int sym2[2];
-	uint8_t *Aw = A + t.base;
 #pragma unroll
-	for (int h = 0; h < 2; ++h) {
-		const uint32_t x = (uint32_t)(h * 256) + threadIdx.x;
-		int sym = 7; bool head = false;
-		if (x < nval) {
-			sym = (int)(av[h] & 7);
-			head = (x == 0 && first_tile) || (uv[h] != up[h]);
-			Aw[x] = (uint8_t)(sym | (head ? 0x80 : 0));
-			single = single && head;
-		}
-		sym2[h] = sym;
-		const int c = h * 4 + w;
-		uint64_t bm[6];                                             // all ballots, then one lane-0 block that stores them (group_setup)
-#pragma unroll
-		for (int s = 0; s < 6; ++s) bm[s] = ballot64(sym == s);
-		const uint64_t hm = ballot64(head);
-		if (ln == 0) {
-#pragma unroll
-			for (int s = 0; s < 6; ++s) s_bal[c][s] = bm[s];
-			s_head[c] = hm;
-		}
-	}
-	if (has_next) single = single && un != uv[1];
-	// "every string of the tile is a group of its own": a scalar comparison per wave, a flag per wave, ONE barrier (the one the tile summaries need
-	// anyway) -- __syncthreads_and was a DPP reduction, an LDS atomic and three barriers
-	{ const uint64_t sm = ballot64(single); if (ln == 0) s_ok[w] = sm == ~0ull ? 1u : 0u; }
-	__syncthreads();
-	const uint4 okv = *(const uint4*)s_ok;
-	const bool allsingle = (okv.x & okv.y & okv.z & okv.w) != 0;
-	const bool fused = ae && allsingle;
-	if (fused) {
-		P *Eb = INS_E + t.base; uint8_t *Ib = INS_A + t.base;     // slot + segstart = t.base + x
-		const P slot0 = (P)(t.lt * STILE);
+	for (int q = 0; q < NT; ++q) {
+		nval[q] = have[q] ? (uint32_t)min((uint64_t)STILE, t[q].segend - t[q].base) : 0u;   // strings in this tile
+		const uint8_t *Ab = A + t[q].base; const P *Ub = U + t[q].base;
+		first_tile[q] = t[q].base == t[q].segstart;
 #pragma unroll
 		for (int h = 0; h < 2; ++h) {
 			const uint32_t x = (uint32_t)(h * 256) + threadIdx.x;
-			if (x >= nval) continue;
-			Eb[x] = (P)(uv[h] - (slot0 + (P)x));                   // empty interval: the new symbol goes to l - F (pre-round coordinates), F = slot = lt * STILE + x
-			Ib[x] = (uint8_t)sym2[h];
+			RB2_UNDEFV(av[q][h]); RB2_UNDEFV(uv[q][h]); RB2_UNDEFV(up[q][h]);   // (only looked at where x < nval)
+			if (x < nval[q]) { av[q][h] = Ab[x]; uv[q][h] = Ub[x]; up[q][h] = (x > 0 || !first_tile[q]) ? Ub[(int32_t)x - 1] : (P)0; }
+		}
+		has_next[q] = last_thread && have[q] && t[q].base + STILE < t[q].segend;   // the string behind the tile (same bucket): does it start a group?
+		un[q] = 0;
+		if (has_next[q]) un[q] = Ub[STILE];
+	}
+#pragma unroll
+	for (int q = 0; q < NT; ++q) {
+		bool single = true;                                       // my strings are groups of their own (and, last thread: so is the tile's end)
+		uint8_t *Aw = A + t[q].base;
+#pragma unroll
+		for (int h = 0; h < 2; ++h) {
+			const uint32_t x = (uint32_t)(h * 256) + threadIdx.x;
+			int sym = 7; bool head = false;
+			if (x < nval[q]) {
+				sym = (int)(av[q][h] & 7);
+				head = (x == 0 && first_tile[q]) || (uv[q][h] != up[q][h]);
+				Aw[x] = (uint8_t)(sym | (head ? 0x80 : 0));
+				single = single && head;
+			}
+			av[q][h] = (uint32_t)sym;                                   // (the symbol from here on)
+			const int c = h * 4 + w;
+			uint64_t bm[6];                                             // all ballots, then one lane-0 block that stores them (group_setup)
+#pragma unroll
+			for (int s = 0; s < 6; ++s) bm[s] = ballot64(sym == s);
+			const uint64_t hm = ballot64(head);
+			if (ln == 0) {
+#pragma unroll
+				for (int s = 0; s < 6; ++s) s_bal[q][c][s] = bm[s];
+				s_head[q][c] = hm;
+			}
+		}
+		if (has_next[q]) single = single && un[q] != uv[q][1];
+		// "every string of the tile is a group of its own": a scalar comparison per wave, a flag per wave, ONE barrier (the one the tile summaries need
+		// anyway) -- __syncthreads_and was a DPP reduction, an LDS atomic and three barriers
+		{ const uint64_t sm = ballot64(single); if (ln == 0) s_ok[q][w] = sm == ~0ull ? 1u : 0u; }
+	}
+	__syncthreads();
+	bool allsingle[NT], fused[NT];
+#pragma unroll
+	for (int q = 0; q < NT; ++q) {
+		const uint4 okv = *(const uint4*)s_ok[q];
+		allsingle[q] = (okv.x & okv.y & okv.z & okv.w) != 0;
+		fused[q] = ae && allsingle[q];
+		if (fused[q]) {
+			P *Eb = INS_E + t[q].base; uint8_t *Ib = INS_A + t[q].base;     // slot + segstart = t.base + x
+			const P slot0 = (P)(t[q].lt * STILE);
+#pragma unroll
+			for (int h = 0; h < 2; ++h) {
+				const uint32_t x = (uint32_t)(h * 256) + threadIdx.x;
+				if (x >= nval[q]) continue;
+				Eb[x] = (P)(uv[q][h] - (slot0 + (P)x));                // empty interval: the new symbol goes to l - F (pre-round coordinates), F = slot = lt * STILE + x
+				Ib[x] = (uint8_t)av[q][h];
+			}
 		}
 	}
-	if (threadIdx.x < 6) {
-		const int s = threadIdx.x;
+	if (threadIdx.x < 6 * NT) {                                 // six threads per tile write its summary
+		const int q = NT > 1 ? (int)(threadIdx.x >= 6) : 0, s = (int)threadIdx.x - 6 * q;
+		const bool q1 = NT > 1 && q;                               // (selects, not arrays indexed by q: those would live in scratch)
+		const bool hv = q1 ? have[NT - 1] : true, as = q1 ? allsingle[NT - 1] : allsingle[0], fu = q1 ? fused[NT - 1] : fused[0];
+		const uint32_t nv = q1 ? nval[NT - 1] : nval[0], mytile = tile + (uint32_t)q;
 		uint32_t run = 0, fhpre = 0, lhpre = 0; int fh = -1, lh = -1;
-		if (allsingle) {                                        // (block-uniform; the rule from round ~14 on) every string is a head: the first one is string 0, the last one string nval - 1
+		if (as) {                                               // (the rule from round ~14 on) every string is a head: the first one is string 0, the last one string nval - 1
 #pragma unroll
-			for (int c = 0; c < 8; ++c) run += __popcll(s_bal[c][s]);
-			if (nval) { fh = 0; lh = (int)nval - 1; lhpre = run - (uint32_t)((s_bal[lh >> 6][s] >> (lh & 63)) & 1ull); }
+			for (int c = 0; c < 8; ++c) run += __popcll(s_bal[q][c][s]);
+			if (nv) { fh = 0; lh = (int)nv - 1; lhpre = run - (uint32_t)((s_bal[q][lh >> 6][s] >> (lh & 63)) & 1ull); }
 		} else
 		for (int c = 0; c < 8; ++c) {
-			const uint64_t hm = s_head[c], bm = s_bal[c][s];
+			const uint64_t hm = s_head[q][c], bm = s_bal[q][c][s];
 			if (hm) {
 				const int f = __builtin_ctzll(hm), l = 63 - __builtin_clzll(hm);
 				if (fh < 0) { fh = c * 64 + f; fhpre = run + __popcll(bm & lt_mask(f)); }
@@ -390,8 +419,10 @@ template <bool STRIDE, typename P = uint64_t, bool SPLIT = false> __global__ __l
 			}
 			run += __popcll(bm);
 		}
-		trec.hist(s, tile) = run; trec.fhpre(s, tile) = fhpre; trec.lhpre(s, tile) = lhpre;
-		if (s == 0) { trec.fh(tile) = fh; trec.lh(tile) = lh | (fused ? TILE_DONE : 0) | (allsingle ? TILE_SINGLE : 0); }   // (all-single: every string is a head, lh >= 0)
+		if (hv) {
+			trec.hist(s, mytile) = run; trec.fhpre(s, mytile) = fhpre; trec.lhpre(s, mytile) = lhpre;
+			if (s == 0) { trec.fh(mytile) = fh; trec.lh(mytile) = lh | (fu ? TILE_DONE : 0) | (as ? TILE_SINGLE : 0); }   // (all-single: every string is a head, lh >= 0)
+		}
 	}
 	if (!STRIDE) return;
 	}
