@@ -139,6 +139,25 @@ int64_t rb2_hip_load_fmd(rb2_hip_t *h, const void *fmd, int64_t n_bytes);
 /* the same for a file that is read into memory first; a file that cannot be opened or read is fatal with its name */
 int64_t rb2_hip_load_fmd_file(rb2_hip_t *h, const char *path);
 
+/* Take strings out of the index again (no counterpart in the reference, whose ropes only grow).  ids: n string
+ * ids in host memory, in any order, duplicates allowed -- a string id is a row of the `$` block, what rb2_hip_extract takes and
+ * rb2_hip_locate / rb2_hip_string_ids give; in input order id k is the k-th string inserted.  Afterwards the index is the BWT of the
+ * remaining strings, byte for byte what rb2_hip_download_rope gives for an index built from them alone in the same order.  The ids of
+ * the survivors close ranks: old id k becomes k minus the number of deleted ids below k.  Returns the rows removed (symbols plus
+ * sentinels of the deleted strings), counted on the device.
+ * The call finishes a lazy insert first, leaves the dense layout with plain windows, drops the sampled suffix array and returns when
+ * the new index is in place; n == 0 returns 0 and changes nothing (not the layout, not the suffix array).  Deleting every string
+ * leaves an empty index that takes inserts as after rb2_hip_reset.  Cost: one LF walk per deleted string and one streaming rewrite of
+ * the index (k_del_*, csrc/rb2_delete.h); device memory: the second pool side plus 8 bytes of marks per 64 rows and 12 bytes per leaf.
+ * Fatal, each with a message of its own and before anything is changed: an id below 0 or not below the number of strings; n < 0; a
+ * rank of a sharded index; a walk that does not end within the rows of the index or leaves it (a loaded index that is no BWT of
+ * complete strings).
+ * rb2_hip_delete_stats: what the last deletion met -- out[0] rows removed, out[1] source groups of 64 rows that held rows, out[2] those
+ * of them whose kept rows had to be closed up by the bit compress (the others are copied by a shift), out[3] leaf slots read,
+ * out[4] leaf slots written. */
+int64_t rb2_hip_delete_strings(rb2_hip_t *h, int64_t n, const int64_t *ids);
+void rb2_hip_delete_stats(rb2_hip_t *h, int64_t out[5]);
+
 /* optional capacity hint (like the reference sizing its buffers from -m, main.c:136): make room for batches
  * of up to batch_bytes bytes / batch_strings strings and an index of total_symbols symbols, so that
  * rb2_hip_insert_multi* never has to grow (reallocate + copy) a buffer.  Any argument may be 0. */
@@ -203,7 +222,7 @@ void rb2_hip_smem_dev(rb2_hip_t *h, int64_t n, const uint8_t *qry, const int64_t
  * rb2_hip_ssa_build walks every string once (k_ssa_build) and keeps (k, j) of every row x with x % 2^log2_step == 0, the length of every
  * string, and the string behind every whole-string row: 16 bytes per sample and 16 per string of device memory.  It returns the samples
  * stored, ceil(N / 2^log2_step); an empty index gives 0.  log2_step outside 0 .. 30 is fatal.  The array describes the rows as they are
- * now: an insert, rb2_hip_load_ropes, rb2_hip_load_fmd* and rb2_hip_reset drop it (rb2_hip_ssa_drop does so on request and frees its
+ * now: an insert, rb2_hip_load_ropes, rb2_hip_load_fmd*, rb2_hip_delete_strings and rb2_hip_reset drop it (rb2_hip_ssa_drop does so on request and frees its
  * memory, rb2_hip_destroy too); a change between the dense and the sparse layout does not.  Building again replaces it.
  * rb2_hip_ssa_info: out[0] 1 when an array is valid, out[1] its log2_step, out[2] its samples, out[3] the bytes of device memory held. */
 int64_t rb2_hip_ssa_build(rb2_hip_t *h, int log2_step);

@@ -18,6 +18,7 @@
 #include "rb2_kernels.h"
 #include "rb2_query.h"
 #include "rb2_fmd_load.h"
+#include "rb2_delete.h"
 
 using namespace rb2;
 
@@ -277,6 +278,7 @@ struct rb2_hip_s {
 	int ts_fold = SCHUNK;               // up to this many chunks of string tiles k_tscan3 scans the chunk totals itself (no k_tscan2 launch); RB2_TS_FOLD lowers it (tests)
 	int ts_max = TS_MAX;                // batches with fewer string tiles run their counting tail in one single-block launch (k_tscan_setup); RB2_TS_MAX lowers it (tests)
 	int trace = 0;                      // RB2_HIP_TRACE=1: per-round kernel times + merge path statistics on stderr
+	int64_t del_stats[5] = {0, 0, 0, 0, 0};   // the last rb2_hip_delete_strings: rows removed, source groups that held rows, those that needed the compress, source leaves, destination leaves
 };
 
 namespace {
@@ -406,7 +408,7 @@ static uint64_t max_batch_strings()
 }
 
 /* The sampled suffix array belongs to one state of the rows.  Whatever is about to change the rows -- a batch (batch_begin: both inserts,
- * one engine or a rank), a loader (ld_zero_pool), rb2_hip_reset -- calls this first; rb2_hip_ssa_drop and rb2_hip_destroy free it the same
+ * one engine or a rank), a loader or a deletion (ld_zero_pool), rb2_hip_reset -- calls this first; rb2_hip_ssa_drop and rb2_hip_destroy free it the same
  * way.  A re-layout moves leaves, not rows, and does not come here. */
 static void index_rows_change(rb2_hip_t *h, bool drained = false)
 {
@@ -1338,14 +1340,14 @@ static uint64_t ld_piece_table(rb2_hip_t *h, const char *who, const uint64_t tot
 	}
 	return leaf;
 }
-// the zeroed pool of `leaf` leaves the pieces are ORed into
-static PoolView ld_zero_pool(rb2_hip_t *h, uint64_t leaf)
+// the zeroed pool of `leaf` leaves the pieces are ORed into: pool side ps (the loaders: the current one; a deletion: the other)
+static PoolView ld_zero_pool(rb2_hip_t *h, uint64_t leaf, int ps)
 {
 	hipStream_t st = h->st;
 	index_rows_change(h);
 	h->sparse = false; h->sp_backoff = h->sp_penalty = 0;      /* what is loaded is the dense layout */
-	h->pool[h->pside].ensure(leaf + SB, false, st);
-	PoolView pv = h->pool[h->pside].view();
+	h->pool[ps].ensure(leaf + SB, false, st);
+	PoolView pv = h->pool[ps].view();
 	if (leaf) {
 		HIPCHK(hipMemsetAsync(pv.data, 0, leaf * (uint64_t)LEAFB, st));
 		HIPCHK(hipMemsetAsync(pv.own, 0, leaf * sizeof(LeafMeta), st));
@@ -1405,7 +1407,7 @@ void rb2_hip_load_ropes(rb2_hip_t *h, const uint8_t *const rle[6], const int64_t
 	RopeDesc rp[NR];
 	LdPieces tab[6];
 	const uint64_t leaf = ld_piece_table(h, "load_ropes", tot, rp, tab);
-	PoolView pv = ld_zero_pool(h, leaf);
+	PoolView pv = ld_zero_pool(h, leaf, h->pside);
 	std::vector<uint64_t> off;
 	for (int b = 0; b < 6; ++b) {
 		if (nblk[b] == 0) continue;
@@ -1491,7 +1493,7 @@ int64_t rb2_hip_load_fmd(rb2_hip_t *h, const void *fmd, int64_t n_bytes)
 	RopeDesc rp[NR];
 	LdPieces tab[6];
 	const uint64_t leaf = ld_piece_table(h, "load_fmd", tot, rp, tab);
-	PoolView pv = ld_zero_pool(h, leaf);
+	PoolView pv = ld_zero_pool(h, leaf, h->pside);
 	FmdPieces gp;
 	memset(&gp, 0, sizeof(gp));
 	for (int b = 0; b < 6; ++b)
@@ -1526,6 +1528,88 @@ int64_t rb2_hip_load_fmd_file(rb2_hip_t *h, const char *path)
 	if (got != img.size()) { rb2_fatal("[rb2_hip] load_fmd: cannot read %s (%zu of %zu bytes)\n", path, got, img.size()); }
 	return rb2_hip_load_fmd(h, img.data(), (int64_t)img.size());
 }
+
+/* ---- deleting strings (kernels in rb2_delete.h) ------------------------------ */
+
+int64_t rb2_hip_delete_strings(rb2_hip_t *h, int64_t n, const int64_t *ids)
+{ finish_pending(h);
+	HIPCHK(hipSetDevice(h->dev));
+	hipStream_t st = h->st;
+	if (h->nranks > 1) { rb2_fatal("[rb2_hip] delete_strings: this handle holds only its own sub-ropes of a sharded index; a deletion needs the whole index on one engine\n"); }
+	if (n < 0) { rb2_fatal("[rb2_hip] delete_strings: the number of ids must not be negative (got %lld)\n", (long long)n); }
+	const uint64_t nstr = h->h_rope[0].n;                      // C[1]: rope $ is one piece
+	for (int64_t i = 0; i < n; ++i)
+		if (ids[i] < 0 || (uint64_t)ids[i] >= nstr) { rb2_fatal("[rb2_hip] delete_strings: ids[%lld] = %lld is no string of the index (it holds %llu)\n", (long long)i, (long long)ids[i], (unsigned long long)nstr); }
+	if (n == 0) return 0;
+	ensure_dense(h);
+	require_plain(h, "delete_strings");
+	double t_ph[6]; int n_ph = 0;                              // RB2_HIP_TRACE=1: the host clock behind a synchronise after every phase
+	auto phase = [&]() { if (h->trace) { HIPCHK(hipStreamSynchronize(st)); t_ph[n_ph++] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); } };
+	phase();
+	uint64_t nleaf = 0;                                        // leaf slots of the source, up to the end of its last piece
+	for (int r = 0; r < NR; ++r) if (h->h_rope[r].nleaves) nleaf = std::max(nleaf, h->h_rope[r].leaf0 + h->h_rope[r].nleaves);
+	const int64_t CH = 1 << 24;                                // DPP rows per launch
+	DevBuf<int64_t> d_ids; DevBuf<unsigned long long> marks, tally; DevBuf<uint32_t> lkept; DevBuf<uint64_t> lbase;
+	d_ids.ensure((size_t)n); marks.ensure(nleaf * LEAFG); tally.ensure(DEL_WORDS); lkept.ensure(nleaf); lbase.ensure(nleaf);
+	h->qtab.ensure(1);
+	HIPCHK(hipMemcpyAsync(d_ids.p, ids, (size_t)n * 8, hipMemcpyHostToDevice, st));
+	HIPCHK(hipMemsetAsync(marks.p, 0, nleaf * LEAFG * 8, st));
+	HIPCHK(hipMemsetAsync(tally.p, 0, DEL_WORDS * 8, st));
+	const PoolView src = h->pool[h->pside].view();
+	hipLaunchKernelGGL(k_qtab, dim3(1), dim3(64), 0, st, (const Ctl*)h->ctl, h->side, src, h->qtab.p);
+	for (int64_t i0 = 0; i0 < n; i0 += CH)
+		hipLaunchKernelGGL(k_del_mark, dim3(cdiv((uint64_t)std::min(CH, n - i0), QPB)), dim3(256), 0, st, (const QTab*)h->qtab.p, src, (const int64_t*)d_ids.p + i0, (uint64_t)std::min(CH, n - i0),
+				marks.p, tally.p + DEL_BAD);
+	phase();
+	for (uint64_t l0 = 0; l0 < nleaf; l0 += (uint64_t)CH)
+		hipLaunchKernelGGL(k_del_count, dim3(cdiv(std::min<uint64_t>((uint64_t)CH, nleaf - l0), QPB)), dim3(256), 0, st, (const QTab*)h->qtab.p, src, l0, nleaf,
+				(const unsigned long long*)marks.p, lkept.p, tally.p);
+	unsigned long long t_h[DEL_WORDS];
+	HIPCHK(hipMemcpyAsync(t_h, tally.p, sizeof(t_h), hipMemcpyDeviceToHost, st));
+	HIPCHK(hipGetLastError());
+	HIPCHK(hipStreamSynchronize(st));
+	phase();
+	auto free_all = [&]() { d_ids.release(); marks.release(); tally.release(); lkept.release(); lbase.release(); };
+	if (t_h[DEL_BAD]) { free_all(); rb2_fatal("[rb2_hip] delete_strings: the walk of a string did not end within the rows of the index (the index is no BWT of complete strings)\n"); }
+	uint64_t tot[6][6], removed = 0;
+	memset(tot, 0, sizeof(tot));
+	for (int r = 0; r < NR; ++r) {
+		for (int a = 0; a < 6; ++a) tot[rope_sym(r)][a] += t_h[r * 6 + a];
+		removed += t_h[DEL_REMOVED + r];
+	}
+	RopeDesc rp[NR];
+	LdPieces tab[6];
+	const uint64_t leaf = ld_piece_table(h, "delete_strings", tot, rp, tab);   // (its consistency check: whole strings were removed)
+	DelPieces dp;
+	for (int r = 0; r < NR; ++r) {
+		uint64_t kept = 0;
+		for (int a = 0; a < 6; ++a) kept += t_h[r * 6 + a];
+		if (kept != rp[r].n) { free_all(); rb2_fatal("[rb2_hip] delete_strings: piece %d keeps %llu rows where the other ropes imply %llu (not a BWT of complete strings?)\n", r, (unsigned long long)kept, (unsigned long long)rp[r].n); }
+		dp.leaf0[r] = rp[r].leaf0;
+	}
+	const int ps = h->pside ^ 1;
+	PoolView dst = ld_zero_pool(h, leaf, ps);                  // (drops the sampled suffix array)
+	phase();
+	if (leaf) {
+		hipLaunchKernelGGL(k_del_scan, dim3(NR), dim3(256), 0, st, (const QTab*)h->qtab.p, (const uint32_t*)lkept.p, lbase.p);
+		for (uint64_t l0 = 0; l0 < nleaf; l0 += (uint64_t)CH)
+			hipLaunchKernelGGL(k_del_compact, dim3(cdiv(std::min<uint64_t>((uint64_t)CH, nleaf - l0), QPB)), dim3(256), 0, st, (const QTab*)h->qtab.p, src, l0, nleaf,
+					(const unsigned long long*)marks.p, (const uint64_t*)lbase.p, dp, (unsigned long long*)dst.data);
+		HIPCHK(hipGetLastError());
+	}
+	phase();
+	h->pside = ps; h->pool_compact = false;                    // `side` stays, as in a re-layout: the descriptors are rewritten in place
+	ld_finish(h, rp, leaf, dst, tally.p);
+	phase();
+	if (h->trace) fprintf(stderr, "[rb2_hip] delete_strings: %lld ids, %llu rows: mark %.3f ms, count %.3f, zeroed destination %.3f, scan + compact %.3f, own counts + directory %.3f\n", (long long)n,
+			(unsigned long long)removed, t_ph[1] - t_ph[0], t_ph[2] - t_ph[1], t_ph[3] - t_ph[2], t_ph[4] - t_ph[3], t_ph[5] - t_ph[4]);
+	h->del_stats[0] = (int64_t)removed; h->del_stats[1] = (int64_t)t_h[DEL_GROUPS]; h->del_stats[2] = (int64_t)t_h[DEL_SLOW];
+	h->del_stats[3] = (int64_t)nleaf; h->del_stats[4] = (int64_t)leaf;
+	free_all();
+	return (int64_t)removed;
+}
+
+void rb2_hip_delete_stats(rb2_hip_t *h, int64_t out[5]) { for (int i = 0; i < 5; ++i) out[i] = h->del_stats[i]; }
 
 /* ---- rope sharding across GPUs ------------------------------------------- */
 

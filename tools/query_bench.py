@@ -26,6 +26,13 @@ on the index of the first cases (single strand), overlap_dev on P whole reads of
 one per rank pair -- and records per second, with the fastest and slowest of the three runs) and backward_search_dev on the same reads
 in the same run; then, on an index of both strands, the baseline a user could compose before: every suffix of a read a pattern of its
 own, count(revcomp(suffix) + $) through rb2_hip_backward_search, against rb2_hip_overlap on the same few thousand reads.
+With --delete FRACTION only string deletion is measured and appended to "delete" in the --out file, whose other entries stay: on the
+index of the first cases, rb2_hip_delete_strings of a seeded random FRACTION of the strings -- seconds of the call (host clock: it returns
+when the new index is in place), pool bytes read plus written per second (the leaves read and the leaves written once each, and all the
+traffic of the passes: the planes read twice, the marks, the zeroed destination), and the share of the source groups that took the fast
+path (a shift, no compress).  The same run times what a user could do before: rb2_hip_reset, then one insert of the survivors, whose
+text is put on the device outside the timed region.  In input order (--so 0) the survivors are the same strings and the two indexes are
+compared by their checksums; in the other orders an id is no read number, so the rebuild takes a random subset of the reads of the same size.
 """
 import argparse
 import json
@@ -497,6 +504,54 @@ def kmers_case(a, res):
     g.close()
 
 
+def delete_case(a, res):
+    L = 101
+    n = a.reads or -(-(int(4 * 1024 ** 3 * 0.97) + 1) // (L + 1))
+    nb = n * (L + 1)
+    g = HipBwt(a.so)
+    p = g.dev_alloc(nb)
+    t = time.perf_counter()
+    g.synth_reads(p, 0, n, L, seed=42)
+    g.insert_multi_dev(p, nb)
+    g.sync()
+    build_s = time.perf_counter() - t
+    symbols = int(g.counts().sum())
+    keep = np.random.RandomState(17).rand(n) >= a.delete
+    ids = np.flatnonzero(~keep)
+    t = time.perf_counter()
+    rows = g.delete(ids)
+    sec = time.perf_counter() - t
+    st = g.delete_stats()
+    hashes = g.rope_hashes() if a.so == 0 else None
+    pool = (st["leaves_read"] + st["leaves_written"]) * LEAF_BYTES
+    traffic = st["leaves_read"] * (2 * LEAF_BYTES + 3 * 128 + 12 + 12) + st["leaves_written"] * 2 * LEAF_BYTES   # planes twice, marks zeroed + read twice, kept counts and bases; zeroed + written
+    case = {"fraction": a.delete, "sorting_order": a.so, "reads": n, "symbols": symbols, "build_seconds": build_s, "ids": int(len(ids)), "rows_removed": rows,
+            "seconds": sec, "pool_bytes": pool, "pool_bytes_per_s": pool / sec, "traffic_bytes": traffic, "traffic_bytes_per_s": traffic / sec,
+            "fraction_of_hbm_peak": traffic / sec / HBM_PEAK, "groups": st["groups"], "groups_compressed": st["groups_compressed"],
+            "fast_path_share": 1.0 - st["groups_compressed"] / max(st["groups"], 1), "measured": True}
+    # what a user could do before: reset, insert the survivors again (their text already on the device)
+    host = np.empty(nb, np.uint8)
+    g.synth_reads(p, 0, n, L, seed=42)
+    g.sync()
+    g.L.rb2_hip_memcpy(g.h, host.ctypes.data, p, nb, 1)
+    surv = np.ascontiguousarray(host.reshape(n, L + 1)[keep]).reshape(-1)
+    del host
+    g.L.rb2_hip_memcpy(g.h, p, surv.ctypes.data, len(surv), 0)
+    g.sync()
+    t = time.perf_counter()
+    g.reset()
+    g.insert_multi_dev(p, len(surv))
+    g.sync()
+    alt = time.perf_counter() - t
+    case["rebuild_seconds"] = alt
+    case["rebuild_over_delete"] = alt / sec
+    case["rebuild_same_strings"] = a.so == 0
+    case["rebuild_equals_delete"] = (g.rope_hashes() == hashes) if a.so == 0 else None
+    g.dev_free(p)
+    g.close()
+    res.setdefault("delete", []).append(case)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default="")
@@ -516,7 +571,16 @@ def main():
     ap.add_argument("--approx", action="store_true", help="only the approximate search (added to an existing --out file)")
     ap.add_argument("--approx-queries", type=int, default=1_000_000)
     ap.add_argument("--approx-steps", type=int, default=1 << 16, help="max_steps of the approximate search")
+    ap.add_argument("--delete", type=float, default=0.0, help="only string deletion: delete this fraction of the strings (appended to an existing --out file)")
     a = ap.parse_args()
+    if a.delete > 0:
+        res = {"cases": []}
+        if a.out and os.path.exists(a.out):
+            with open(a.out) as f:
+                res = json.load(f)
+        delete_case(a, res)
+        finish(a, res)
+        return
     if a.approx:
         res = {"cases": []}
         if a.out and os.path.exists(a.out):
