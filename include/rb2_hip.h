@@ -325,6 +325,32 @@ int64_t rb2_hip_approx(rb2_hip_t *h, int64_t n, const uint8_t *qry, const int64_
  * does not see the lengths, so the stacks are sized for 8192 symbols: always 256 MiB once there are more than some 500 queries */
 void    rb2_hip_approx_dev(rb2_hip_t *h, int64_t n, const uint8_t *qry, const int64_t *off, int max_mm, int64_t min_occ, int64_t max_steps, int64_t max_recs, int64_t *rec, int64_t *cnt);
 
+/* ---- duplicate and contained strings: which strings an overlap graph, a unitig builder or a dedup step drops first ----
+ * For string k (ids as in rb2_hip_extract: rows of the `$` block) with text S, |S| >= 1, symbols compared as codes (an N equals only an N):
+ *   occ      occurrences of S as a substring of all indexed strings, itself included: hi - lo of rb2_hip_backward_search on S
+ *   n_equal  strings whose text is exactly S, itself included
+ *   rank     the position of k among those n_equal strings in row order; exactly one string of every class has rank 0 (in input order
+ *            the one with the lowest id)
+ *   flag     bit 0 (1): rank > 0 -- a copy of a string that stands before it; bit 1 (2): occ > n_equal -- S lies inside a longer string,
+ *            or twice inside one.  4: the empty string (every other field 0).  -1: an id outside [0, C[1]).  -2: the walk left the index
+ *            or did not end within N steps (a loaded index that is no BWT of complete strings).  Neither -1 nor -2 is an error, and both
+ *            leave the other fields 0.
+ *   walked   the LF steps taken: |S| whenever flag is 1, 2 or 3, possibly fewer for flag 0
+ * rb2_hip_contained: rec[5*i ..] = flag, occ, n_equal, rank, walked of string ids[i]; ids == NULL means the ids 0 .. n-1 (n = C[1] for the
+ * whole index; a surplus gives flag -1).  Returns the number of records with a flag in 1 .. 4: the strings rb2_hip_delete_strings would
+ * take out to leave every text once and inside no other.  n < 0 is fatal, n == 0 returns 0.
+ * One fused walk per string (k_contain), one string per 16 lanes: the walk of k starts at row k, [lo, hi) = [0, N), ahi = C[1]; a step
+ * reads the symbol c of the row, stops at `$`, and otherwise moves row, lo, hi and ahi each to C[c] + occ(c, .).  After j steps [lo, hi) is
+ * the interval of the last j symbols of S and [lo, ahi) that of those symbols followed by `$` (`$` sorts first), lo <= row < ahi <= hi.  At
+ * the `$`: occ = hi - lo, n_equal = occ($,ahi) - occ($,lo), rank = occ($,row) - occ($,lo).  As soon as hi - lo == 1 after a step the
+ * suffix read so far occurs once, so S does: the walk stops with flag 0, occ = n_equal = 1, rank 0 -- after about log4(N) symbols for a
+ * string that is no copy and lies in no other.  RB2_CONTAIN_EARLY=0 in the environment, read on every call, turns that exit off (tests).
+ * Like every query the call reads the index and nothing else (the layout and a sampled suffix array stay as they are), waits for a lazy
+ * insert and is fatal on one rank of a sharded index; the host variant stages chunks of at most 2^24 ids (RB2_QUERY_CHUNK lowers it). */
+int64_t rb2_hip_contained(rb2_hip_t *h, int64_t n, const int64_t *ids, int64_t *rec);
+/* the same with ids (or NULL) and rec in this device's memory, asynchronous on the handle's stream (no return value: read the flags) */
+void    rb2_hip_contained_dev(rb2_hip_t *h, int64_t n, const int64_t *ids, int64_t *rec);
+
 /* 64-bit checksum of rope b computed on the device (position-weighted sum over the packed words of its pieces): equal for
  * equal symbol sequences however the index was built (one engine, N ranks, an .fmr loaded back), sensitive to order.  Lets
  * tests compare indexes of 10^11 symbols without moving them off the device (the reference has no counterpart; its ropes are

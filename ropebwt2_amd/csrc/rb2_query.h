@@ -595,4 +595,71 @@ template <bool SPARSE> __global__ __launch_bounds__(256) void k_approx(const QTa
 	}
 }
 
+// ---- duplicate and contained strings ----
+// The walk of string k (row = k, then LF steps to the first `$`) visits the rows of its own suffixes.  Next to the row it carries, for the
+// suffix of the j symbols read so far, lo and hi -- [lo, hi) is the interval of that suffix -- and ahi: [lo, ahi) is the interval of the
+// suffix followed by `$` (`$` sorts first, so the two share their lower end); all four move to C[c] + occ(c, .) with the symbol c of the
+// row, and lo <= row < ahi <= hi holds throughout.  At the `$` the suffix is the whole text S of the string: occ = hi - lo occurrences of S
+// in all strings, n_equal = occ($, ahi) - occ($, lo) strings whose text is S, rank = occ($, row) - occ($, lo) of them in front of string k.
+
+// occ(c, x), and *z = occ($, x) if asked: the column of the step out of the six counts of a rank (selects: QPair::at)
+template <bool SPARSE> __device__ __forceinline__ uint64_t qocc(const QTab &T, const PoolView &pv, uint64_t x, int c, uint64_t *z = nullptr)
+{
+	uint64_t v[6];
+	qrank<SPARSE>(T, pv, x, v);
+	if (z) *z = v[0];
+	return QPair<SPARSE>::at(v, c);
+}
+
+// rec[5i ..] = flag, occ, n_equal, rank, walked (include/rb2_hip.h) of string ids[i], or of string id0 + i when ids is NULL; one string
+// per DPP row.  early: stop with (0, 1, 1, 0, steps) as soon as hi - lo == 1 -- the suffix occurs once, so the string does.  Once
+// ahi - lo == 1 the interval [lo, ahi) is the row itself and stays so: ahi is no longer ranked.  The guard is that of k_ssa_build: the
+// steps are counted against N and a row is tested against N before it is ranked, so on an index that is no BWT of complete strings a walk
+// ends with flag -2 and no row outside the index is read (lo, hi and ahi never exceed N: qrank takes x <= N).
+// Left alone the compiler takes 100 VGPRs for the sparse layout (4 waves per SIMD) and 92 for the dense one; held to 5 waves, as k_smem is,
+// it needs 91 and 92 and no scratch.
+template <bool SPARSE> __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(5, 5))) void k_contain(const QTab *Tg, PoolView pv, const int64_t *ids, int64_t id0, uint64_t n, int early, int64_t *rec)
+{
+	__shared__ QTab T;
+	qtab_load(Tg, T);
+	const QRow R = qrow();
+	if (R.i >= n) return;
+	const uint64_t N = T.row0[NR], nstr = qC(T, 1);
+	const int64_t k = ids ? ids[R.i] : id0 + (int64_t)R.i;
+	int64_t flag = 0;
+	uint64_t occ = 0, neq = 0, rank = 0, j = 0;
+	if (k < 0 || (uint64_t)k >= nstr) flag = -1;
+	else {
+		uint64_t row = (uint64_t)k, lo = 0, hi = N, ahi = nstr;
+		for (;;) {
+			uint64_t cr[6];
+			uint32_t c;
+			qrank<SPARSE>(T, pv, row, cr, &c);
+			if (c == 0) {                                          // the string's own `$`: [lo, hi) is the interval of its text
+				if (j == 0) { flag = 4; break; }
+				occ = hi - lo; neq = 1;
+				if (ahi - lo != 1) {
+					uint64_t zl, zh;
+					qocc<SPARSE>(T, pv, lo, 0, &zl); qocc<SPARSE>(T, pv, ahi, 0, &zh);
+					neq = zh - zl; rank = cr[0] - zl;
+				}
+				flag = (rank != 0 ? 1 : 0) | ((int64_t)occ > (int64_t)neq ? 2 : 0);
+				break;
+			}
+			if (j >= N) { flag = -2; break; }
+			const uint64_t C = qC(T, (int)c);
+			const bool one = ahi - lo == 1;
+			row = C + QPair<SPARSE>::at(cr, (int)c);
+			lo = C + qocc<SPARSE>(T, pv, lo, (int)c);
+			hi = C + qocc<SPARSE>(T, pv, hi, (int)c);
+			ahi = one ? min(lo + 1, N) : C + qocc<SPARSE>(T, pv, ahi, (int)c);
+			++j;
+			if (row >= N) { flag = -2; break; }
+			if (early && hi - lo == 1) { occ = neq = 1; break; }
+		}
+		if (flag < 0 || flag == 4) occ = neq = rank = j = 0;
+	}
+	qstore(rec, R.i, 1, 0, R.g, flag, occ, neq, rank, j);
+}
+
 } // namespace rb2

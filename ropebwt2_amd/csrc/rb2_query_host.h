@@ -45,10 +45,12 @@ static void dev_chunks(int64_t n, F launch)
 	for (int64_t i0 = 0; i0 < n; i0 += CH) launch(i0, std::min(CH, n - i0));
 }
 
-/* the inputs of a host variant, in host memory: n packed strings (w == 0: bytes, and v = their n + 1 offsets) or n tuples of w int64 (v) */
+/* the inputs of a host variant, in host memory: n packed strings (w == 0: bytes, and v = their n + 1 offsets) or n tuples of w int64 (v;
+ * NULL: the items are their own numbers and nothing is copied) */
 struct QInput { const uint8_t *bytes; const int64_t *v; int w; };
 /* a chunk of them on the device: v as it was cut from the host's (offsets still count from the first byte of the whole input, base of them
- * in front of bytes), and tail, room behind v for what the kernel writes per item beside its records */
+ * in front of bytes; tuples: base = the number of the chunk's first item, v = NULL when the host gave none), and tail, room behind v for
+ * what the kernel writes per item beside its records */
 struct QStaged { const uint8_t *bytes; const int64_t *v; int64_t base; int64_t *tail; };
 
 static void check_offsets(const char *who, const char *what, int64_t n, const int64_t *off)
@@ -61,16 +63,16 @@ static void check_offsets(const char *who, const char *what, int64_t n, const in
 static QStaged stage_inputs(rb2_hip_t *h, const QInput &in, int64_t i0, int64_t nc, int64_t tail)
 {
 	const int64_t nw = in.w ? nc * in.w : nc + 1, first = in.w ? i0 * in.w : i0;
-	int64_t base = 0;
+	int64_t base = in.w ? i0 : 0;
 	h->qin.ensure((size_t)(nw + tail));
-	HIPCHK(hipMemcpyAsync(h->qin.p, in.v + first, (size_t)nw * 8, hipMemcpyHostToDevice, h->st));
+	if (in.v) HIPCHK(hipMemcpyAsync(h->qin.p, in.v + first, (size_t)nw * 8, hipMemcpyHostToDevice, h->st));
 	if (!in.w) {
 		base = in.v[i0];
 		const int64_t nb = in.v[i0 + nc] - base;
 		h->qbytes.ensure((size_t)std::max<int64_t>(nb, 1));
 		if (nb) HIPCHK(hipMemcpyAsync(h->qbytes.p, in.bytes + base, (size_t)nb, hipMemcpyHostToDevice, h->st));
 	}
-	return {h->qbytes.p, h->qin.p, base, h->qin.p + nw};
+	return {h->qbytes.p, in.v ? h->qin.p : nullptr, base, h->qin.p + nw};
 }
 
 /* the host variants with one fixed result of words int64 per item: launch(nc, staged inputs, results) per chunk, one synchronise each */
@@ -474,4 +476,39 @@ void rb2_hip_approx_dev(rb2_hip_t *h, int64_t n, const uint8_t *qry, const int64
 	approx_check("approx_dev", max_mm, min_occ, max_steps, max_recs);
 	dev_chunks(n, [&](int64_t i0, int64_t nc) {
 		launch_approx(h, nc, qry, off + i0, 0, APPROX_MAX_LEN, max_mm, min_occ, max_steps, max_recs, rec + i0 * max_recs * 4, cnt + i0); });
+}
+
+/* ---- duplicate and contained strings: one fused LF walk per string (k_contain) ---- */
+
+/* RB2_CONTAIN_EARLY=0 in the environment, read on every call, makes every walk run to its `$` (tests, and the bench's comparison) */
+static int contain_early()
+{
+	const char *e = getenv("RB2_CONTAIN_EARLY");
+	return !(e && strcmp(e, "0") == 0);
+}
+
+/* n strings: ids (device memory) or, when ids is NULL, id0 .. id0 + n - 1 */
+static void launch_contain(rb2_hip_t *h, int64_t n, const int64_t *ids, int64_t id0, int early, int64_t *rec)
+{
+	qlaunch(h, k_contain<true>, k_contain<false>, (uint64_t)n, ids, id0, n, early, rec);
+}
+
+int64_t rb2_hip_contained(rb2_hip_t *h, int64_t n, const int64_t *ids, int64_t *rec)
+{
+	query_begin(h, "rb2_hip_contained");
+	if (n < 0) { rb2_fatal("[rb2_hip] rb2_hip_contained: the number of ids must not be negative (got %lld)\n", (long long)n); }
+	if (n == 0) return 0;
+	const int early = contain_early();
+	staged_results(h, n, {nullptr, ids, 1}, 5, rec, [&](int64_t nc, const QStaged &s, int64_t *d_rec) { launch_contain(h, nc, s.v, s.base, early, d_rec); });
+	int64_t flagged = 0;
+	for (int64_t i = 0; i < n; ++i) flagged += rec[5 * i] >= 1 && rec[5 * i] <= 4;
+	return flagged;
+}
+
+void rb2_hip_contained_dev(rb2_hip_t *h, int64_t n, const int64_t *ids, int64_t *rec)
+{
+	query_begin(h, "rb2_hip_contained_dev");
+	if (n < 0) { rb2_fatal("[rb2_hip] rb2_hip_contained_dev: the number of ids must not be negative (got %lld)\n", (long long)n); }
+	const int early = contain_early();
+	dev_chunks(n, [&](int64_t i0, int64_t nc) { launch_contain(h, nc, ids ? ids + i0 : nullptr, i0, early, rec + 5 * i0); });
 }

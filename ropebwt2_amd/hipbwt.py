@@ -68,6 +68,8 @@ def load_hip_lib():
         "rb2_hip_kmers": (i64, [vp, i32, i64, i32, i64, vp, i64, vp, vp]),
         "rb2_hip_approx": (i64, [vp, i64, vp, vp, i32, i64, i64, i64, vp, vp]),
         "rb2_hip_approx_dev": (None, [vp, i64, vp, vp, i32, i64, i64, i64, vp, vp]),
+        "rb2_hip_contained": (i64, [vp, i64, vp, vp]),
+        "rb2_hip_contained_dev": (None, [vp, i64, vp, vp]),
         "rb2_hip_reserve": (None, [vp, i64, i64, i64]),
         "rb2_hip_num_subropes": (i32, []),
         "rb2_hip_memcpy": (None, [vp, vp, vp, i64, i32]),
@@ -135,7 +137,7 @@ ABI_SYMBOLS = [
     "rb2_hip_backward_search", "rb2_hip_backward_search_dev", "rb2_hip_extend", "rb2_hip_extract", "rb2_hip_smem", "rb2_hip_smem_dev", "rb2_hip_dev_alloc",
     "rb2_hip_ssa_build", "rb2_hip_ssa_drop", "rb2_hip_ssa_info", "rb2_hip_locate", "rb2_hip_locate_dev",
     "rb2_hip_overlap", "rb2_hip_overlap_dev", "rb2_hip_string_ids", "rb2_hip_string_ids_dev", "rb2_hip_kmers",
-    "rb2_hip_approx", "rb2_hip_approx_dev",
+    "rb2_hip_approx", "rb2_hip_approx_dev", "rb2_hip_contained", "rb2_hip_contained_dev",
     "rb2_hip_num_subropes", "rb2_hip_memcpy", "rb2_hip_use_stream",
     "rb2_hip_dev_free", "rb2_hip_synth_reads", "rb2_hip_synth_reads_cov", "rb2_hip_synth_reads_skew", "rb2_hip_sync", "rb2_hip_sparse_stats", "rb2_hip_layout_stats", "rb2_hip_rewind_stats", "rb2_hip_window_stats", "rb2_hip_host_register", "rb2_hip_host_unregister", "rb2_hip_profile",
     "rb2_hip_profile_get", "rb2_hip_kernel_name", "rb2_hip_layout",
@@ -590,6 +592,53 @@ class HipBwt:
     def approx_dev(self, n, qry_dev, off_dev, rec_dev, cnt_dev, max_mm, min_occ=1, max_steps=1 << 16, max_recs=64):
         """rb2_hip_approx_dev: all four pointers in this device's memory; asynchronous on the handle's stream"""
         self.L.rb2_hip_approx_dev(self.h, n, qry_dev, off_dev, int(max_mm), min_occ, max_steps, max_recs, rec_dev, cnt_dev)
+
+    # -- duplicate and contained strings (include/rb2_hip.h) -------------------------------------------------------------------------
+    def contained_raw(self, ids=None):
+        """rb2_hip_contained as it is: an (n, 5) int64 array, rows = flag, occ, n_equal, rank, walked of the strings ids (any integer
+        sequence or array; None: every string of the index).  flag: bit 0 a copy of a string before it, bit 1 inside another string,
+        4 an empty string, -1 an id that is no string, -2 a walk that did not end"""
+        if ids is None:
+            n, p = int(self.counts()[:, 0].sum()), None
+        else:
+            ids = np.ascontiguousarray(np.asarray(ids, dtype=np.int64).reshape(-1))
+            n, p = len(ids), ids.ctypes.data
+        rec = np.zeros((n, 5), np.int64)
+        if n:
+            self.L.rb2_hip_contained(self.h, n, p, rec.ctypes.data)
+        return rec
+
+    def contained_dev(self, n, ids_dev, rec_dev):
+        """rb2_hip_contained_dev: ids_dev (None or 0: the ids 0 .. n-1) and rec_dev (5 n int64) in this device's memory; asynchronous on
+        the handle's stream"""
+        self.L.rb2_hip_contained_dev(self.h, n, ids_dev or None, rec_dev)
+
+    def contained(self, ids=None):
+        """the flags of contained_raw alone: 0 for a string that is the first of its text and lies inside no other"""
+        return self.contained_raw(ids)[:, 0].copy()
+
+    def reduce(self, duplicates=True, contained=True, empty=True, pairs=False):
+        """delete the copies (flag bit 0), the strings that lie inside another (bit 1) and the empty strings, as chosen, and return their
+        old ids, sorted: contained_raw() followed by delete().  pairs: the index holds both strands, strings 2i and 2i+1 a read and its
+        reverse complement, and a pair goes only when both its members are selected (a palindromic read and its copy stay together);
+        an odd number of strings raises ValueError"""
+        flag = self.contained_raw()[:, 0]
+        sel = np.zeros(len(flag), bool)
+        live = (flag >= 1) & (flag <= 3)
+        if duplicates:
+            sel |= live & ((flag & 1) != 0)
+        if contained:
+            sel |= live & ((flag & 2) != 0)
+        if empty:
+            sel |= flag == 4
+        if pairs:
+            if len(flag) % 2:
+                raise ValueError("reduce(pairs=True): %d strings are no pairs of strands" % len(flag))
+            sel = np.repeat(sel[0::2] & sel[1::2], 2)
+        ids = np.flatnonzero(sel).astype(np.int64)
+        if len(ids):
+            self.delete(ids)
+        return ids
 
     # -- measurement helpers ----------------------------------------------------------------
     def dev_alloc(self, nbytes):

@@ -33,6 +33,12 @@ traffic of the passes: the planes read twice, the marks, the zeroed destination)
 path (a shift, no compress).  The same run times what a user could do before: rb2_hip_reset, then one insert of the survivors, whose
 text is put on the device outside the timed region.  In input order (--so 0) the survivors are the same strings and the two indexes are
 compared by their checksums; in the other orders an id is no read number, so the rebuild takes a random subset of the reads of the same size.
+With --contained only the duplicate / containment query is measured and appended to "contained" in the --out file, whose other entries
+stay: contained_dev over every string of the default index (unique reads) and of an index of reads drawn from one genome at 30x (equal
+start positions give real copies), with the early exit and with RB2_CONTAIN_EARLY=0 -- strings and LF steps per second, the mean steps
+per string and the share of every flag.  On a sample of the strings the same run times rb2_hip_contained through host buffers against what
+a user could compose before, rb2_hip_extract of the sample followed by rb2_hip_backward_search of the extracted strings, and compares
+the occurrences the two report.
 """
 import argparse
 import json
@@ -552,6 +558,66 @@ def delete_case(a, res):
     res.setdefault("delete", []).append(case)
 
 
+def contained_case(a, res):
+    L = 101
+    n = a.reads or -(-(int(4 * 1024 ** 3 * 0.97) + 1) // (L + 1))
+    nb = n * (L + 1)
+    for name, glen in (("default: unique reads", 0), ("reads of one genome at 30x", n * L // 30)):
+        g = HipBwt(a.so)
+        p = g.dev_alloc(nb)
+        t = time.perf_counter()
+        g.synth_reads(p, 0, n, L, seed=42, genome_len=glen)
+        g.insert_multi_dev(p, nb)
+        g.sync()
+        build_s = time.perf_counter() - t
+        g.dev_free(p)
+        case = {"index": name, "reads": n, "read_len": L, "genome_len": glen, "sorting_order": a.so, "symbols": int(g.counts().sum()), "build_seconds": build_s,
+                "layout": g.layout_stats(), "runs": [], "measured": True}
+        print("contained: %s built in %.1f s" % (name, build_s), file=sys.stderr, flush=True)
+        d_rec = g.dev_alloc(40 * n)
+        rec = np.zeros((n, 5), np.int64)
+        full_occ = None
+        for early in (1, 0):
+            os.environ["RB2_CONTAIN_EARLY"] = str(early)
+            sec = timed(lambda: g.contained_dev(n, None, d_rec), g.sync, reps=3 if early else 1)
+            g.L.rb2_hip_memcpy(g.h, rec.ctypes.data, d_rec, rec.nbytes, 1)
+            steps = int(rec[:, 4].sum())
+            share = np.bincount(np.clip(rec[:, 0], -2, 4) + 2, minlength=7) / n
+            case["runs"].append({"early_exit": bool(early), "seconds": sec, "strings_per_s": n / sec, "lf_steps": steps, "lf_steps_per_s": steps / sec,
+                                 "ranks_per_s_at_most": 4 * steps / sec, "mean_walked": steps / n,
+                                 "flag_share": {str(f): float(share[f + 2]) for f in (0, 1, 2, 3, 4, -1, -2)}})
+            print("contained: early exit %d: %.3f s" % (early, sec), file=sys.stderr, flush=True)
+            if not early:
+                full_occ = rec[:, 1].copy()
+        g.dev_free(d_rec)
+        os.environ.pop("RB2_CONTAIN_EARLY", None)
+        # the composition the call replaces, through the host, on a sample: extract, then backward_search of what came out
+        m = min(a.contained_sample, n)
+        ids = np.sort(np.random.RandomState(5).choice(n, size=m, replace=False)).astype(np.int64)
+        out3 = np.zeros((m, 3), np.int64)
+
+        def composed():
+            _, txt, ln = g.extract_raw(ids, L)
+            off = np.concatenate([[0], np.cumsum(ln)]).astype(np.int64)
+            flat = np.ascontiguousarray(txt.reshape(-1)) if (ln == L).all() else np.ascontiguousarray(np.concatenate([txt[i, :ln[i]] for i in range(m)]))
+            g.L.rb2_hip_backward_search(g.h, m, flat.ctypes.data, off.ctypes.data, out3.ctypes.data)
+        csec = timed(composed, lambda: None)
+        got = {}
+
+        def fused():
+            got["rec"] = g.contained_raw(ids)
+        fsec = timed(fused, lambda: None)
+        os.environ["RB2_CONTAIN_EARLY"] = "0"
+        fsec0 = timed(fused, lambda: None)
+        os.environ.pop("RB2_CONTAIN_EARLY", None)
+        case["sample"] = {"strings": m, "composed_extract_then_backward_search_seconds": csec, "contained_host_seconds": fsec,
+                          "contained_host_seconds_no_early_exit": fsec0, "composed_over_fused": csec / fsec, "composed_over_fused_no_early_exit": csec / fsec0,
+                          "equals_fused": bool(np.array_equal(out3[:, 1] - out3[:, 0], full_occ[ids]) and np.array_equal(got["rec"][:, 1], full_occ[ids])),
+                          "note": "the composition yields occ alone; n_equal and rank would take an overlap call more"}
+        g.close()
+        res.setdefault("contained", []).append(case)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default="")
@@ -572,7 +638,17 @@ def main():
     ap.add_argument("--approx-queries", type=int, default=1_000_000)
     ap.add_argument("--approx-steps", type=int, default=1 << 16, help="max_steps of the approximate search")
     ap.add_argument("--delete", type=float, default=0.0, help="only string deletion: delete this fraction of the strings (appended to an existing --out file)")
+    ap.add_argument("--contained", action="store_true", help="only the duplicate / containment query (appended to an existing --out file)")
+    ap.add_argument("--contained-sample", type=int, default=1_000_000, help="strings of the sample the composition extract + backward_search is timed on")
     a = ap.parse_args()
+    if a.contained:
+        res = {"cases": []}
+        if a.out and os.path.exists(a.out):
+            with open(a.out) as f:
+                res = json.load(f)
+        contained_case(a, res)
+        finish(a, res)
+        return
     if a.delete > 0:
         res = {"cases": []}
         if a.out and os.path.exists(a.out):
