@@ -351,6 +351,47 @@ int64_t rb2_hip_contained(rb2_hip_t *h, int64_t n, const int64_t *ids, int64_t *
 /* the same with ids (or NULL) and rec in this device's memory, asynchronous on the handle's stream (no return value: read the flags) */
 void    rb2_hip_contained_dev(rb2_hip_t *h, int64_t n, const int64_t *ids, int64_t *rec);
 
+/* ---- irreducible overlaps: the edges of a string graph, transitive reduction included ----
+ * n queries as for rb2_hip_approx (nt6 codes 1..5 in text order, concatenated in qry[off[i] .. off[i+1]); 0, a code above 5 or a length above
+ * 8192 makes the query malformed).  A candidate of a query q of L symbols is (T, l, X): T a string of the index, min_ovlp <= l < L,
+ * T[:l] == q[L-l:] with no N in it (as in rb2_hip_overlap the search stops at the first N from the end), X = T[l:] with 1 <= |X| <= max_ext
+ * and only A C G T in it.  l == L is no candidate, nor is a string that is a proper suffix of q (|X| = 0).  A candidate (T, l, X) is
+ * reducible when another candidate (U, l', X') has X' a proper prefix of X, or X' == X and l' > l: q reaches T through U.  Every other
+ * candidate is irreducible, and there is one record per distinct (l, X) among those: rec[(i*max_recs + k)*4 ..] = l, ext, zlo, zhi with
+ * ext = |X|.  [zlo, zhi) is a range of `$` ranks for rb2_hip_string_ids, and THE STRINGS IT NAMES ARE THE REVERSE COMPLEMENTS revcomp(T)
+ * OF THE NEIGHBOURS, NOT THE NEIGHBOURS T THEMSELVES: the extension runs over the twin interval, the interval of the reverse complement,
+ * and that is what it yields.  On an index of both strands there are exactly zhi - zlo strings T (where a read and its reverse complement
+ * are the strings 2i and 2i + 1, T = id ^ 1).  The order of a query's records is unspecified.
+ * cnt[i] >= 0: the records found, which may exceed max_recs: exactly max_recs are stored then, every one a true record, none twice.  0 for
+ * the empty query, -1 for a malformed one.  cnt[i] <= -2: the query used up max_steps -- a step is one pair of ranks -- with -2 - cnt[i]
+ * records found by then and min(-2 - cnt[i], max_recs) of them stored, every one true, none twice: the convention of rb2_hip_approx.
+ * Only the records stored are meaningful: the host variant returns the others as zeros, the device variant leaves them untouched.
+ * Returns the number of records stored.  Fatal: min_ovlp, max_steps or max_recs below 1; max_ext outside 1 .. 8192 (n <= 0 returns first).
+ * The arithmetic (k_irreducible, one query per 16 lanes; it is the same on any BWT, and on an index of one strand the records are
+ * whatever it gives: the call returns and stays in bounds):
+ *   1. the backward search of rb2_hip_overlap, carrying the bi-interval: (x0, x1, size) = (C[c], C[comp c], C[c+1] - C[c]) for the last
+ *      symbol c.  The turn of the last m symbols takes the ranks at x0 and x0 + size; with nd the `$`s between them, min_ovlp <= m < L and
+ *      nd > 0 add the entry (m, lo = x1, hi = x1 + nd), the interval of revcomp(q[L-m:]) followed by `$`; then the step by q[L-1-m] moves
+ *      x0 and size as a backward search does and x1 as rb2_hip_extend does, in the complement order $ T G C A N.  The search ends behind
+ *      the turn of m == L, at an N, or when the interval empties: at most L steps.
+ *   2. depth first over the extensions: a node is a depth d and a list of entries (l, lo, hi); the root is the list of 1.  Visiting a
+ *      node takes the ranks cl, ch at lo, hi of every entry, one step each.  If d >= 1 and some entry has ch[$] > cl[$], the record
+ *      (l, d, cl[$], ch[$]) of the one with the largest l among those is reported and the node is closed.  Otherwise, if d < max_ext, its
+ *      child for a = A, C, G, T in that order is the list of the non-empty (l, C[a] + cl[a], C[a] + ch[a]): the extension by comp(a).
+ *   3. before every step, a query that has taken max_steps ends over budget.
+ * The stacks live in device memory: 66 bytes per entry, min((Lmax - min_ovlp) * (max_ext + 1), max_steps) entries per row of the launch,
+ * 256 MiB at the most for all rows (RB2_IRRED_SCRATCH in the environment, read on every call, lowers that; a single row may be larger
+ * alone; rows take further queries a launch apart, and the results depend on none of this).  Lmax is the longest query of the call.  The
+ * host variant stages chunks whose records (chunk * max_recs * 32 bytes) stay under 256 MiB, one query at the least.
+ * Like every query the call waits for a lazy insert, reads the index and nothing else (a sampled suffix array stays valid, and none is
+ * needed), and is fatal on one rank of a sharded index. */
+int64_t rb2_hip_irreducible(rb2_hip_t *h, int64_t n, const uint8_t *qry, const int64_t *off, int64_t min_ovlp, int64_t max_ext, int64_t max_steps, int64_t max_recs,
+                            int64_t *rec, int64_t *cnt);
+/* the same with qry, off, rec and cnt in this device's memory, asynchronous on the handle's stream (no return value: read cnt).  The host
+ * does not see the lengths: the stacks are sized for max_len symbols (1 .. 8192, anything else is fatal), and a longer query is malformed */
+void    rb2_hip_irreducible_dev(rb2_hip_t *h, int64_t n, const uint8_t *qry, const int64_t *off, int64_t max_len, int64_t min_ovlp, int64_t max_ext, int64_t max_steps,
+                                int64_t max_recs, int64_t *rec, int64_t *cnt);
+
 /* 64-bit checksum of rope b computed on the device (position-weighted sum over the packed words of its pieces): equal for
  * equal symbol sequences however the index was built (one engine, N ranks, an .fmr loaded back), sensitive to order.  Lets
  * tests compare indexes of 10^11 symbols without moving them off the device (the reference has no counterpart; its ropes are

@@ -239,7 +239,7 @@ struct rb2_hip_s {
 	DevBuf<uint64_t> qbuf;              // rank queries and their answers
 	DevBuf<QTab> qtab;                  // FM-index queries (rb2_query.h): the piece table of the launch ...
 	DevBuf<uint8_t> qbytes; DevBuf<int64_t> qin, qout;   // ... and the staging buffers of the host variants
-	DevBuf<uint8_t> qscr;                // ... and the stacks of k_approx's rows
+	DevBuf<uint8_t> qscr;                // ... and the stacks of k_approx's and k_irreducible's rows
 	// sampled suffix array (rb2_hip_ssa_build): it describes the rows as they were when it was built (index_rows_change)
 	DevBuf<uint64_t> ssa_smp, ssa_len, ssa_head;   // (string, step) of every row x with x % 2^ssa_s == 0; length of every string; string of the q-th whole-string row
 	bool ssa_valid = false; int ssa_s = 0; int64_t ssa_n = 0; uint64_t ssa_nstr = 0;   // ssa_n samples, ssa_nstr strings

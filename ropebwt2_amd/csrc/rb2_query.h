@@ -662,4 +662,122 @@ template <bool SPARSE> __global__ __launch_bounds__(256) __attribute__((amdgpu_w
 	qstore(rec, R.i, 1, 0, R.g, flag, occ, neq, rank, j);
 }
 
+// ---- irreducible overlaps: the edges of a string graph ----
+// The backward search of k_overlap, carrying the bi-interval (x0, x1, sz) as k_smem does: when nd strings begin with the last m symbols
+// of the query, [x1, x1 + nd) is the interval of revcomp(those symbols) followed by `$` on an index of both strands (`$` sorts first) --
+// an ENTRY (m, lo, hi).  Extending an entry to the left by a is extending the overlap to the right by comp(a), and a `$` in front of it
+// (occ($, hi) > occ($, lo)) is a string revcomp(T) that ends there: T = the overlap followed by the extension.  All entries of a query
+// are extended together, depth first: a node is the list of entries still alive after d symbols; one pair of ranks per entry gives its
+// `$` range and its four children.  The first node of a branch where a string ends is closed with one record -- that of its entry with
+// the longest overlap --: what is still alive there is reached through that string.
+//
+// One query per DPP row, control uniform within the row; a row takes the queries i = row, row + rows, ...  The stack is the path, in the
+// row's part of scr (irred_row_bytes(cap, max_ext) bytes), the frames of its nodes behind each other; entry e is written when it is ranked:
+//   kid[8 e + 2 (a - 1) ..] = lo, hi of child a of entry e    (lanes 0 .. 7 store one word each: one 64-byte line)      el[e] = its overlap length
+//   fs[d], fa[d]              the first entry of frame d and the next child to try there, kept while frame d + 1 is the top one
+// so that coming back to a node costs loads and no rank.  kid is written by eight lanes and read by all sixteen: the vector memory
+// operations of one wave are performed in order, the fences keep the compiler from moving them.  el, fs and fa are written by every lane
+// with the same value, each lane reads its own.  The entries of the root are ranked as the search finds them, not behind it: the steps are
+// the same, and a query that runs out of them in either has no record yet.
+// Every pair of ranks is a step, and every entry written has cost one: at max_steps the query ends with cnt = -2 - (records so far).  The
+// frames 0 .. max_ext hold at most L - min_ovlp entries each, so e < cap = irred_entry_cap() whatever the index holds (tested all the same).
+// rec[(i * max_recs + k) * 4 ..] = l, ext, zlo, zhi for k < max_recs, by lanes 0 .. 3; cnt[i] as in include/rb2_hip.h.
+
+// ranks the entry (l, [lo, hi)) and writes it as entry e of the stack; zlo, zhi = the `$`s in front of its two ends
+template <bool SPARSE> __device__ __forceinline__ void irred_rank(const QTab &T, const PoolView &pv, uint64_t lo, uint64_t hi, uint64_t *kid, uint16_t *el, int64_t e, uint32_t l,
+                                                                  uint32_t g, uint64_t &zlo, uint64_t &zhi)
+{
+	const QPair<SPARSE> P(T, pv, lo, hi);
+	uint64_t klo[4], khi[4], v = 0;
+#pragma unroll
+	for (int a = 1; a <= 4; ++a) P.child(T, a, klo[a - 1], khi[a - 1]);
+#pragma unroll
+	for (int w = 0; w < 8; ++w) if (g == (uint32_t)w) v = w & 1 ? khi[w >> 1] : klo[w >> 1];
+	if (g < 8) kid[8 * e + g] = v;
+	el[e] = (uint16_t)l;
+	__builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+	zlo = P.cl[0]; zhi = P.ch[0];
+}
+
+template <bool SPARSE> __global__ __launch_bounds__(256) void k_irreducible(const QTab *Tg, PoolView pv, const uint8_t *qry, const int64_t *off, int64_t base, uint64_t n,
+                                                                            int64_t min_ovlp, int64_t max_ext, int64_t max_steps, int64_t max_recs, int64_t lmax,
+                                                                            uint64_t rows, int64_t cap, uint8_t *scr, int64_t *rec, int64_t *cnt)
+{
+	__shared__ QTab T;
+	qtab_load(Tg, T);
+	const QRow R = qrow();
+	if (R.i >= rows) return;
+	const uint64_t N = T.row0[NR];
+	const int64_t nf = irred_frames(cap, max_ext);
+	uint64_t *kid = (uint64_t*)(scr + R.i * (uint64_t)irred_row_bytes(cap, max_ext));
+	uint32_t *fs = (uint32_t*)(kid + 8 * cap);
+	uint16_t *el = (uint16_t*)((uint8_t*)fs + irred_pad(4 * nf));
+	uint8_t *fa = (uint8_t*)el + irred_pad(2 * cap);
+	for (uint64_t i = R.i; i < n; i += rows) {
+		const int64_t L = off[i + 1] - off[i];
+		const QSlice S = qslice<false>(qry, off, base, i, L > min(lmax, IRRED_MAX_LEN));   // (longer than the host sized the stacks for: malformed, and not read)
+		if (S.bad || L == 0) { if (R.g == 0) cnt[i] = S.bad ? -1 : 0; continue; }
+		int64_t steps = 0, k = 0, top = 0;                         // top: the entries on the stack
+		bool over = false;
+		const int c0 = S.q[L - 1];
+		if (c0 < 5) {                                              // the search: the turn of m ranks the interval of the last m symbols
+			uint64_t x0 = qC(T, c0), x1 = qC(T, 5 - c0), sz = qC(T, c0 + 1) - x0;
+			for (int64_t m = 1; sz > 0; ++m) {
+				if (steps >= max_steps) { over = true; break; }
+				++steps;
+				const int c = m < L ? S.q[L - 1 - m] : 5;
+				uint64_t nd, add, nx0 = 0, nx1 = 0;
+				{
+					const QPair<SPARSE> P(T, pv, x0, x0 + sz);
+					add = nd = P.size(0);                          // the other end in the complement order $ T G C A N
+#pragma unroll
+					for (int b = 4; b >= 2; --b) if (b > c) add += P.size(b);
+					if (c < 5) P.child(T, c, nx0, nx1);
+				}
+				if (m >= min_ovlp && m < L && nd > 0) {            // an entry of the root
+					if (steps >= max_steps || top >= cap) { over = true; break; }
+					++steps;
+					uint64_t zl, zh;
+					irred_rank<SPARSE>(T, pv, min(x1, N), min(x1 + nd, N), kid, el, top, (uint32_t)m, R.g, zl, zh);   // (one strand: the twin interval may leave the index)
+					++top;
+				}
+				if (c == 5) break;                                 // the whole query, or an N
+				x1 += add; x0 = nx0; sz = nx1 - nx0;
+			}
+		}
+		if (!over && top > 0) {
+			int64_t d = 0, f0 = 0;                                 // the top frame: the node at depth d, entries [f0, top)
+			int a = 1;                                             // its next child
+			for (;;) {
+				if (a > 4) {                                       // no child left: back to the frame below
+					if (d == 0) break;
+					top = f0; --d;
+					f0 = (int64_t)fs[d]; a = fa[d];
+					continue;
+				}
+				int64_t nt = top;                                  // child a, the node at depth d + 1: its entries [top, nt)
+				uint32_t bl = 0;
+				uint64_t bzl = 0, bzh = 0;
+				for (int64_t e = f0; e < top; ++e) {
+					__builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+					const uint64_t lo = kid[8 * e + 2 * (a - 1)], hi = kid[8 * e + 2 * (a - 1) + 1];
+					if (lo >= hi) continue;
+					if (steps >= max_steps || nt >= cap) { over = true; break; }
+					++steps;
+					const uint32_t l = el[e];
+					uint64_t zl, zh;
+					irred_rank<SPARSE>(T, pv, lo, hi, kid, el, nt, l, R.g, zl, zh);
+					++nt;
+					if (zh > zl && (bzh == bzl || l > bl)) { bl = l; bzl = zl; bzh = zh; }   // a string ends here: the longest overlap names the node
+				}
+				if (over) break;
+				if (bzh > bzl) { qstore(rec, i, max_recs, k, R.g, bl, d + 1, bzl, bzh); ++k; ++a; }
+				else if (nt > top && d + 1 < max_ext) { fs[d] = (uint32_t)f0; fa[d] = (uint8_t)(a + 1); ++d; f0 = top; top = nt; a = 1; }
+				else ++a;                                          // empty, or as deep as an extension goes
+			}
+		}
+		if (R.g == 0) cnt[i] = over ? -2 - k : k;
+	}
+}
+
 } // namespace rb2

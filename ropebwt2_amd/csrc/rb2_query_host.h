@@ -512,3 +512,55 @@ void rb2_hip_contained_dev(rb2_hip_t *h, int64_t n, const int64_t *ids, int64_t 
 	const int early = contain_early();
 	dev_chunks(n, [&](int64_t i0, int64_t nc) { launch_contain(h, nc, ids ? ids + i0 : nullptr, i0, early, rec + 5 * i0); });
 }
+
+/* ---- irreducible overlaps: the neighbours of a read in a string graph (k_irreducible) ---- */
+
+/* scratch for the stacks of a launch: IRRED_SCRATCH_BYTES; RB2_IRRED_SCRATCH in the environment, read on every call, lowers it (tests of the row cap) */
+static int64_t irred_scratch()
+{
+	const char *e = getenv("RB2_IRRED_SCRATCH");
+	const int64_t v = e ? atoll(e) : 0;
+	return v > 0 ? std::min(v, IRRED_SCRATCH_BYTES) : IRRED_SCRATCH_BYTES;
+}
+
+/* n queries, all device pointers, none that counts longer than lmax symbols: one launch, the stacks sized from the entries a row can hold */
+static void launch_irreducible(rb2_hip_t *h, int64_t n, const uint8_t *qry, const int64_t *off, int64_t base, int64_t lmax, int64_t min_ovlp, int64_t max_ext,
+                               int64_t max_steps, int64_t max_recs, int64_t *rec, int64_t *cnt)
+{
+	const int64_t cap = irred_entry_cap(lmax, min_ovlp, max_ext, max_steps), row = irred_row_bytes(cap, max_ext), rows = irred_rows(n, row, irred_scratch());
+	h->qscr.ensure((size_t)(rows * row));
+	qlaunch(h, k_irreducible<true>, k_irreducible<false>, (uint64_t)rows, qry, off, base, n, min_ovlp, max_ext, max_steps, max_recs, lmax, rows, cap, h->qscr.p, rec, cnt);
+}
+
+static void irreducible_check(const char *who, int64_t max_len, int64_t min_ovlp, int64_t max_ext, int64_t max_steps, int64_t max_recs)
+{
+	if (min_ovlp < 1) { rb2_fatal("[rb2_hip] %s: min_ovlp must be at least 1 (got %lld)\n", who, (long long)min_ovlp); }
+	if (max_ext < 1 || max_ext > IRRED_MAX_LEN) { rb2_fatal("[rb2_hip] %s: max_ext must be 1 .. %lld (got %lld)\n", who, (long long)IRRED_MAX_LEN, (long long)max_ext); }
+	if (max_steps < 1) { rb2_fatal("[rb2_hip] %s: max_steps must be at least 1 (got %lld)\n", who, (long long)max_steps); }
+	if (max_recs < 1) { rb2_fatal("[rb2_hip] %s: max_recs must be at least 1 (got %lld)\n", who, (long long)max_recs); }
+	if (max_len < 1 || max_len > IRRED_MAX_LEN) { rb2_fatal("[rb2_hip] %s: max_len must be 1 .. %lld (got %lld)\n", who, (long long)IRRED_MAX_LEN, (long long)max_len); }
+}
+
+int64_t rb2_hip_irreducible(rb2_hip_t *h, int64_t n, const uint8_t *qry, const int64_t *off, int64_t min_ovlp, int64_t max_ext, int64_t max_steps, int64_t max_recs,
+                            int64_t *rec, int64_t *cnt)
+{
+	query_begin(h, "irreducible");
+	if (n <= 0) return 0;
+	irreducible_check("irreducible", 1, min_ovlp, max_ext, max_steps, max_recs);
+	check_offsets("irreducible", "query", n, off);
+	int64_t lmax = 1;                                              // the longest query that is not malformed by its length alone
+	for (int64_t i = 0; i < n; ++i) if (off[i + 1] - off[i] <= IRRED_MAX_LEN) lmax = std::max(lmax, off[i + 1] - off[i]);
+	return staged_records(h, n, {qry, off, 0}, 4, max_recs, rec, cnt, [&](int64_t nc, const QStaged &s, int64_t *d_rec, int64_t *d_cnt) {
+		launch_irreducible(h, nc, s.bytes, s.v, s.base, lmax, min_ovlp, max_ext, max_steps, max_recs, d_rec, d_cnt); },
+		[](int64_t c) { return c >= 0 ? c : c <= -2 ? -2 - c : 0; });     // a query that ran out of steps keeps what it had found
+}
+
+void rb2_hip_irreducible_dev(rb2_hip_t *h, int64_t n, const uint8_t *qry, const int64_t *off, int64_t max_len, int64_t min_ovlp, int64_t max_ext, int64_t max_steps,
+                             int64_t max_recs, int64_t *rec, int64_t *cnt)
+{
+	query_begin(h, "irreducible_dev");
+	if (n <= 0) return;
+	irreducible_check("irreducible_dev", max_len, min_ovlp, max_ext, max_steps, max_recs);
+	dev_chunks(n, [&](int64_t i0, int64_t nc) {
+		launch_irreducible(h, nc, qry, off + i0, 0, max_len, min_ovlp, max_ext, max_steps, max_recs, rec + i0 * max_recs * 4, cnt + i0); });
+}

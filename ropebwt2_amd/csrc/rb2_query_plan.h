@@ -120,3 +120,42 @@ RB2_PLAN_HD inline int approx_bound(const uint8_t *q, int64_t L, int64_t N, int6
 
 /* D[p - 1] from what approx_bound left: the substitutions every match needs in front of position p */
 RB2_PLAN_HD inline int approx_need(const uint8_t *G, int pieces, int64_t p) { return p > 0 ? pieces - (int)G[p - 1] : 0; }
+
+/* ---- irreducible overlaps (rb2_hip_irreducible: kernel k_irreducible in rb2_query.h, host side in rb2_query_host.h) ----
+ * The stack of a row is a list of entries, the frames of the nodes on the current path behind each other (frame d = the entries of the
+ * node at depth d, in increasing overlap length).  An entry is written when it is ranked, and every pair of ranks is a step. */
+static const int64_t IRRED_MAX_LEN = 8192;                     /* symbols of a query, and of an extension, at the most: an overlap length has 16 bits */
+static const int64_t IRRED_ROWS = 16 * 2048;                   /* DPP rows of a launch at the most (2048 blocks: eight per CU); a row takes queries a launch apart */
+static const int64_t IRRED_SCRATCH_BYTES = (int64_t)256 << 20; /* the stacks of all rows of a launch stay under this (one row may be larger alone) */
+
+/* entries a row holds at the most for queries of up to lmax symbols (1 .. IRRED_MAX_LEN), min_ovlp >= 1, max_ext in 1 .. IRRED_MAX_LEN and
+ * max_steps >= 1: the frames 0 .. max_ext of a path hold at most lmax - min_ovlp entries each (the overlap lengths min_ovlp .. lmax - 1),
+ * and no more entries are ever written than steps taken; one at the least */
+constexpr int64_t irred_entry_cap(int64_t lmax, int64_t min_ovlp, int64_t max_ext, int64_t max_steps)
+{
+	int64_t e = lmax > min_ovlp ? (lmax - min_ovlp) * (max_ext + 1) : 0;
+	if (e > max_steps) e = max_steps;
+	return e < 1 ? 1 : e;
+}
+
+/* frames whose first entry and next child a row remembers: a frame below the top one was pushed at a depth below max_ext, and every frame
+ * of the path holds at least one of the cap entries */
+constexpr int64_t irred_frames(int64_t cap, int64_t max_ext) { return cap < max_ext ? cap : max_ext; }
+
+constexpr int64_t irred_pad(int64_t bytes) { return (bytes + 7) & ~(int64_t)7; }
+
+/* the stack of one row: per entry the intervals of its four children (64 bytes: one line) and its overlap length (2 bytes), per frame
+ * its first entry (4 bytes) and the next child to try (1 byte), each array padded to 8 bytes */
+constexpr int64_t irred_row_bytes(int64_t cap, int64_t max_ext)
+{
+	return 64 * cap + irred_pad(4 * irred_frames(cap, max_ext)) + irred_pad(2 * cap) + irred_pad(irred_frames(cap, max_ext));
+}
+
+/* rows of a launch over n (>= 1) queries with stacks of row_bytes each in `bytes` of scratch: at most n and IRRED_ROWS, one at the least */
+constexpr int64_t irred_rows(int64_t n, int64_t row_bytes, int64_t bytes)
+{
+	int64_t r = bytes / row_bytes;
+	if (r > IRRED_ROWS) r = IRRED_ROWS;
+	if (r > n) r = n;
+	return r < 1 ? 1 : r;
+}

@@ -70,6 +70,8 @@ def load_hip_lib():
         "rb2_hip_approx_dev": (None, [vp, i64, vp, vp, i32, i64, i64, i64, vp, vp]),
         "rb2_hip_contained": (i64, [vp, i64, vp, vp]),
         "rb2_hip_contained_dev": (None, [vp, i64, vp, vp]),
+        "rb2_hip_irreducible": (i64, [vp, i64, vp, vp, i64, i64, i64, i64, vp, vp]),
+        "rb2_hip_irreducible_dev": (None, [vp, i64, vp, vp, i64, i64, i64, i64, i64, vp, vp]),
         "rb2_hip_reserve": (None, [vp, i64, i64, i64]),
         "rb2_hip_num_subropes": (i32, []),
         "rb2_hip_memcpy": (None, [vp, vp, vp, i64, i32]),
@@ -138,6 +140,7 @@ ABI_SYMBOLS = [
     "rb2_hip_ssa_build", "rb2_hip_ssa_drop", "rb2_hip_ssa_info", "rb2_hip_locate", "rb2_hip_locate_dev",
     "rb2_hip_overlap", "rb2_hip_overlap_dev", "rb2_hip_string_ids", "rb2_hip_string_ids_dev", "rb2_hip_kmers",
     "rb2_hip_approx", "rb2_hip_approx_dev", "rb2_hip_contained", "rb2_hip_contained_dev",
+    "rb2_hip_irreducible", "rb2_hip_irreducible_dev",
     "rb2_hip_num_subropes", "rb2_hip_memcpy", "rb2_hip_use_stream",
     "rb2_hip_dev_free", "rb2_hip_synth_reads", "rb2_hip_synth_reads_cov", "rb2_hip_synth_reads_skew", "rb2_hip_sync", "rb2_hip_sparse_stats", "rb2_hip_layout_stats", "rb2_hip_rewind_stats", "rb2_hip_window_stats", "rb2_hip_host_register", "rb2_hip_host_unregister", "rb2_hip_profile",
     "rb2_hip_profile_get", "rb2_hip_kernel_name", "rb2_hip_layout",
@@ -211,10 +214,10 @@ def unpack_subs(subs):
 
 
 class StepBudgetExceeded(RuntimeError):
-    """HipBwt.approx: some queries used up max_steps before their search ended; .queries lists them, .results holds what approx() would
-    have returned, with the matches those queries had found so far"""
-    def __init__(self, queries, results):
-        RuntimeError.__init__(self, "approx: %d queries ran out of steps (the first: %s); raise max_steps or lower max_mm" % (len(queries), queries[:5]))
+    """HipBwt.approx, HipBwt.irreducible: some queries used up max_steps before their search ended; .queries lists them, .results holds
+    what the call would have returned, with what those queries had found so far"""
+    def __init__(self, queries, results, who="approx", lower="max_mm"):
+        RuntimeError.__init__(self, "%s: %d queries ran out of steps (the first: %s); raise max_steps or lower %s" % (who, len(queries), queries[:5], lower))
         self.queries, self.results = queries, results
 
 
@@ -639,6 +642,66 @@ class HipBwt:
         if len(ids):
             self.delete(ids)
         return ids
+
+    # -- irreducible overlaps: the edges of a string graph (include/rb2_hip.h) -----------------------------------------------------
+    def irreducible_raw(self, queries, min_ovlp, max_ext, max_steps=1 << 16, max_recs=16):
+        """rb2_hip_irreducible as it is: (records stored, rec (n, max_recs, 4) int64 = l, ext, zlo, zhi, cnt (n,) int64).  [zlo, zhi) are
+        `$` ranks for string_ids_raw and name the REVERSE COMPLEMENTS of the neighbours.  cnt[i] >= 0: the records found, min(cnt[i],
+        max_recs) of them stored; -1: a malformed query; <= -2: out of steps with -2 - cnt[i] records found.  The records not stored are
+        zeros, the order of a query's records is unspecified"""
+        qry, off = pack_patterns(queries)
+        return self._records(self.L.rb2_hip_irreducible, len(off) - 1, (qry.ctypes.data, off.ctypes.data, min_ovlp, max_ext, max_steps, max_recs), max_recs, 4, False)
+
+    def irreducible_dev(self, n, qry_dev, off_dev, rec_dev, cnt_dev, max_len, min_ovlp, max_ext, max_steps=1 << 16, max_recs=16):
+        """rb2_hip_irreducible_dev: all four pointers in this device's memory; asynchronous on the handle's stream.  A query of more than
+        max_len (1 .. 8192) symbols is malformed"""
+        self.L.rb2_hip_irreducible_dev(self.h, n, qry_dev, off_dev, max_len, min_ovlp, max_ext, max_steps, max_recs, rec_dev, cnt_dev)
+
+    def irreducible(self, queries, min_ovlp, max_ext=None, max_steps=1 << 16, max_recs=16, max_hits=8, pairs=False):
+        """the irreducible overlaps of every query (str / bytes over ACGTN, or nt6 arrays) with the strings of an index of both strands:
+        per query the sorted list of (string id, l, ext) -- the string continues the query by ext symbols behind an overlap of l, and no
+        other such string lies on the way to it --, at most max_recs distinct (l, extension) per query and max_hits strings of each; None
+        for a malformed query.  The ids are those of the REVERSE COMPLEMENTS of the neighbours (that is what the index yields) unless
+        pairs: then the index is taken to hold a read and its reverse complement as the strings 2i and 2i + 1 (input order, as
+        reduce(pairs=True) leaves it) and the id returned is id ^ 1, the neighbour itself; ValueError for another sorting order or an
+        odd number of strings.  max_ext=None: the longest query.  Needs build_ssa() (none is built here).  Raises StepBudgetExceeded
+        as approx() does"""
+        if pairs and (self.so != 0 or int(self.counts()[:, 0].sum()) % 2):
+            raise ValueError("irreducible(pairs=True): the index must be in input order and hold an even number of strings")
+        if max_ext is None:
+            max_ext = min(max(max((len(encode_pattern(q)) for q in queries), default=1), 1), 8192)
+        _, rec, cnt = self.irreducible_raw(queries, min_ovlp, max_ext, max_steps, max_recs)
+        have = np.minimum(np.where(cnt <= -2, -2 - cnt, np.maximum(cnt, 0)), max_recs)
+        live = np.arange(max_recs)[None, :] < have[:, None]
+        who = np.nonzero(live)[0]
+        recs = rec[live]
+        out = [None if c == -1 else [] for c in cnt.tolist()]
+        if len(recs):
+            max_hits = max(min(int(max_hits), int((recs[:, 3] - recs[:, 2]).max())), 1)          # no wider than the widest range
+            _, ids, n_ids = self.string_ids_raw(recs[:, 2:], max_hits)
+            for i, l, e, k, row in zip(who.tolist(), recs[:, 0].tolist(), recs[:, 1].tolist(), np.minimum(n_ids, max_hits).tolist(), ids.tolist()):
+                out[i] += [(s ^ 1 if pairs else s, l, e) for s in row[:k]]
+        out = [o if o is None else sorted(o) for o in out]
+        if (cnt <= -2).any():
+            raise StepBudgetExceeded(np.flatnonzero(cnt <= -2).tolist(), out, "irreducible", "max_ext")
+        return out
+
+    def edges(self, ids=None, min_ovlp=1, **kw):
+        """the edges of the string graph that leave the strings ids (None: every string): their text is read with extract() and asked
+        with irreducible(..., **kw).  An (m, 4) int64 array, rows = src, dst, l, ext sorted; dst as irreducible() names it (the neighbour
+        itself with pairs=True)"""
+        n = int(self.counts()[:, 0].sum())
+        ids = np.arange(n, dtype=np.int64) if ids is None else np.asarray(ids, dtype=np.int64).reshape(-1)
+        if len(ids) == 0:
+            return np.zeros((0, 4), np.int64)
+        max_len = 64
+        texts = self.extract(ids, max_len)
+        while any(t is None for t in texts):                        # (longer than the guess: read again with room)
+            max_len *= 4
+            texts = self.extract(ids, max_len)
+        res = self.irreducible(texts, min_ovlp, **kw)
+        rows = [(int(s), d, l, e) for s, r in zip(ids.tolist(), res) for d, l, e in (r or [])]
+        return np.array(sorted(rows), np.int64).reshape(-1, 4)
 
     # -- measurement helpers ----------------------------------------------------------------
     def dev_alloc(self, nbytes):

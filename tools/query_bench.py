@@ -39,6 +39,15 @@ start positions give real copies), with the early exit and with RB2_CONTAIN_EARL
 per string and the share of every flag.  On a sample of the strings the same run times rb2_hip_contained through host buffers against what
 a user could compose before, rb2_hip_extract of the sample followed by rb2_hip_backward_search of the extracted strings, and compares
 the occurrences the two report.
+With --irreducible only the irreducible-overlap query is measured and stored under "irreducible" in the --out file, whose other entries
+stay: an index of both strands of reads drawn from one genome at 30x, in input order, after reduce(pairs=True); irreducible_dev over
+--irreducible-queries reads of the index (their text read back with extract) at --irreducible-min-ovlp, max_ext = read length - min_ovlp
+-- queries per second, median of three after a warm-up with the fastest and the slowest beside it, rank pairs per second from a lower
+bound of the steps (the call does not report the steps of a query: the search takes one per symbol, every entry of the root one, and
+a record of extension e at least e more), records per query and the share of the overlap records of the same reads (rb2_hip_overlap,
+lengths below the read's own) that survive.  On 4000 reads the same run times what a user could compose before -- overlaps(), extract of
+every neighbour, and the pruning on the host (tests/irreducible_ref.py: edges_by_composition) -- against irreducible(pairs=True), and
+compares the edge sets (equals_fused).
 """
 import argparse
 import json
@@ -618,6 +627,81 @@ def contained_case(a, res):
         res.setdefault("contained", []).append(case)
 
 
+def irreducible_case(a, res):
+    import irreducible_ref as IR
+    L, M = 101, 4
+    n = a.reads or 4_000_000
+    min_ovlp = a.irreducible_min_ovlp
+    max_ext = L - min_ovlp                                          # reads of one length: a neighbour leaves the read by L - l symbols
+    g = HipBwt(0)                                                   # input order: strings 2i and 2i + 1 are a read and its reverse complement
+    nb = 2 * n * (L + 1)
+    p = g.dev_alloc(nb)
+    t = time.perf_counter()
+    g.synth_reads(p, 0, n, L, seed=42, strand=1, genome_len=n * L // 30)
+    g.insert_multi_dev(p, nb)
+    g.sync()
+    build_s = time.perf_counter() - t
+    g.dev_free(p)
+    t = time.perf_counter()
+    gone = g.reduce(pairs=True)
+    reduce_s = time.perf_counter() - t
+    left = int(g.counts()[:, 0].sum())
+    index = {"reads": n, "read_len": L, "genome_len": n * L // 30, "strands": 2, "sorting_order": 0, "build_seconds": build_s, "reduce_pairs_seconds": reduce_s,
+             "strings_removed": int(len(gone)), "strings": left, "symbols": int(g.counts().sum()), "layout": g.layout_stats()}
+    print("irreducible: index of %d strings built in %.1f s, reduced in %.1f s" % (left, build_s, reduce_s), file=sys.stderr, flush=True)
+    P = min(a.irreducible_queries, left)
+    ids = np.sort(np.random.RandomState(5).choice(left, size=P, replace=False)).astype(np.int64)
+    _, txt, ln = g.extract_raw(ids, L)
+    assert (ln == L).all()
+    flat = np.ascontiguousarray(txt.reshape(-1)); off = np.arange(P + 1, dtype=np.int64) * L
+    dq, do, dr, dc, dv = g.dev_alloc(len(flat)), g.dev_alloc(8 * (P + 1)), g.dev_alloc(32 * M * P), g.dev_alloc(8 * P), g.dev_alloc(24 * (max_ext + 1) * P)
+    g.L.rb2_hip_memcpy(g.h, dq, flat.ctypes.data, len(flat), 0)
+    g.L.rb2_hip_memcpy(g.h, do, off.ctypes.data, 8 * (P + 1), 0)
+    sec, lo, hi = spread(lambda: g.irreducible_dev(P, dq, do, dr, dc, L, min_ovlp, max_ext, a.irreducible_steps, M), g.sync)
+    cnt = np.zeros(P, np.int64); rec = np.zeros((P, M, 4), np.int64)
+    g.L.rb2_hip_memcpy(g.h, cnt.ctypes.data, dc, 8 * P, 1)
+    g.L.rb2_hip_memcpy(g.h, rec.ctypes.data, dr, rec.nbytes, 1)
+    osec, _, _ = spread(lambda: g.overlap_dev(P, dq, do, dv, dc, min_ovlp, max_ext + 1), g.sync)
+    ocnt = np.zeros(P, np.int64)
+    g.L.rb2_hip_memcpy(g.h, ocnt.ctypes.data, dc, 8 * P, 1)
+    for q in (dq, do, dr, dc, dv):
+        g.dev_free(q)
+    assert (cnt != -1).all() and (ocnt >= 1).all()                  # a read of the index finds itself at its full length: that record is no candidate
+    found = np.where(cnt <= -2, -2 - cnt, cnt)
+    live = np.arange(M)[None, :] < np.minimum(found, M)[:, None]
+    least = int(P * L + (ocnt - 1).sum() + rec[:, :, 1][live].sum())
+    row = {"case": "irreducible_dev, %d reads of the index (%d bp), min_ovlp=%d max_ext=%d max_steps=%d max_recs=%d" % (P, L, min_ovlp, max_ext, a.irreducible_steps, M),
+           "measured": True, "queries": P, "seconds": sec, "seconds_fastest": lo, "seconds_slowest": hi, "queries_per_s": P / sec,
+           "rank_pairs_at_least": least, "rank_pairs_per_s_at_least": least / sec, "records": int(found.sum()), "records_per_query": float(found.sum() / P),
+           "queries_out_of_steps": int((cnt <= -2).sum()), "queries_with_more_than_max_recs": int((found > M).sum()),
+           "overlap_records_below_full_length": int((ocnt - 1).sum()), "share_of_overlap_records_that_survive": float(found.sum() / max((ocnt - 1).sum(), 1)),
+           "overlap_dev_seconds_same_reads": osec}
+    print("irreducible: %d queries in %.3f s" % (P, sec), file=sys.stderr, flush=True)
+    # the composition it replaces, on few reads: overlaps, the text of every neighbour, the pruning on the host
+    g.build_ssa(5)
+    nq = min(a.baseline_queries // 5, P)                            # (4000 reads by default)
+    qs = list(txt[:nq])
+    got = {}
+
+    def composed():
+        ov = g.overlaps(qs, min_ovlp, max_hits=64)
+        ov = [[(k, l) for k, l in o if l < L] for o in ov]
+        need = np.unique(np.array([k for o in ov for k, _ in o], np.int64))
+        texts = dict(zip(need.tolist(), g.extract(need, L)))
+        got["composed"] = [sorted(IR.edges_by_composition(texts, o, max_ext)) for o in ov]
+
+    def fused():
+        got["fused"] = g.irreducible(qs, min_ovlp, max_ext, max_steps=a.irreducible_steps, max_recs=64, max_hits=64, pairs=True)
+    csec = timed(composed, lambda: None, reps=1)
+    fsec = timed(fused, lambda: None, reps=1)
+    brow = {"case": "baseline: overlaps(), extract of every neighbour, pruning on the host; %d reads" % nq, "measured": True, "queries": nq, "seconds": csec,
+            "seconds_per_query": csec / nq, "edges": int(sum(len(e) for e in got["composed"])), "equals_fused": bool(got["composed"] == got["fused"])}
+    frow = {"case": "irreducible(pairs=True) (host buffers, string ids resolved), the baseline's %d reads" % nq, "measured": True, "queries": nq, "seconds": fsec,
+            "seconds_per_query": fsec / nq, "edges": int(sum(len(e) for e in got["fused"])), "composed_over_fused": csec / fsec}
+    g.close()
+    res["irreducible"] = {"index": index, "cases": [row, brow, frow]}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default="")
@@ -640,7 +724,19 @@ def main():
     ap.add_argument("--delete", type=float, default=0.0, help="only string deletion: delete this fraction of the strings (appended to an existing --out file)")
     ap.add_argument("--contained", action="store_true", help="only the duplicate / containment query (appended to an existing --out file)")
     ap.add_argument("--contained-sample", type=int, default=1_000_000, help="strings of the sample the composition extract + backward_search is timed on")
+    ap.add_argument("--irreducible", action="store_true", help="only the irreducible-overlap query (added to an existing --out file)")
+    ap.add_argument("--irreducible-queries", type=int, default=1_000_000)
+    ap.add_argument("--irreducible-min-ovlp", type=int, default=40)
+    ap.add_argument("--irreducible-steps", type=int, default=1 << 16, help="max_steps of the irreducible-overlap query")
     a = ap.parse_args()
+    if a.irreducible:
+        res = {"cases": []}
+        if a.out and os.path.exists(a.out):
+            with open(a.out) as f:
+                res = json.load(f)
+        irreducible_case(a, res)
+        finish(a, res)
+        return
     if a.contained:
         res = {"cases": []}
         if a.out and os.path.exists(a.out):
