@@ -392,6 +392,50 @@ int64_t rb2_hip_irreducible(rb2_hip_t *h, int64_t n, const uint8_t *qry, const i
 void    rb2_hip_irreducible_dev(rb2_hip_t *h, int64_t n, const uint8_t *qry, const int64_t *off, int64_t max_len, int64_t min_ovlp, int64_t max_ext, int64_t max_steps,
                                 int64_t max_recs, int64_t *rec, int64_t *cnt);
 
+/* ---- unitigs: the maximal unbranched paths of a string graph and their texts (csrc/rb2_unitig.h) ----
+ * THE GRAPH.  n_str vertices 0 .. n_str-1 and m edges, rows of four int64 src, dst, l, ext (the shape of HipBwt.edges; l is not read).  An
+ * edge with src or dst outside [0, n_str) or ext < 1 is IGNORED: counted in info, part of no degree.  outdeg(u) and indeg(v) count the
+ * others; a duplicate edge counts twice, a self loop in both degrees.  An edge u -> v is a LINK when outdeg(u) == 1 && indeg(v) == 1, so
+ * every vertex has at most one successor and one predecessor through links, and the components of the link relation -- the CHAINS -- are
+ * open paths (a lone vertex is a chain of one) and cycles.  The HEAD of an open chain is its vertex without a predecessor; the head of
+ * a cycle is its smallest vertex id, and the link into it is the CLOSING LINK.
+ * vtx[4v ..] = head, rank, off, ext_in of vertex v: the head of its chain, the links from the head to v, the sum of ext over those
+ * links, and ext of the link into v -- -1 for the head of an open chain; for the head of a cycle the ext of the closing link, which is
+ * >= 1 and marks the chain as circular.  The closing link is counted in no rank and no off.
+ * info = chains, cycles, vertices of the longest chain, edges ignored.  Returns the number of chains.
+ * The call does not read the index (n_str is the caller's), waits for a lazy insert and is fatal for n_str or m outside 0 .. 2^36.  Chains
+ * are found by pointer jumping: 2 ceil(log2(n_str)) + 5 launches whatever the graph holds, nothing read back between them; 96 bytes of
+ * device memory per vertex.  The host variant stages the edges in chunks of 2^24 (RB2_QUERY_CHUNK lowers that) and synchronises once. */
+int64_t rb2_hip_unitig_chains(rb2_hip_t *h, int64_t n_str, int64_t m, const int64_t *edges, int64_t *vtx, int64_t info[4]);
+/* the same with edges, vtx (4 n_str int64) and info (4 int64) in this device's memory, asynchronous on the handle's stream (no return value: read info) */
+void    rb2_hip_unitig_chains_dev(rb2_hip_t *h, int64_t n_str, int64_t m, const int64_t *edges, int64_t *vtx, int64_t *info);
+/* THE TEXT of the chains vtx describes, on an index whose string ids are the rows of the `$` block (as for rb2_hip_contained); n_str must
+ * equal the number of strings of the index.  The text of the chain with head h and vertices h = v0, v1, .. vk (by rank) is text(v0)
+ * followed by the last ext_in(vi) symbols of text(vi) for i = 1 .. k, nt6 codes in text order; its length is len(v0) + off(vk).  If
+ * ext_in(vi) > len(vi) (an edge list that does not belong to this index) the piece is the last len(vi) symbols with code 0 in front of
+ * them, and the chain is counted in info as one with a SHORT PIECE; every store stays inside the slice of its chain.  A circular chain is
+ * cut at its head: the closing link adds nothing.
+ * A chain is SELECTED when it has at least min_reads vertices and, with canonical != 0, its smallest vertex id is even: on a graph that
+ * is symmetric under v <-> v ^ 1 (strings 2i and 2i + 1 a read and its reverse complement) that keeps exactly one of every unitig and
+ * its reverse complement, and a chain that is its own reverse complement once.  The selected chains are numbered by increasing head id:
+ * urec[5u ..] = head, n_reads, text_off, text_len, flags of chain u, flags bit 0 = circular, bit 1 = had a short piece; text_off is the
+ * exclusive prefix sum of text_len in that order, the text is txt[text_off, text_off + text_len).  A chain is STORED when u < cap_u and
+ * text_off + text_len <= cap_txt; the others are counted, and neither their record nor their slice is written (the convention of
+ * rb2_hip_kmers' max_recs).  cap_u == 0 or cap_txt == 0 stores nothing and still returns the sizes: that is how a caller sizes urec and txt.
+ * info = chains selected, total text length of the selected, selected chains with a short piece, chains stored.  Returns the chains stored.
+ * A row of vtx whose head is outside [0, n_str) makes its vertex a chain of its own with the short-piece flag; such a row is followed
+ * nowhere, and whatever vtx holds the call stays inside urec, txt and the index (a row whose off or ext_in is negative or above 2^48 adds
+ * no piece and flags its chain; sums stop at 2^62).
+ * Like every query the call waits for a lazy insert, reads the index and nothing else, and is fatal on one rank of a sharded index; fatal
+ * too: n_str < 0 or unequal to the strings of the index, min_reads < 1, a negative cap.  Every vertex that is no head is walked ext_in
+ * LF steps, stored or not (that is where a short piece shows); a selected head is walked once for its length and once more when stored. */
+int64_t rb2_hip_unitig_text(rb2_hip_t *h, int64_t n_str, const int64_t *vtx, int canonical, int64_t min_reads, int64_t cap_u, int64_t cap_txt, int64_t *urec, uint8_t *txt,
+                            int64_t info[4]);
+/* the same with vtx, urec (5 cap_u int64) and txt (cap_txt bytes) in this device's memory and info in host memory: the call synchronises
+ * the handle's stream once, behind its last kernel, to read the four counts */
+int64_t rb2_hip_unitig_text_dev(rb2_hip_t *h, int64_t n_str, const int64_t *vtx, int canonical, int64_t min_reads, int64_t cap_u, int64_t cap_txt, int64_t *urec, uint8_t *txt,
+                                int64_t info[4]);
+
 /* 64-bit checksum of rope b computed on the device (position-weighted sum over the packed words of its pieces): equal for
  * equal symbol sequences however the index was built (one engine, N ranks, an .fmr loaded back), sensitive to order.  Lets
  * tests compare indexes of 10^11 symbols without moving them off the device (the reference has no counterpart; its ropes are

@@ -17,6 +17,7 @@
 #include "rb2_hip.h"
 #include "rb2_kernels.h"
 #include "rb2_query.h"
+#include "rb2_unitig.h"
 #include "rb2_fmd_load.h"
 #include "rb2_delete.h"
 

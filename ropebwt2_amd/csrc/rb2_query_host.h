@@ -564,3 +564,202 @@ void rb2_hip_irreducible_dev(rb2_hip_t *h, int64_t n, const uint8_t *qry, const 
 	dev_chunks(n, [&](int64_t i0, int64_t nc) {
 		launch_irreducible(h, nc, qry, off + i0, 0, max_len, min_ovlp, max_ext, max_steps, max_recs, rec + i0 * max_recs * 4, cnt + i0); });
 }
+
+/* ---- unitigs: the chains of an edge list and their texts (rb2_unitig.h) ---- */
+
+static const int64_t UT_MAX_N = (int64_t)1 << 36;              /* vertices and edges of a call at the most: the scans launch n / 4096 blocks */
+static const int64_t UT_LAUNCH = 1 << 24;                      /* DPP rows (vertices) per launch of the pieces' walks: 2^28 threads */
+
+/* one thread per item, the threads striding over what UT_BLOCKS blocks do not cover; nothing for no items */
+template <typename... P, typename... A>
+static void ulaunch(rb2_hip_t *h, void (*k)(P...), int64_t items, A... a)
+{
+	if (items <= 0) return;
+	hipLaunchKernelGGL(k, dim3((unsigned)std::min<uint64_t>(cdiv((uint64_t)items, 256), UT_BLOCKS)), dim3(256), 0, h->st, static_cast<P>(a)...);
+	HIPCHK(hipGetLastError());
+}
+
+/* pointer jumps that reach the head of every chain of n vertices: the smallest K with 2^K >= n */
+static int unitig_doublings(int64_t n)
+{
+	int k = 0;
+	while (((int64_t)1 << k) < n) ++k;
+	return k;
+}
+
+struct UtChainBufs { unsigned long long *ctr; uint32_t *outdeg, *indeg; int64_t *inedge, *pred; UtState *st[2]; };
+
+/* the scratch of a chains call in qscr, counters and degrees zeroed */
+static UtChainBufs unitig_chain_bufs(rb2_hip_t *h, int64_t n)
+{
+	h->qscr.ensure((size_t)(UT_CTRS + 12 * n) * 8);
+	int64_t *w = (int64_t*)h->qscr.p;
+	UtChainBufs b;
+	b.ctr = (unsigned long long*)w; w += UT_CTRS;
+	b.outdeg = (uint32_t*)w; b.indeg = b.outdeg + n; w += n;
+	b.inedge = w; w += 2 * n;
+	b.pred = w; w += n;
+	b.st[0] = (UtState*)w; w += 4 * n;
+	b.st[1] = (UtState*)w;
+	HIPCHK(hipMemsetAsync(b.ctr, 0, (size_t)(UT_CTRS + n) * 8, h->st));
+	return b;
+}
+
+/* behind the degrees: links, the jumps of the open chains, the cut, the jumps of the cycles, vtx (device memory) */
+static void unitig_rank(rb2_hip_t *h, const UtChainBufs &b, int64_t n, int64_t *vtx)
+{
+	const int K = unitig_doublings(n);
+	int cur = 0;
+	ulaunch(h, k_unitig_link, n, n, b.outdeg, b.indeg, b.inedge, b.st[0], b.pred, vtx);
+	for (int pass = 0; pass < 2; ++pass) {
+		for (int k = 0; k < K; ++k, cur ^= 1) ulaunch(h, k_unitig_jump, n, n, b.st[cur], b.st[cur ^ 1]);
+		if (pass == 0) { ulaunch(h, k_unitig_cut, n, n, b.st[cur], b.st[cur ^ 1], b.pred, vtx); cur ^= 1; }
+	}
+	ulaunch(h, k_unitig_fin, n, n, b.st[cur], vtx, b.ctr);
+}
+
+static void unitig_chains_check(rb2_hip_t *h, const char *who, int64_t n, int64_t m)
+{
+	finish_pending(h);
+	HIPCHK(hipSetDevice(h->dev));
+	if (n < 0 || n > UT_MAX_N || m < 0 || m > UT_MAX_N) { rb2_fatal("[rb2_hip] %s: n_str and m must be 0 .. 2^36 (got %lld, %lld)\n", who, (long long)n, (long long)m); }
+}
+
+int64_t rb2_hip_unitig_chains(rb2_hip_t *h, int64_t n_str, int64_t m, const int64_t *edges, int64_t *vtx, int64_t info[4])
+{
+	unitig_chains_check(h, "unitig_chains", n_str, m);
+	const UtChainBufs b = unitig_chain_bufs(h, n_str);
+	h->qout.ensure((size_t)(4 * n_str + 4));
+	const int64_t CH = query_chunk();
+	for (int64_t i0 = 0; i0 < m; i0 += CH) {                       // the edges in chunks: a degree needs no other edge
+		const int64_t mc = std::min(CH, m - i0);
+		const QStaged s = stage_inputs(h, {nullptr, edges, 4}, i0, mc, 0);
+		ulaunch(h, k_unitig_deg, mc, s.v, mc, n_str, b.outdeg, b.indeg, b.inedge, b.ctr);
+	}
+	unitig_rank(h, b, n_str, h->qout.p);
+	int64_t inf[4];
+	hipLaunchKernelGGL(k_unitig_info, dim3(1), dim3(64), 0, h->st, (const unsigned long long*)b.ctr, h->qout.p + 4 * n_str);
+	HIPCHK(hipGetLastError());
+	if (n_str) HIPCHK(hipMemcpyAsync(vtx, h->qout.p, (size_t)n_str * 32, hipMemcpyDeviceToHost, h->st));
+	HIPCHK(hipMemcpyAsync(inf, h->qout.p + 4 * n_str, sizeof(inf), hipMemcpyDeviceToHost, h->st));
+	HIPCHK(hipStreamSynchronize(h->st));
+	if (info) memcpy(info, inf, sizeof(inf));
+	return inf[0];
+}
+
+void rb2_hip_unitig_chains_dev(rb2_hip_t *h, int64_t n_str, int64_t m, const int64_t *edges, int64_t *vtx, int64_t *info)
+{
+	unitig_chains_check(h, "unitig_chains_dev", n_str, m);
+	const UtChainBufs b = unitig_chain_bufs(h, n_str);
+	dev_chunks(m, [&](int64_t i0, int64_t mc) { ulaunch(h, k_unitig_deg, mc, edges + 4 * i0, mc, n_str, b.outdeg, b.indeg, b.inedge, b.ctr); });
+	unitig_rank(h, b, n_str, vtx);
+	hipLaunchKernelGGL(k_unitig_info, dim3(1), dim3(64), 0, h->st, (const unsigned long long*)b.ctr, info);
+	HIPCHK(hipGetLastError());
+}
+
+/* exclusive prefix sums of x[0 .. n) in place on the device, their total into *total */
+static void unitig_scan(rb2_hip_t *h, uint64_t *x, int64_t n, uint64_t *bsum, unsigned long long *total)
+{
+	const uint64_t nb = cdiv((uint64_t)n, UT_SCAN);
+	hipLaunchKernelGGL(k_unitig_scan_sum, dim3((unsigned)nb), dim3(256), 0, h->st, (const uint64_t*)x, (uint64_t)n, bsum);
+	hipLaunchKernelGGL(k_unitig_scan_top, dim3(1), dim3(256), 0, h->st, bsum, nb, total);
+	hipLaunchKernelGGL(k_unitig_scan_add, dim3((unsigned)nb), dim3(256), 0, h->st, x, (uint64_t)n, (const uint64_t*)bsum);
+	HIPCHK(hipGetLastError());
+}
+
+static void unitig_text_check(rb2_hip_t *h, const char *who, int64_t n, int64_t min_reads, int64_t cap_u, int64_t cap_txt, const void *urec, const void *txt)
+{
+	query_begin(h, who);
+	if (n < 0 || n > UT_MAX_N) { rb2_fatal("[rb2_hip] %s: n_str must be 0 .. 2^36 (got %lld)\n", who, (long long)n); }
+	if (min_reads < 1) { rb2_fatal("[rb2_hip] %s: min_reads must be at least 1 (got %lld)\n", who, (long long)min_reads); }
+	if (cap_u < 0 || cap_txt < 0) { rb2_fatal("[rb2_hip] %s: cap_u and cap_txt must not be negative (got %lld, %lld)\n", who, (long long)cap_u, (long long)cap_txt); }
+	if (cap_u > 0 && cap_txt > 0 && (!urec || !txt)) { rb2_fatal("[rb2_hip] %s: %s is NULL but its size is not 0\n", who, urec ? "txt" : "urec"); }
+	if ((uint64_t)n != h->h_rope[0].n) { rb2_fatal("[rb2_hip] %s: n_str = %lld, but the index holds %llu strings\n", who, (long long)n, (unsigned long long)h->h_rope[0].n); }
+}
+
+/* vtx, urec and txt in device memory; one synchronise, behind which info is what the counters say.  Returns the chains stored */
+static int64_t unitig_text_run(rb2_hip_t *h, int64_t n, const int64_t *vtx, int canonical, int64_t min_reads, int64_t cap_u, int64_t cap_txt, int64_t *urec, uint8_t *txt, int64_t info[4])
+{
+	int64_t inf[4] = {0, 0, 0, 0};
+	if (n > 0) {
+		if (cap_u == 0 || cap_txt == 0) cap_u = cap_txt = 0;       // sizes only
+		const int64_t nb = (int64_t)cdiv((uint64_t)n, UT_SCAN);
+		h->qscr.ensure((size_t)(UT_CTRS + 10 * n + nb + 1) * 8);
+		uint64_t *w = (uint64_t*)h->qscr.p;
+		unsigned long long *ctr = (unsigned long long*)w; w += UT_CTRS;
+		UtHeads H; UtSel S;
+		H.cnt = (unsigned long long*)w; w += n;
+		H.off = (unsigned long long*)w; w += n;
+		S.toff = w; w += n;
+		H.flg = (uint32_t*)w; w += n;                              // (zeroed up to here)
+		H.mn = (unsigned long long*)w; w += n;
+		H.u = (int64_t*)w; w += n;
+		S.head = (int64_t*)w; w += n;
+		S.len = w; w += n;
+		S.tlen = w; w += n;
+		uint64_t *bsum = w;
+		HIPCHK(hipMemsetAsync(ctr, 0, (size_t)(UT_CTRS + 4 * n) * 8, h->st));
+		HIPCHK(hipMemsetAsync(H.mn, 0xff, (size_t)n * 8, h->st));
+		ulaunch(h, k_unitig_sum, n, n, vtx, H);
+		ulaunch(h, k_unitig_sel, n, n, H, canonical, min_reads);
+		unitig_scan(h, (uint64_t*)H.u, n, bsum, ctr + UT_NSEL);
+		ulaunch(h, k_unitig_list, n, n, H, S, canonical, min_reads);
+		const uint64_t rows = (uint64_t)std::min<int64_t>(n, UT_ROWS);
+		qlaunch(h, k_unitig_len<true>, k_unitig_len<false>, rows, n, ctr, H, S);
+		unitig_scan(h, S.toff, n, bsum, ctr + UT_TOTAL);
+		if (cap_u) qlaunch(h, k_unitig_text<true, true>, k_unitig_text<false, true>, rows, n, 0, 0, vtx, ctr, H, S, cap_u, cap_txt, txt);
+		for (int64_t v0 = 0; v0 < n; v0 += UT_LAUNCH) {              // (always: a short piece shows in the walk, stored or not)
+			const int64_t nv = std::min(UT_LAUNCH, n - v0);
+			qlaunch(h, k_unitig_text<true, false>, k_unitig_text<false, false>, (uint64_t)nv, n, v0, nv, vtx, ctr, H, S, cap_u, cap_txt, txt);
+		}
+		ulaunch(h, k_unitig_rec, n, n, ctr, H, S, cap_u, cap_txt, urec);
+		unsigned long long c[UT_CTRS];
+		HIPCHK(hipMemcpyAsync(c, ctr, sizeof(c), hipMemcpyDeviceToHost, h->st));
+		HIPCHK(hipStreamSynchronize(h->st));
+		inf[0] = (int64_t)c[UT_NSEL]; inf[1] = (int64_t)c[UT_TOTAL]; inf[2] = (int64_t)c[UT_SHORT]; inf[3] = (int64_t)c[UT_STORED];
+	}
+	if (info) memcpy(info, inf, sizeof(inf));
+	return inf[3];
+}
+
+int64_t rb2_hip_unitig_text_dev(rb2_hip_t *h, int64_t n_str, const int64_t *vtx, int canonical, int64_t min_reads, int64_t cap_u, int64_t cap_txt, int64_t *urec, uint8_t *txt,
+                                int64_t info[4])
+{
+	unitig_text_check(h, "unitig_text_dev", n_str, min_reads, cap_u, cap_txt, urec, txt);
+	return unitig_text_run(h, n_str, vtx, canonical ? 1 : 0, min_reads, cap_u, cap_txt, urec, txt, info);
+}
+
+int64_t rb2_hip_unitig_text(rb2_hip_t *h, int64_t n_str, const int64_t *vtx, int canonical, int64_t min_reads, int64_t cap_u, int64_t cap_txt, int64_t *urec, uint8_t *txt,
+                            int64_t info[4])
+{
+	unitig_text_check(h, "unitig_text", n_str, min_reads, cap_u, cap_txt, urec, txt);
+	if (cap_u == 0 || cap_txt == 0) cap_u = cap_txt = 0;
+	cap_u = std::min(cap_u, n_str);                                // (no more chains than vertices)
+	h->qout.ensure((size_t)(4 * n_str + 5 * cap_u + 1));
+	h->qbytes.ensure((size_t)std::max<int64_t>(cap_txt, 1));
+	int64_t *d_urec = h->qout.p + 4 * n_str;
+	if (n_str) HIPCHK(hipMemcpyAsync(h->qout.p, vtx, (size_t)n_str * 32, hipMemcpyHostToDevice, h->st));
+	if (cap_u) HIPCHK(hipMemsetAsync(d_urec, 0xff, (size_t)cap_u * 40, h->st));   // (head -1: a chain that is not stored)
+	if (cap_txt) HIPCHK(hipMemsetAsync(h->qbytes.p, 0, (size_t)cap_txt, h->st));  // (what no piece of a damaged vtx covers comes back as 0)
+	int64_t inf[4];
+	const int64_t stored = unitig_text_run(h, n_str, h->qout.p, canonical ? 1 : 0, min_reads, cap_u, cap_txt, d_urec, h->qbytes.p, inf);
+	if (info) memcpy(info, inf, sizeof(inf));
+	if (stored > 0) {                                              // only the stored chains reach the caller's buffers: the others' records and slices stay as they were
+		std::vector<int64_t> ur((size_t)cap_u * 5);
+		const int64_t nu = std::min(cap_u, inf[0]);
+		HIPCHK(hipMemcpyAsync(ur.data(), d_urec, (size_t)nu * 40, hipMemcpyDeviceToHost, h->st));
+		HIPCHK(hipStreamSynchronize(h->st));
+		int64_t lo = -1, hi = -1;                                  // (the slices of stored chains lie behind each other: one copy per run of them)
+		auto flush = [&]() { if (hi > lo) HIPCHK(hipMemcpyAsync(txt + lo, h->qbytes.p + lo, (size_t)(hi - lo), hipMemcpyDeviceToHost, h->st)); };
+		for (int64_t u = 0; u < nu; ++u) {
+			const int64_t *r = ur.data() + 5 * u;
+			if (r[0] < 0) continue;
+			memcpy(urec + 5 * u, r, 40);
+			if (r[2] != hi) { flush(); lo = r[2]; }
+			hi = r[2] + r[3];
+		}
+		flush();
+		HIPCHK(hipStreamSynchronize(h->st));
+	}
+	return stored;
+}

@@ -72,6 +72,10 @@ def load_hip_lib():
         "rb2_hip_contained_dev": (None, [vp, i64, vp, vp]),
         "rb2_hip_irreducible": (i64, [vp, i64, vp, vp, i64, i64, i64, i64, vp, vp]),
         "rb2_hip_irreducible_dev": (None, [vp, i64, vp, vp, i64, i64, i64, i64, i64, vp, vp]),
+        "rb2_hip_unitig_chains": (i64, [vp, i64, i64, vp, vp, vp]),
+        "rb2_hip_unitig_chains_dev": (None, [vp, i64, i64, vp, vp, vp]),
+        "rb2_hip_unitig_text": (i64, [vp, i64, vp, i32, i64, i64, i64, vp, vp, vp]),
+        "rb2_hip_unitig_text_dev": (i64, [vp, i64, vp, i32, i64, i64, i64, vp, vp, vp]),
         "rb2_hip_reserve": (None, [vp, i64, i64, i64]),
         "rb2_hip_num_subropes": (i32, []),
         "rb2_hip_memcpy": (None, [vp, vp, vp, i64, i32]),
@@ -141,6 +145,7 @@ ABI_SYMBOLS = [
     "rb2_hip_overlap", "rb2_hip_overlap_dev", "rb2_hip_string_ids", "rb2_hip_string_ids_dev", "rb2_hip_kmers",
     "rb2_hip_approx", "rb2_hip_approx_dev", "rb2_hip_contained", "rb2_hip_contained_dev",
     "rb2_hip_irreducible", "rb2_hip_irreducible_dev",
+    "rb2_hip_unitig_chains", "rb2_hip_unitig_chains_dev", "rb2_hip_unitig_text", "rb2_hip_unitig_text_dev",
     "rb2_hip_num_subropes", "rb2_hip_memcpy", "rb2_hip_use_stream",
     "rb2_hip_dev_free", "rb2_hip_synth_reads", "rb2_hip_synth_reads_cov", "rb2_hip_synth_reads_skew", "rb2_hip_sync", "rb2_hip_sparse_stats", "rb2_hip_layout_stats", "rb2_hip_rewind_stats", "rb2_hip_window_stats", "rb2_hip_host_register", "rb2_hip_host_unregister", "rb2_hip_profile",
     "rb2_hip_profile_get", "rb2_hip_kernel_name", "rb2_hip_layout",
@@ -702,6 +707,62 @@ class HipBwt:
         res = self.irreducible(texts, min_ovlp, **kw)
         rows = [(int(s), d, l, e) for s, r in zip(ids.tolist(), res) for d, l, e in (r or [])]
         return np.array(sorted(rows), np.int64).reshape(-1, 4)
+
+    # -- unitigs: the chains of a string graph and their texts (include/rb2_hip.h) ---------------------------------------------------
+    def unitig_chains(self, edges, n_str=None):
+        """rb2_hip_unitig_chains: the chains of the edge list edges (m, 4) int64 = src, dst, l, ext (what edges() returns) over n_str
+        vertices (None: the strings of the index).  Returns (vtx (n_str, 4) int64 = head, rank, off, ext_in, info (4,) int64 = chains,
+        cycles, vertices of the longest chain, edges ignored)"""
+        edges = np.ascontiguousarray(np.asarray(edges, dtype=np.int64).reshape(-1, 4))
+        n = int(self.counts()[:, 0].sum()) if n_str is None else int(n_str)
+        vtx = np.zeros((max(n, 0), 4), np.int64)
+        info = np.zeros(4, np.int64)
+        self.L.rb2_hip_unitig_chains(self.h, n, len(edges), edges.ctypes.data, vtx.ctypes.data, info.ctypes.data)
+        return vtx, info
+
+    def unitig_chains_dev(self, n_str, m, edges_dev, vtx_dev, info_dev):
+        """rb2_hip_unitig_chains_dev: all three pointers in this device's memory; asynchronous on the handle's stream"""
+        self.L.rb2_hip_unitig_chains_dev(self.h, n_str, m, edges_dev, vtx_dev, info_dev)
+
+    def unitig_text_raw(self, vtx, canonical=False, min_reads=1, cap_u=0, cap_txt=0, fill=0):
+        """rb2_hip_unitig_text as it is: (chains stored, urec (cap_u, 5) int64, txt (cap_txt,) uint8, info (4,) int64 = chains selected,
+        their total text length, those with a short piece, chains stored); urec and txt start as fill, and what belongs to a chain that
+        is not stored stays so"""
+        vtx = np.ascontiguousarray(np.asarray(vtx, dtype=np.int64).reshape(-1, 4))
+        urec = np.full((max(int(cap_u), 0), 5), fill, np.int64)
+        txt = np.full(max(int(cap_txt), 0), fill, np.uint8)
+        info = np.zeros(4, np.int64)
+        stored = self.L.rb2_hip_unitig_text(self.h, len(vtx), vtx.ctypes.data, int(bool(canonical)), int(min_reads), int(cap_u), int(cap_txt),
+                                            urec.ctypes.data if len(urec) else None, txt.ctypes.data if len(txt) else None, info.ctypes.data)
+        return int(stored), urec, txt, info
+
+    def unitig_text(self, vtx, canonical=False, min_reads=1):
+        """the texts of the chains vtx (unitig_chains) describes: one call with caps 0 for the sizes, one that stores.  Returns (urec (k, 5)
+        int64 = head, n_reads, text_off, text_len, flags (bit 0 circular, bit 1 a short piece) of the selected chains by increasing head,
+        txt uint8: the nt6 text of chain u is txt[text_off : text_off + text_len])"""
+        _, _, _, info = self.unitig_text_raw(vtx, canonical, min_reads)
+        stored, urec, txt, info = self.unitig_text_raw(vtx, canonical, min_reads, int(info[0]), int(info[1]))
+        assert stored == len(urec) == info[0]
+        return urec, txt
+
+    def unitig_text_dev(self, n_str, vtx_dev, urec_dev, txt_dev, canonical=False, min_reads=1, cap_u=0, cap_txt=0):
+        """rb2_hip_unitig_text_dev: vtx, urec (5 cap_u int64) and txt (cap_txt bytes) in this device's memory.  Synchronises the handle's
+        stream once; returns (chains stored, info (4,) int64)"""
+        info = np.zeros(4, np.int64)
+        stored = self.L.rb2_hip_unitig_text_dev(self.h, n_str, vtx_dev, int(bool(canonical)), int(min_reads), int(cap_u), int(cap_txt), urec_dev or None, txt_dev or None,
+                                                info.ctypes.data)
+        return int(stored), info
+
+    def unitigs(self, min_ovlp, canonical=True, min_reads=1, **kw):
+        """the unitigs of the string graph of an index of both strands in input order, strings 2i and 2i + 1 a read and its reverse
+        complement (as reduce(pairs=True) leaves it): edges(min_ovlp=min_ovlp, pairs=True, **kw), unitig_chains, unitig_text.  A list of
+        (text as an nt6 uint8 array, the read ids in chain order, circular) by increasing head id; canonical: one of every unitig and
+        its reverse complement.  Needs build_ssa() (none is built here)"""
+        vtx, _ = self.unitig_chains(self.edges(min_ovlp=min_ovlp, pairs=True, **kw))
+        urec, txt = self.unitig_text(vtx, canonical, min_reads)
+        order = np.lexsort((vtx[:, 1], vtx[:, 0]))                  # by head, then by rank
+        first = np.searchsorted(vtx[order, 0], urec[:, 0])
+        return [(txt[o:o + l].copy(), order[f:f + k].copy(), bool(fl & 1)) for (hd, k, o, l, fl), f in zip(urec.tolist(), first.tolist())]
 
     # -- measurement helpers ----------------------------------------------------------------
     def dev_alloc(self, nbytes):

@@ -48,6 +48,15 @@ a record of extension e at least e more), records per query and the share of the
 lengths below the read's own) that survive.  On 4000 reads the same run times what a user could compose before -- overlaps(), extract of
 every neighbour, and the pruning on the host (tests/irreducible_ref.py: edges_by_composition) -- against irreducible(pairs=True), and
 compares the edge sets (equals_fused).
+With --unitigs only the unitig calls are measured and stored under "unitigs" in the --out file, whose other entries stay: the index of
+--irreducible (both strands of reads drawn from one genome at 30x, input order, after reduce(pairs=True); --reads, default 1 000 000);
+its edges come from rb2_hip_irreducible over every string and rb2_hip_string_ids, put together with numpy (not timed: HipBwt.edges
+walks Python lists).  unitig_chains_dev and unitig_text_dev (canonical, caps from a sizing call that is timed by itself) are timed
+separately -- host clock round a synchronise, median of three after a warm-up -- and reported with the chains, the longest chain, the
+doublings queued, the total text and the LF steps per second (one step per symbol written).  The composition it replaces is timed on a
+sample the host can follow: the first --unitig-sample vertices of the longest chain and the edges among them -- the Python chain walk
+of tests/unitig_ref.py (chains) plus extract() of every read of the sample and the gluing of texts() -- against unitig_chains and
+unitig_text (host buffers, min_reads=2) on the same edges; the texts are compared (equals_fused).
 """
 import argparse
 import json
@@ -702,6 +711,107 @@ def irreducible_case(a, res):
     res["irreducible"] = {"index": index, "cases": [row, brow, frow]}
 
 
+def unitig_case(a, res):
+    import unitig_ref as U
+    L, M = 101, 8
+    n = a.reads or 1_000_000
+    min_ovlp = a.irreducible_min_ovlp
+    g = HipBwt(0)
+    nb = 2 * n * (L + 1)
+    p = g.dev_alloc(nb)
+    g.synth_reads(p, 0, n, L, seed=42, strand=1, genome_len=n * L // 30)
+    g.insert_multi_dev(p, nb)
+    g.sync()
+    g.dev_free(p)
+    gone = g.reduce(pairs=True)
+    ns = int(g.counts()[:, 0].sum())
+    g.build_ssa(5)
+    # the edges of every string: irreducible records, their `$` ranges resolved to ids, rows src, dst, l, ext
+    t = time.perf_counter()
+    _, txt, ln = g.extract_raw(np.arange(ns, dtype=np.int64), L)
+    assert (ln == L).all()
+    flat = np.ascontiguousarray(txt.reshape(-1)); off = np.arange(ns + 1, dtype=np.int64) * L
+    rec = np.zeros((ns, M, 4), np.int64); cnt = np.zeros(ns, np.int64)
+    g.L.rb2_hip_irreducible(g.h, ns, flat.ctypes.data, off.ctypes.data, min_ovlp, L - min_ovlp, a.irreducible_steps, M, rec.ctypes.data, cnt.ctypes.data)
+    assert (cnt != -1).all()
+    found = np.where(cnt <= -2, -2 - cnt, cnt)                      # (a read out of steps or of slots keeps the records it has: the graph is what it is)
+    live = np.arange(M)[None, :] < np.minimum(found, M)[:, None]
+    who, recs = np.nonzero(live)[0], rec[live]
+    H8 = 8
+    _, ids, n_ids = g.string_ids_raw(recs[:, 2:], H8)
+    hit = np.arange(H8)[None, :] < np.minimum(n_ids, H8)[:, None]
+    rows = np.nonzero(hit)[0]
+    edges = np.ascontiguousarray(np.stack([who[rows], ids[hit] ^ 1, recs[rows, 0], recs[rows, 1]], 1).astype(np.int64))
+    m = len(edges)
+    edges_s = time.perf_counter() - t
+    del txt, flat, rec
+    index = {"reads": n, "read_len": L, "genome_len": n * L // 30, "strands": 2, "sorting_order": 0, "strings_removed": int(len(gone)), "strings": ns,
+             "symbols": int(g.counts().sum()), "min_ovlp": min_ovlp, "edges": m,
+             "reads_out_of_steps": int((cnt <= -2).sum()), "reads_with_more_records_than_slots": int((found > M).sum()), "ranges_wider_than_slots": int((n_ids > H8).sum()), "edges_seconds_not_part_of_the_measurement": edges_s, "layout": g.layout_stats()}
+    print("unitigs: %d strings, %d edges in %.1f s" % (ns, m, edges_s), file=sys.stderr, flush=True)
+    de, dv, di = g.dev_alloc(max(edges.nbytes, 8)), g.dev_alloc(32 * ns), g.dev_alloc(32)
+    g.L.rb2_hip_memcpy(g.h, de, edges.ctypes.data, edges.nbytes, 0)
+    csec, clo, chi = spread(lambda: g.unitig_chains_dev(ns, m, de, dv, di), g.sync)
+    info = np.zeros(4, np.int64); vtx = np.zeros((ns, 4), np.int64)
+    g.L.rb2_hip_memcpy(g.h, info.ctypes.data, di, 32, 1)
+    g.L.rb2_hip_memcpy(g.h, vtx.ctypes.data, dv, vtx.nbytes, 1)
+    K = 0
+    while (1 << K) < ns:
+        K += 1
+    crow = {"case": "unitig_chains_dev, %d vertices, %d edges" % (ns, m), "measured": True, "seconds": csec, "seconds_fastest": clo, "seconds_slowest": chi,
+            "vertices_per_s": ns / csec, "chains": int(info[0]), "cycles": int(info[1]), "longest_chain": int(info[2]), "edges_ignored": int(info[3]),
+            "doublings_queued": 2 * K, "launches": 2 * K + 5 + -(-m // (1 << 24))}
+    got = {}
+
+    def size():
+        got["size"] = g.unitig_text_dev(ns, dv, None, None, True, 1, 0, 0)
+    ssec, _, _ = spread(size, lambda: None)
+    sel, total = int(got["size"][1][0]), int(got["size"][1][1])
+    du, dt = g.dev_alloc(max(40 * sel, 8)), g.dev_alloc(max(total, 8))
+
+    def text():
+        got["text"] = g.unitig_text_dev(ns, dv, du, dt, True, 1, sel, total)
+    tsec, tlo, thi = spread(text, lambda: None)
+    stored, tinfo = got["text"]
+    urec = np.zeros((sel, 5), np.int64)
+    g.L.rb2_hip_memcpy(g.h, urec.ctypes.data, du, urec.nbytes, 1)
+    chosen = np.zeros(ns, bool); chosen[urec[:, 0]] = True
+    steps_all = int(L * sel * 2 + vtx[chosen[vtx[:, 0]] & (vtx[:, 0] != np.arange(ns)), 3].sum())   # two walks per selected head, ext_in steps for every other vertex of a selected chain
+    trow = {"case": "unitig_text_dev canonical=1 min_reads=1, caps from the sizing call", "measured": True, "seconds": tsec, "seconds_fastest": tlo, "seconds_slowest": thi,
+            "sizing_call_seconds": ssec, "chains_selected": sel, "chains_stored": int(stored), "total_text": total, "chains_with_a_short_piece": int(tinfo[2]),
+            "lf_steps": steps_all, "lf_steps_per_s": steps_all / tsec, "text_bytes_per_s": total / tsec}
+    for q in (de, dv, di, du, dt):
+        g.dev_free(q)
+    print("unitigs: chains %.4f s, text %.4f s" % (csec, tsec), file=sys.stderr, flush=True)
+    # the composition on a sample: the first vertices of the longest chain, the edges among them
+    h0 = int(vtx[np.argmax(vtx[:, 1]), 0])
+    S = min(a.unitig_sample, int(info[2]))
+    V = np.sort(np.flatnonzero((vtx[:, 0] == h0) & (vtx[:, 1] < S)))
+    inV = np.zeros(ns, bool); inV[V] = True
+    sub = np.ascontiguousarray(edges[inV[edges[:, 0]] & inV[edges[:, 1]]])
+    loc = sub.copy(); loc[:, 0] = np.searchsorted(V, sub[:, 0]); loc[:, 1] = np.searchsorted(V, sub[:, 1])
+
+    def composed():
+        v, _ = U.chains(len(V), loc)
+        strings = g.extract(V, L)
+        got["composed"] = U.texts(strings, v, False, 2)
+
+    def fused():
+        v, _ = g.unitig_chains(sub)
+        got["fused"] = g.unitig_text(v, False, 2)
+    bsec = timed(composed, lambda: None, reps=1)
+    fsec = timed(fused, lambda: None, reps=1)
+    cu, ct, _ = got["composed"]
+    fu, ft = got["fused"]
+    same = bool(np.array_equal(ct, ft) and np.array_equal(V[cu[:, 0]], fu[:, 0]) and np.array_equal(cu[:, 1:], fu[:, 1:]))
+    brow = {"case": "baseline: Python chain walk (tests/unitig_ref.py chains) + extract of every read + gluing, the first %d vertices of the longest chain and the %d edges among them" % (len(V), len(sub)),
+            "measured": True, "seconds": bsec, "unitigs": int(len(cu)), "text": int(len(ct)), "equals_fused": same}
+    frow = {"case": "unitig_chains + unitig_text (host buffers, min_reads=2) on the same edges", "measured": True, "seconds": fsec, "unitigs": int(len(fu)), "text": int(len(ft)),
+            "composed_over_fused": bsec / fsec}
+    g.close()
+    res["unitigs"] = {"index": index, "cases": [crow, trow, brow, frow]}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default="")
@@ -728,7 +838,17 @@ def main():
     ap.add_argument("--irreducible-queries", type=int, default=1_000_000)
     ap.add_argument("--irreducible-min-ovlp", type=int, default=40)
     ap.add_argument("--irreducible-steps", type=int, default=1 << 16, help="max_steps of the irreducible-overlap query")
+    ap.add_argument("--unitigs", action="store_true", help="only the unitig calls (added to an existing --out file)")
+    ap.add_argument("--unitig-sample", type=int, default=20_000, help="vertices of the sample the host composition is timed on")
     a = ap.parse_args()
+    if a.unitigs:
+        res = {"cases": []}
+        if a.out and os.path.exists(a.out):
+            with open(a.out) as f:
+                res = json.load(f)
+        unitig_case(a, res)
+        finish(a, res)
+        return
     if a.irreducible:
         res = {"cases": []}
         if a.out and os.path.exists(a.out):
