@@ -15,6 +15,7 @@
  *   mr_itr_first/next_block      mrope.c:111-130         rb2_hip_rope_bytes() + rb2_hip_download_rope()
  *   mr_restore / rope_restore    mrope.c:145, rope.c:308 rb2_hip_load_ropes()
  *   rld_restore                  rld0.c:246-300          rb2_hip_load_fmd[_file]()
+ *   rld_enc .. rld_dump          rld0.c:107-244          rb2_hip_save_fmd[_file]()
  *
  * Run-length byte streams crossing this boundary use ropebwt2's "43+3" codec (rle.h:39-75), so
  * the host can splice them straight into rope leaves.  The device itself only ever emits the
@@ -138,6 +139,30 @@ void rb2_hip_load_ropes(rb2_hip_t *h, const uint8_t *const rle[6], const int64_t
 int64_t rb2_hip_load_fmd(rb2_hip_t *h, const void *fmd, int64_t n_bytes);
 /* the same for a file that is read into memory first; a file that cannot be opened or read is fatal with its name */
 int64_t rb2_hip_load_fmd_file(rb2_hip_t *h, const char *path);
+
+/* ---- the index as an .fmd image (csrc/rb2_fmd_save.h, csrc/rb2_fmd_plan.h) ----
+ * The image is fermi's "RLD\3": what `ropebwt2 -d` and rb2_fmd_write produce from the same BWT, byte for byte -- an 80-byte header, the
+ * stream of n_bytes (blocks of 8 words: the run-length delta codes of the six ropes one after the other, equal neighbours merged across
+ * leaves, pieces and ropes) and n_frames rank frames of 56 bytes.  The SIZE of the image is 80 + n_bytes + 56 n_frames.
+ * rb2_hip_save_fmd returns SIZE and writes the image to dst (host memory) only if dst != NULL and cap >= SIZE; otherwise it writes
+ * NOTHING, not a byte of dst, and still returns SIZE: a caller sizes with one call and fetches with a second (the handle remembers SIZE
+ * until the rows change or a sampled suffix array is built or dropped, so the second call encodes once).  It synchronises before it returns.
+ * rb2_hip_save_fmd_file writes the same bytes to path: the stream goes out at its file offset while later parts are still being encoded,
+ * the header and the rank frames are written last.  Returns SIZE, or -1 when the file cannot be opened or written -- the caller's error,
+ * nothing fatal; what the file holds then is undefined.
+ * Both calls leave the index UNCHANGED: the same rows, counts and rope hashes, the sampled suffix array kept; like rb2_hip_stream_rope they
+ * finish a lazy insert and may leave a sparse layout for the dense one.  An EMPTY index gives the image the host writer gives for no run at
+ * all: the header, an all-zero first block, a closing header of two zero words and one zero frame, 216 bytes.
+ * Everything from the bit planes to the finished words happens on the device, in batches of at most 2^24 runs (RB2_FMDS_BATCH lowers
+ * that, RB2_FMDS_SEG sets the runs per segment of the block-boundary tables, 96 .. 8192; both are read once per call and exist for tests);
+ * the host copies finished bytes out of two pinned buffers.  Device memory for it does not grow with the index: at most 1.3 GB.
+ * Runs below 2^51 symbols, as for the host writer and the loader.  One case is outside the byte-for-byte promise: a run of 2^50 symbols or
+ * more (a 64-bit code) that arrives right behind a code ending on a word boundary makes the host writer, like rld0.c:145, shift a word by
+ * 64, so there is no defined image to equal; the encoder places such a code like any other.  No index a device holds comes near it.  Fatal: one rank of a sharded index; an index of more rows than 2^24
+ * rank frames cover (with frames of 2^11 rows, as reads give them, 3.4e10 rows); a block of 2^30 symbols or more right in front of the
+ * last block of a chunk of 2^23 words, whose header of seven words leaves that block no payload word (the reference misbehaves there). */
+int64_t rb2_hip_save_fmd(rb2_hip_t *h, void *dst, int64_t cap);
+int64_t rb2_hip_save_fmd_file(rb2_hip_t *h, const char *path);
 
 /* Take strings out of the index again (no counterpart in the reference, whose ropes only grow).  ids: n string
  * ids in host memory, in any order, duplicates allowed -- a string id is a row of the `$` block, what rb2_hip_extract takes and

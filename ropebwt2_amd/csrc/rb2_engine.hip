@@ -20,6 +20,10 @@
 #include "rb2_unitig.h"
 #include "rb2_fmd_load.h"
 #include "rb2_delete.h"
+#include "rb2_fmd_save.h"
+#include <cerrno>
+#include <fcntl.h>
+#include <unistd.h>
 
 using namespace rb2;
 
@@ -270,6 +274,8 @@ struct rb2_hip_s {
 	int nactive = 1;                    // ranks that own a sub-rope other than rope $ (sizes the grids of a sharded rank: tile_grid)
 	DevBuf<uint8_t> xstage, xpack; DevBuf<uint16_t> xnb; DevBuf<uint64_t> xoff;   // k_export staging, packed bytes, chunk offsets
 	uint8_t *xhost[2] = {nullptr, nullptr}; uint64_t *xtot[2] = {nullptr, nullptr}; hipEvent_t xev[2] = {nullptr, nullptr};   // pinned double buffer
+	int64_t fmds_size = -1;             // rb2_hip_save_fmd: the size of the image of the rows as they are (-1: not known; dropped by index_rows_change, i.e. with the
+	                                    // sampled suffix array: by whatever changes the rows, and by rb2_hip_ssa_build / rb2_hip_ssa_drop, which costs one more sizing pass)
 	int compact_ok = 1;                 // RB2_COMPACT=0: dense rounds always write plain (three-plane) windows
 	int compact_stats = 0;              // RB2_COMPACT_STATS=1: k_merge counts the windows it writes per format (rb2_hip_window_stats)
 	int64_t n_compact_rounds = 0;       // dense rounds that were allowed to write compact windows
@@ -414,6 +420,7 @@ static uint64_t max_batch_strings()
 static void index_rows_change(rb2_hip_t *h, bool drained = false)
 {
 	h->ssa_valid = false; h->ssa_s = 0; h->ssa_n = 0; h->ssa_nstr = 0;
+	h->fmds_size = -1;
 	if (!h->ssa_smp.p && !h->ssa_len.p && !h->ssa_head.p) return;
 	if (!drained) HIPCHK(hipStreamSynchronize(h->st));         // a rb2_hip_locate_dev may still be reading it
 	h->ssa_smp.release(); h->ssa_len.release(); h->ssa_head.release();
@@ -1704,6 +1711,219 @@ void rb2_hip_rank1a(rb2_hip_t *h, int b, int64_t x, int64_t cx[6])
 } // extern "C"
 #include "rb2_query_host.h"                                  /* the FM-index queries: their host side (templates: C++ linkage) */
 extern "C" {
+
+/* ---- the index as an .fmd image (kernels in rb2_fmd_save.h, the arithmetic in rb2_fmd_plan.h) ---------------- */
+
+static uint64_t fmds_knob(const char *name, uint64_t dflt, uint64_t lo, uint64_t hi)
+{
+	const char *e = getenv(name);
+	const long long v = e ? atoll(e) : 0;
+	return v > 0 ? std::min<uint64_t>(std::max<uint64_t>((uint64_t)v, lo), hi) : dflt;
+}
+
+/* where the finished bytes go: host memory or a file, at their offset in the image */
+struct FmdsOut { uint8_t *dst; int fd; bool err; };
+static void fmds_put(FmdsOut &o, const void *src, size_t n, uint64_t off)
+{
+	if (o.dst) { memcpy(o.dst + off, src, n); return; }
+	const char *q = (const char*)src;
+	while (n > 0 && !o.err) {
+		const ssize_t k = pwrite(o.fd, q, n, (off_t)off);
+		if (k < 0) { if (errno == EINTR) continue; o.err = true; break; }
+		q += k; n -= (size_t)k; off += (uint64_t)k;
+	}
+}
+
+constexpr uint64_t FMDS_BATCH_MAX = 1ull << 24;            /* run heads per batch */
+constexpr uint64_t FMDS_BUCKET_CAP = 1ull << 24;           /* buckets of rows whose last header is kept for the rank frames */
+
+/* the image of the index to o (null: only its size is wanted: nothing is written, no block is staged).  Returns the size. */
+static int64_t fmds_encode(rb2_hip_t *h, FmdsOut *o)
+{
+	hipStream_t st = h->st;
+	uint64_t total = 0, mcnt[6] = {0, 0, 0, 0, 0, 0};
+	for (int r = 0; r < NR; ++r) { total += h->h_rope[r].n; for (int a = 0; a < 6; ++a) mcnt[a] += h->h_rope[r].cnt[a]; }
+	uint8_t hdr[80];
+	const uint32_t ab = 6u << 16 | 3u;
+	memset(hdr, 0, sizeof(hdr));
+	memcpy(hdr, "RLD\3", 4); memcpy(hdr + 4, &ab, 4); memcpy(hdr + 32, mcnt, 48);
+	if (total == 0) {                                          /* block 0 and the closing header hold zeros, and so does the one frame */
+		const uint64_t n_bytes = 80, n_frames = 1;
+		memcpy(hdr + 16, &n_bytes, 8); memcpy(hdr + 24, &n_frames, 8);
+		if (o) { uint8_t z[80 + 56]; memset(z, 0, sizeof(z)); fmds_put(*o, z, sizeof(z), 80); fmds_put(*o, hdr, 80, 0); }
+		return (int64_t)fmds_image_size(n_bytes, n_frames);
+	}
+	const uint32_t SEG = (uint32_t)fmds_knob("RB2_FMDS_SEG", 4096, FMDS_SEG_MIN, FMDS_SEG_MAX);
+	const uint64_t RCAP = std::min<uint64_t>(fmds_knob("RB2_FMDS_BATCH", FMDS_BATCH_MAX, 2048, FMDS_BATCH_MAX), (total + LEAF - 1) / LEAF * LEAF + 2048);
+	const uint64_t OUTCAP = std::min<uint64_t>(RCAP + 1, FMDS_CHUNK_BLOCKS);   /* blocks a batch emits at the most: each holds a run (the closing header none), and a batch ends with its chunk */
+	const uint64_t nseg_max = RCAP / SEG + 2, ng_max = nseg_max / FMDS_GROUP + 2;
+	const int bbits = fmds_bucket_bits(total, FMDS_BUCKET_CAP);
+	const uint64_t nbk = (total >> bbits) + 2;
+	DevBuf<uint64_t> recb[2], tab, gtab, lastcnt, bidx, bS, bpart, outd[2];
+	DevBuf<uint32_t> W, nxt, wg, part;
+	DevBuf<FmdsEntry> gst, sst;
+	DevBuf<FmdsState> dstate;
+	recb[0].ensure(RCAP + 2); recb[1].ensure(RCAP + 2); W.ensure(RCAP + 2); nxt.ensure(RCAP + 2); wg.ensure(RCAP / LEAF / 16 + 4); part.ensure(RCAP / 1024 + 4);
+	tab.ensure(nseg_max * FMDS_ENTRIES); gtab.ensure(ng_max * FMDS_ENTRIES); gst.ensure(ng_max); sst.ensure(nseg_max); lastcnt.ensure(nseg_max * 7); dstate.ensure(1);
+	HIPCHK(hipMemsetAsync(dstate.p, 0, sizeof(FmdsState), st));
+	uint8_t *outh[2] = {nullptr, nullptr};
+	FmdsState *hst = nullptr;
+	hipEvent_t evS, evO[2];
+	HIPCHK(hipHostMalloc((void**)&hst, sizeof(FmdsState), hipHostMallocDefault));
+	HIPCHK(hipEventCreateWithFlags(&evS, hipEventDisableTiming));
+	for (int i = 0; i < 2; ++i) HIPCHK(hipEventCreateWithFlags(&evO[i], hipEventDisableTiming));
+	if (o) {
+		bidx.ensure(nbk); bS.ensure(nbk); bpart.ensure(nbk / 1024 + 4);
+		HIPCHK(hipMemsetAsync(bidx.p, 0, nbk * 8, st)); HIPCHK(hipMemsetAsync(bS.p, 0, nbk * 8, st));
+		for (int i = 0; i < 2; ++i) { outd[i].ensure(OUTCAP * FMDS_BW); HIPCHK(hipHostMalloc((void**)&outh[i], OUTCAP * FMDS_BW * 8, hipHostMallocDefault)); }
+	}
+	auto free_all = [&]() {                                    /* everything the call holds, on every way out */
+		hipStreamSynchronize(st);
+		for (int i = 0; i < 2; ++i) { if (outh[i]) hipHostFree(outh[i]); outh[i] = nullptr; hipEventDestroy(evO[i]); outd[i].release(); }
+		hipHostFree(hst); hipEventDestroy(evS);
+		recb[0].release(); recb[1].release(); W.release(); nxt.release(); wg.release(); part.release(); tab.release(); gtab.release(); gst.release(); sst.release(); lastcnt.release(); dstate.release();
+		bidx.release(); bS.release(); bpart.release();
+	};
+	auto give_up = [&]() { free_all(); if (o && o->fd >= 0) close(o->fd); };   /* in front of a fatal error: its handler may return to the caller's caller */
+	const PoolView pv = h->pool[h->pside].view();
+	int r = 0, par = 0, buf = 0, rb = 0;                      /* rb: which of the two head arrays holds this batch */
+	uint64_t lc = 0, P0 = 0, ncur = 0, blk0 = 0;
+	uint32_t type0 = 0, ftype = 0;
+	bool done = false;
+	auto skip = [&]() { while (r < NR && lc * LEAF >= h->h_rope[r].n) { P0 += h->h_rope[r].n; ++r; lc = 0; } };   /* pieces in row order are sub-ropes 0 .. NR - 1 */
+	struct { bool on; int buf; uint64_t blk0, nout; bool done; uint32_t type; } pend = {false, 0, 0, 0, false, 0};
+	auto drain = [&]() {                                       /* the blocks of the batch before: out of their pinned buffer */
+		if (!pend.on) return;
+		HIPCHK(hipEventSynchronize(evO[pend.buf]));
+		const uint64_t nb = pend.done ? (pend.nout - 1) * 64 + fmds_hdr_words(pend.type) * 8 : pend.nout * 64;
+		fmds_put(*o, outh[pend.buf], (size_t)nb, 80 + pend.blk0 * 64);
+		pend.on = false;
+	};
+	skip();
+	while (!done) {
+		DevBuf<uint64_t> &rec = recb[rb];
+		uint64_t nl = 0;
+		const uint32_t *nnew = nullptr;
+		if (r < NR) {
+			const RopeDesc &d = h->h_rope[r];
+			const uint64_t avail = RCAP > ncur + 1 ? (RCAP - ncur - 1) / LEAF : 0;
+			nl = std::min<uint64_t>(avail, (d.n + LEAF - 1) / LEAF - lc);
+			if (nl) {
+				const uint64_t nwg = (nl + 15) / 16;
+				const FmdsInCount ic{wg.p, nwg};
+				hipLaunchKernelGGL(k_fmds_heads<false>, dim3((unsigned)nwg), dim3(256), 0, st, pv, d.leaf0, d.n, lc, (uint32_t)nl, P0, ncur, rec.p, wg.p);
+				hipLaunchKernelGGL((k_fmds_scan_part<false, uint32_t, FmdsInCount>), dim3(cdiv(nwg, 1024)), dim3(256), 0, st, ic, part.p);
+				hipLaunchKernelGGL((k_fmds_scan_top<false, uint32_t, FmdsInCount>), dim3(1), dim3(256), 0, st, ic, part.p);
+				hipLaunchKernelGGL((k_fmds_scan_apply<false, uint32_t, FmdsInCount>), dim3(cdiv(nwg, 1024)), dim3(256), 0, st, ic, (const uint32_t*)part.p, wg.p);
+				hipLaunchKernelGGL(k_fmds_heads<true>, dim3((unsigned)nwg), dim3(256), 0, st, pv, d.leaf0, d.n, lc, (uint32_t)nl, P0, ncur, rec.p, wg.p);
+				nnew = wg.p + nwg;
+				lc += nl;
+				skip();
+			}
+		}
+		const uint32_t flush = r == NR;
+		hipLaunchKernelGGL(k_fmds_begin, dim3(1), dim3(1), 0, st, dstate.p, rec.p, ncur, nnew, flush, total, type0, blk0);
+		const uint64_t mub = ncur + nl * LEAF + 1;              /* heads at the most (the grids below are sized for them; the kernels read the count) */
+		const FmdsInWidth iw{rec.p, dstate.p};
+		hipLaunchKernelGGL((k_fmds_scan_part<false, uint32_t, FmdsInWidth>), dim3(cdiv(mub, 1024)), dim3(256), 0, st, iw, part.p);
+		hipLaunchKernelGGL((k_fmds_scan_top<false, uint32_t, FmdsInWidth>), dim3(1), dim3(256), 0, st, iw, part.p);
+		hipLaunchKernelGGL((k_fmds_scan_apply<false, uint32_t, FmdsInWidth>), dim3(cdiv(mub, 1024)), dim3(256), 0, st, iw, (const uint32_t*)part.p, W.p);
+		hipLaunchKernelGGL(k_fmds_next, dim3(cdiv(mub + 1, 256)), dim3(256), 0, st, (const FmdsState*)dstate.p, (const uint64_t*)rec.p, (const uint32_t*)W.p, nxt.p);
+		const uint64_t nseg = mub / SEG + 1, ng = (nseg + FMDS_GROUP - 1) / FMDS_GROUP;
+		hipLaunchKernelGGL(k_fmds_table, dim3((unsigned)nseg), dim3(320), 0, st, (const FmdsState*)dstate.p, (const uint32_t*)nxt.p, SEG, tab.p);
+		hipLaunchKernelGGL(k_fmds_group, dim3((unsigned)ng), dim3(320), 0, st, (const FmdsState*)dstate.p, (const uint64_t*)tab.p, SEG, gtab.p);
+		hipLaunchKernelGGL(k_fmds_resolve, dim3(1), dim3(1), 0, st, dstate.p, (const uint64_t*)rec.p, (const uint32_t*)W.p, (const uint32_t*)nxt.p, (const uint64_t*)tab.p, (const uint64_t*)gtab.p, SEG, gst.p);
+		HIPCHK(hipMemcpyAsync(hst, dstate.p, sizeof(FmdsState), hipMemcpyDeviceToHost, st));
+		HIPCHK(hipEventRecord(evS, st));
+		if (o) {
+			hipLaunchKernelGGL(k_fmds_down, dim3(cdiv(ng, 64)), dim3(64), 0, st, (const FmdsState*)dstate.p, (const uint64_t*)tab.p, SEG, (const FmdsEntry*)gst.p, sst.p);
+			hipLaunchKernelGGL(k_fmds_write, dim3((unsigned)nseg), dim3(256), 0, st, dstate.p, (const uint64_t*)rec.p, (const uint32_t*)W.p, (const uint32_t*)nxt.p, (const FmdsEntry*)sst.p, SEG, par,
+					outd[buf].p, lastcnt.p, bidx.p, bS.p, bbits);
+			hipLaunchKernelGGL(k_fmds_hdrfix, dim3(cdiv(nseg, 256)), dim3(256), 0, st, (const FmdsState*)dstate.p, (const FmdsEntry*)sst.p, (const uint32_t*)nxt.p, (const uint64_t*)lastcnt.p, SEG, par, outd[buf].p);
+		}
+		hipLaunchKernelGGL(k_fmds_carry, dim3((unsigned)std::min<uint64_t>(cdiv(mub + 1, 256), 2048)), dim3(256), 0, st, (const FmdsState*)dstate.p, (const uint64_t*)rec.p, recb[rb ^ 1].p);
+		HIPCHK(hipGetLastError());
+		HIPCHK(hipEventSynchronize(evS));                          /* one wait per batch: what it emits and what it leaves decide the next one */
+		const FmdsState S = *hst;
+		if (S.err) { give_up(); rb2_fatal("[rb2_hip] save_fmd: a block of 2^30 symbols or more right in front of the last block of a chunk of 2^23 words: its header leaves no payload word (not supported)\n"); }
+		if (S.nout > OUTCAP || S.carry > S.m) { give_up(); rb2_fatal("[rb2_hip] save_fmd: internal: a batch of %llu runs emits %llu blocks and goes on at run %llu\n", (unsigned long long)S.m, (unsigned long long)S.nout, (unsigned long long)S.carry); }
+		if (o && S.nout) {
+			HIPCHK(hipMemcpyAsync(outh[buf], outd[buf].p, S.nout * 64, hipMemcpyDeviceToHost, st));
+			HIPCHK(hipEventRecord(evO[buf], st));
+		}
+		if (o) drain();                                          /* (while the device works on this batch's blocks) */
+		if (o && S.nout) { pend.on = true; pend.buf = buf; pend.blk0 = blk0; pend.nout = S.nout; pend.done = S.done != 0; pend.type = S.ctype; buf ^= 1; }
+		if (S.nout == 0 && nl == 0 && !S.done) { give_up(); rb2_fatal("[rb2_hip] save_fmd: internal: a batch of %llu runs neither emits a block nor has room for a leaf\n", (unsigned long long)S.m); }
+		if (S.nout) par ^= 1;
+		rb ^= 1;
+		ncur = S.m - S.carry; type0 = S.ctype; blk0 += S.nout;
+		done = S.done != 0; ftype = S.ctype;
+	}
+	if (o) drain();
+	const uint64_t n_bytes = (blk0 - 1) * 64 + fmds_hdr_words(ftype) * 8;
+	const int ibits = fmds_ibits(total, n_bytes);
+	const uint64_t n_frames = fmds_n_frames(total, ibits);
+	if (ibits < bbits) { give_up(); rb2_fatal("[rb2_hip] save_fmd: %llu rows need rank frames of 2^%d rows, finer than the 2^%d the encoder keeps for them (%llu buckets)\n", (unsigned long long)total, ibits, bbits, (unsigned long long)FMDS_BUCKET_CAP); }
+	if (o) {
+		for (uint64_t *b : {bidx.p, bS.p}) {                      /* every bucket: the last header up to it */
+			const FmdsInMax im{b, nbk};
+			hipLaunchKernelGGL((k_fmds_scan_part<true, uint64_t, FmdsInMax>), dim3(cdiv(nbk, 1024)), dim3(256), 0, st, im, bpart.p);
+			hipLaunchKernelGGL((k_fmds_scan_top<true, uint64_t, FmdsInMax>), dim3(1), dim3(256), 0, st, im, bpart.p);
+			hipLaunchKernelGGL((k_fmds_scan_apply<true, uint64_t, FmdsInMax>), dim3(cdiv(nbk, 1024)), dim3(256), 0, st, im, (const uint64_t*)bpart.p, b);
+		}
+		h->qtab.ensure(1);
+		hipLaunchKernelGGL(k_qtab, dim3(1), dim3(64), 0, st, (const Ctl*)h->ctl, h->side, pv, h->qtab.p);
+		const uint64_t FSTEP = OUTCAP * FMDS_BW / 7;             /* frames per staging round */
+		for (uint64_t f0 = 0; f0 < n_frames; f0 += FSTEP) {
+			const uint64_t nf = std::min(FSTEP, n_frames - f0);
+			hipLaunchKernelGGL(k_fmds_frames, dim3(cdiv(nf, QPB)), dim3(256), 0, st, (const QTab*)h->qtab.p, pv, (const uint64_t*)bidx.p, (const uint64_t*)bS.p, nbk, ibits, bbits, f0, nf, outd[0].p);
+			HIPCHK(hipGetLastError());
+			HIPCHK(hipMemcpyAsync(outh[0], outd[0].p, nf * 56, hipMemcpyDeviceToHost, st));
+			HIPCHK(hipStreamSynchronize(st));
+			fmds_put(*o, outh[0], (size_t)(nf * 56), 80 + n_bytes + f0 * 56);
+		}
+		memcpy(hdr + 16, &n_bytes, 8); memcpy(hdr + 24, &n_frames, 8);
+		fmds_put(*o, hdr, 80, 0);                                 /* the header goes last */
+	}
+	HIPCHK(hipStreamSynchronize(st));
+	free_all();
+	return (int64_t)fmds_image_size(n_bytes, n_frames);
+}
+
+/* what both calls do first: the index as the export needs it */
+static void fmds_begin(rb2_hip_t *h)
+{
+	finish_pending(h);
+	HIPCHK(hipSetDevice(h->dev));
+	if (h->nranks > 1) { rb2_fatal("[rb2_hip] save_fmd: this handle holds only its own sub-ropes of a sharded index; an .fmd needs the whole index on one engine\n"); }
+	ensure_dense(h);
+	require_plain(h, "save_fmd");
+}
+
+int64_t rb2_hip_save_fmd(rb2_hip_t *h, void *dst, int64_t cap)
+{
+	fmds_begin(h);
+	if (h->fmds_size < 0) h->fmds_size = fmds_encode(h, nullptr);   /* the size is known only when the last block is: nothing is written before it is */
+	const int64_t size = h->fmds_size;
+	if (!dst || cap < size) return size;
+	FmdsOut o = {(uint8_t*)dst, -1, false};
+	const int64_t got = fmds_encode(h, &o);
+	if (got != size) { rb2_fatal("[rb2_hip] save_fmd: internal: the image has %lld bytes, the sizing pass said %lld\n", (long long)got, (long long)size); }
+	return size;
+}
+
+int64_t rb2_hip_save_fmd_file(rb2_hip_t *h, const char *path)
+{
+	fmds_begin(h);                                             /* (first: what is fatal here must not leave a truncated file behind) */
+	const int fd = path ? open(path, O_WRONLY | O_CREAT | O_TRUNC, 0666) : -1;
+	if (fd < 0) return -1;
+	FmdsOut o = {nullptr, fd, false};
+	const int64_t size = fmds_encode(h, &o);
+	if (close(fd) != 0) o.err = true;
+	if (o.err) return -1;
+	h->fmds_size = size;
+	return size;
+}
 
 /* checksum of sub-rope r (k_piece_hash); the handle must hold the piece in the dense layout */
 static uint64_t piece_hash(rb2_hip_t *h, int r)

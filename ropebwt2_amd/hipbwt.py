@@ -46,6 +46,8 @@ def load_hip_lib():
         "rb2_hip_load_ropes": (None, [vp, vp, vp]),
         "rb2_hip_load_fmd": (i64, [vp, vp, i64]),
         "rb2_hip_load_fmd_file": (i64, [vp, C.c_char_p]),
+        "rb2_hip_save_fmd": (i64, [vp, vp, i64]),
+        "rb2_hip_save_fmd_file": (i64, [vp, C.c_char_p]),
         "rb2_hip_delete_strings": (i64, [vp, i64, vp]),
         "rb2_hip_delete_stats": (None, [vp, vp]),
         "rb2_hip_rank1a": (None, [vp, i32, i64, vp]),
@@ -139,7 +141,7 @@ def load_hip_lib():
 ABI_SYMBOLS = [
     "rb2_hip_device_count", "rb2_hip_set_fatal_handler", "rb2_hip_create", "rb2_hip_destroy", "rb2_hip_sorting_order", "rb2_hip_reset",
     "rb2_hip_insert_multi", "rb2_hip_insert_multi_dev", "rb2_hip_set_lazy", "rb2_hip_wait", "rb2_hip_last_batch_counts", "rb2_hip_prefetch", "rb2_hip_mem_info", "rb2_hip_get_counts", "rb2_hip_rope_bytes",
-    "rb2_hip_download_rope", "rb2_hip_stream_rope", "rb2_hip_load_ropes", "rb2_hip_load_fmd", "rb2_hip_load_fmd_file", "rb2_hip_delete_strings", "rb2_hip_delete_stats", "rb2_hip_rank1a", "rb2_hip_rank_batch", "rb2_hip_reserve",
+    "rb2_hip_download_rope", "rb2_hip_stream_rope", "rb2_hip_load_ropes", "rb2_hip_load_fmd", "rb2_hip_load_fmd_file", "rb2_hip_save_fmd", "rb2_hip_save_fmd_file", "rb2_hip_delete_strings", "rb2_hip_delete_stats", "rb2_hip_rank1a", "rb2_hip_rank_batch", "rb2_hip_reserve",
     "rb2_hip_backward_search", "rb2_hip_backward_search_dev", "rb2_hip_extend", "rb2_hip_extract", "rb2_hip_smem", "rb2_hip_smem_dev", "rb2_hip_dev_alloc",
     "rb2_hip_ssa_build", "rb2_hip_ssa_drop", "rb2_hip_ssa_info", "rb2_hip_locate", "rb2_hip_locate_dev",
     "rb2_hip_overlap", "rb2_hip_overlap_dev", "rb2_hip_string_ids", "rb2_hip_string_ids_dev", "rb2_hip_kmers",
@@ -356,6 +358,20 @@ class HipBwt:
             return int(self.L.rb2_hip_load_fmd_file(self.h, os.fsencode(src)))
         img = _fmd_image(src)
         return int(self.L.rb2_hip_load_fmd(self.h, img.ctypes.data, len(img)))
+
+    def save_fmd(self, path=None):
+        """the index as an .fmd image (rb2_hip_save_fmd): what `ropebwt2 -d` writes for the same BWT, byte for byte.  Without a path the image
+        comes back as a uint8 array; with one it is written there and its size is returned (OSError when the file cannot be written)."""
+        if path is not None:
+            n = int(self.L.rb2_hip_save_fmd_file(self.h, os.fsencode(path)))
+            if n < 0:
+                raise OSError("cannot write %s" % (path,))
+            return n
+        size = int(self.L.rb2_hip_save_fmd(self.h, None, 0))
+        img = np.empty(size, dtype=np.uint8)
+        got = int(self.L.rb2_hip_save_fmd(self.h, img.ctypes.data, size))
+        assert got == size, (got, size)
+        return img
 
     def delete(self, ids):
         """take the strings with these ids (rows of the $ block: what extract() takes and locate() gives; any integer sequence or

@@ -812,6 +812,70 @@ def unitig_case(a, res):
     res["unitigs"] = {"index": index, "cases": [crow, trow, brow, frow]}
 
 
+def save_fmd_case(a, res):
+    """rb2_hip_save_fmd against the route the host layer offers for the same bytes: rb2_hip_stream_rope of the six ropes into the parallel host
+    writer (rb2_fmdp_*, 16 threads) and rb2_fmd_write to /dev/shm.  Warm-up, then the median of three; both routes end synchronised."""
+    import ctypes as C
+    from ropebwt2_amd.build import lib_path
+    L = 101
+    n = a.reads or 20_000_000
+    g = HipBwt(a.so)
+    p = g.dev_alloc(n * (L + 1))
+    t = time.perf_counter()
+    g.synth_reads(p, 0, n, L, seed=42)
+    g.insert_multi_dev(p, n * (L + 1))
+    g.sync()
+    build_s = time.perf_counter() - t
+    g.dev_free(p)
+    symbols = int(g.counts().sum())
+    W = C.CDLL(lib_path("libropebwt2.so"))
+    W.rb2_fmdp_init.restype = C.c_void_p; W.rb2_fmdp_init.argtypes = [C.c_int, C.c_int64]
+    W.rb2_fmdp_expect.argtypes = [C.c_void_p, C.c_int64]
+    W.rb2_fmdp_finish.restype = C.c_void_p; W.rb2_fmdp_finish.argtypes = [C.c_void_p]
+    W.rb2_fmd_write_path.argtypes = [C.c_void_p, C.c_char_p]
+    W.rb2_fmd_destroy.argtypes = [C.c_void_p]
+    push = C.cast(W.rb2_fmdp_push_runs, C.c_void_p)                # (user, runs, n_bytes): the callback rb2_hip_stream_rope wants
+    shm = "/dev/shm/rb2_save_fmd_bench_%d.fmd" % os.getpid()
+
+    def host_route():
+        w = W.rb2_fmdp_init(16, 0)
+        W.rb2_fmdp_expect(w, symbols)
+        for b in range(6):
+            g.L.rb2_hip_stream_rope(g.h, b, push, w)
+        f = W.rb2_fmdp_finish(w)
+        assert W.rb2_fmd_write_path(f, shm.encode()) == 0
+        W.rb2_fmd_destroy(f)
+    out = {}
+
+    def cold():                                                   # what a caller pays who saves once: the sizing pass, then the pass that writes
+        g.L.rb2_hip_ssa_drop(g.h)                                 # (drops the size the handle remembers from the call before; there is no suffix array to free)
+        out["img"] = g.save_fmd()
+
+    def warm():                                                   # the size still remembered: the writing pass alone
+        out["img"] = g.save_fmd()
+
+    def sizing():
+        g.L.rb2_hip_ssa_drop(g.h)
+        out["size"] = int(g.L.rb2_hip_save_fmd(g.h, None, 0))
+    try:
+        cold_s = timed(cold, lambda: None)
+        warm_s = timed(warm, lambda: None)
+        size_s = timed(sizing, lambda: None)
+        file_s = timed(lambda: g.save_fmd(shm), lambda: None)     # no sizing pass, nothing remembered is used
+        same_file = bool(np.array_equal(np.fromfile(shm, np.uint8), out["img"]))
+        host_s = timed(host_route, lambda: None)
+        same = bool(np.array_equal(np.fromfile(shm, np.uint8), out["img"]))
+    finally:
+        if os.path.exists(shm):
+            os.remove(shm)
+    size = int(len(out["img"]))
+    res["save_fmd"] = {"reads": n, "read_len": L, "sorting_order": a.so, "symbols": symbols, "build_seconds": build_s, "file_bytes": size,
+                       "save_fmd_seconds": cold_s, "save_fmd_size_remembered_seconds": warm_s, "sizing_call_seconds": size_s, "save_fmd_file_seconds": file_s,
+                       "host_route_seconds": host_s, "host_over_device": host_s / cold_s, "host_over_device_file": host_s / file_s,
+                       "images_equal": same, "file_equals_memory": same_file, "file_gb_per_s": size / cold_s / 1e9, "measured": True}
+    g.close()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default="")
@@ -840,7 +904,16 @@ def main():
     ap.add_argument("--irreducible-steps", type=int, default=1 << 16, help="max_steps of the irreducible-overlap query")
     ap.add_argument("--unitigs", action="store_true", help="only the unitig calls (added to an existing --out file)")
     ap.add_argument("--unitig-sample", type=int, default=20_000, help="vertices of the sample the host composition is timed on")
+    ap.add_argument("--save-fmd", action="store_true", help="only the device .fmd encoder against the host writer (added to an existing --out file)")
     a = ap.parse_args()
+    if a.save_fmd:
+        res = {"cases": []}
+        if a.out and os.path.exists(a.out):
+            with open(a.out) as f:
+                res = json.load(f)
+        save_fmd_case(a, res)
+        finish(a, res)
+        return
     if a.unitigs:
         res = {"cases": []}
         if a.out and os.path.exists(a.out):
