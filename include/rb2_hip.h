@@ -594,6 +594,15 @@ void rb2_hip_layout_stats(rb2_hip_t *h, int64_t out[8]);
  * of a single-engine insert is counted here unless RB2_LAZY_VERDICT=0; RB2_VERDICT_POLL=0 (tests) defers the host's look at the
  * verdict to the next drain, which makes rewinds deep. */
 void rb2_hip_rewind_stats(rb2_hip_t *h, int64_t out[4]);
+/* rounds of one-member groups (a single engine): the device reports, without a synchronisation, the first round of a batch in
+ * which every interval was empty and every string a group of its own; from then on the host knows every interval empty and the dense rounds
+ * launch no k_prep.  out[0] = 0 (dense rounds launched with a k_advance instantiation of their own: measured, no gain, not part of the library),
+ * out[1] = dense rounds without a k_prep<AE> launch since create, out[2] = round of the last batch at which the device first reported the
+ * state (-1: never), out[3] = round of the last batch from which the host used it (-1: never).  RB2_STEADY=0 at create keeps the k_prep<AE>
+ * launch of every round (the report is still read);
+ * RB2_STEADY_AHEAD=n (default 3, 0: no bound) is how many rounds an insert that is waited for may queue ahead of the last round reported until
+ * the state is reached or 48 rounds of the batch are queued. */
+void rb2_hip_steady_stats(rb2_hip_t *h, int64_t out[4]);
 /* window formats of the dense layout (a window = 4 leaves = 4096 symbols; csrc/rb2_merge.h): out[0..3] = windows the dense merge wrote
  * plain (three bit planes) / compact with no, one, two lines of exception positions -- counted on the device only when the handle was
  * created with RB2_COMPACT_STATS=1 in the environment (zeros otherwise) --, out[4] = dense rounds that were allowed to write compact

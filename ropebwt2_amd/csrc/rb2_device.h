@@ -135,6 +135,10 @@ struct Ctl {
 	// k_merge_leaf works on one list.  wcnt[c * WLS] = entries of list c.
 	uint32_t wcnt[16 * 32];
 	unsigned long long wfmt[4]; // windows k_merge wrote in each format (rb2_merge.h), counted only when asked for (RB2_COMPACT_STATS=1: one atomic per window)
+	// ---- rounds of one-member groups ("the steady round")
+	uint32_t unfused[2];    // [p] != 0: in the round of parity p k_sym met a tile it could not place itself (not TILE_DONE).  A flag: plain stores; the setup of the round in front clears it, like ne
+	uint32_t was_fused;     // some round of the batch was reported fused (setup_body, one engine)
+	uint32_t steady_bad;    // sticky: round steady_bad - 1 was not fused behind a round that was -- the rule the host skips k_prep<AE> by does not hold (batch_end: fatal)
 };
 constexpr int GCN = NR * 6 + 2;         // words of the per-round count matrix buffers: NR x 6 counts + [NR * 6] = "some string of this rank has a non-empty
                                         // interval this round" (summed over the ranks of a sharded index like the counts: zero = every rank may launch the
@@ -151,13 +155,13 @@ struct Mailbox {
 	volatile uint32_t progress;         // the in-place round whose splits the device has reached, + 1 (split_body): how far the host may run ahead
 	uint32_t pad0;
 	volatile unsigned long long hmax;   // (round << 40 | size of the largest piece after it) as k_setup last reported it, 0 = nothing yet (setup_body)
-	uint64_t pad1;
+	volatile unsigned long long steady; // ((round + 1) << 1 | every interval of the round was empty and k_sym placed every tile itself) as k_setup last reported it, 0 = nothing yet (setup_body; one engine)
 	volatile unsigned long long hne;    // rank of a sharded index: (round << 32 | some rank holds a non-empty interval) as k_mround last saw it, ~0 = nothing yet
 	uint64_t pad2[3];
 	volatile uint32_t ne[NE_RING][2];   // ctl->ne after each round (ne_snapshot: a copy behind the round), 0xffffffff = not landed yet
 };
 static_assert(offsetof(Mailbox, void_round) == 0 && offsetof(Mailbox, respread) == 4 && offsetof(Mailbox, progress) == 8, "mailbox layout");
-static_assert(offsetof(Mailbox, hmax) == 16 && offsetof(Mailbox, hne) == 32 && offsetof(Mailbox, ne) == 64, "mailbox layout");
+static_assert(offsetof(Mailbox, hmax) == 16 && offsetof(Mailbox, steady) == 24 && offsetof(Mailbox, hne) == 32 && offsetof(Mailbox, ne) == 64, "mailbox layout");
 static_assert(sizeof(Mailbox) == 64 + 8 * NE_RING, "mailbox layout");
 
 // one string's state on the wire (24 B): a = l (48 bits) | size[15:0] << 48;  b = id | size[47:16] << 32;  w = the symbol cursor.

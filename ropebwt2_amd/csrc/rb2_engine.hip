@@ -219,6 +219,12 @@ struct rb2_hip_s {
 	                                    // many rounds late at worst (RB2_RUN_AHEAD)
 	int verdict_poll = 1;               // RB2_VERDICT_POLL=0 (tests): the host does not poll the verdict word while it queues rounds -- it learns of a void round only when it
 	                                    // drains the stream (a re-layout, a widening, the end of the batch), so a void round is taken back from behind every round queued since
+	// rounds of one-member groups ("the steady round"): once the device has reported a round in which every interval was empty and k_sym placed every
+	// tile itself (Mailbox::steady), the host knows every interval empty and the dense rounds of one engine launch no k_prep<AE> for the rest of the batch
+	int steady_on = 1;                  // RB2_STEADY=0: the report is read and the bound below holds, but k_prep<AE> is launched as before
+	int steady_ahead = 3;               // RB2_STEADY_AHEAD: until the report says so (or round STEADY_BOUND_ROUNDS of the batch), an insert that is waited for queues at most this many rounds ahead of the last round reported; 0: no bound
+	bool steady_launched = false;       // a round of this batch relied on the report: batch_end looks at Ctl::steady_bad
+	int64_t n_prep_skipped = 0, steady_seen = -1, steady_used = -1;   // rb2_hip_steady_stats
 	int64_t n_rewind = 0, n_rewound = 0, rewind_max = 0, n_rewind_even = 0;   // void rounds taken back from behind queued rounds: how many, rounds taken back, deepest, of even depth (rb2_hip_rewind_stats)
 	unsigned long long *pair_d = nullptr, *pair_h = nullptr;   // k_pair_hist: what the batch just uploaded adds to the count matrix (device, pinned host)
 	bool pair_valid = false;
@@ -372,6 +378,7 @@ struct BatchState {
 	int cur = 0;                            // string array side
 	bool known_ae = false;                  // the host can tell that every interval of the batch is empty: input order, or an empty index
 	bool known_ae0 = false;                 // ... from the start of the batch (what a rollback falls back to: insert_dev)
+	bool known_steady = false;              // the device has reported a round of fused tiles only (Mailbox::steady): every later round of the batch is one (insert_dev; never set on a rank)
 	uint64_t counted = (uint64_t)-1;        // round whose counting phase (round_counts) is already queued
 	uint64_t setup_round = (uint64_t)-1;    // round whose k_setup ran inside its counting phase (k_tscan_setup) ...
 	bool setup_sparse = false; uint64_t setup_epoch = 0;   // ... for this layout, at this layout epoch (a re-layout in between: k_setup runs again)
@@ -400,6 +407,7 @@ template <class P> StrArrays<P> str_arrays(rb2_hip_t *h, const BatchState &B)
 template <class F> inline void with_pos(rb2_hip_t *h, const BatchState &B, F f) { if (h->pos32) f(str_arrays<uint32_t>(h, B)); else f(str_arrays<uint64_t>(h, B)); }
 
 inline volatile unsigned long long *hmax_report(const rb2_hip_t *h) { return h->pos32 ? &h->mb_d->hmax : nullptr; }   // where k_setup reports its (round, largest piece) to maybe_widen
+inline volatile unsigned long long *steady_report(const rb2_hip_t *h) { return h->nranks == 1 ? &h->mb_d->steady : nullptr; }   // where k_setup reports (round, every tile fused) to insert_dev
 inline uint32_t split_cap(const rb2_hip_t *h) { return (uint32_t)std::min<uint64_t>(h->SPL.cap, 0xffffffffu); }   // leaves an in-place round may list for splitting (k_part_sparse -> k_split)
 
 // A batch may hold at most this many strings (32-bit slots, tile numbers and work orders).  The reference takes any count
@@ -475,6 +483,8 @@ bool batch_begin(rb2_hip_t *h, BatchState &B, int64_t len64, const uint8_t *s, b
 		h->want_pos32 = false;
 		h->mb_h->hmax = 0;                                       // (round, largest piece) as k_setup last reported it: nothing yet
 		h->mb_h->progress = 0;                                   // (in-place rounds the device has come through: none of this batch)
+		h->mb_h->steady = 0;                                     // (round, every tile fused) as k_setup last reported it: nothing yet
+		h->steady_seen = h->steady_used = -1; h->steady_launched = false;
 	}
 	{
 		Scope sc(h, RB2_K_INIT, 0);
@@ -584,7 +594,7 @@ void round_counts(rb2_hip_t *h, BatchState &B, uint64_t r, bool spec = false)
 	  Scope sc(h, RB2_K_TSCAN, units);
 	  const int do_setup = h->nranks == 1;
 	  const unsigned grid = (unsigned)std::max(1, std::min<int>(TSB, h->ts_blocks)) + (scan2_tail ? 7u : 0u);   // (+ one block per column of the chunk bases)
-	  hipLaunchKernelGGL((h->sparse ? k_tscan_setup<true> : k_tscan_setup<false>), dim3(grid), dim3(SCHUNK), 0, st, h->ctl, sd, (int)(r & 1), trs, h->tfix.p, h->gcnt, do_setup, (int)spec, (uint32_t)r, hmax_report(h), scan2_tail);
+	  hipLaunchKernelGGL((h->sparse ? k_tscan_setup<true> : k_tscan_setup<false>), dim3(grid), dim3(SCHUNK), 0, st, h->ctl, sd, (int)(r & 1), trs, h->tfix.p, h->gcnt, do_setup, (int)spec, (uint32_t)r, hmax_report(h), scan2_tail, steady_report(h));
 	  if (do_setup) mark_setup(h, B, r);
 	} else
 	{ Scope sc(h, RB2_K_TSCAN, units);
@@ -595,14 +605,17 @@ void round_counts(rb2_hip_t *h, BatchState &B, uint64_t r, bool spec = false)
 	    hipLaunchKernelGGL(k_tscan3<false>, dim3(B.nsc), dim3(SCHUNK), 0, st, h->ctl, sd, trs, h->cpart.p, h->tsc.p);
 	  }
 	  const int do_setup = h->nranks == 1;                     // one GPU: k_setup of the round rides on block 0 of k_tfix (the local count matrix is the global one)
-	  hipLaunchKernelGGL(k_tfix, dim3(std::max<unsigned>(1u, cdiv(B.nst_ub, 256))), dim3(256), 0, st, h->ctl, sd, (int)(r & 1), trs, h->tsc.p, h->tfix.p, h->gcnt, do_setup, (int)h->sparse, (uint32_t)r, hmax_report(h), (int)spec);
+	  hipLaunchKernelGGL(k_tfix, dim3(std::max<unsigned>(1u, cdiv(B.nst_ub, 256))), dim3(256), 0, st, h->ctl, sd, (int)(r & 1), trs, h->tsc.p, h->tfix.p, h->gcnt, do_setup, (int)h->sparse, (uint32_t)r, hmax_report(h), (int)spec, steady_report(h));
 	  if (do_setup) mark_setup(h, B, r); }
 	tl_slow(h, "tile scans");
 }
 
 // the k_prep pair of round r: the variant for non-empty intervals unless the host knows that there are none (B.known_ae), then the all-empty one
+// ... and none at all in a dense round once the device has reported a round of fused tiles only (B.known_steady): every tile carries TILE_DONE,
+// the kernel would return for all of them (setup_body checks that no round behind a fused one is anything else: Ctl::steady_bad)
 template <bool SPARSE, class P> void launch_prep(rb2_hip_t *h, const BatchState &B, uint64_t r, const PoolView &oldp, const StrArrays<P> &S)
 {
+	if (!SPARSE && B.known_steady && h->steady_on && h->nranks == 1) { ++h->n_prep_skipped; h->steady_launched = true; return; }
 	Scope sc(h, RB2_K_PREP, (int64_t)B.m);
 	const int sd = h->side, par = (int)(r & 1), is_comp = h->so == RB2_SO_RCLO;
 	const unsigned tg = grid8((unsigned)rank_share(h, B.nst_ub));
@@ -637,7 +650,7 @@ void round_merge(rb2_hip_t *h, BatchState &B, uint64_t r, ShardRec *send, bool c
 	if ((uint64_t)nlf * 64 >= (1ull << 32)) { rb2_fatal("[rb2_hip] the index is too large for one k_merge launch (%llu symbols: a launch is capped at 2^32 threads)\n", (unsigned long long)n_new_ub); }
 	if (!setup_done(h, B, r, false))
 	{ Scope sc(h, RB2_K_TSCAN, 0);
-	  hipLaunchKernelGGL(k_setup<false>, dim3(1), dim3(64), 0, st, h->ctl, sd, h->gcnt, (int)(r & 1), (uint32_t)r, hmax_report(h), (int)(h->push[0] != nullptr)); }
+	  hipLaunchKernelGGL(k_setup<false>, dim3(1), dim3(64), 0, st, h->ctl, sd, h->gcnt, (int)(r & 1), (uint32_t)r, hmax_report(h), (int)(h->push[0] != nullptr), steady_report(h)); }
 	with_pos(h, B, [&](const auto &S) { using P = std::remove_pointer_t<decltype(S.L)>;
 	launch_prep<false>(h, B, r, oldp, S);
 	tl_slow(h, "k_prep");
@@ -736,6 +749,39 @@ void wait_progress(rb2_hip_t *h, uint64_t r)
 	}
 }
 
+// The report "every interval of round q was empty and k_sym placed every tile itself" (Mailbox::steady, setup_body) holds for every later round of the
+// batch: two strings whose rows differ never share a row again (their new rows are C[a] + ranks on the new rope that count their own inserted symbols),
+// and empty intervals stay empty (ne_snapshot).  The host reads the word when it queues a round, without synchronising.  Until it says so an insert that
+// is waited for anyway (not lazy) stays at most steady_ahead rounds ahead of the last round reported -- eleven launches take the host well under 0.1 ms and
+// the device 1.5 ms, and a host that queues twenty rounds ahead hears twenty rounds late -- in the manner of wait_progress; the bound ends with the flag
+// or at round STEADY_BOUND_ROUNDS of the batch (data that never gets there is not throttled for a whole batch).
+constexpr uint64_t STEADY_BOUND_ROUNDS = 48;
+void steady_poll(rb2_hip_t *h, BatchState &B, uint64_t r, bool bound)
+{
+	if (B.known_steady) return;
+	auto reported = [&](unsigned long long v) -> int64_t { return v ? (int64_t)(v >> 1) - 1 : -1; };   // the round of the last report, -1: none yet
+	unsigned long long v = h->mb_h->steady;
+	if (bound && h->steady_ahead > 0 && r < STEADY_BOUND_ROUNDS && !(v & 1ull) && (int64_t)r - reported(v) > (int64_t)h->steady_ahead) {
+		const auto t_spin = std::chrono::steady_clock::now();
+		for (uint32_t spins = 0; !((v = h->mb_h->steady) & 1ull) && (int64_t)r - reported(v) > (int64_t)h->steady_ahead && !h->mb_h->void_round; ++spins) {
+			if ((spins & 1023u) == 1023u) {
+				if (hipStreamQuery(h->st) == hipSuccess) break;         // (everything queued is done: nothing more will be reported)
+				if (std::chrono::steady_clock::now() - t_spin > std::chrono::seconds(2)) { HIPCHK(hipStreamSynchronize(h->st)); break; }   // (a report that does not come: wait the plain way)
+			}
+#if defined(__x86_64__) || defined(__i386__)
+			__builtin_ia32_pause();
+#else
+			std::this_thread::yield();
+#endif
+		}
+		v = h->mb_h->steady;
+	}
+	if (!(v & 1ull)) return;
+	B.known_steady = true; B.known_ae = true;                  // (a fused tile is a tile of empty intervals)
+	h->steady_seen = reported(v);
+	if (h->steady_on) h->steady_used = (int64_t)r;
+}
+
 // Take back the in-place rounds r_void .. r - 1 (round r is next): every kernel of the void round and of those queued behind it returned (a void
 // round is sticky: rb2_kernels.h k_part_sparse), only the host's bookkeeping rewinds.  A round whose verdict was waited for is the one round in
 // flight.  Returns r - r_void; the caller redoes round r_void densely.
@@ -768,7 +814,7 @@ bool round_merge_sparse(rb2_hip_t *h, BatchState &B, uint64_t r, ShardRec *send 
 	if (!setup_done(h, B, r, true))
 	{ Scope sc(h, RB2_K_TSCAN, 0);
 	  require_verdicts_seen(h, r, "k_setup of in-place round");
-	  hipLaunchKernelGGL(k_setup<true>, dim3(1), dim3(64), 0, st, h->ctl, sd, h->gcnt, (int)(r & 1), (uint32_t)r, hmax_report(h), (int)(h->push[0] != nullptr)); }
+	  hipLaunchKernelGGL(k_setup<true>, dim3(1), dim3(64), 0, st, h->ctl, sd, h->gcnt, (int)(r & 1), (uint32_t)r, hmax_report(h), (int)(h->push[0] != nullptr), steady_report(h)); }
 	const bool lazy = lazy_round(h, spec);                     // no verdict read here: the caller polls (insert_dev)
 	if (!lazy) { h->mb_h->void_round = 0; h->mb_h->respread = 0; }   // the verdict words the splits write
 	else if (h->spec_rounds > (uint64_t)h->run_ahead) wait_progress(h, r);
@@ -833,6 +879,13 @@ void batch_end(rb2_hip_t *h)
 	h->cur_round = -1;
 	HIPCHK(hipGetLastError());
 	fetch_ropes(h);
+	if (h->steady_launched) {                                   // the guard of setup_body: a round that was not what the host believed
+		uint32_t bad = 0;
+		HIPCHK(hipMemcpyAsync(&bad, &h->ctl->steady_bad, 4, hipMemcpyDeviceToHost, h->st));
+		HIPCHK(hipStreamSynchronize(h->st));
+		h->steady_launched = false;
+		if (bad) { rb2_fatal("[rb2_hip] internal: round %u is not a round of one-member groups behind a round that was\n", bad - 1u); }
+	}
 	drain_profile(h);
 }
 
@@ -944,6 +997,7 @@ void insert_dev(rb2_hip_t *h, int64_t len64, const uint8_t *s, bool lazy = false
 {
 	if (h->nranks > 1) { rb2_fatal("[rb2_hip] this handle is one rank of a rope-sharded index: insert through its rb2_hip_multi_t\n"); }
 	BatchState B;
+	const bool will_lazy = lazy && h->lazy_insert && !h->prof && !h->debug;   // returns with the rounds queued (below): its caller overlaps them with its own work and is not held back
 	h->want_pos32 = true;                                       // (one engine, whole index: the narrow position storage may be used)
 	if (!batch_begin(h, B, len64, s, true)) {
 		// more strings than one batch may hold: two batches, one after the other (the second half moves to a 16-byte aligned place)
@@ -973,6 +1027,7 @@ void insert_dev(rb2_hip_t *h, int64_t len64, const uint8_t *s, bool lazy = false
 		if (!rv) {
 			if (h->timeline > 1 && (r < 4 || r % 10 == 0)) fprintf(stderr, "[rb2_hip] t = %8.3f ms  queueing round %llu\n", std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count() - h->tl_base, (unsigned long long)r);
 			if (!B.known_ae && r > 0 && ne_all_empty_from(h, r)) B.known_ae = true;
+			steady_poll(h, B, r, !will_lazy);
 			if (!(rv = maybe_widen(h, B, r)) && !(rv = verdict_check(h, false)) && !choose_layout(h, B, r, B.m)) rv = verdict_check(h, true);
 		}
 		if (rv) {
@@ -985,6 +1040,9 @@ void insert_dev(rb2_hip_t *h, int64_t len64, const uint8_t *s, bool lazy = false
 			// when they really run (the void round's k_advance never set the flag): forget them, and what the host concluded from them
 			B.known_ae = B.known_ae0;
 			memset((void*)h->mb_h->ne, 0xff, sizeof(h->mb_h->ne));
+			// the same for the report of fused rounds (the counting tails queued behind a void round return before they report, and the stream is drained:
+			// nothing is on its way): the rounds redone from here report again
+			B.known_steady = false; h->mb_h->steady = 0;
 			r = r_void;
 			void_to_dense(h, B, r);
 			round_counts(h, B, r);
@@ -996,7 +1054,7 @@ void insert_dev(rb2_hip_t *h, int64_t len64, const uint8_t *s, bool lazy = false
 		round_merge_any(h, B, r, nullptr, true);
 		++r;
 	}
-	if (lazy && h->lazy_insert && !h->prof && !h->debug) { h->cur_round = -1; HIPCHK(hipGetLastError()); h->pending_end = true; return; }
+	if (will_lazy) { h->cur_round = -1; HIPCHK(hipGetLastError()); h->pending_end = true; return; }
 	batch_end(h);
 	batch_trace(h);
 }
@@ -1063,6 +1121,8 @@ rb2_hip_t *rb2_hip_create(int device, int sorting_order)
 	if (getenv("RB2_LAZY_VERDICT")) h->lazy_verdict = atoi(getenv("RB2_LAZY_VERDICT"));
 	if (getenv("RB2_RUN_AHEAD")) h->run_ahead = std::max(1, atoi(getenv("RB2_RUN_AHEAD")));
 	if (getenv("RB2_VERDICT_POLL")) h->verdict_poll = atoi(getenv("RB2_VERDICT_POLL"));
+	if (getenv("RB2_STEADY")) h->steady_on = atoi(getenv("RB2_STEADY")) != 0;
+	if (getenv("RB2_STEADY_AHEAD")) h->steady_ahead = std::max(0, atoi(getenv("RB2_STEADY_AHEAD")));
 	{ Ctl *hc = (Ctl*)calloc(1, sizeof(Ctl)); for (int b = 0; b < NR; ++b) hc->own[b] = 1; HIPCHK(hipMemcpy(h->ctl, hc, sizeof(Ctl), hipMemcpyHostToDevice)); free(hc); }
 	HIPCHK(hipMemsetAsync(h->d_tmp, 0, 256, h->st));
 	memset(h->h_rope, 0, sizeof(h->h_rope));
@@ -2026,6 +2086,12 @@ void rb2_hip_layout_stats(rb2_hip_t *h, int64_t out[8])
 	HIPCHK(hipStreamSynchronize(h->st));
 	out[0] = h->n_relayout; out[1] = h->n_void; out[2] = h->n_sparse_rounds; out[3] = h->sparse ? 1 : 0;
 	out[4] = h->n_respread; out[5] = (int64_t)ns; out[6] = h->n_grow_in_rounds; out[7] = h->n_plain_handover;
+}
+
+void rb2_hip_steady_stats(rb2_hip_t *h, int64_t out[4])
+{ finish_pending(h);
+	out[0] = 0;                                                 // (rounds launched with a k_advance of their own: measured, no gain, taken out -- DESIGN 10)
+	out[1] = h->n_prep_skipped; out[2] = h->steady_seen; out[3] = h->steady_used;
 }
 
 void rb2_hip_rewind_stats(rb2_hip_t *h, int64_t out[4])

@@ -251,6 +251,8 @@ __global__ void k_batch_setup(Ctl *ctl, int side, uint64_t m, uint64_t len, int 
 	ctl->n0 = n0; ctl->n_strings = m; ctl->max_len = 0; ctl->len = len;
 	ctl->ne[0] = (is_srt && n0) ? 1u : 0u;          // round 0: [0, n0) for every string in the sorted modes (mrope.c:280-283)
 	ctl->ne[1] = 0;
+	ctl->unfused[0] = ctl->unfused[1] = 0;          // (k_sym of a round sets its word, the setup of the round in front cleared it: setup_body)
+	ctl->was_fused = 0;
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -387,6 +389,9 @@ template <bool STRIDE, typename P = uint64_t, bool SPLIT = false> __global__ __l
 		const uint4 okv = *(const uint4*)s_ok[q];
 		allsingle[q] = (okv.x & okv.y & okv.z & okv.w) != 0;
 		fused[q] = ae && allsingle[q];
+		// the round is not one of fused tiles only (a flag: plain store; setup_body reports it).  Queued behind a void in-place round this launch reads
+		// arrays that round never wrote: it says nothing (its counting tail returns as well, and the round is counted again)
+		if (!fused[q] && have[q] && threadIdx.x == 0 && !(SPLIT && ctl->overflow)) ((Ctl*)ctl)->unfused[par] = 1;
 		if (fused[q]) {
 			P *Eb = INS_E + t[q].base; uint8_t *Ib = INS_A + t[q].base;     // slot + segstart = t.base + x
 			const P slot0 = (P)(t[q].lt * STILE);
@@ -551,11 +556,11 @@ template <bool FOLD> __global__ __launch_bounds__(SCHUNK) void k_tscan3(const Ct
 // Block 0 also writes the rows of the count matrix this rank can see -- gcnt[r * 6 + a] = members of (local) bucket r inserting a --
 // and word NR * 6 of the buffer (GCN, rb2_device.h), and, on one GPU (do_setup), runs k_setup of the round on its first wave: the local
 // matrix IS the global one.  (Two launches of their own before; nothing k_setup writes is read by the other blocks of this kernel.)
-template <bool SPARSE> __device__ __forceinline__ void setup_body(Ctl *ctl, int side, const uint64_t *gcnt, int par, uint32_t round, volatile unsigned long long *hmax, bool keep_ne = false);
+template <bool SPARSE> __device__ __forceinline__ void setup_body(Ctl *ctl, int side, const uint64_t *gcnt, int par, uint32_t round, volatile unsigned long long *hmax, volatile unsigned long long *steady, bool keep_ne = false);
 // spec: as in k_tscan_setup below -- queued before the host saw the verdict of the in-place round in front of it; a void round (ctl->overflow) is redone
 // from its own counting phase, and k_setup of the NEXT round must not have replaced the descriptors it starts from.
 __global__ __launch_bounds__(256) void k_tfix(Ctl *ctl, int side, int par, const TileRecs trec, const TileScan *tsc, TileFix *tf, uint64_t *gcnt, int do_setup, int sparse,
-		uint32_t round, volatile unsigned long long *hmax, int spec)
+		uint32_t round, volatile unsigned long long *hmax, int spec, volatile unsigned long long *steady)
 {
 	__shared__ uint32_t s_t0[NR + 1];
 	__shared__ uint64_t s_g[NR * 6];
@@ -569,7 +574,7 @@ __global__ __launch_bounds__(256) void k_tfix(Ctl *ctl, int side, int par, const
 		if (i == NR * 6) gcnt[NR * 6] = ctl->ne[par];
 		if (do_setup) {                                          // (block-uniform)
 			__syncthreads();
-			if (i < 64) { if (sparse) setup_body<true>(ctl, side, s_g, par, round, hmax); else setup_body<false>(ctl, side, s_g, par, round, hmax); }
+			if (i < 64) { if (sparse) setup_body<true>(ctl, side, s_g, par, round, hmax, steady); else setup_body<false>(ctl, side, s_g, par, round, hmax, steady); }
 		}
 	}
 	const uint32_t tile = blockIdx.x * 256 + threadIdx.x;
@@ -602,12 +607,25 @@ __global__ __launch_bounds__(256) void k_tfix(Ctl *ctl, int side, int par, const
 // SPARSE: the round inserts in place -- every piece keeps its slots (leaf0, nleaves, sb0), only n and the counts move.
 // hmax (Mailbox::hmax in pinned host memory, may be null): the round and the size of the largest piece after it -- what the host needs to know
 // to keep the per-string positions in 32-bit storage for as long as they fit (rb2_device.h "P"; one 8-byte store, no copy command)
+// steady (Mailbox::steady in pinned host memory, may be null): the round, and whether every interval of it was empty and k_sym placed the new
+// symbols of every tile itself (no tile set ctl->unfused[par]) -- true of every later round of the batch then ("the steady round"):
+// the host knows every interval empty and launches no k_prep<AE> in dense rounds once it has read that.  Reported in every round, whatever the positions' width.
 // keep_ne: the next round's "some interval is non-empty" flag is not cleared here (PEER transport of a sharded index: the other ranks'
 // k_advance set it, and they may run ahead of this rank's k_mround; the host clears it before the round's counting phase instead)
-template <bool SPARSE> __device__ __forceinline__ void setup_body(Ctl *ctl, int side, const uint64_t *gcnt /* global or LDS */, int par, uint32_t round, volatile unsigned long long *hmax, bool keep_ne)
+template <bool SPARSE> __device__ __forceinline__ void setup_body(Ctl *ctl, int side, const uint64_t *gcnt /* global or LDS */, int par, uint32_t round, volatile unsigned long long *hmax, volatile unsigned long long *steady, bool keep_ne)
 {
 	const int r = lane_id();
 	if (r == 0) { if (!keep_ne) ctl->ne[par ^ 1] = 0; ctl->overflow = 0; ctl->sbfull = 0; ctl->nsplit2[round & 1u] = 0; }   // ne: k_advance / k_munpack of this round count into it
+	if (r == 0) {                                              // k_sym of this round has run, k_sym of the next has not: report its word, clear the next one's
+		const uint32_t uf = ctl->unfused[par];
+		ctl->unfused[par ^ 1] = 0;
+		if (steady) {
+			*steady = ((unsigned long long)round + 1ull) << 1 | (uf ? 0ull : 1ull);
+			// the guard of what the host does with the report: a round that is not fused behind one that was cannot happen; if it does it is not silent (batch_end)
+			if (uf && ctl->was_fused) ctl->steady_bad = round + 1u;
+			if (!uf) ctl->was_fused = 1;
+		}
+	}
 	if (r < WLC) ctl->wcnt[r * WLS] = 0;                       // the work lists of a sparse round
 	if (r == 0) ctl->wstride = max(1u, (ctl->seg[side].tile0[NR] + WLC - 1) / WLC) * STILE;   // wstride / STILE consecutive tiles share a list, a tile appends at most STILE orders
 	const bool ok = r < NR;
@@ -669,10 +687,10 @@ template <bool SPARSE> __device__ __forceinline__ void setup_body(Ctl *ctl, int 
 	}
 	if (ok) ctl->dest[r][0] = 0;
 }
-template <bool SPARSE> __global__ __launch_bounds__(64) void k_setup(Ctl *ctl, int side, const uint64_t *gcnt, int par, uint32_t round, volatile unsigned long long *hmax, int keep_ne)
+template <bool SPARSE> __global__ __launch_bounds__(64) void k_setup(Ctl *ctl, int side, const uint64_t *gcnt, int par, uint32_t round, volatile unsigned long long *hmax, int keep_ne, volatile unsigned long long *steady)
 {
 	if (blockIdx.x) return;
-	setup_body<SPARSE>(ctl, side, gcnt, par, round, hmax, keep_ne != 0);
+	setup_body<SPARSE>(ctl, side, gcnt, par, round, hmax, steady, keep_ne != 0);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -696,7 +714,7 @@ static_assert(sizeof(TileFix) == TFW * 4, "TileFix is written out as 26 dwords")
 // splits keep a superblock's 32 leaves in 64 of them: 215 spilled registers, the job 8 % slower.)
 constexpr int TSB = 4;                      // blocks of k_tscan_setup
 template <bool SPARSE> __global__ __launch_bounds__(SCHUNK) void k_tscan_setup(Ctl *ctl, int side, int par, const TileRecs trec, TileFix *tf, uint64_t *gcnt, int do_setup, int spec,
-		uint32_t round, volatile unsigned long long *hmax, SbBase *scan2)
+		uint32_t round, volatile unsigned long long *hmax, SbBase *scan2, volatile unsigned long long *steady)
 {
 	__shared__ uint32_t s_pre[6][TS_MAX + 4];                    // exclusive prefix of hist over all tiles; [.][nt] = total
 	__shared__ uint32_t s_out[SCHUNK / 64][32 * TFW];            // per wave: 32 TileFix records on their way out (coalesced stores)
@@ -769,7 +787,7 @@ template <bool SPARSE> __global__ __launch_bounds__(SCHUNK) void k_tscan_setup(C
 	// and its ten 64-bit wave scans in a row were 4 us at the end of the kernel with fifteen waves waiting
 	constexpr int NWV = SCHUNK / 64;
 	const int tw0 = (do_setup ? NWV - 1 : NWV);                 // waves of block 0 that write tile records
-	if (lead && do_setup && wv == NWV - 1) { setup_body<SPARSE>(ctl, side, s_g, par, round, hmax); return; }
+	if (lead && do_setup && wv == NWV - 1) { setup_body<SPARSE>(ctl, side, s_g, par, round, hmax, steady); return; }
 	const uint32_t nscanb = gridDim.x - (scan2 ? 7u : 0u);      // (a launch of one block: everything here)
 	const uint32_t wid = lead ? (uint32_t)wv : (uint32_t)tw0 + (blockIdx.x - 1u) * NWV + (uint32_t)wv, tw = (uint32_t)tw0 + (nscanb - 1u) * NWV;   // my number among the writing waves / how many there are
 	uint32_t *so = s_out[wv];

@@ -124,7 +124,7 @@ template <bool SPARSE> __global__ __launch_bounds__(256) void k_mround(Ctl *ctl,
 	}
 	__syncthreads();
 	if (t == 0) { tab->total = s_tot; tab->npieces = s_np; tab->pad = 0; }
-	if (t < 64) setup_body<SPARSE>(ctl, side, g, par, round, hmax, peer != 0);
+	if (t < 64) setup_body<SPARSE>(ctl, side, g, par, round, hmax, nullptr, peer != 0);
 }
 
 // records -> next round's SoA arrays in bucket order, fetched from wherever k_mround says they are: the
