@@ -603,6 +603,12 @@ void rb2_hip_rewind_stats(rb2_hip_t *h, int64_t out[4]);
  * RB2_STEADY_AHEAD=n (default 3, 0: no bound) is how many rounds an insert that is waited for may queue ahead of the last round reported until
  * the state is reached or 48 rounds of the batch are queued. */
 void rb2_hip_steady_stats(rb2_hip_t *h, int64_t out[4]);
+/* lean rounds ("the lean round"): a dense round of a single engine that the host knows to be one of one-member groups and empty
+ * intervals when it queues its counting phase writes no insert list (INS_E / INS_A); the window search and the merge read the strings' positions and
+ * symbols in its place.  out[0] = dense rounds run lean since create, out[1] = the stage in force: 0 = off, 1 = no insert list (RB2_STEADY_LEAN=0 / 1 at
+ * create, default 1; a larger value means 1 -- a second stage, k_sym reading the symbols only, was measured and is not part of the library;
+ * RB2_STEADY=0 switches it off as well). */
+void rb2_hip_lean_stats(rb2_hip_t *h, int64_t out[2]);
 /* window formats of the dense layout (a window = 4 leaves = 4096 symbols; csrc/rb2_merge.h): out[0..3] = windows the dense merge wrote
  * plain (three bit planes) / compact with no, one, two lines of exception positions -- counted on the device only when the handle was
  * created with RB2_COMPACT_STATS=1 in the environment (zeros otherwise) --, out[4] = dense rounds that were allowed to write compact

@@ -225,6 +225,9 @@ struct rb2_hip_s {
 	int steady_ahead = 3;               // RB2_STEADY_AHEAD: until the report says so (or round STEADY_BOUND_ROUNDS of the batch), an insert that is waited for queues at most this many rounds ahead of the last round reported; 0: no bound
 	bool steady_launched = false;       // a round of this batch relied on the report: batch_end looks at Ctl::steady_bad
 	int64_t n_prep_skipped = 0, steady_seen = -1, steady_used = -1;   // rb2_hip_steady_stats
+	// ... and run "lean" ("the lean round"): k_sym writes no INS_E / INS_A, k_part and k_merge read L and A in their place
+	int lean = 1;                       // RB2_STEADY_LEAN: 0 = off, 1 = on (a larger value means 1: the second stage was measured and taken out); RB2_STEADY=0 switches it off as well
+	int64_t n_lean_rounds = 0;          // dense rounds run lean (rb2_hip_lean_stats)
 	int64_t n_rewind = 0, n_rewound = 0, rewind_max = 0, n_rewind_even = 0;   // void rounds taken back from behind queued rounds: how many, rounds taken back, deepest, of even depth (rb2_hip_rewind_stats)
 	unsigned long long *pair_d = nullptr, *pair_h = nullptr;   // k_pair_hist: what the batch just uploaded adds to the count matrix (device, pinned host)
 	bool pair_valid = false;
@@ -380,6 +383,8 @@ struct BatchState {
 	bool known_ae0 = false;                 // ... from the start of the batch (what a rollback falls back to: insert_dev)
 	bool known_steady = false;              // the device has reported a round of fused tiles only (Mailbox::steady): every later round of the batch is one (insert_dev; never set on a rank)
 	uint64_t counted = (uint64_t)-1;        // round whose counting phase (round_counts) is already queued
+	int lean = 0;                           // ... and the last counting phase queued was a lean one (decided at its k_sym launch; round_merge follows THIS, never known_steady:
+	                                        // a round counted before the host heard the report holds INS_E / INS_A and is merged from them)
 	uint64_t setup_round = (uint64_t)-1;    // round whose k_setup ran inside its counting phase (k_tscan_setup) ...
 	bool setup_sparse = false; uint64_t setup_epoch = 0;   // ... for this layout, at this layout epoch (a re-layout in between: k_setup runs again)
 };
@@ -541,7 +546,7 @@ uint32_t maybe_widen(rb2_hip_t *h, BatchState &B, uint64_t r)
 		hipLaunchKernelGGL(k_widen, dim3(cdiv(B.m, 256)), dim3(256), 0, st, (const uint32_t*)h->INS_E.p, a->p, B.m);
 	}
 	h->pos32 = false;
-	B.counted = (uint64_t)-1;                                  // a counting phase queued ahead wrote INS_E in the narrow form (k_sym's fused k_prep): count again
+	B.counted = (uint64_t)-1; B.lean = 0;                      // a counting phase queued ahead wrote INS_E in the narrow form (k_sym's fused k_prep): count again (INS_E above is scratch, never data)
 	if (h->trace) fprintf(stderr, "[rb2_hip] round %llu: positions widened to 64 bits (largest piece known: %llu symbols, %llu rounds ago)\n", (unsigned long long)r, (unsigned long long)known, (unsigned long long)since);
 	return 0;
 }
@@ -562,7 +567,8 @@ void require_verdicts_seen(const rb2_hip_t *h, uint64_t r, const char *what)
 // phase 1 of a round: next symbols, group heads, tile scans, the rows of the count matrix seen here
 // spec: follows the in-place round r - 1 while its verdict is still on its way (round_merge_sparse): the k_sym launch also does that round's
 // leaf splits, the verdict event follows it (unless the verdict is polled: lazy_round), and the k_setup riding on the tail returns on a void round
-void round_counts(rb2_hip_t *h, BatchState &B, uint64_t r, bool spec = false)
+// allow_lean = false: a round counted lean that cannot be merged densely after all is counted again with INS_E / INS_A (round_merge_any)
+void round_counts(rb2_hip_t *h, BatchState &B, uint64_t r, bool spec = false, bool allow_lean = true)
 {
 	hipStream_t st = h->st;
 	const int sd = h->side;
@@ -570,6 +576,8 @@ void round_counts(rb2_hip_t *h, BatchState &B, uint64_t r, bool spec = false)
 	h->cur_round = (int)r;
 	const TileRecs trs = { (uint32_t*)h->trec.p, (uint32_t)(h->trec.cap & ~(size_t)3) };   // (20 columns of cap words in the 80-byte records' space)
 	tl_slow(h, "start of round_counts");
+	// lean: the dense one-engine launch k_sym<false, P, false> of a batch the host knows steady (the in-place layout's k_part_sparse / k_merge_leaf need INS_E / INS_A)
+	B.lean = (allow_lean && !spec && h->nranks == 1 && !h->sparse && B.known_steady && h->steady_on) ? h->lean : 0;
 	const bool one_launch_tail = B.nst_ub < (unsigned)h->ts_max;  // few tiles (long reads): the counting tail is one launch (k_tscan_setup)
 	if (!spec) require_verdicts_seen(h, r, "counting phase without spec of round");   // (its k_setup runs whatever ctl->overflow says)
 	SplitArgs sp; memset(&sp, 0, sizeof(sp));
@@ -587,6 +595,7 @@ void round_counts(rb2_hip_t *h, BatchState &B, uint64_t r, bool spec = false)
 	      hipLaunchKernelGGL((k_sym<false, P, true>), dim3((unsigned)rank_share(h, B.nst_ub) + sp.nsplitb + (sp.scan2 ? 1u : 0u)), dim3(256), 0, st, h->ctl, sd, (int)(r & 1), S, trs, sp);
 	    } else
 	    if (h->nranks > 1) hipLaunchKernelGGL((k_sym<true, P>), dim3(grid8((unsigned)rank_share(h, B.nst_ub))), dim3(256), 0, st, h->ctl, sd, (int)(r & 1), S, trs, sp);
+	    else if (B.lean) hipLaunchKernelGGL((k_sym<false, P, false, true>), dim3(grid8(cdiv(B.nst_ub, (unsigned)SYM_PAIR))), dim3(256), 0, st, h->ctl, sd, (int)(r & 1), S, trs, sp);
 	    else hipLaunchKernelGGL((k_sym<false, P>), dim3(grid8(cdiv(B.nst_ub, (unsigned)SYM_PAIR))), dim3(256), 0, st, h->ctl, sd, (int)(r & 1), S, trs, sp); }); }   // (one engine: a block takes SYM_PAIR tiles)
 	tl_slow(h, "k_sym");
 	if (spec && !lazy_round(h, spec)) HIPCHK(hipEventRecord(h->ev_flag, st));   // (the splits left the verdict in pinned memory)
@@ -651,14 +660,21 @@ void round_merge(rb2_hip_t *h, BatchState &B, uint64_t r, ShardRec *send, bool c
 	if (!setup_done(h, B, r, false))
 	{ Scope sc(h, RB2_K_TSCAN, 0);
 	  hipLaunchKernelGGL(k_setup<false>, dim3(1), dim3(64), 0, st, h->ctl, sd, h->gcnt, (int)(r & 1), (uint32_t)r, hmax_report(h), (int)(h->push[0] != nullptr), steady_report(h)); }
+	// the forms of k_part / k_merge follow how the round was COUNTED (B.lean, round_counts): a lean count left no INS_E / INS_A
+	const bool lean = B.lean != 0;
+	if (lean && (h->nranks != 1 || h->sparse || !B.known_steady)) { rb2_fatal("[rb2_hip] internal: round %llu was counted lean and is not merged as a steady dense round\n", (unsigned long long)r); }
+	if (lean) ++h->n_lean_rounds;
 	with_pos(h, B, [&](const auto &S) { using P = std::remove_pointer_t<decltype(S.L)>;
 	launch_prep<false>(h, B, r, oldp, S);
 	tl_slow(h, "k_prep");
 	{ Scope sc(h, RB2_K_PART, units);
-	  RB2_LAUNCH_STRIDE(h, (k_part<true, P>), (k_part<false, P>), dim3(cdiv(wg + NR, 255)), dim3(256), 0, st, h->ctl, sd, S.INS_E, h->LD.p, h->pool_compact ? (const uint8_t*)oldp.xh : (const uint8_t*)nullptr); }   // (the formats of the old windows: only a pool side the compact-capable merge wrote has any but plain)
+	  const uint8_t *old_xh = h->pool_compact ? (const uint8_t*)oldp.xh : (const uint8_t*)nullptr;
+	  if (lean) hipLaunchKernelGGL((k_part<false, P, true>), dim3(cdiv(wg + NR, 255)), dim3(256), 0, st, h->ctl, sd, (const P*)S.L, h->LD.p, old_xh);
+	  else RB2_LAUNCH_STRIDE(h, (k_part<true, P>), (k_part<false, P>), dim3(cdiv(wg + NR, 255)), dim3(256), 0, st, h->ctl, sd, S.INS_E, h->LD.p, old_xh); }   // (the formats of the old windows: only a pool side the compact-capable merge wrote has any but plain)
 	tl_slow(h, "k_part");
 	{ Scope sc(h, RB2_K_MERGE, units);
-	  RB2_LAUNCH_STRIDE(h, (k_merge<true, P>), (k_merge<false, P>), dim3(grid8(cdiv(wg, MMW))), dim3(64 * MMW), 0, st, h->ctl, h->LD.p, oldp, newp, S.INS_E, S.INS_A, S.RKREL, (int)compact_out | (h->compact_stats ? 2 : 0), (int)(r & 1)); }
+	  if (lean) hipLaunchKernelGGL((k_merge<false, P, true>), dim3(grid8(cdiv(wg, MMW))), dim3(64 * MMW), 0, st, h->ctl, h->LD.p, oldp, newp, (const P*)S.L, (const uint8_t*)S.A, S.RKREL, (int)compact_out | (h->compact_stats ? 2 : 0), (int)(r & 1));
+	  else RB2_LAUNCH_STRIDE(h, (k_merge<true, P>), (k_merge<false, P>), dim3(grid8(cdiv(wg, MMW))), dim3(64 * MMW), 0, st, h->ctl, h->LD.p, oldp, newp, S.INS_E, S.INS_A, S.RKREL, (int)compact_out | (h->compact_stats ? 2 : 0), (int)(r & 1)); }
 	tl_slow(h, "k_merge");
 	{ Scope sc(h, RB2_K_META, units);
 	  build_directory(h, sd ^ 1, h->pside ^ 1, std::min<uint64_t>(B.nsb_ub, n_new_ub / (LEAF * SB) + NR + 1), false, false, (uint64_t)wg * WPL / SB + NR + 1); }
@@ -670,6 +686,7 @@ void round_merge(rb2_hip_t *h, BatchState &B, uint64_t r, ShardRec *send, bool c
 	HIPCHK(hipGetLastError());                                  // a refused launch (grid limits) must not go unnoticed until the end of the batch
 	tl_slow(h, "ne snapshot");
 	h->side ^= 1; h->pside ^= 1; B.cur ^= 1;
+	B.lean = 0;                                                 // (the record belongs to the round just merged)
 	h->pool_compact = compact_out;
 	if (compact_out) ++h->n_compact_rounds;
 }
@@ -793,7 +810,7 @@ int64_t take_back(rb2_hip_t *h, BatchState &B, uint64_t r_void, uint64_t r)
 	HIPCHK(hipMemsetAsync(&h->ctl->overflow, 0, 4, h->st));
 	h->spec_rounds = 0; h->mb_h->void_round = 0;
 	h->mb_h->progress = (uint32_t)r_void;                      // (the rounds behind the void one reported themselves done; wait_progress reads it)
-	B.counted = (uint64_t)-1; B.setup_round = (uint64_t)-1;
+	B.counted = (uint64_t)-1; B.setup_round = (uint64_t)-1; B.lean = 0;
 	return depth;
 }
 
@@ -943,6 +960,7 @@ void void_to_dense(rb2_hip_t *h, BatchState &B, uint64_t r)
 void round_merge_any(rb2_hip_t *h, BatchState &B, uint64_t r, ShardRec *send, bool spec)
 {
 	if (h->sparse) {
+		if (B.lean) round_counts(h, B, r, false, false);       // counted lean, run in place after all: k_part_sparse / k_merge_leaf read INS_E / INS_A -- count again (round_counts counts no round lean on the in-place layout: a guard)
 		if (round_merge_sparse(h, B, r, send, spec)) { if (h->sp_penalty > 0 && (h->n_sparse_rounds & 63) == 0) --h->sp_penalty; return; }
 		// void round: redone on the dense layout
 		void_to_dense(h, B, r);
@@ -1042,7 +1060,7 @@ void insert_dev(rb2_hip_t *h, int64_t len64, const uint8_t *s, bool lazy = false
 			memset((void*)h->mb_h->ne, 0xff, sizeof(h->mb_h->ne));
 			// the same for the report of fused rounds (the counting tails queued behind a void round return before they report, and the stream is drained:
 			// nothing is on its way): the rounds redone from here report again
-			B.known_steady = false; h->mb_h->steady = 0;
+			B.known_steady = false; h->mb_h->steady = 0; B.lean = 0;   // (... and lean with it: the redone rounds write INS_E / INS_A until the device reports again)
 			r = r_void;
 			void_to_dense(h, B, r);
 			round_counts(h, B, r);
@@ -1122,6 +1140,8 @@ rb2_hip_t *rb2_hip_create(int device, int sorting_order)
 	if (getenv("RB2_RUN_AHEAD")) h->run_ahead = std::max(1, atoi(getenv("RB2_RUN_AHEAD")));
 	if (getenv("RB2_VERDICT_POLL")) h->verdict_poll = atoi(getenv("RB2_VERDICT_POLL"));
 	if (getenv("RB2_STEADY")) h->steady_on = atoi(getenv("RB2_STEADY")) != 0;
+	if (getenv("RB2_STEADY_LEAN")) h->lean = std::min(1, std::max(0, atoi(getenv("RB2_STEADY_LEAN"))));
+	if (!h->steady_on) h->lean = 0;
 	if (getenv("RB2_STEADY_AHEAD")) h->steady_ahead = std::max(0, atoi(getenv("RB2_STEADY_AHEAD")));
 	{ Ctl *hc = (Ctl*)calloc(1, sizeof(Ctl)); for (int b = 0; b < NR; ++b) hc->own[b] = 1; HIPCHK(hipMemcpy(h->ctl, hc, sizeof(Ctl), hipMemcpyHostToDevice)); free(hc); }
 	HIPCHK(hipMemsetAsync(h->d_tmp, 0, 256, h->st));
@@ -2097,6 +2117,11 @@ void rb2_hip_steady_stats(rb2_hip_t *h, int64_t out[4])
 void rb2_hip_rewind_stats(rb2_hip_t *h, int64_t out[4])
 { finish_pending(h);
 	out[0] = h->n_rewind; out[1] = h->n_rewound; out[2] = h->rewind_max; out[3] = h->n_rewind_even;
+}
+
+void rb2_hip_lean_stats(rb2_hip_t *h, int64_t out[2])
+{ finish_pending(h);
+	out[0] = h->n_lean_rounds; out[1] = h->lean;
 }
 
 void rb2_hip_window_stats(rb2_hip_t *h, int64_t out[6])

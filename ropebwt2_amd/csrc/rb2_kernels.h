@@ -307,8 +307,12 @@ constexpr int32_t TILE_SINGLE = 0x20000;     // ... every string of the tile is 
 #define RB2_SYM_PAIR 1
 #endif
 constexpr int SYM_PAIR = RB2_SYM_PAIR != 0 ? 2 : 1;   // tiles per block of k_sym<false, P, false> (the host sizes its grid by it)
-template <bool STRIDE, typename P = uint64_t, bool SPLIT = false> __global__ __launch_bounds__(256) void k_sym(const Ctl *ctl, int side, int par, StrArrays<P> S, TileRecs trec, SplitArgs sp)
+// LEAN (one engine, dense, once the host knows the batch steady: DESIGN 10, "the lean round"): the same kernel without the INS_E / INS_A stores of a
+// fused tile -- in such a round k_part and k_merge read L and A in their place (E[q] + q == L[q]); heads, tile records and Ctl::unfused as ever.
+// (A form that read A only and set no head flags -- k_advance took every string for a head -- was measured and taken out: k_part then reads L cold.)
+template <bool STRIDE, typename P = uint64_t, bool SPLIT = false, bool LEAN = false> __global__ __launch_bounds__(256) void k_sym(const Ctl *ctl, int side, int par, StrArrays<P> S, TileRecs trec, SplitArgs sp)
 {
+	static_assert(!LEAN || (!STRIDE && !SPLIT), "the lean round is a dense round of one engine");
 	constexpr int NT = (STRIDE || SPLIT) ? 1 : SYM_PAIR;       // tiles per trip
 	const P *L = S.L, *UU = S.U; P *INS_E = S.INS_E; uint8_t *INS_A = S.INS_A, *A = S.A;   // A in: the symbol every string inserts this round (k_init_strings / k_advance); out: + the group-head flag
 	__shared__ uint64_t s_bal[NT][8][6], s_head[NT][8];
@@ -392,7 +396,7 @@ template <bool STRIDE, typename P = uint64_t, bool SPLIT = false> __global__ __l
 		// the round is not one of fused tiles only (a flag: plain store; setup_body reports it).  Queued behind a void in-place round this launch reads
 		// arrays that round never wrote: it says nothing (its counting tail returns as well, and the round is counted again)
 		if (!fused[q] && have[q] && threadIdx.x == 0 && !(SPLIT && ctl->overflow)) ((Ctl*)ctl)->unfused[par] = 1;
-		if (fused[q]) {
+		if (!LEAN && fused[q]) {
 			P *Eb = INS_E + t[q].base; uint8_t *Ib = INS_A + t[q].base;     // slot + segstart = t.base + x
 			const P slot0 = (P)(t[q].lt * STILE);
 #pragma unroll
@@ -1102,7 +1106,8 @@ template <bool AE, bool SPARSE = false, bool STRIDE = false, typename P = uint64
 // A block covers 256 boundaries = 255 windows (boundaries overlap by one between blocks).
 // ---------------------------------------------------------------------------------------------
 
-template <bool STRIDE, typename P = uint64_t> __global__ __launch_bounds__(256) void k_part(const Ctl *ctl, int side, const P *INS_E, LeafDesc *LD, const uint8_t *old_xh)
+// LEAN: INS_E is the L array of a lean round: L[q] is the final position E[q] + q itself.
+template <bool STRIDE, typename P = uint64_t, bool LEAN = false> __global__ __launch_bounds__(256) void k_part(const Ctl *ctl, int side, const P *INS_E, LeafDesc *LD, const uint8_t *old_xh)
 {
 	__shared__ uint64_t s_wf0[NR + 1];
 	__shared__ uint32_t s_q[256];
@@ -1122,7 +1127,7 @@ template <bool STRIDE, typename P = uint64_t> __global__ __launch_bounds__(256) 
 		uint64_t lo = 0, hi = sg.cnt[b];
 		while (lo < hi) {
 			const uint64_t mid = (lo + hi) >> 1;
-			if (E[mid] + mid >= o) hi = mid; else lo = mid + 1;
+			if ((LEAN ? (uint64_t)E[mid] : E[mid] + mid) >= o) hi = mid; else lo = mid + 1;
 		}
 		q = (uint32_t)lo;
 	}

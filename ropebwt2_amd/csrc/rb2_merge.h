@@ -123,7 +123,10 @@ __device__ __forceinline__ uint64_t stage_bits(const uint32_t *pl, uint32_t dk, 
 // r05 first cut of the compact format: 25 % fewer bytes, 323 VALU, 11 % SLOWER), so every step is written for instruction count: lane
 // offsets in 32 bits on uniform bases, funnel shifts of dwords for the unaligned plane windows, gaps opened by additions, scans inside
 // the DPP row (= leaf) only, exception bookkeeping from numbers the counts already provide.
-template <bool FULL, int GPL_, typename P> __device__ __forceinline__ void merge_window(const LeafDesc &d, uint64_t *lds, const int ln,
+// LEAN ("the lean round"): INS_E / INS_A are the round's L and A arrays -- every string is a group of its own with an empty interval, so
+// L[q] is the final position of insert q in its piece and, windows being WIN-aligned inside a piece, its low bits are the place in the window; A
+// carries flags above the symbol.
+template <bool FULL, int GPL_, typename P, bool LEAN = false> __device__ __forceinline__ void merge_window(const LeafDesc &d, uint64_t *lds, const int ln,
 		const PoolView &oldp, const PoolView &newp, const P *__restrict__ INS_E, const uint8_t *__restrict__ INS_A, uint16_t *RKREL, const int compact_out, unsigned long long *wfmt)
 {
 	static_assert(GPL_ == 1, "one group per lane");
@@ -178,19 +181,19 @@ template <bool FULL, int GPL_, typename P> __device__ __forceinline__ void merge
 		wt0 = obw[w2]; wt1 = obw[w2 + LEAFG];
 		if (h1 == WF_PLAIN) wt2 = obw[w2 + 2 * LEAFG];
 	}
-	auto put_new = [&](uint32_t p, uint32_t ix /* p >> 6 */, uint32_t a) {
+	auto put_new = [&](uint32_t p, uint32_t ix /* p >> 6 */, uint32_t a /* LEAN: with the flags of A above the symbol -- masked where they matter, never in the branch of the load (the wave would wait there, in front of the plane loads) */) {
 		const unsigned long long bit = 1ull << (p & 63);
 		atomicOr((unsigned long long*)&LF[ix], bit);
 		if (a & 1u) atomicOr((unsigned long long*)&LX[ix], bit);
 		if (a & 2u) atomicOr((unsigned long long*)&LX[WG + ix], bit);
-		if ((0x21u >> a) & 1u) atomicOr((unsigned long long*)&LX[2 * WG + ix], bit);   // plane 2': $ and N
+		if ((0x21u >> (LEAN ? a & 7u : a)) & 1u) atomicOr((unsigned long long*)&LX[2 * WG + ix], bit);   // plane 2': $ and N
 	};
-	const uint32_t p_first = e_first - i0lo + ln32;             // final position E[q] + q, relative to the window (kept for step 5)
+	const uint32_t p_first = LEAN ? e_first & (uint32_t)(WIN - 1) : e_first - i0lo + ln32;             // final position E[q] + q, relative to the window (kept for step 5)
 	uint32_t g_first = p_first >> 6;                            // its group (kept as well; opaque, or the index below becomes (p >> 3) & ~7: three instructions for two)
 	asm volatile("" : "+v"(g_first));
 	if (ln32 < ni) put_new(p_first, g_first, a_first);
 	if (ni > 64u)                                               // (more than 64 new symbols: rare in steady state -- a scalar test in front of the loop's vector one)
-		for (uint32_t jj = ln32 + 64; jj < ni; jj += 64) { const uint32_t p = (uint32_t)E0[jj] - i0lo + jj; put_new(p, p >> 6, A0[jj]); }
+		for (uint32_t jj = ln32 + 64; jj < ni; jj += 64) { const uint32_t p = LEAN ? (uint32_t)E0[jj] & (uint32_t)(WIN - 1) : (uint32_t)E0[jj] - i0lo + jj; put_new(p, p >> 6, A0[jj]); }
 	{	// exceptions -> plane 2' bits of the staged groups: entry e of window ow + wi is bit e & 63 of its group e >> 6 = staged group (e >> 6) + 64 wi - g0
 		auto x_in = [&](uint32_t e, uint32_t idx_m1 /* entry number - 1 */, uint32_t cnt, uint32_t delta) {
 			const uint32_t k = (e >> 6) + delta;
@@ -272,7 +275,8 @@ template <bool FULL, int GPL_, typename P> __device__ __forceinline__ void merge
 	uint16_t *RK0 = RKREL + d.ins0;
 	for (uint32_t jj = ln32; jj < ni; jj += 64) {
 		uint32_t p = p_first, a = a_first, lo = g_first;
-		if (jj != ln32) { a = A0[jj]; p = (uint32_t)E0[jj] - i0lo + jj; lo = p >> 6; }   // more than 64 new symbols in the window: read them again
+		if (jj != ln32) { a = A0[jj]; p = LEAN ? (uint32_t)E0[jj] & (uint32_t)(WIN - 1) : (uint32_t)E0[jj] - i0lo + jj; lo = p >> 6; }   // more than 64 new symbols in the window: read them again
+		if (LEAN) a &= 7u;
 		uint32_t r = LP[8 * lo + a];                               // equal symbols in the groups of its leaf in front of its group
 		// all-ones where its code in the planes ($ <-> T) has the bit set: bit a of the set of symbols whose code has it (plane 0: A G N, plane 1: C T... as
 		// numbers: 1 3 5 / 2 3 / 0 5) -- one signed bit-field extract per plane; then, per half, three three-input bit operations (v_bitop3_b32)
@@ -308,10 +312,11 @@ template <bool FULL, int GPL_, typename P> __device__ __forceinline__ void merge
 #define RB2_MMW 4                            // waves (= windows) per block of k_merge
 #endif
 constexpr int MMW = RB2_MMW;
-template <bool STRIDE, typename P = uint64_t> __global__ __launch_bounds__(64 * MMW) void k_merge(const Ctl *ctl, const LeafDesc *__restrict__ LD, PoolView oldp, PoolView newp,
+template <bool STRIDE, typename P = uint64_t, bool LEAN = false> __global__ __launch_bounds__(64 * MMW) void k_merge(const Ctl *ctl, const LeafDesc *__restrict__ LD, PoolView oldp, PoolView newp,
 		const P *__restrict__ INS_E, const uint8_t *__restrict__ INS_A, uint16_t *RKREL, int compact_out, int par)
 {
 	__shared__ __align__(16) uint64_t lds[MMW][MergeLds<GPL>::WORDS];
+	static_assert(!LEAN || !STRIDE, "the lean round is a dense round of one engine");
 	const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
 	const int ln = lane_id();
 	// Compact windows only when the device itself knows that no string has a non-empty interval any more (ctl->ne of this round: once zero
@@ -326,8 +331,8 @@ template <bool STRIDE, typename P = uint64_t> __global__ __launch_bounds__(64 * 
 	LeafDesc d = LD[gw];
 	const uint64_t nwin = ctl->wf0[NR];
 	for (; gw < nwin; gw += (uint64_t)gridDim.x * MMW, d = LD[gw < nwin ? gw : 0]) {
-		if ((d.nvalid & 0x3fffu) == WIN) merge_window<true, GPL, P>(d, lds[wv], ln, oldp, newp, INS_E, INS_A, RKREL, compact_out, (unsigned long long*)ctl->wfmt);
-		else merge_window<false, GPL, P>(d, lds[wv], ln, oldp, newp, INS_E, INS_A, RKREL, compact_out, (unsigned long long*)ctl->wfmt);
+		if ((d.nvalid & 0x3fffu) == WIN) merge_window<true, GPL, P, LEAN>(d, lds[wv], ln, oldp, newp, INS_E, INS_A, RKREL, compact_out, (unsigned long long*)ctl->wfmt);
+		else merge_window<false, GPL, P, LEAN>(d, lds[wv], ln, oldp, newp, INS_E, INS_A, RKREL, compact_out, (unsigned long long*)ctl->wfmt);
 		if (!STRIDE) return;                                    // (one GPU: the grid covers every window; no loop, no extra registers)
 		if (gw + (uint64_t)gridDim.x * MMW < nwin) { __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront"); __builtin_amdgcn_wave_barrier(); }   // the wave's LDS arrays are reused
 	}

@@ -92,6 +92,7 @@ def load_hip_lib():
         "rb2_hip_layout_stats": (None, [vp, vp]),
         "rb2_hip_rewind_stats": (None, [vp, vp]),
         "rb2_hip_steady_stats": (None, [vp, vp]),
+        "rb2_hip_lean_stats": (None, [vp, vp]),
         "rb2_hip_window_stats": (None, [vp, vp]),
         "rb2_hip_host_register": (C.c_int, [vp, C.c_int64]),
         "rb2_hip_host_unregister": (C.c_int, [vp]),
@@ -150,7 +151,7 @@ ABI_SYMBOLS = [
     "rb2_hip_irreducible", "rb2_hip_irreducible_dev",
     "rb2_hip_unitig_chains", "rb2_hip_unitig_chains_dev", "rb2_hip_unitig_text", "rb2_hip_unitig_text_dev",
     "rb2_hip_num_subropes", "rb2_hip_memcpy", "rb2_hip_use_stream",
-    "rb2_hip_dev_free", "rb2_hip_synth_reads", "rb2_hip_synth_reads_cov", "rb2_hip_synth_reads_skew", "rb2_hip_sync", "rb2_hip_sparse_stats", "rb2_hip_layout_stats", "rb2_hip_rewind_stats", "rb2_hip_steady_stats", "rb2_hip_window_stats", "rb2_hip_host_register", "rb2_hip_host_unregister", "rb2_hip_profile",
+    "rb2_hip_dev_free", "rb2_hip_synth_reads", "rb2_hip_synth_reads_cov", "rb2_hip_synth_reads_skew", "rb2_hip_sync", "rb2_hip_sparse_stats", "rb2_hip_layout_stats", "rb2_hip_rewind_stats", "rb2_hip_steady_stats", "rb2_hip_lean_stats", "rb2_hip_window_stats", "rb2_hip_host_register", "rb2_hip_host_unregister", "rb2_hip_profile",
     "rb2_hip_profile_get", "rb2_hip_kernel_name", "rb2_hip_layout",
     "rb2_hip_multi_create", "rb2_hip_multi_unique_id", "rb2_hip_multi_create_rank", "rb2_hip_multi_destroy", "rb2_hip_default_owners",
     "rb2_hip_multi_nranks", "rb2_hip_multi_transport", "rb2_hip_multi_nlocal", "rb2_hip_multi_engine", "rb2_hip_multi_insert_multi", "rb2_hip_multi_insert_multi_dev",
@@ -817,6 +818,12 @@ class HipBwt:
         a = np.zeros(4, np.int64)
         self.L.rb2_hip_steady_stats(self.h, a.ctypes.data)
         return {"advance_single": int(a[0]), "prep_skipped": int(a[1]), "reported_at": int(a[2]), "used_from": int(a[3])}
+
+    def lean_stats(self):
+        """lean rounds (rb2_hip_lean_stats): dense rounds run without an insert list since create / the stage in force (0: off; RB2_STEADY_LEAN)"""
+        a = np.zeros(2, np.int64)
+        self.L.rb2_hip_lean_stats(self.h, a.ctypes.data)
+        return {"rounds": int(a[0]), "stage": int(a[1])}
 
     def window_stats(self):
         a = np.zeros(6, np.int64)
