@@ -467,6 +467,47 @@ int64_t rb2_hip_unitig_text_dev(rb2_hip_t *h, int64_t n_str, const int64_t *vtx,
  * compared through their .fmd) */
 uint64_t rb2_hip_rope_hash(rb2_hip_t *h, int b);
 
+/* ---- the strings of the index, packed, and one index merged into another (csrc/rb2_unpack.h, csrc/rb2_merge_plan.h) ----
+ * rb2_hip_unpack[_dev]: the packed inverse BWT of the strings first .. first + n - 1 (ids are rows of the `$` block, as everywhere else).
+ * txt[off[i] .. off[i + 1]) holds string first + i followed by one 0 byte, off[0] = 0; an empty string is a lone 0.  reversed != 0: every
+ * string LAST symbol first, and txt[0 .. SIZE) is byte for byte a batch rb2_hip_insert_multi[_dev] accepts (each string reversed and
+ * 0-terminated); reversed == 0: text order.  Returns SIZE = the sum of the lengths + n.  off (n + 1 values) is written whenever it is
+ * not NULL; txt is written only if it is not NULL and cap >= SIZE -- otherwise the call writes NOTHING to txt, not one byte, and still
+ * returns SIZE: size with one call, fetch with a second (rb2_hip_save_fmd's convention).  n == 0 returns 0 (off[0] = 0).
+ * The _dev variant takes txt and off in device memory; it synchronises the handle's stream ONCE, behind the lengths, to return SIZE
+ * (as rb2_hip_unitig_text_dev does), copies the offsets to off and queues the text kernel behind that, asynchronously.  The host variant
+ * stages through the query host layer: the lengths in chunks of RB2_QUERY_CHUNK strings, the texts in chunks of at most that many
+ * whole strings and 256 MiB of text (one string when it alone is longer), so never more than that is held on the device at once.
+ * Like every query both wait for a lazy insert, read the index and nothing else -- layout, sampled suffix array and rope hashes are what
+ * they were -- and work on the dense and on the sparse layout.  Cost: two LF walks per string (lengths, then texts); the text walk
+ * collects 16 symbols per DPP row and writes them with one store instruction.
+ * Fatal, each with a message of its own and before anything is written: one rank of a sharded index; first < 0, n < 0 or first + n above
+ * the number of strings; cap < 0; a walk that does not end within N steps or leaves the rows of the index (a loaded index that is no BWT
+ * of complete strings).
+ *
+ * rb2_hip_merge inserts ALL strings of src into dst as rb2_hip_insert_multi_dev would, in dst's own sorting order: the strings go in the
+ * order of src's `$` block (in input order string k of src gets the id n_dst + k), in batches of at most batch_bytes bytes of batch
+ * text, cut only between strings; a single string longer than the budget is a batch of its own.  The batch is rb2_hip_unpack_dev's
+ * reversed output and never leaves the device.  Returns the symbols added, sentinels included.  info (may be NULL) = strings merged,
+ * symbols merged without sentinels, batches, bytes of the largest batch.
+ * Afterwards dst is byte for byte (rb2_hip_download_rope, rb2_hip_save_fmd, rb2_hip_rope_hash) the index built from dst's strings followed
+ * by src's, whatever batch_bytes is: the BWT of a set of strings does not depend on how their insertion is cut into batches, in any
+ * sorting order.  src is UNCHANGED (rope hashes, layout, sampled suffix array); dst's sampled suffix array is dropped, as after any insert.
+ * An empty src returns 0 and changes nothing; an empty dst ends up holding src's strings, rebuilt in dst's sorting order.
+ * batch_bytes == 0 picks a default from rb2_hip_mem_info at the time of the call: a sixteenth of the free device memory, at least 1 MiB
+ * and at most 4 GiB; whatever batch_bytes says, a batch holds no more strings than a quarter of the free memory has room for at 128
+ * bytes each (the per-string state of an insert; never fewer than 2^20) and no more than the 2^32 - 1024 one batch of the engine may
+ * hold.  RB2_MERGE_BATCH in the environment, read on every call, replaces the default (tests).
+ * The call returns when dst is complete.  The two handles have streams of their own: the call synchronises src's stream behind every
+ * batch text and dst's behind every insert -- two synchronisations per batch, next to those an insert makes anyway.
+ * Device memory beyond the two indexes: one batch text, 8 bytes per string of src (the offsets, which never reach the host: it reads
+ * 8 bytes per 4096 strings once, and the 4096 offsets around every cut), and what an insert of that batch into dst takes.
+ * Fatal, each with a message of its own and before anything is changed: dst == src; handles on different devices; either handle one
+ * rank of a sharded index; batch_bytes < 0; a walk in src that does not end (as above). */
+int64_t rb2_hip_unpack(rb2_hip_t *h, int64_t first, int64_t n, int reversed, int64_t cap, uint8_t *txt, int64_t *off);
+int64_t rb2_hip_unpack_dev(rb2_hip_t *h, int64_t first, int64_t n, int reversed, int64_t cap, uint8_t *txt, int64_t *off);
+int64_t rb2_hip_merge(rb2_hip_t *dst, rb2_hip_t *src, int64_t batch_bytes, int64_t info[4]);
+
 /* ---- rope sharding across GPUs ---------------------------------------------------------------
  * The unit of ownership is a SUB-ROPE: rope b is kept as six independent pieces (b,x), x = the symbol that follows b in the
  * row's suffix (piece (b,x) holds exactly the b-symbols of rope x; rope $ is one piece; NR = 31 pieces, see rb2_device.h).

@@ -18,6 +18,8 @@
 #include "rb2_kernels.h"
 #include "rb2_query.h"
 #include "rb2_unitig.h"
+#include "rb2_unpack.h"
+#include "rb2_merge_plan.h"
 #include "rb2_fmd_load.h"
 #include "rb2_delete.h"
 #include "rb2_fmd_save.h"

@@ -763,3 +763,156 @@ int64_t rb2_hip_unitig_text(rb2_hip_t *h, int64_t n_str, const int64_t *vtx, int
 	}
 	return stored;
 }
+
+/* ---- the strings of the index, packed, and one index merged into another (rb2_unpack.h, rb2_merge_plan.h) ---- */
+
+static void unpack_check(rb2_hip_t *h, const char *who, int64_t first, int64_t n, int64_t cap)
+{
+	query_begin(h, who);
+	const uint64_t nstr = h->h_rope[0].n;                          // C[1]: rope $ is one piece
+	if (first < 0 || n < 0 || (uint64_t)first > nstr || (uint64_t)n > nstr - (uint64_t)first) {
+		rb2_fatal("[rb2_hip] %s: strings %lld .. %lld + %lld are no range of the index (it holds %llu)\n", who, (long long)first, (long long)first, (long long)n, (unsigned long long)nstr); }
+	if (cap < 0) { rb2_fatal("[rb2_hip] %s: cap must not be negative (got %lld)\n", who, (long long)cap); }
+}
+
+/* what the offsets of a range need beside themselves, in qscr: ctr[0] = walks that did not end, ctr[1] = the sum of all; the scan's block sums */
+struct UnpackScr { unsigned long long *ctr; uint64_t *bsum; };
+
+/* x[0 .. n] (device) = the offsets of the packed strings first .. first + n - 1: their lengths + 1 by one walk each, x[n] = 0, summed in
+ * place.  Queued on the handle's stream */
+static UnpackScr unpack_offsets(rb2_hip_t *h, int64_t first, int64_t n, uint64_t *x)
+{
+	h->qscr.ensure((size_t)(2 + cdiv((uint64_t)n + 1, UT_SCAN)) * 8);
+	const UnpackScr s = {(unsigned long long*)h->qscr.p, (uint64_t*)h->qscr.p + 2};
+	HIPCHK(hipMemsetAsync(s.ctr, 0, 16, h->st));
+	HIPCHK(hipMemsetAsync(x + n, 0, 8, h->st));
+	dev_chunks(n, [&](int64_t i0, int64_t nc) { qlaunch(h, k_unpack_len<true>, k_unpack_len<false>, (uint64_t)nc, first + i0, nc, x + i0, s.ctr); });
+	unitig_scan(h, x, n + 1, s.bsum, s.ctr + 1);
+	return s;
+}
+
+/* behind a synchronise: c = the two counters of unpack_offsets.  Returns the sum */
+static int64_t unpack_total(const char *who, const unsigned long long c[2])
+{
+	if (c[0]) { rb2_fatal("[rb2_hip] %s: the walk of a string did not end within the rows of the index (the index is no BWT of complete strings)\n", who); }
+	return (int64_t)c[1];
+}
+
+/* the texts of strings first .. first + n - 1 into txt[off[i] - base ..), all device pointers, off their n + 1 offsets; queued */
+static void unpack_texts(rb2_hip_t *h, int64_t first, int64_t n, const int64_t *off, int64_t base, int reversed, int64_t cap, uint8_t *txt)
+{
+	dev_chunks(n, [&](int64_t i0, int64_t nc) {
+		qlaunch(h, k_unpack_text<true>, k_unpack_text<false>, (uint64_t)nc, first + i0, nc, off + i0, base, reversed ? 1 : 0, cap, txt); });
+}
+
+int64_t rb2_hip_unpack_dev(rb2_hip_t *h, int64_t first, int64_t n, int reversed, int64_t cap, uint8_t *txt, int64_t *off)
+{
+	unpack_check(h, "unpack_dev", first, n, cap);
+	if (n == 0) { if (off) HIPCHK(hipMemsetAsync(off, 0, 8, h->st)); return 0; }
+	h->qin.ensure((size_t)n + 1);                                   // the offsets are made here: the caller's off is written behind the check of the walks
+	uint64_t *x = (uint64_t*)h->qin.p;
+	const UnpackScr s = unpack_offsets(h, first, n, x);
+	unsigned long long c[2];
+	HIPCHK(hipMemcpyAsync(c, s.ctr, sizeof(c), hipMemcpyDeviceToHost, h->st));
+	HIPCHK(hipStreamSynchronize(h->st));
+	const int64_t size = unpack_total("unpack_dev", c);
+	if (off) HIPCHK(hipMemcpyAsync(off, x, (size_t)(n + 1) * 8, hipMemcpyDeviceToDevice, h->st));
+	if (txt && cap >= size) unpack_texts(h, first, n, (const int64_t*)x, 0, reversed, size, txt);
+	return size;
+}
+
+int64_t rb2_hip_unpack(rb2_hip_t *h, int64_t first, int64_t n, int reversed, int64_t cap, uint8_t *txt, int64_t *off)
+{
+	unpack_check(h, "unpack", first, n, cap);
+	if (n == 0) { if (off) off[0] = 0; return 0; }
+	const int64_t CH = query_chunk();
+	std::vector<int64_t> o((size_t)n + 1);                         // (the caller's off is written behind the check of the walks)
+	int64_t run = 0;
+	for (int64_t i0 = 0; i0 < n; i0 += CH) {                        // the offsets, chunk by chunk: each chunk's count from 0, the host adds what stands in front
+		const int64_t nc = std::min(CH, n - i0);
+		h->qin.ensure((size_t)nc + 1);
+		const UnpackScr s = unpack_offsets(h, first + i0, nc, (uint64_t*)h->qin.p);
+		unsigned long long c[2];
+		HIPCHK(hipMemcpyAsync(c, s.ctr, sizeof(c), hipMemcpyDeviceToHost, h->st));
+		HIPCHK(hipMemcpyAsync(o.data() + i0, h->qin.p, (size_t)(nc + 1) * 8, hipMemcpyDeviceToHost, h->st));
+		HIPCHK(hipStreamSynchronize(h->st));
+		unpack_total("unpack", c);
+		for (int64_t i = i0; i <= i0 + nc; ++i) o[(size_t)i] += run;
+		run = o[(size_t)(i0 + nc)];
+	}
+	const int64_t size = o[(size_t)n];
+	if (off) memcpy(off, o.data(), (size_t)(n + 1) * 8);
+	if (!txt || cap < size) return size;
+	for (int64_t i0 = 0; i0 < n; ) {                                // the texts: whole strings, at most CH of them and QUERY_STAGE_BYTES of text (one string when it alone is longer)
+		const int64_t lim = std::min(n, i0 + CH);
+		int64_t i1 = std::upper_bound(o.begin() + i0 + 1, o.begin() + lim + 1, o[(size_t)i0] + QUERY_STAGE_BYTES) - o.begin() - 1;
+		i1 = std::max(i1, i0 + 1);
+		const int64_t nc = i1 - i0, base = o[(size_t)i0], nb = o[(size_t)i1] - base;
+		const QStaged s = stage_inputs(h, {nullptr, o.data(), 1}, i0, nc + 1, 0);
+		h->qbytes.ensure((size_t)nb);
+		unpack_texts(h, first + i0, nc, s.v, base, reversed, nb, h->qbytes.p);
+		HIPCHK(hipMemcpyAsync(txt + base, h->qbytes.p, (size_t)nb, hipMemcpyDeviceToHost, h->st));
+		HIPCHK(hipStreamSynchronize(h->st));
+		i0 = i1;
+	}
+	return size;
+}
+
+/* the byte budget of a merge's batches and (*max_strings) the strings one may hold: rb2_merge_plan.h says how both follow from the free memory */
+static int64_t merge_budget(rb2_hip_t *dst, int64_t batch_bytes, int64_t *max_strings)
+{
+	int64_t fr = 0, tot = 0;
+	rb2_hip_mem_info(dst->dev, &fr, &tot);
+	*max_strings = merge_string_cap(fr, (int64_t)max_batch_strings() - 1);
+	if (batch_bytes > 0) return batch_bytes;
+	const char *e = getenv("RB2_MERGE_BATCH");
+	const int64_t v = e ? atoll(e) : 0;
+	return v > 0 ? v : merge_default_budget(fr);
+}
+
+int64_t rb2_hip_merge(rb2_hip_t *dst, rb2_hip_t *src, int64_t batch_bytes, int64_t info[4])
+{
+	if (!dst || !src || dst == src) { rb2_fatal("[rb2_hip] merge: dst and src must be two different handles\n"); }
+	if (dst->dev != src->dev) { rb2_fatal("[rb2_hip] merge: dst is on device %d and src on device %d; both indexes must be on one device\n", dst->dev, src->dev); }
+	if (dst->nranks > 1 || src->nranks > 1) { rb2_fatal("[rb2_hip] merge: %s holds only its own sub-ropes of a sharded index; a merge needs both indexes whole, each on one engine\n", dst->nranks > 1 ? "dst" : "src"); }
+	if (batch_bytes < 0) { rb2_fatal("[rb2_hip] merge: batch_bytes must not be negative (got %lld)\n", (long long)batch_bytes); }
+	finish_pending(dst);
+	query_begin(src, "merge");
+	int64_t inf[4] = {0, 0, 0, 0};
+	if (info) memcpy(info, inf, sizeof(inf));
+	const int64_t n = (int64_t)src->h_rope[0].n, B = UT_SCAN, nb = (int64_t)cdiv((uint64_t)n, UT_SCAN);
+	if (n == 0) return 0;
+	/* the offsets of all of src's strings in one batch text stay on the device (8 bytes a string, in src's staging buffer); the host gets the block sums */
+	src->qin.ensure((size_t)n + 1);
+	uint64_t *x = (uint64_t*)src->qin.p;
+	const UnpackScr s = unpack_offsets(src, 0, n, x);
+	unsigned long long c[2];
+	std::vector<uint64_t> bsum((size_t)nb), blk((size_t)B);
+	HIPCHK(hipMemcpyAsync(c, s.ctr, sizeof(c), hipMemcpyDeviceToHost, src->st));
+	HIPCHK(hipMemcpyAsync(bsum.data(), s.bsum, (size_t)nb * 8, hipMemcpyDeviceToHost, src->st));
+	HIPCHK(hipStreamSynchronize(src->st));
+	const int64_t total = unpack_total("merge", c);
+	int64_t max_strings;
+	const int64_t budget = merge_budget(dst, batch_bytes, &max_strings);
+	HIPCHK(hipSetDevice(dst->dev));
+	DevBuf<uint8_t> text;
+	text.ensure((size_t)std::min(budget, total) + 64);
+	int64_t i0 = 0, off0 = 0;
+	while (i0 < n) {
+		const MergeCut cut = merge_next_cut(bsum.data(), nb, n, (uint64_t)total, B, i0, (uint64_t)off0, (uint64_t)budget, max_strings, blk.data(), [&](int64_t b, uint64_t *buf) {
+			HIPCHK(hipMemcpyAsync(buf, x + b * B, (size_t)std::min(B, n - b * B) * 8, hipMemcpyDeviceToHost, src->st));
+			HIPCHK(hipStreamSynchronize(src->st)); });
+		const int64_t len = (int64_t)cut.off_end - off0;
+		text.ensure((size_t)len + 64);                              // (grows for a string longer than the budget only)
+		unpack_texts(src, i0, cut.end - i0, (const int64_t*)x + i0, off0, 1, len, text.p);
+		HIPCHK(hipStreamSynchronize(src->st));                      // the two handles have streams of their own: the batch is complete before dst reads it ...
+		rb2_hip_insert_multi_dev(dst, len, text.p);
+		HIPCHK(hipStreamSynchronize(dst->st));                      // ... and read before src writes the next one
+		++inf[2]; inf[3] = std::max(inf[3], len);
+		i0 = cut.end; off0 = (int64_t)cut.off_end;
+	}
+	text.release();
+	inf[0] = n; inf[1] = total - n;
+	if (info) memcpy(info, inf, sizeof(inf));
+	return total;
+}

@@ -78,6 +78,9 @@ def load_hip_lib():
         "rb2_hip_unitig_chains_dev": (None, [vp, i64, i64, vp, vp, vp]),
         "rb2_hip_unitig_text": (i64, [vp, i64, vp, i32, i64, i64, i64, vp, vp, vp]),
         "rb2_hip_unitig_text_dev": (i64, [vp, i64, vp, i32, i64, i64, i64, vp, vp, vp]),
+        "rb2_hip_unpack": (i64, [vp, i64, i64, i32, i64, vp, vp]),
+        "rb2_hip_unpack_dev": (i64, [vp, i64, i64, i32, i64, vp, vp]),
+        "rb2_hip_merge": (i64, [vp, vp, i64, vp]),
         "rb2_hip_reserve": (None, [vp, i64, i64, i64]),
         "rb2_hip_num_subropes": (i32, []),
         "rb2_hip_memcpy": (None, [vp, vp, vp, i64, i32]),
@@ -150,6 +153,7 @@ ABI_SYMBOLS = [
     "rb2_hip_approx", "rb2_hip_approx_dev", "rb2_hip_contained", "rb2_hip_contained_dev",
     "rb2_hip_irreducible", "rb2_hip_irreducible_dev",
     "rb2_hip_unitig_chains", "rb2_hip_unitig_chains_dev", "rb2_hip_unitig_text", "rb2_hip_unitig_text_dev",
+    "rb2_hip_unpack", "rb2_hip_unpack_dev", "rb2_hip_merge",
     "rb2_hip_num_subropes", "rb2_hip_memcpy", "rb2_hip_use_stream",
     "rb2_hip_dev_free", "rb2_hip_synth_reads", "rb2_hip_synth_reads_cov", "rb2_hip_synth_reads_skew", "rb2_hip_sync", "rb2_hip_sparse_stats", "rb2_hip_layout_stats", "rb2_hip_rewind_stats", "rb2_hip_steady_stats", "rb2_hip_lean_stats", "rb2_hip_window_stats", "rb2_hip_host_register", "rb2_hip_host_unregister", "rb2_hip_profile",
     "rb2_hip_profile_get", "rb2_hip_kernel_name", "rb2_hip_layout",
@@ -783,6 +787,41 @@ class HipBwt:
         return [(txt[o:o + l].copy(), order[f:f + k].copy(), bool(fl & 1)) for (hd, k, o, l, fl), f in zip(urec.tolist(), first.tolist())]
 
     # -- measurement helpers ----------------------------------------------------------------
+    # -- the strings back out of the index, and one index into another (include/rb2_hip.h) ------------
+    def _n_strings(self):
+        """strings the index holds: the rows of the $ block"""
+        return int(self.counts()[:, 0].sum())
+
+    def unpack_raw(self, first=0, n=None, reversed=False):
+        """rb2_hip_unpack: (txt, off) of strings first .. first + n - 1 (n = None: up to the last): txt[off[i]:off[i + 1]] = string first + i
+        and one 0, last symbol first when reversed (then txt is a batch insert_multi accepts).  Sizes with one call, fetches with a second"""
+        if n is None:
+            n = self._n_strings() - first
+        off = np.zeros(max(n, 0) + 1, np.int64)
+        size = int(self.L.rb2_hip_unpack(self.h, first, n, int(bool(reversed)), 0, None, off.ctypes.data))
+        txt = np.empty(size, np.uint8)
+        if size:
+            got = int(self.L.rb2_hip_unpack(self.h, first, n, int(bool(reversed)), size, txt.ctypes.data, off.ctypes.data))
+            assert got == size, (got, size)
+        return txt, off
+
+    def unpack(self, first=0, n=None):
+        """strings first .. first + n - 1 of the index in text order, one nt6 array each"""
+        txt, off = self.unpack_raw(first, n, False)
+        return [txt[off[i]:off[i + 1] - 1].copy() for i in range(len(off) - 1)]
+
+    def unpack_dev(self, first, n, reversed, cap, txt_dev, off_dev):
+        """rb2_hip_unpack_dev: txt_dev (cap bytes) and off_dev (n + 1 int64) in this device's memory, either may be None; returns SIZE
+        behind one synchronise, the text kernel is queued on the handle's stream"""
+        return int(self.L.rb2_hip_unpack_dev(self.h, first, n, int(bool(reversed)), cap, txt_dev, off_dev))
+
+    def merge(self, other, batch_bytes=0):
+        """rb2_hip_merge: insert every string of `other` (a HipBwt on the same device; unchanged) into this index, in batches of at most
+        batch_bytes bytes of text (0: a default from the free memory).  Returns (strings, symbols without sentinels, batches, largest batch)"""
+        info = np.zeros(4, np.int64)
+        self.L.rb2_hip_merge(self.h, other.h, batch_bytes, info.ctypes.data)
+        return tuple(int(v) for v in info)
+
     def dev_alloc(self, nbytes):
         return self.L.rb2_hip_dev_alloc(self.h, nbytes)
 

@@ -57,6 +57,10 @@ doublings queued, the total text and the LF steps per second (one step per symbo
 sample the host can follow: the first --unitig-sample vertices of the longest chain and the edges among them -- the Python chain walk
 of tests/unitig_ref.py (chains) plus extract() of every read of the sample and the gluing of texts() -- against unitig_chains and
 unitig_text (host buffers, min_reads=2) on the same edges; the texts are compared (equals_fused).
+With --merge only rb2_hip_unpack_dev and rb2_hip_merge are measured and stored under "merge" in the --out file, whose other entries stay:
+symbols per second of unpack_dev in both directions against rb2_hip_extract of the same strings (max_len = the read length), and the merge
+of an index of a quarter as many other reads into the benchmark index against extract + a host pass + rb2_hip_insert_multi from the host
+buffer into an identical index (merge_case).
 """
 import argparse
 import json
@@ -876,6 +880,81 @@ def save_fmd_case(a, res):
     g.close()
 
 
+def merge_case(a, res):
+    """rb2_hip_unpack_dev and rb2_hip_merge.  Unpack: symbols per second of unpack_dev over the whole index and over
+    the first R strings, in both directions, of the host variant and of rb2_hip_extract on the same R strings (max_len = the read length: no
+    padding).  Merge: an index of a quarter as many other reads merged into the benchmark index, against what a user could do before --
+    rb2_hip_extract of the source's strings, reversing and terminating them on the host, rb2_hip_insert_multi from that host buffer into an
+    identical index.  Every figure: the median, the fastest and the slowest of three after a warm-up; each run starts from a rebuilt
+    destination (outside the timed region) and ends synchronised."""
+    L = 101
+    n = a.reads or 20_000_000
+    m = n // 4
+    R = min(a.rows, n)
+    g, src = HipBwt(a.so), HipBwt(a.so)
+    p, ps = g.dev_alloc(n * (L + 1)), src.dev_alloc(m * (L + 1))
+    g.synth_reads(p, 0, n, L, seed=42)
+    src.synth_reads(ps, n, m, L, seed=42)                          # the reads behind those of the destination
+    g.sync(); src.sync()
+
+    def rebuild():
+        g.reset()
+        g.insert_multi_dev(p, n * (L + 1))
+        g.sync()
+    t = time.perf_counter(); rebuild(); build_s = time.perf_counter() - t
+    src.insert_multi_dev(ps, m * (L + 1))
+    src.sync()
+    src.dev_free(ps)
+    symbols = int(g.counts().sum())
+    out = {"reads": n, "read_len": L, "sorting_order": a.so, "symbols": symbols, "build_seconds": build_s, "unpack": [], "measured": True}
+    stat = lambda ts: {"seconds": float(np.median(ts)), "fastest": float(min(ts)), "slowest": float(max(ts))}
+    # ---- unpack
+    dt, do = g.dev_alloc(n * (L + 1) + 64), g.dev_alloc(8 * (n + 1))
+    rows = np.arange(R, dtype=np.int64)
+    for name, k, fn in (("unpack_dev all, text order", n, lambda: g.unpack_dev(0, n, False, n * (L + 1), dt, do)),
+                        ("unpack_dev all, reversed", n, lambda: g.unpack_dev(0, n, True, n * (L + 1), dt, do)),
+                        ("unpack_dev R, text order", R, lambda: g.unpack_dev(0, R, False, R * (L + 1), dt, do)),
+                        ("unpack_dev R, reversed", R, lambda: g.unpack_dev(0, R, True, R * (L + 1), dt, do)),
+                        ("unpack (host) R, text order", R, lambda: g.unpack_raw(0, R, False)),
+                        ("extract (host) R, max_len = read length", R, lambda: g.extract_raw(rows, L))):
+        med, lo, hi = spread(fn, g.sync)
+        out["unpack"].append({"name": name, "strings": k, "symbols": k * L, "seconds": med, "fastest": lo, "slowest": hi, "symbols_per_s": k * L / med,
+                              "lf_steps_per_s": (1 if "extract" in name else 2) * k * (L + 1) / med})
+    u = {c["name"]: c for c in out["unpack"]}
+    out["unpack_dev_over_extract"] = u["unpack_dev R, text order"]["symbols_per_s"] / u["extract (host) R, max_len = read length"]["symbols_per_s"]
+    out["unpack_host_over_extract"] = u["unpack (host) R, text order"]["symbols_per_s"] / u["extract (host) R, max_len = read length"]["symbols_per_s"]
+    g.dev_free(dt); g.dev_free(do)
+    # ---- merge
+    t_merge, t_extract, t_pack, t_insert, info, hashes = [], [], [], [], None, [None, None]
+    for rep in range(4):                                           # the first is the warm-up
+        if rep:
+            rebuild()
+        t = time.perf_counter(); info = g.merge(src); g.sync(); t_merge.append(time.perf_counter() - t)
+    hashes[0] = g.rope_hashes()
+    for rep in range(4):
+        rebuild()
+        t0 = time.perf_counter()
+        fit, txt, ln = src.extract_raw(np.arange(m, dtype=np.int64), L)
+        t1 = time.perf_counter()
+        buf = np.zeros((m, L + 1), np.uint8)
+        buf[:, :L] = txt[:, ::-1]
+        buf = buf.reshape(-1)
+        t2 = time.perf_counter()
+        g.insert_multi(buf); g.sync()
+        t3 = time.perf_counter()
+        assert fit == m and (ln == L).all()
+        t_extract.append(t1 - t0); t_pack.append(t2 - t1); t_insert.append(t3 - t2)
+    hashes[1] = g.rope_hashes()
+    path = [x + y + z for x, y, z in zip(t_extract, t_pack, t_insert)]
+    out["merge"] = {"src_reads": m, "src_symbols": m * L, "info": list(info), "merge": stat(t_merge[1:]), "extract": stat(t_extract[1:]), "host_pass": stat(t_pack[1:]),
+                    "insert_multi_host_buffer": stat(t_insert[1:]), "extract_pack_insert": stat(path[1:]),
+                    "insert_over_merge": float(np.median(t_insert[1:]) / np.median(t_merge[1:])), "path_over_merge": float(np.median(path[1:]) / np.median(t_merge[1:])),
+                    "same_index": hashes[0] == hashes[1]}
+    g.dev_free(p)
+    g.close(); src.close()
+    res["merge"] = out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default="")
@@ -905,7 +984,16 @@ def main():
     ap.add_argument("--unitigs", action="store_true", help="only the unitig calls (added to an existing --out file)")
     ap.add_argument("--unitig-sample", type=int, default=20_000, help="vertices of the sample the host composition is timed on")
     ap.add_argument("--save-fmd", action="store_true", help="only the device .fmd encoder against the host writer (added to an existing --out file)")
+    ap.add_argument("--merge", action="store_true", help="only unpack and merge (added to an existing --out file)")
     a = ap.parse_args()
+    if a.merge:
+        res = {"cases": []}
+        if a.out and os.path.exists(a.out):
+            with open(a.out) as f:
+                res = json.load(f)
+        merge_case(a, res)
+        finish(a, res)
+        return
     if a.save_fmd:
         res = {"cases": []}
         if a.out and os.path.exists(a.out):
