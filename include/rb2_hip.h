@@ -508,6 +508,42 @@ int64_t rb2_hip_unpack(rb2_hip_t *h, int64_t first, int64_t n, int reversed, int
 int64_t rb2_hip_unpack_dev(rb2_hip_t *h, int64_t first, int64_t n, int reversed, int64_t cap, uint8_t *txt, int64_t *off);
 int64_t rb2_hip_merge(rb2_hip_t *dst, rb2_hip_t *src, int64_t batch_bytes, int64_t info[4]);
 
+/* ---- the string graph of the index's own strings (csrc/rb2_graph.h, csrc/rb2_graph_plan.h) ----
+ * The irreducible overlaps of the strings first .. first + n - 1 of the index (the SOURCES; ids are rows of the `$` block, as everywhere
+ * else) as an edge list that never leaves the device: rows of four int64 src, dst, l, ext, the shape rb2_hip_unitig_chains reads.
+ * For the source s with text S the RECORDS are those rb2_hip_irreducible gives for the query S, under that call's definition and
+ * unchanged, with these min_ovlp, max_ext, max_steps and max_recs: have(s) = min(found, max_recs) of them are stored, found following
+ * that call's cnt (cnt >= 0: cnt; cnt <= -2, a source that ran out of max_steps: -2 - cnt, and what it found by then is true and is
+ * used; a source of more than 8192 symbols has no record and no edge).  The record (l, ext, zlo, zhi) yields min(zhi - zlo, max_hits)
+ * EDGES s, dst, l, ext: dst is the string behind the (zlo + k)-th `$`, read from the whole-string table of the sampled suffix array
+ * exactly as rb2_hip_string_ids reads it -- the REVERSE COMPLEMENT of the neighbour, as the index yields it -- or, with pairs != 0,
+ * that id ^ 1: the neighbour itself on an index whose strings 2i and 2i + 1 are a read and its reverse complement.
+ * The rows come in increasing src; the order of the rows of one source is unspecified.  Returns m, the edges of all sources, and stores
+ * the first min(m, cap) rows in the order it produces them: every source below the one that is cut is complete, and nothing is written
+ * from row cap on.  cap == 0 with edges == NULL counts only: size with one call, fetch with a second.
+ * info = m, rows stored, sources that found more than max_recs records, stored records whose range held more than max_hits strings,
+ * sources that ran out of max_steps, sources longer than 8192 symbols, 0, 0 (reserved).  n == 0 returns 0 with info zeroed.
+ * Cost: per source two LF walks (rb2_hip_unpack's: lengths, texts), the search of rb2_hip_irreducible, and 32 bytes written per edge.
+ * The sources are taken in chunks of whole strings: at most RB2_GRAPH_CHUNK strings (in the environment, read on every call; 2^24
+ * otherwise and at the most), at most 256 MiB of packed text and at most 256 MiB of records (chunk * max_recs * 32 bytes); a single string
+ * is a chunk whatever it takes.  The lengths are known on the device only: a chunk tries a number of strings, the device cuts them at
+ * the text budget, and the strings tried and not taken are measured again by the next chunk (a quarter more than fitted is tried then).
+ * The host synchronises once per chunk, behind the lengths, and once at the end for info; the rows depend on none of this.
+ * Device memory beyond the output: one chunk's text, records and 24 bytes a string, and the stacks of rb2_hip_irreducible (sized for the
+ * longest string of the chunk; RB2_IRRED_SCRATCH applies) -- nothing that grows with the index.  The host variant holds cap rows on the
+ * device for the time of the call and copies min(m, cap) of them back.
+ * Like every query the call waits for a lazy insert, reads the index and nothing else -- layout, rope hashes and the sampled suffix array
+ * stay as they were -- and works on the dense and on the sparse layout.  It needs a valid sampled suffix array of any step.
+ * Fatal, each with a message of its own and before any launch: no sampled suffix array (call rb2_hip_ssa_build first); one rank of a
+ * sharded index; first < 0, n < 0 or first + n above the number of strings; cap < 0, or edges NULL with cap > 0; min_ovlp, max_steps or
+ * max_recs below 1, max_ext outside 1 .. 8192 (rb2_hip_irreducible's); max_hits < 1; pairs != 0 on an odd number of strings.  A walk
+ * that does not end (a loaded index that is no BWT of complete strings) is fatal as for rb2_hip_unpack. */
+int64_t rb2_hip_string_graph(rb2_hip_t *h, int64_t first, int64_t n, int64_t min_ovlp, int64_t max_ext, int64_t max_steps, int64_t max_recs, int64_t max_hits, int pairs,
+                             int64_t cap, int64_t *edges, int64_t info[8]);
+/* the same with edges (4 cap int64) in this device's memory and info in host memory: what rb2_hip_unitig_chains_dev reads next */
+int64_t rb2_hip_string_graph_dev(rb2_hip_t *h, int64_t first, int64_t n, int64_t min_ovlp, int64_t max_ext, int64_t max_steps, int64_t max_recs, int64_t max_hits, int pairs,
+                                 int64_t cap, int64_t *edges, int64_t info[8]);
+
 /* ---- rope sharding across GPUs ---------------------------------------------------------------
  * The unit of ownership is a SUB-ROPE: rope b is kept as six independent pieces (b,x), x = the symbol that follows b in the
  * row's suffix (piece (b,x) holds exactly the b-symbols of rope x; rope $ is one piece; NR = 31 pieces, see rb2_device.h).

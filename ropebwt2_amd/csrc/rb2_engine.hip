@@ -19,6 +19,7 @@
 #include "rb2_query.h"
 #include "rb2_unitig.h"
 #include "rb2_unpack.h"
+#include "rb2_graph.h"
 #include "rb2_merge_plan.h"
 #include "rb2_fmd_load.h"
 #include "rb2_delete.h"

@@ -699,7 +699,8 @@ template <bool SPARSE> __device__ __forceinline__ void irred_rank(const QTab &T,
 	zlo = P.cl[0]; zhi = P.ch[0];
 }
 
-template <bool SPARSE> __global__ __launch_bounds__(256) void k_irreducible(const QTab *Tg, PoolView pv, const uint8_t *qry, const int64_t *off, int64_t base, uint64_t n,
+// END0: every query is followed by one closing 0 inside its slice (the packed strings of rb2_unpack.h, asked as they lie: rb2_graph.h)
+template <bool SPARSE, bool END0 = false> __global__ __launch_bounds__(256) void k_irreducible(const QTab *Tg, PoolView pv, const uint8_t *qry, const int64_t *off, int64_t base, uint64_t n,
                                                                             int64_t min_ovlp, int64_t max_ext, int64_t max_steps, int64_t max_recs, int64_t lmax,
                                                                             uint64_t rows, int64_t cap, uint8_t *scr, int64_t *rec, int64_t *cnt)
 {
@@ -714,8 +715,8 @@ template <bool SPARSE> __global__ __launch_bounds__(256) void k_irreducible(cons
 	uint16_t *el = (uint16_t*)((uint8_t*)fs + irred_pad(4 * nf));
 	uint8_t *fa = (uint8_t*)el + irred_pad(2 * cap);
 	for (uint64_t i = R.i; i < n; i += rows) {
-		const int64_t L = off[i + 1] - off[i];
-		const QSlice S = qslice<false>(qry, off, base, i, L > min(lmax, IRRED_MAX_LEN));   // (longer than the host sized the stacks for: malformed, and not read)
+		const int64_t L = off[i + 1] - off[i] - (END0 ? 1 : 0);
+		const QSlice S = qslice<END0>(qry, off, base, i, L > min(lmax, IRRED_MAX_LEN) || (END0 && L < 0));   // (longer than the host sized the stacks for: malformed, and not read)
 		if (S.bad || L == 0) { if (R.g == 0) cnt[i] = S.bad ? -1 : 0; continue; }
 		int64_t steps = 0, k = 0, top = 0;                         // top: the entries on the stack
 		bool over = false;

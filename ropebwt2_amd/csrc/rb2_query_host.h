@@ -5,6 +5,7 @@
 #pragma once
 #include "rb2_query_plan.h"
 #include "rb2_kmer_plan.h"
+#include "rb2_graph_plan.h"
 
 /* queries per launch: 16 threads each, so 2^24 stay far below the 2^32 threads of one launch; RB2_QUERY_CHUNK lowers it (tests of the chunking) */
 static int64_t query_chunk()
@@ -915,4 +916,113 @@ int64_t rb2_hip_merge(rb2_hip_t *dst, rb2_hip_t *src, int64_t batch_bytes, int64
 	inf[0] = n; inf[1] = total - n;
 	if (info) memcpy(info, inf, sizeof(inf));
 	return total;
+}
+
+/* ---- the string graph of the index's own strings (rb2_graph.h, rb2_graph_plan.h) ---- */
+
+/* strings of a chunk at the most: RB2_GRAPH_CHUNK in the environment, read on every call; RB2_QUERY_CHUNK's limit otherwise and at the most */
+static int64_t graph_chunk()
+{
+	const int64_t CH = 1 << 24;
+	const char *e = getenv("RB2_GRAPH_CHUNK");
+	const int64_t v = e ? atoll(e) : 0;
+	return v > 0 ? std::min(v, CH) : CH;
+}
+
+static void string_graph_check(rb2_hip_t *h, const char *who, int64_t first, int64_t n, int64_t min_ovlp, int64_t max_ext, int64_t max_steps, int64_t max_recs, int64_t max_hits,
+                               int pairs, int64_t cap, const int64_t *edges)
+{
+	finish_pending(h);
+	const uint64_t nstr = h->h_rope[0].n;                          // C[1]: rope $ is one piece
+	if (h->nranks > 1) rb2_fatal("[rb2_hip] %s: this handle holds only its own sub-ropes of a sharded index; queries need the whole index on one engine\n", who);
+	if (!h->ssa_valid) { rb2_fatal("[rb2_hip] %s: the index has no sampled suffix array (none was built, or the index changed since): call rb2_hip_ssa_build first\n", who); }
+	if (first < 0 || n < 0 || (uint64_t)first > nstr || (uint64_t)n > nstr - (uint64_t)first) {
+		rb2_fatal("[rb2_hip] %s: strings %lld .. %lld + %lld are no range of the index (it holds %llu)\n", who, (long long)first, (long long)first, (long long)n, (unsigned long long)nstr); }
+	if (cap < 0) { rb2_fatal("[rb2_hip] %s: cap must not be negative (got %lld)\n", who, (long long)cap); }
+	if (cap > 0 && !edges) { rb2_fatal("[rb2_hip] %s: edges is NULL but cap is not 0\n", who); }
+	irreducible_check(who, 1, min_ovlp, max_ext, max_steps, max_recs);
+	if (max_hits < 1) { rb2_fatal("[rb2_hip] %s: max_hits must be at least 1 (got %lld)\n", who, (long long)max_hits); }
+	if (pairs && nstr % 2) { rb2_fatal("[rb2_hip] %s: pairs needs strings 2i and 2i + 1 to be the two strands of a read, but the index holds %llu strings\n", who, (unsigned long long)nstr); }
+}
+
+/* edges (cap rows) in device memory, behind string_graph_check; info = the eight counts.  One synchronise per chunk and one at the end */
+static int64_t string_graph_run(rb2_hip_t *h, const char *who, int64_t first, int64_t n, int64_t min_ovlp, int64_t max_ext, int64_t max_steps, int64_t max_recs, int64_t max_hits,
+                                int pairs, int64_t cap, int64_t *edges, int64_t info[8])
+{
+	int64_t inf[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+	if (info) memcpy(info, inf, sizeof(inf));
+	if (n == 0) return 0;
+	query_begin(h, who);
+	GraphPlan plan = graph_plan(graph_chunk(), max_recs);
+	/* qin for the whole call, so that it never moves: the offsets of a chunk, its cnt, its edge counts, their block sums, the words of the call */
+	const int64_t most = std::min(plan.limit, n), nbs = (int64_t)cdiv((uint64_t)most + 1, UT_SCAN);
+	h->qin.ensure((size_t)(3 * most + 2 + nbs + GR_WORDS));
+	uint64_t *x = (uint64_t*)h->qin.p, *e = x + most + 1, *bsum = e + most + 1;
+	int64_t *cnt = (int64_t*)(bsum + nbs);
+	unsigned long long *gc = (unsigned long long*)(cnt + most);
+	HIPCHK(hipMemsetAsync(gc, 0, GR_WORDS * 8, h->st));
+	for (int64_t i0 = 0; i0 < n; ) {
+		const int64_t tried = graph_try(plan, n - i0);
+		const UnpackScr s = unpack_offsets(h, first + i0, tried, x);
+		hipLaunchKernelGGL(k_graph_cut, dim3(1), dim3(1), 0, h->st, (const uint64_t*)x, (uint64_t)tried, (uint64_t)GRAPH_TEXT_BYTES, gc);
+		ulaunch(h, k_graph_lmax, tried, (const uint64_t*)x, gc);
+		unsigned long long c[2], g[3];
+		HIPCHK(hipMemcpyAsync(c, s.ctr, sizeof(c), hipMemcpyDeviceToHost, h->st));
+		HIPCHK(hipMemcpyAsync(g, gc, sizeof(g), hipMemcpyDeviceToHost, h->st));
+		HIPCHK(hipStreamSynchronize(h->st));
+		unpack_total(who, c);
+		const int64_t nc = (int64_t)g[GR_TOOK], nb = (int64_t)g[GR_BYTES];
+		const int64_t lmax = std::min(std::max<int64_t>((int64_t)g[GR_LMAX] - 1, 1), IRRED_MAX_LEN);
+		if (nc < 1 || nc > tried) { rb2_fatal("[rb2_hip] %s: a chunk of %lld strings out of %lld tried\n", who, (long long)nc, (long long)tried); }
+		h->qbytes.ensure((size_t)std::max<int64_t>(nb, 1));
+		h->qout.ensure((size_t)(nc * max_recs) * 4);
+		unpack_texts(h, first + i0, nc, (const int64_t*)x, 0, 0, nb, h->qbytes.p);
+		{
+			const int64_t ecap = irred_entry_cap(lmax, min_ovlp, max_ext, max_steps), row = irred_row_bytes(ecap, max_ext), rows = irred_rows(nc, row, irred_scratch());
+			h->qscr.ensure((size_t)(rows * row));
+			qlaunch(h, k_irreducible<true, true>, k_irreducible<false, true>, (uint64_t)rows, (const uint8_t*)h->qbytes.p, (const int64_t*)x, 0, nc, min_ovlp, max_ext, max_steps, max_recs, lmax,
+					rows, ecap, h->qscr.p, h->qout.p, cnt);
+		}
+		ulaunch(h, k_graph_count, nc, nc, (const int64_t*)x, (const int64_t*)h->qout.p, (const int64_t*)cnt, max_recs, max_hits, e, gc);
+		HIPCHK(hipMemsetAsync(e + nc, 0, 8, h->st));
+		unitig_scan(h, e, nc + 1, bsum, gc + GR_CHUNK);
+		hipLaunchKernelGGL(k_graph_emit, dim3((unsigned)cdiv((uint64_t)nc, QPB)), dim3(256), 0, h->st, (uint64_t)nc, first + i0, (const int64_t*)h->qout.p, (const int64_t*)cnt, (const uint64_t*)e,
+				max_recs, max_hits, pairs ? 1 : 0, (const uint64_t*)h->ssa_head.p, h->ssa_nstr, (const unsigned long long*)gc, (uint64_t)cap, edges);
+		HIPCHK(hipGetLastError());
+		graph_took(plan, tried, nc);
+		i0 += nc;
+	}
+	unsigned long long g[GR_WORDS];
+	HIPCHK(hipMemcpyAsync(g, gc, sizeof(g), hipMemcpyDeviceToHost, h->st));
+	HIPCHK(hipStreamSynchronize(h->st));
+	inf[0] = (int64_t)std::min<unsigned long long>(g[GR_BASE] + g[GR_CHUNK], UT_SAT);
+	inf[1] = std::min(inf[0], cap);
+	inf[2] = (int64_t)g[GR_OVER_RECS]; inf[3] = (int64_t)g[GR_OVER_HITS]; inf[4] = (int64_t)g[GR_OVER_STEPS]; inf[5] = (int64_t)g[GR_TOO_LONG];
+	if (info) memcpy(info, inf, sizeof(inf));
+	return inf[0];
+}
+
+int64_t rb2_hip_string_graph_dev(rb2_hip_t *h, int64_t first, int64_t n, int64_t min_ovlp, int64_t max_ext, int64_t max_steps, int64_t max_recs, int64_t max_hits, int pairs,
+                                 int64_t cap, int64_t *edges, int64_t info[8])
+{
+	string_graph_check(h, "string_graph_dev", first, n, min_ovlp, max_ext, max_steps, max_recs, max_hits, pairs, cap, edges);
+	return string_graph_run(h, "string_graph_dev", first, n, min_ovlp, max_ext, max_steps, max_recs, max_hits, pairs, cap, edges, info);
+}
+
+int64_t rb2_hip_string_graph(rb2_hip_t *h, int64_t first, int64_t n, int64_t min_ovlp, int64_t max_ext, int64_t max_steps, int64_t max_recs, int64_t max_hits, int pairs,
+                             int64_t cap, int64_t *edges, int64_t info[8])
+{
+	string_graph_check(h, "string_graph", first, n, min_ovlp, max_ext, max_steps, max_recs, max_hits, pairs, cap, edges);
+	HIPCHK(hipSetDevice(h->dev));
+	DevBuf<int64_t> rows;                                          // the output on the device: cap rows, of which min(m, cap) come back
+	if (cap > 0 && n > 0) rows.ensure((size_t)cap * 4);
+	int64_t inf[8];
+	const int64_t m = string_graph_run(h, "string_graph", first, n, min_ovlp, max_ext, max_steps, max_recs, max_hits, pairs, cap, rows.p, inf);
+	if (inf[1] > 0) {
+		HIPCHK(hipMemcpyAsync(edges, rows.p, (size_t)inf[1] * 32, hipMemcpyDeviceToHost, h->st));
+		HIPCHK(hipStreamSynchronize(h->st));
+	}
+	rows.release();
+	if (info) memcpy(info, inf, sizeof(inf));
+	return m;
 }

@@ -81,6 +81,8 @@ def load_hip_lib():
         "rb2_hip_unpack": (i64, [vp, i64, i64, i32, i64, vp, vp]),
         "rb2_hip_unpack_dev": (i64, [vp, i64, i64, i32, i64, vp, vp]),
         "rb2_hip_merge": (i64, [vp, vp, i64, vp]),
+        "rb2_hip_string_graph": (i64, [vp, i64, i64, i64, i64, i64, i64, i64, i32, i64, vp, vp]),
+        "rb2_hip_string_graph_dev": (i64, [vp, i64, i64, i64, i64, i64, i64, i64, i32, i64, vp, vp]),
         "rb2_hip_reserve": (None, [vp, i64, i64, i64]),
         "rb2_hip_num_subropes": (i32, []),
         "rb2_hip_memcpy": (None, [vp, vp, vp, i64, i32]),
@@ -154,6 +156,7 @@ ABI_SYMBOLS = [
     "rb2_hip_irreducible", "rb2_hip_irreducible_dev",
     "rb2_hip_unitig_chains", "rb2_hip_unitig_chains_dev", "rb2_hip_unitig_text", "rb2_hip_unitig_text_dev",
     "rb2_hip_unpack", "rb2_hip_unpack_dev", "rb2_hip_merge",
+    "rb2_hip_string_graph", "rb2_hip_string_graph_dev",
     "rb2_hip_num_subropes", "rb2_hip_memcpy", "rb2_hip_use_stream",
     "rb2_hip_dev_free", "rb2_hip_synth_reads", "rb2_hip_synth_reads_cov", "rb2_hip_synth_reads_skew", "rb2_hip_sync", "rb2_hip_sparse_stats", "rb2_hip_layout_stats", "rb2_hip_rewind_stats", "rb2_hip_steady_stats", "rb2_hip_lean_stats", "rb2_hip_window_stats", "rb2_hip_host_register", "rb2_hip_host_unregister", "rb2_hip_profile",
     "rb2_hip_profile_get", "rb2_hip_kernel_name", "rb2_hip_layout",
@@ -785,6 +788,96 @@ class HipBwt:
         order = np.lexsort((vtx[:, 1], vtx[:, 0]))                  # by head, then by rank
         first = np.searchsorted(vtx[order, 0], urec[:, 0])
         return [(txt[o:o + l].copy(), order[f:f + k].copy(), bool(fl & 1)) for (hd, k, o, l, fl), f in zip(urec.tolist(), first.tolist())]
+
+    # -- the string graph of the index's own strings, on the device (include/rb2_hip.h) ---------------------
+    def _graph_args(self, who, first, n, max_ext, pairs):
+        """(first, n, max_ext) with the defaults filled in: n = None: up to the last string; max_ext = None: the longest string of the
+        index, read from the offsets of one sizing call (8 bytes a string: pass max_ext on an index where that matters)"""
+        total = self._n_strings()
+        if pairs and (self.so != 0 or total % 2):
+            raise ValueError("%s(pairs=True): the index must be in input order and hold an even number of strings" % who)
+        if n is None:
+            n = total - first
+        if max_ext is None:
+            off = np.zeros(total + 1, np.int64)
+            self.L.rb2_hip_unpack(self.h, 0, total, 0, 0, None, off.ctypes.data)
+            max_ext = min(max(int(np.diff(off).max()) - 1 if total else 1, 1), 8192)
+        return int(first), int(n), int(max_ext)
+
+    def string_graph_dev(self, first, n, edges_dev, cap, min_ovlp=1, max_ext=8192, max_steps=1 << 16, max_recs=16, max_hits=8, pairs=False):
+        """rb2_hip_string_graph_dev: edges_dev (4 cap int64; None or 0 with cap 0 counts only) in this device's memory.  Returns (m, info (8,)
+        int64 = m, rows stored, sources over max_recs, records over max_hits, sources out of steps, sources over 8192 symbols, 0, 0)"""
+        info = np.zeros(8, np.int64)
+        m = self.L.rb2_hip_string_graph_dev(self.h, first, n, min_ovlp, max_ext, max_steps, max_recs, max_hits, int(bool(pairs)), int(cap), edges_dev or None, info.ctypes.data)
+        return int(m), info
+
+    def string_graph_raw(self, first, n, cap, min_ovlp=1, max_ext=8192, max_steps=1 << 16, max_recs=16, max_hits=8, pairs=False, fill=0):
+        """rb2_hip_string_graph as it is: (m, edges (cap, 4) int64 that start as fill, info (8,) int64); cap 0 passes NULL"""
+        edges = np.full((max(int(cap), 0), 4), fill, np.int64)
+        info = np.zeros(8, np.int64)
+        m = self.L.rb2_hip_string_graph(self.h, first, n, min_ovlp, max_ext, max_steps, max_recs, max_hits, int(bool(pairs)), int(cap), edges.ctypes.data if len(edges) else None,
+                                        info.ctypes.data)
+        return int(m), edges, info
+
+    def string_graph(self, first=0, n=None, min_ovlp=1, max_ext=None, max_steps=1 << 16, max_recs=16, max_hits=8, pairs=False):
+        """the edges of the string graph that leave the strings first .. first + n - 1 (n = None: up to the last), found on the device by
+        one call: (edges (m, 4) int64 = src, dst, l, ext by increasing src, info (8,) int64 as string_graph_dev returns it).  dst as
+        irreducible() names it: the reverse complement of the neighbour, or the neighbour itself with pairs=True (ValueError as there).
+        Sizes with a guess of two edges a source and repeats once with cap = m when the guess was short.  A source that is cut by
+        max_recs, max_hits or max_steps shows in info[2:5] only.  Needs build_ssa() (none is built here)"""
+        first, n, max_ext = self._graph_args("string_graph", first, n, max_ext, pairs)
+        kw = dict(min_ovlp=min_ovlp, max_ext=max_ext, max_steps=max_steps, max_recs=max_recs, max_hits=max_hits, pairs=pairs)
+        m, edges, info = self.string_graph_raw(first, n, 2 * n + 16, **kw)
+        if m > len(edges):
+            m, edges, info = self.string_graph_raw(first, n, m, **kw)
+        return edges[:m].copy(), info
+
+    def assemble(self, min_ovlp, canonical=True, min_reads=1, **kw):
+        """what unitigs() returns, with the graph, the chains and the texts made on the device: string_graph_dev, unitig_chains_dev and
+        unitig_text_dev on buffers from dev_alloc; only the unitigs' records, their text and the chain order come back.  kw: max_ext,
+        max_steps, max_recs, max_hits of string_graph().  Returns (unitigs, info): info = what string_graph_dev reports (info[2:6] != 0:
+        sources whose edges were cut short, which unitigs() raises for or passes over in silence)"""
+        _, n, max_ext = self._graph_args("assemble", 0, None, kw.pop("max_ext", None), True)
+        kw.update(min_ovlp=min_ovlp, max_ext=max_ext, pairs=True)
+        ptrs = []
+
+        def alloc(nbytes):
+            ptrs.append(self.dev_alloc(max(int(nbytes), 8)))
+            return ptrs[-1]
+
+        def fetch(dev, shape, dtype):
+            a = np.zeros(shape, dtype)
+            if a.nbytes:
+                self.L.rb2_hip_memcpy(self.h, a.ctypes.data, dev, a.nbytes, 1)
+            return a
+        try:
+            cap = 2 * n + 16
+            d_edges = alloc(32 * cap)
+            m, info = self.string_graph_dev(0, n, d_edges, cap, **kw)
+            if m > cap:                                             # (the guess was short: once more with room for all)
+                self.dev_free(ptrs.pop())
+                cap = m
+                d_edges = alloc(32 * cap)
+                m, info = self.string_graph_dev(0, n, d_edges, cap, **kw)
+            d_vtx, d_cinfo = alloc(32 * n), alloc(32)
+            self.unitig_chains_dev(n, m, d_edges, d_vtx, d_cinfo)
+            _, tinfo = self.unitig_text_dev(n, d_vtx, None, None, canonical, min_reads)
+            cap_u, cap_txt = int(tinfo[0]), int(tinfo[1])
+            d_urec, d_txt = alloc(40 * cap_u), alloc(cap_txt)
+            if cap_u and cap_txt:
+                stored, _ = self.unitig_text_dev(n, d_vtx, d_urec, d_txt, canonical, min_reads, cap_u, cap_txt)
+                assert stored == cap_u, (stored, cap_u)
+            self.sync()
+            urec = fetch(d_urec, (cap_u, 5), np.int64) if cap_txt else np.zeros((0, 5), np.int64)
+            txt = fetch(d_txt, cap_txt, np.uint8)
+            vtx = fetch(d_vtx, (n, 4), np.int64)[:, :2]            # head and rank: the chain order
+            self.sync()
+        finally:
+            for d in ptrs:
+                self.dev_free(d)
+        order = np.lexsort((vtx[:, 1], vtx[:, 0]))
+        first = np.searchsorted(vtx[order, 0], urec[:, 0])
+        return [(txt[o:o + l].copy(), order[f:f + k].copy(), bool(fl & 1)) for (hd, k, o, l, fl), f in zip(urec.tolist(), first.tolist())], info
 
     # -- measurement helpers ----------------------------------------------------------------
     # -- the strings back out of the index, and one index into another (include/rb2_hip.h; DESIGN.md section 22) ------------

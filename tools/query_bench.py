@@ -57,6 +57,11 @@ doublings queued, the total text and the LF steps per second (one step per symbo
 sample the host can follow: the first --unitig-sample vertices of the longest chain and the edges among them -- the Python chain walk
 of tests/unitig_ref.py (chains) plus extract() of every read of the sample and the gluing of texts() -- against unitig_chains and
 unitig_text (host buffers, min_reads=2) on the same edges; the texts are compared (equals_fused).
+With --graph only rb2_hip_string_graph is measured and stored under "string_graph" in the --out file, whose other entries stay: the index of
+--unitigs (--reads, default 1 000 000) with its suffix array; (a) string_graph_dev over every string -- sources and edges per second, median
+of three after a warm-up with the fastest and the slowest beside it; (b) HipBwt.edges() on the first --unitig-sample strings against
+string_graph on the same strings (host buffers; the rows are compared: equals_fused); (c) irreducible_dev alone on the same strings, their
+texts already on the device, against string_graph_dev measured next to it: what unpacking, counting, scanning and emitting cost on top.
 With --merge only rb2_hip_unpack_dev and rb2_hip_merge are measured and stored under "merge" in the --out file, whose other entries stay:
 symbols per second of unpack_dev in both directions against rb2_hip_extract of the same strings (max_len = the read length), and the merge
 of an index of a quarter as many other reads into the benchmark index against extract + a host pass + rb2_hip_insert_multi from the host
@@ -816,6 +821,74 @@ def unitig_case(a, res):
     res["unitigs"] = {"index": index, "cases": [crow, trow, brow, frow]}
 
 
+def graph_case(a, res):
+    """--graph: rb2_hip_string_graph_dev on the both-strand read index of --unitigs (reduced, suffix array at log2_step 5)"""
+    L, M, H8 = 101, 8, 8
+    n = a.reads or 1_000_000
+    min_ovlp = a.irreducible_min_ovlp
+    kw = dict(min_ovlp=min_ovlp, max_ext=L - min_ovlp, max_steps=a.irreducible_steps, max_recs=M, max_hits=H8, pairs=True)
+    g = HipBwt(0)
+    nb = 2 * n * (L + 1)
+    p = g.dev_alloc(nb)
+    g.synth_reads(p, 0, n, L, seed=42, strand=1, genome_len=n * L // 30)
+    g.insert_multi_dev(p, nb)
+    g.sync()
+    g.dev_free(p)
+    gone = g.reduce(pairs=True)
+    ns = int(g.counts()[:, 0].sum())
+    g.build_ssa(5)
+    # (a) the whole graph: a counting call sizes the rows, the timed calls store them
+    m, info = g.string_graph_dev(0, ns, None, 0, **kw)
+    de = g.dev_alloc(max(32 * m, 8))
+    got = {}
+
+    def full():
+        got["full"] = g.string_graph_dev(0, ns, de, m, **kw)
+    sec, lo, hi = spread(full, lambda: None)
+    m2, info = got["full"]
+    assert m2 == m and info[1] == m
+    index = {"reads": n, "read_len": L, "genome_len": n * L // 30, "strands": 2, "sorting_order": 0, "strings_removed": int(len(gone)), "strings": ns,
+             "symbols": int(g.counts().sum()), "ssa_log2_step": 5, "layout": g.layout_stats()}
+    arow = {"case": "(a) string_graph_dev over all %d strings, min_ovlp=%d max_ext=%d max_steps=%d max_recs=%d max_hits=%d pairs=1" % (ns, min_ovlp, L - min_ovlp, a.irreducible_steps, M, H8),
+            "measured": True, "sources": ns, "edges": m, "seconds": sec, "seconds_fastest": lo, "seconds_slowest": hi, "sources_per_s": ns / sec, "edges_per_s": m / sec,
+            "edge_bytes_per_s": 32 * m / sec, "info": [int(v) for v in info]}
+    print("graph: %d sources, %d edges in %.3f s" % (ns, m, sec), file=sys.stderr, flush=True)
+    # (c) the glue: the search alone on the same strings, their texts already on the device
+    _, txt, ln = g.extract_raw(np.arange(ns, dtype=np.int64), L)
+    assert (ln == L).all()
+    flat = np.ascontiguousarray(txt.reshape(-1)); off = np.arange(ns + 1, dtype=np.int64) * L
+    dq, do, dr, dc = g.dev_alloc(len(flat)), g.dev_alloc(8 * (ns + 1)), g.dev_alloc(32 * M * ns), g.dev_alloc(8 * ns)
+    g.L.rb2_hip_memcpy(g.h, dq, flat.ctypes.data, len(flat), 0)
+    g.L.rb2_hip_memcpy(g.h, do, off.ctypes.data, 8 * (ns + 1), 0)
+    isec, ilo, ihi = spread(lambda: g.irreducible_dev(ns, dq, do, dr, dc, L, min_ovlp, L - min_ovlp, a.irreducible_steps, M), g.sync)
+    sec2, lo2, hi2 = spread(full, lambda: None)                       # (again, next to it in time)
+    for q in (dq, do, dr, dc, de):
+        g.dev_free(q)
+    del txt, flat
+    crow = {"case": "(c) irreducible_dev alone on the same %d strings, texts resident, against string_graph_dev measured next to it" % ns, "measured": True,
+            "irreducible_dev_seconds": isec, "irreducible_dev_fastest": ilo, "irreducible_dev_slowest": ihi,
+            "string_graph_dev_seconds": sec2, "string_graph_dev_fastest": lo2, "string_graph_dev_slowest": hi2,
+            "glue_seconds": sec2 - isec, "string_graph_over_irreducible": sec2 / isec}
+    # (b) against the host composition, on a sample the Python loop can follow
+    S = min(a.unitig_sample, ns)
+
+    def composed():
+        got["composed"] = g.edges(np.arange(S, dtype=np.int64), **kw)
+
+    def fused():
+        got["fused"] = g.string_graph(0, S, **kw)
+    bsec = timed(composed, lambda: None, reps=1)                      # (edges() raises when a read of the sample runs out of max_steps: raise --irreducible-steps then)
+    fsec, flo, fhi = spread(fused, lambda: None)
+    f_edges, f_info = got["fused"]
+    same = bool(np.array_equal(f_edges[np.lexsort(f_edges.T[::-1])], got["composed"]))
+    brow = {"case": "(b) baseline: HipBwt.edges() (extract, irreducible, string_ids through host buffers, Python tuples), the first %d strings" % S, "measured": True,
+            "sources": S, "seconds": bsec, "edges": int(len(got["composed"])), "sources_per_s": S / bsec, "equals_fused": same}
+    frow = {"case": "(b) string_graph (host buffers) on the same %d strings" % S, "measured": True, "sources": S, "seconds": fsec, "seconds_fastest": flo, "seconds_slowest": fhi,
+            "edges": int(len(f_edges)), "sources_per_s": S / fsec, "info": [int(v) for v in f_info], "composed_over_fused": bsec / fsec}
+    g.close()
+    res["string_graph"] = {"index": index, "cases": [arow, brow, frow, crow]}
+
+
 def save_fmd_case(a, res):
     """rb2_hip_save_fmd against the route the host layer offers for the same bytes: rb2_hip_stream_rope of the six ropes into the parallel host
     writer (rb2_fmdp_*, 16 threads) and rb2_fmd_write to /dev/shm.  Warm-up, then the median of three; both routes end synchronised."""
@@ -985,7 +1058,16 @@ def main():
     ap.add_argument("--unitig-sample", type=int, default=20_000, help="vertices of the sample the host composition is timed on")
     ap.add_argument("--save-fmd", action="store_true", help="only the device .fmd encoder against the host writer (added to an existing --out file)")
     ap.add_argument("--merge", action="store_true", help="only unpack and merge (added to an existing --out file)")
+    ap.add_argument("--graph", action="store_true", help="only the string graph on the device (added to an existing --out file)")
     a = ap.parse_args()
+    if a.graph:
+        res = {"cases": []}
+        if a.out and os.path.exists(a.out):
+            with open(a.out) as f:
+                res = json.load(f)
+        graph_case(a, res)
+        finish(a, res)
+        return
     if a.merge:
         res = {"cases": []}
         if a.out and os.path.exists(a.out):
