@@ -32,6 +32,9 @@
  *     larger batches simply stay on the dense path -- a performance boundary, not an error;
  *   - leaf slots of one pool are addressed with 32 bits in the sparse layout (the work orders, the split list): 2^32 slots = 4.3 T symbols;
  *   - symbols must be nt6 codes 0..5, the buffer must end with a sentinel (mrope.c:268);
+ *   - rb2_hip_load_ropes takes at most 2^20 run codes longer than 4096 symbols per rope, rb2_hip_load_fmd at most 2^20 per file
+ *     (what counts is the part of one code inside one piece: a run written as several codes counts once per code, a code cut by a
+ *     piece border once per part; codes of symbol 0 do not count; the list of parts that get a workgroup of their own has that many slots);
  *   - the index lives in HBM: 2 x 0.38 B per symbol (dense layout) plus ~100 B per string of the batch; running out of device
  *     memory reports the size that was needed.
  *

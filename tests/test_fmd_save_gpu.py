@@ -10,6 +10,7 @@ import pytest
 import fmd_ref
 import helpers as H
 from fmd_save_ref import fmd_of, write_fmd
+from fmd_streams import run8
 from ropebwt2_amd.hipbwt import encode_runs
 
 pytestmark = pytest.mark.gpu
@@ -103,22 +104,18 @@ def test_built_index(hip, tmp_path, so, variant):
 
 # ---- merging across ropes, empty ropes, long runs -------------------------------------------------------------------------------------
 
-def _run8(l, c):
-    """one 8-byte run of the 43+3 codec (rle.h:53-75), as hipbwt.encode_runs writes runs of 2^19 symbols and more"""
-    tail = [0x80 | (l >> (6 * k)) & 0x3f for k in range(7)]
-    return np.array([0xF0 | (l >> 42) << 3 | c] + tail[::-1], np.uint8)
-
-
 def test_type2_header_and_a_run_over_2_20_leaves(hip, tmp_path):
     n = 1 << 30
     # one string of 2^30 A's: rope $ = A; rope A = 2^30 - 1 A's, then $ -- the A of rope $ and the A's of rope A are one run
-    rles = [encode_runs([1]), np.concatenate([_run8(n - 1, 1), encode_runs([0])])] + [np.zeros(0, np.uint8)] * 4
+    rles = [encode_runs([1]), np.concatenate([run8(n - 1, 1), encode_runs([0])])] + [np.zeros(0, np.uint8)] * 4
     g = hip.HipBwt(0)
     g.load_ropes(rles)
     want = write_fmd(tmp_path / "t2.fmd", pushes=[(1, 1), (n - 1, 1), (1, 0)])
     words = fmd_ref.parse(want.tobytes())["words"]
     assert len(words) == 8 + 7 and int(words[8]) >> 62 == 2
     same(g.save_fmd(), want, "2^30 A's")
+    with _Env(RB2_FMDS_SEG="96"):                                    # the type-2 header opens a segment of its own kind, at the default batch
+        same(g.save_fmd(), want, "2^30 A's, segments of 96 runs")
     g.close()
 
 
