@@ -685,10 +685,17 @@ void rb2_hip_rewind_stats(rb2_hip_t *h, int64_t out[4]);
 void rb2_hip_steady_stats(rb2_hip_t *h, int64_t out[4]);
 /* lean rounds ("the lean round"): a dense round of a single engine that the host knows to be one of one-member groups and empty
  * intervals when it queues its counting phase writes no insert list (INS_E / INS_A); the window search and the merge read the strings' positions and
- * symbols in its place.  out[0] = dense rounds run lean since create, out[1] = the stage in force: 0 = off, 1 = no insert list (RB2_STEADY_LEAN=0 / 1 at
- * create, default 1; a larger value means 1 -- a second stage, k_sym reading the symbols only, was measured and is not part of the library;
- * RB2_STEADY=0 switches it off as well). */
+ * symbols in its place.  out[0] = dense rounds run lean since create, out[1] = the stage in force: 0 = off, 1 = no insert list, 2 = no insert list and
+ * the round is counted from the symbols alone (RB2_STEADY_LEAN=0 / 1 / 2 at create; a larger value means 2; RB2_STEADY=0 switches it off as well).
+ * Stage 2 takes the lean rounds whose counting tail is the three-launch form only: a handle created with it reports 1 until it has queued such a
+ * round (batches of few string tiles never do: their lean rounds are stage-1 rounds), 2 from then on. */
 void rb2_hip_lean_stats(rb2_hip_t *h, int64_t out[2]);
+/* stage 2 of the lean round ("the lean count"): one small launch (k_count_lean) writes the tile records and chunk totals of
+ * the round from the strings' symbols, in the place of the k_sym and k_tscan1 launches.  out[0] = rounds counted that way since create, out[1] =
+ * audit rounds (every RB2_LEAN_AUDIT-th lean round of a batch, default 8, 0 = never, is counted by k_sym as in stage 1: it looks at the positions
+ * and keeps the guard of the steady round alive), out[2] = rounds in which both ways ran and were compared (RB2_LEAN_VERIFY=1 at create; tests),
+ * out[3] = words in which they differed (a difference is fatal at the end of its batch). */
+void rb2_hip_lean_count_stats(rb2_hip_t *h, int64_t out[4]);
 /* window formats of the dense layout (a window = 4 leaves = 4096 symbols; csrc/rb2_merge.h): out[0..3] = windows the dense merge wrote
  * plain (three bit planes) / compact with no, one, two lines of exception positions -- counted on the device only when the handle was
  * created with RB2_COMPACT_STATS=1 in the environment (zeros otherwise) --, out[4] = dense rounds that were allowed to write compact

@@ -139,6 +139,7 @@ struct Ctl {
 	uint32_t unfused[2];    // [p] != 0: in the round of parity p k_sym met a tile it could not place itself (not TILE_DONE).  A flag: plain stores; the setup of the round in front clears it, like ne
 	uint32_t was_fused;     // some round of the batch was reported fused (setup_body, one engine)
 	uint32_t steady_bad;    // sticky: round steady_bad - 1 was not fused behind a round that was -- the rule the host skips k_prep<AE> by does not hold (batch_end: fatal)
+	uint32_t lean_mismatch; // RB2_LEAN_VERIFY: words of the tile records / chunk totals in which k_count_lean and k_sym + k_tscan1 differed (k_lean_compare; batch_end: fatal)
 };
 constexpr int GCN = NR * 6 + 2;         // words of the per-round count matrix buffers: NR x 6 counts + [NR * 6] = "some string of this rank has a non-empty
                                         // interval this round" (summed over the ranks of a sharded index like the counts: zero = every rank may launch the

@@ -229,8 +229,16 @@ struct rb2_hip_s {
 	bool steady_launched = false;       // a round of this batch relied on the report: batch_end looks at Ctl::steady_bad
 	int64_t n_prep_skipped = 0, steady_seen = -1, steady_used = -1;   // rb2_hip_steady_stats
 	// ... and run "lean" ("the lean round"): k_sym writes no INS_E / INS_A, k_part and k_merge read L and A in their place
-	int lean = 1;                       // RB2_STEADY_LEAN: 0 = off, 1 = on (a larger value means 1: the second stage was measured and taken out); RB2_STEADY=0 switches it off as well
+	int lean = 2;                       // RB2_STEADY_LEAN: 0 = off, 1 = on, 2 = on and the round is counted from A alone where it can be (k_count_lean; a larger value means 2); RB2_STEADY=0 switches it off as well
 	int64_t n_lean_rounds = 0;          // dense rounds run lean (rb2_hip_lean_stats)
+	// stage 2 ("the lean count"): nothing looks at L in a round counted by k_count_lean, so every lean_audit-th lean round of a batch is counted by
+	// k_sym as in stage 1 -- a group of two never splits again: the audit round meets it and setup_body reports it (Ctl::steady_bad)
+	int lean_audit = 8;                 // RB2_LEAN_AUDIT: 0 = never
+	bool lean2_met = false;             // some lean counting phase of this handle had the three-launch tail: stage 2 took it (or audited it).  Until then the handle's lean rounds
+	                                    // are stage-1 rounds (k_tscan_setup) and rb2_hip_lean_stats says so
+	int lean_verify = 0;                // RB2_LEAN_VERIFY=1 (tests): k_sym + k_tscan1 of the round run as well, into buffers of their own; k_lean_compare counts the words that differ (batch_end: fatal)
+	int64_t n_lean_counted = 0, n_lean_audit = 0, n_lean_verified = 0, n_lean_mismatch = 0;   // rb2_hip_lean_count_stats
+	DevBuf<TileRec> trec_v; DevBuf<ChunkPart> cpart_v;   // (RB2_LEAN_VERIFY)
 	int64_t n_rewind = 0, n_rewound = 0, rewind_max = 0, n_rewind_even = 0;   // void rounds taken back from behind queued rounds: how many, rounds taken back, deepest, of even depth (rb2_hip_rewind_stats)
 	unsigned long long *pair_d = nullptr, *pair_h = nullptr;   // k_pair_hist: what the batch just uploaded adds to the count matrix (device, pinned host)
 	bool pair_valid = false;
@@ -388,6 +396,9 @@ struct BatchState {
 	uint64_t counted = (uint64_t)-1;        // round whose counting phase (round_counts) is already queued
 	int lean = 0;                           // ... and the last counting phase queued was a lean one (decided at its k_sym launch; round_merge follows THIS, never known_steady:
 	                                        // a round counted before the host heard the report holds INS_E / INS_A and is merged from them)
+	                                        // 2: counted by k_count_lean -- no head flags in A, k_advance takes every string for a head
+	bool lean_audit = false;                // ... lean == 1 because the round is an audit round of stage 2
+	uint64_t n_lean2 = 0;                   // counting phases of this batch that stage 2 could take, audit rounds included (every lean_audit-th is one)
 	uint64_t setup_round = (uint64_t)-1;    // round whose k_setup ran inside its counting phase (k_tscan_setup) ...
 	bool setup_sparse = false; uint64_t setup_epoch = 0;   // ... for this layout, at this layout epoch (a re-layout in between: k_setup runs again)
 };
@@ -402,6 +413,7 @@ void ensure_strings(rb2_hip_t *h, uint64_t m)
 	h->A[0].ensure(m); h->A[1].ensure(m); h->INS_A.ensure(m); h->START.ensure(m + 1);
 	const uint64_t nst = cdiv(m, STILE) + NR;
 	h->trec.ensure(nst + 8 * XCD_RUN + 8); h->tsc.ensure(nst + 8 * XCD_RUN + 8); h->tfix.ensure(nst + 8 * XCD_RUN + 8); h->cpart.ensure(cdiv(nst, SCHUNK) + 1);
+	if (h->lean_verify) { h->trec_v.ensure(nst + 8 * XCD_RUN + 8); h->cpart_v.ensure(cdiv(nst, SCHUNK) + 1); }
 }
 
 // the string arrays of the round as the round kernels see them: side B.cur this round, side B.cur ^ 1 the next, positions stored as P
@@ -582,6 +594,11 @@ void round_counts(rb2_hip_t *h, BatchState &B, uint64_t r, bool spec = false, bo
 	// lean: the dense one-engine launch k_sym<false, P, false> of a batch the host knows steady (the in-place layout's k_part_sparse / k_merge_leaf need INS_E / INS_A)
 	B.lean = (allow_lean && !spec && h->nranks == 1 && !h->sparse && B.known_steady && h->steady_on) ? h->lean : 0;
 	const bool one_launch_tail = B.nst_ub < (unsigned)h->ts_max;  // few tiles (long reads): the counting tail is one launch (k_tscan_setup)
+	// stage 2: k_count_lean in the place of k_sym and k_tscan1 -- the three-launch tail only (k_tscan_setup reads the records of a k_sym launch), and not in an audit round
+	B.lean_audit = false;
+	if (B.lean == 2 && one_launch_tail) B.lean = 1;
+	if (B.lean == 2) h->lean2_met = true;
+	if (B.lean == 2 && h->lean_audit > 0 && ++B.n_lean2 % (uint64_t)h->lean_audit == 0) { B.lean = 1; B.lean_audit = true; }
 	if (!spec) require_verdicts_seen(h, r, "counting phase without spec of round");   // (its k_setup runs whatever ctl->overflow says)
 	SplitArgs sp; memset(&sp, 0, sizeof(sp));
 	if (spec) {
@@ -598,6 +615,16 @@ void round_counts(rb2_hip_t *h, BatchState &B, uint64_t r, bool spec = false, bo
 	      hipLaunchKernelGGL((k_sym<false, P, true>), dim3((unsigned)rank_share(h, B.nst_ub) + sp.nsplitb + (sp.scan2 ? 1u : 0u)), dim3(256), 0, st, h->ctl, sd, (int)(r & 1), S, trs, sp);
 	    } else
 	    if (h->nranks > 1) hipLaunchKernelGGL((k_sym<true, P>), dim3(grid8((unsigned)rank_share(h, B.nst_ub))), dim3(256), 0, st, h->ctl, sd, (int)(r & 1), S, trs, sp);
+	    else if (B.lean == 2) {
+	      hipLaunchKernelGGL(k_count_lean, dim3(B.nsc), dim3(SCHUNK), 0, st, h->ctl, sd, (const uint8_t*)S.A, trs, h->cpart.p);
+	      if (h->lean_verify) {                                    // (tests) the launches this one stands for, into buffers of their own, and the comparison
+	        const TileRecs trv = { (uint32_t*)h->trec_v.p, (uint32_t)(h->trec_v.cap & ~(size_t)3) };
+	        hipLaunchKernelGGL((k_sym<false, P, false, true>), dim3(grid8(cdiv(B.nst_ub, (unsigned)SYM_PAIR))), dim3(256), 0, st, h->ctl, sd, (int)(r & 1), S, trv, sp);
+	        hipLaunchKernelGGL(k_tscan1, dim3(B.nsc), dim3(SCHUNK), 0, st, h->ctl, sd, trv, h->cpart_v.p);
+	        hipLaunchKernelGGL(k_lean_compare, dim3(std::max<unsigned>(1u, cdiv(B.nst_ub, 256))), dim3(256), 0, st, h->ctl, sd, trs, trv, (const ChunkPart*)h->cpart.p, (const ChunkPart*)h->cpart_v.p);
+	        ++h->n_lean_verified;
+	      }
+	    }
 	    else if (B.lean) hipLaunchKernelGGL((k_sym<false, P, false, true>), dim3(grid8(cdiv(B.nst_ub, (unsigned)SYM_PAIR))), dim3(256), 0, st, h->ctl, sd, (int)(r & 1), S, trs, sp);
 	    else hipLaunchKernelGGL((k_sym<false, P>), dim3(grid8(cdiv(B.nst_ub, (unsigned)SYM_PAIR))), dim3(256), 0, st, h->ctl, sd, (int)(r & 1), S, trs, sp); }); }   // (one engine: a block takes SYM_PAIR tiles)
 	tl_slow(h, "k_sym");
@@ -610,7 +637,7 @@ void round_counts(rb2_hip_t *h, BatchState &B, uint64_t r, bool spec = false, bo
 	  if (do_setup) mark_setup(h, B, r);
 	} else
 	{ Scope sc(h, RB2_K_TSCAN, units);
-	  hipLaunchKernelGGL(k_tscan1, dim3(B.nsc), dim3(SCHUNK), 0, st, h->ctl, sd, trs, h->cpart.p);
+	  if (B.lean != 2) hipLaunchKernelGGL(k_tscan1, dim3(B.nsc), dim3(SCHUNK), 0, st, h->ctl, sd, trs, h->cpart.p);   // (k_count_lean wrote the chunks' totals itself)
 	  if (B.nsc <= (unsigned)h->ts_fold) hipLaunchKernelGGL(k_tscan3<true>, dim3(B.nsc), dim3(SCHUNK), 0, st, h->ctl, sd, trs, h->cpart.p, h->tsc.p);   // (the scan over the chunks folded in)
 	  else {
 	    hipLaunchKernelGGL(k_tscan2, dim3(1), dim3(SCHUNK), 0, st, h->ctl, sd, h->cpart.p);
@@ -667,6 +694,7 @@ void round_merge(rb2_hip_t *h, BatchState &B, uint64_t r, ShardRec *send, bool c
 	const bool lean = B.lean != 0;
 	if (lean && (h->nranks != 1 || h->sparse || !B.known_steady)) { rb2_fatal("[rb2_hip] internal: round %llu was counted lean and is not merged as a steady dense round\n", (unsigned long long)r); }
 	if (lean) ++h->n_lean_rounds;
+	if (B.lean == 2) ++h->n_lean_counted; else if (lean && B.lean_audit) ++h->n_lean_audit;
 	with_pos(h, B, [&](const auto &S) { using P = std::remove_pointer_t<decltype(S.L)>;
 	launch_prep<false>(h, B, r, oldp, S);
 	tl_slow(h, "k_prep");
@@ -900,10 +928,12 @@ void batch_end(rb2_hip_t *h)
 	HIPCHK(hipGetLastError());
 	fetch_ropes(h);
 	if (h->steady_launched) {                                   // the guard of setup_body: a round that was not what the host believed
-		uint32_t bad = 0;
-		HIPCHK(hipMemcpyAsync(&bad, &h->ctl->steady_bad, 4, hipMemcpyDeviceToHost, h->st));
+		uint32_t bad2[2] = {0, 0};                                 // steady_bad, lean_mismatch
+		HIPCHK(hipMemcpyAsync(bad2, &h->ctl->steady_bad, 8, hipMemcpyDeviceToHost, h->st));
 		HIPCHK(hipStreamSynchronize(h->st));
 		h->steady_launched = false;
+		const uint32_t bad = bad2[0];
+		if (bad2[1]) { h->n_lean_mismatch += bad2[1]; rb2_fatal("[rb2_hip] internal: k_count_lean and k_sym + k_tscan1 differ in %u words of their tile records / chunk totals (RB2_LEAN_VERIFY)\n", bad2[1]); }
 		if (bad) { rb2_fatal("[rb2_hip] internal: round %u is not a round of one-member groups behind a round that was\n", bad - 1u); }
 	}
 	drain_profile(h);
@@ -1143,8 +1173,10 @@ rb2_hip_t *rb2_hip_create(int device, int sorting_order)
 	if (getenv("RB2_RUN_AHEAD")) h->run_ahead = std::max(1, atoi(getenv("RB2_RUN_AHEAD")));
 	if (getenv("RB2_VERDICT_POLL")) h->verdict_poll = atoi(getenv("RB2_VERDICT_POLL"));
 	if (getenv("RB2_STEADY")) h->steady_on = atoi(getenv("RB2_STEADY")) != 0;
-	if (getenv("RB2_STEADY_LEAN")) h->lean = std::min(1, std::max(0, atoi(getenv("RB2_STEADY_LEAN"))));
+	if (getenv("RB2_STEADY_LEAN")) h->lean = std::min(2, std::max(0, atoi(getenv("RB2_STEADY_LEAN"))));
 	if (!h->steady_on) h->lean = 0;
+	if (getenv("RB2_LEAN_AUDIT")) h->lean_audit = std::max(0, atoi(getenv("RB2_LEAN_AUDIT")));
+	if (getenv("RB2_LEAN_VERIFY")) h->lean_verify = atoi(getenv("RB2_LEAN_VERIFY")) != 0;
 	if (getenv("RB2_STEADY_AHEAD")) h->steady_ahead = std::max(0, atoi(getenv("RB2_STEADY_AHEAD")));
 	{ Ctl *hc = (Ctl*)calloc(1, sizeof(Ctl)); for (int b = 0; b < NR; ++b) hc->own[b] = 1; HIPCHK(hipMemcpy(h->ctl, hc, sizeof(Ctl), hipMemcpyHostToDevice)); free(hc); }
 	HIPCHK(hipMemsetAsync(h->d_tmp, 0, 256, h->st));
@@ -1165,7 +1197,7 @@ void rb2_hip_destroy(rb2_hip_t *h)
 	h->START.release(); h->SIZE.release(); h->INS_E.release(); h->RKREL.release(); h->RKOLD.release(); h->SPL.release(); h->qbuf.release(); h->zblk.release(); h->qtab.release(); h->qbytes.release(); h->qin.release(); h->qout.release(); h->qscr.release();
 	h->LD.release(); h->A[0].release(); h->A[1].release(); h->INS_A.release(); h->sbuf.release(); h->sbuf2.release();
 	if (h->st_copy) HIPCHK(hipStreamDestroy(h->st_copy));
-	h->trec.release(); h->tsc.release(); h->tfix.release(); h->cpart.release(); h->sbtot.release();
+	h->trec.release(); h->tsc.release(); h->tfix.release(); h->cpart.release(); h->sbtot.release(); h->trec_v.release(); h->cpart_v.release();
 	for (auto e : h->evpool) hipEventDestroy(e);
 	HIPCHK(hipHostFree(h->mb_h)); HIPCHK(hipEventDestroy(h->ev_flag));
 
@@ -2124,7 +2156,13 @@ void rb2_hip_rewind_stats(rb2_hip_t *h, int64_t out[4])
 
 void rb2_hip_lean_stats(rb2_hip_t *h, int64_t out[2])
 { finish_pending(h);
-	out[0] = h->n_lean_rounds; out[1] = h->lean;
+	out[0] = h->n_lean_rounds; out[1] = (h->lean == 2 && !h->lean2_met) ? 1 : h->lean;   // (the stage in force: a handle that has only met the one-launch tail runs stage 1)
+}
+
+void rb2_hip_lean_count_stats(rb2_hip_t *h, int64_t out[4])
+{
+	finish_pending(h);
+	out[0] = h->n_lean_counted; out[1] = h->n_lean_audit; out[2] = h->n_lean_verified; out[3] = h->n_lean_mismatch;
 }
 
 void rb2_hip_window_stats(rb2_hip_t *h, int64_t out[6])

@@ -309,7 +309,7 @@ constexpr int32_t TILE_SINGLE = 0x20000;     // ... every string of the tile is 
 constexpr int SYM_PAIR = RB2_SYM_PAIR != 0 ? 2 : 1;   // tiles per block of k_sym<false, P, false> (the host sizes its grid by it)
 // LEAN (one engine, dense, once the host knows the batch steady: DESIGN 10, "the lean round"): the same kernel without the INS_E / INS_A stores of a
 // fused tile -- in such a round k_part and k_merge read L and A in their place (E[q] + q == L[q]); heads, tile records and Ctl::unfused as ever.
-// (A form that read A only and set no head flags -- k_advance took every string for a head -- was measured and taken out: k_part then reads L cold.)
+// (A form of THIS kernel that read A only and set no head flags was measured and taken out; k_count_lean below does that in one block per chunk, chunk totals included.)
 template <bool STRIDE, typename P = uint64_t, bool SPLIT = false, bool LEAN = false> __global__ __launch_bounds__(256) void k_sym(const Ctl *ctl, int side, int par, StrArrays<P> S, TileRecs trec, SplitArgs sp)
 {
 	static_assert(!LEAN || (!STRIDE && !SPLIT), "the lean round is a dense round of one engine");
@@ -465,6 +465,140 @@ __global__ __launch_bounds__(SCHUNK) void k_tscan1(const Ctl *ctl, int side, con
 	int mn = INT_MAX; for (int i = 0; i < SCHUNK / 64; ++i) mn = min(mn, s_wi[i]);
 	p.mx = mx; p.mn = mn;
 	if (threadIdx.x == 0) part[blockIdx.x] = p;
+}
+
+// ---------------------------------------------------------------------------------------------
+// k_count_lean: the k_sym<.., LEAN> and k_tscan1 launches of a lean round in one small launch ("the lean count"; RB2_STEADY_LEAN=2)
+// ---------------------------------------------------------------------------------------------
+// In a lean round every string is a group of its own with an empty interval, so the record of a tile is a function of its bytes of A alone:
+// hist = the tile's count per symbol, fh = 0, lh = nval - 1 | TILE_DONE | TILE_SINGLE, fhpre = 0, lhpre = hist - [the last string's symbol].
+// One block per chunk of SCHUNK tiles (the grid of k_tscan1), thread x owns tile x of the chunk: it looks up the tile's place, and at the end
+// writes its record and adds to the chunk's totals (the ChunkPart k_tscan1 would have written, from the same registers).  In between the block
+// reads A -- and nothing else -- 32 bytes per lane: a tile is 16 lanes = one DPP row, a wave takes four tiles per trip and its own 64 tiles in 16
+// trips, CL_TRIPS of them at a time: every load of a batch is issued before one is looked at, and the next batch's before this one is counted.
+// A tile starts at any byte (seg.start[b] + lt * 512): lane i loads its bytes 32 i .. 32 i + 31 wherever they lie, as two loads of 16 (a 16-byte
+// load of byte alignment is one instruction on gfx950 in the unaligned access mode every HSA process runs in, and the compiler emits it as such) --
+// the tile's own bytes, never one outside it.  In a short tile (the last of a bucket) only the sixteens that belong to it whole are loaded, and the
+// bytes behind the last of them go one to a lane, in a third load of the trip.
+// Symbols are counted as in wave_leaf_counts: the popcounts of bit 0, bit 1, bit 2, bits 0 & 1, bits 0 & 2 over the tile, five 10-bit numbers
+// in two words that reduce over the tile's 16 lanes by DPP; the owner of the tile turns them into the six counts (a batch holds codes 0..5 only:
+// batch_begin).  Flags above the symbol are masked off.  No atomics, no block waits for another.
+constexpr int CL_TRIPS = 4;
+__global__ __launch_bounds__(SCHUNK) void k_count_lean(const Ctl *ctl, int side, const uint8_t *A, TileRecs trec, ChunkPart *part)
+{
+	static_assert(STILE == 512 && SCHUNK == 1024, "a tile is 16 lanes of 32 bytes, a wave owns 64 tiles");
+	struct __attribute__((packed, aligned(1))) U4 { uint32_t x, y, z, w; };   // sixteen bytes at any address
+	__shared__ uint32_t s_t0[NR + 1], s_r0[SCHUNK], s_r1[SCHUNK];
+	__shared__ uint64_t s_st[NR], s_cn[NR], s_sum[SCHUNK / 64][2];
+	__shared__ uint2 s_bn[SCHUNK];                               // a tile's first string and the number of its strings
+	__shared__ int s_mx[SCHUNK / 64], s_mn[SCHUNK / 64];
+	const SegDesc &sg = ctl->seg[side];
+	const uint32_t nt = sg.tile0[NR];
+	if (blockIdx.x * SCHUNK >= nt) return;
+	if (threadIdx.x <= NR) s_t0[threadIdx.x] = sg.tile0[threadIdx.x];
+	if (threadIdx.x < NR) { s_st[threadIdx.x] = sg.start[threadIdx.x]; s_cn[threadIdx.x] = sg.cnt[threadIdx.x]; }
+	__syncthreads();
+	const uint32_t tile = blockIdx.x * SCHUNK + threadIdx.x;
+	const bool ok = tile < nt;
+	uint32_t mybase = 0, mynv = 0, lastsym = 7;
+	if (ok) {
+		int b = 0;                                                // the bucket: as many as there are entries of tile0[1 .. NR] at or below the tile
+#pragma unroll
+		for (int st = 16; st; st >>= 1) if (b + st <= NR && tile >= s_t0[b + st]) b += st;
+		const uint64_t off = (uint64_t)(tile - s_t0[b]) * STILE;
+		mybase = (uint32_t)(s_st[b] + off);                       // (a batch has < 2^32 strings)
+		mynv = (uint32_t)min((uint64_t)STILE, s_cn[b] - off);
+		if (mynv) lastsym = A[(uint64_t)mybase + mynv - 1];       // (looked at in the end)
+	}
+	s_bn[threadIdx.x] = make_uint2(mybase, mynv);
+	__syncthreads();
+	const uint32_t ln = (uint32_t)lane_id(), li = ln & 15u, t0w = (uint32_t)wave_id() * 64u + (ln >> 4);   // trip j: tile t0w + 4 j of the chunk
+	constexpr uint32_t K7 = 0x07070707u, N1 = 0x11111111u;
+	constexpr int NB = 16 / CL_TRIPS;
+	const uint8_t *const safe = (const uint8_t*)ctl;             // sixteen readable bytes for a lane that has none of the tile's (masked off below)
+	U4 wv[2][CL_TRIPS][2];
+	uint32_t nv[2][CL_TRIPS], xb[2][CL_TRIPS];
+	auto issue = [&](const int jb, const int k, U4 &w0, U4 &w1, uint32_t &n, uint32_t &x) {
+		const uint2 bn = s_bn[t0w + 4u * (uint32_t)(jb * CL_TRIPS + k)];
+		const uint8_t *p = A + bn.x;
+		n = bn.y;
+		// unconditional loads (a load in a branch of its own makes every later wait a wait for ALL loads: the next batch's would not stay in flight)
+		w0 = *(const U4*)(32u * li + 16u <= n ? p + 32u * li : safe);
+		w1 = *(const U4*)(32u * li + 32u <= n ? p + 32u * li + 16u : safe);
+		x = 0u;
+		if (li < (n & 15u)) x = p[(n & ~15u) + li];               // a short tile: the bytes behind its last whole sixteen, one a lane
+	};
+	auto count = [&](const int jb, const int k, const U4 &w0, const U4 &w1, const uint32_t n, const uint32_t x) {
+		const uint32_t m0 = 32u * li + 16u <= n ? K7 : 0u, m1 = 32u * li + 32u <= n ? K7 : 0u;   // (a zero byte adds to none of the five counts)
+		const uint32_t X = (w0.x & m0) | (w0.y & m0) << 4, Y = (w0.z & m0) | (w0.w & m0) << 4;   // sixteen symbols, a nibble each
+		const uint32_t Z = (w1.x & m1) | (w1.y & m1) << 4, W = (w1.z & m1) | (w1.w & m1) << 4;
+		const uint32_t X1 = X >> 1, Y1 = Y >> 1, Z1 = Z >> 1, W1 = W >> 1, X2 = X >> 2, Y2 = Y >> 2, Z2 = Z >> 2, W2 = W >> 2;
+		uint32_t p0 = __popc(X & N1) + __popc(Y & N1) + __popc(Z & N1) + __popc(W & N1);
+		uint32_t p1 = __popc(X1 & N1) + __popc(Y1 & N1) + __popc(Z1 & N1) + __popc(W1 & N1);
+		uint32_t p2 = __popc(X2 & N1) + __popc(Y2 & N1) + __popc(Z2 & N1) + __popc(W2 & N1);
+		uint32_t p01 = __popc(X & X1 & N1) + __popc(Y & Y1 & N1) + __popc(Z & Z1 & N1) + __popc(W & W1 & N1);
+		uint32_t p02 = __popc(X & X2 & N1) + __popc(Y & Y2 & N1) + __popc(Z & Z2 & N1) + __popc(W & W2 & N1);
+		if (n != (uint32_t)STILE) { p0 += x & 1u; p1 += (x >> 1) & 1u; p2 += (x >> 2) & 1u; p01 += (x & 3u) == 3u; p02 += (x & 5u) == 5u; }
+		uint32_t r0 = p0 | p1 << 10 | p2 << 20, r1 = p01 | p02 << 10;
+		// sums over the tile's 16 lanes = one DPP row (lane 15 of the row holds them)
+		r0 += dpp0<0x111, 0xf>(r0); r1 += dpp0<0x111, 0xf>(r1); r0 += dpp0<0x112, 0xf>(r0); r1 += dpp0<0x112, 0xf>(r1);
+		r0 += dpp0<0x114, 0xf>(r0); r1 += dpp0<0x114, 0xf>(r1); r0 += dpp0<0x118, 0xf>(r0); r1 += dpp0<0x118, 0xf>(r1);
+		if (li == 15u) { const uint32_t tl = t0w + 4u * (uint32_t)(jb * CL_TRIPS + k); s_r0[tl] = r0; s_r1[tl] = r1; }
+	};
+#pragma unroll
+	for (int k = 0; k < CL_TRIPS; ++k) issue(0, k, wv[0][k][0], wv[0][k][1], nv[0][k], xb[0][k]);
+#pragma unroll
+	for (int jb = 0; jb < NB; ++jb) {                             // the next batch's loads are in flight while this one is counted
+		if (jb + 1 < NB) {
+#pragma unroll
+			for (int k = 0; k < CL_TRIPS; ++k) issue(jb + 1, k, wv[(jb + 1) & 1][k][0], wv[(jb + 1) & 1][k][1], nv[(jb + 1) & 1][k], xb[(jb + 1) & 1][k]);
+		}
+#pragma unroll
+		for (int k = 0; k < CL_TRIPS; ++k) count(jb, k, wv[jb & 1][k][0], wv[jb & 1][k][1], nv[jb & 1][k], xb[jb & 1][k]);
+	}
+	__syncthreads();
+	uint32_t c[6] = {0, 0, 0, 0, 0, 0};
+	if (ok) {
+		const uint32_t r0 = s_r0[threadIdx.x], r1 = s_r1[threadIdx.x];
+		const uint32_t p0 = r0 & 1023u, p1 = (r0 >> 10) & 1023u, p2 = r0 >> 20, p01 = r1 & 1023u, p02 = r1 >> 10;
+		c[3] = p01; c[5] = p02; c[1] = p0 - p01 - p02; c[2] = p1 - p01; c[4] = p2 - p02;
+		c[0] = mynv - (c[1] + c[2] + c[3] + c[4] + c[5]);
+		const uint32_t ls = lastsym & 7u;
+#pragma unroll
+		for (int s = 0; s < 6; ++s) { trec.hist(s, tile) = c[s]; trec.fhpre(s, tile) = 0u; trec.lhpre(s, tile) = mynv ? c[s] - (ls == (uint32_t)s ? 1u : 0u) : 0u; }
+		trec.fh(tile) = mynv ? 0 : -1;
+		trec.lh(tile) = mynv ? ((int32_t)mynv - 1) | TILE_DONE | TILE_SINGLE : -1;
+	}
+	// the chunk's totals: three 21-bit numbers a word (a chunk holds 2^19 strings)
+	const uint64_t w0 = dpp_incl_add64((uint64_t)c[0] | (uint64_t)c[1] << 21 | (uint64_t)c[2] << 42), w1 = dpp_incl_add64((uint64_t)c[3] | (uint64_t)c[4] << 21 | (uint64_t)c[5] << 42);
+	const uint64_t hm = ballot64(ok && mynv != 0);               // the tiles that have a group head
+	if (ln == 63u) { s_sum[wave_id()][0] = w0; s_sum[wave_id()][1] = w1; }
+	if (ln == 0u) {
+		const int tb = (int)(tile);                               // (lane 0: the wave's first tile)
+		s_mx[wave_id()] = hm ? tb + 63 - __builtin_clzll(hm) : -1;
+		s_mn[wave_id()] = hm ? tb + __builtin_ctzll(hm) : INT_MAX;
+	}
+	__syncthreads();
+	if (threadIdx.x == 0) {
+		uint64_t a0 = 0, a1 = 0; int mx = -1, mn = INT_MAX;
+		for (int i = 0; i < SCHUNK / 64; ++i) { a0 += s_sum[i][0]; a1 += s_sum[i][1]; mx = max(mx, s_mx[i]); mn = min(mn, s_mn[i]); }
+		constexpr uint64_t F = (1ull << 21) - 1ull;
+		ChunkPart p;
+		p.sum[0] = (uint32_t)(a0 & F); p.sum[1] = (uint32_t)(a0 >> 21 & F); p.sum[2] = (uint32_t)(a0 >> 42);
+		p.sum[3] = (uint32_t)(a1 & F); p.sum[4] = (uint32_t)(a1 >> 21 & F); p.sum[5] = (uint32_t)(a1 >> 42);
+		p.mx = mx; p.mn = mn;
+		part[blockIdx.x] = p;
+	}
+}
+
+// RB2_LEAN_VERIFY (tests): the records and chunk totals of k_count_lean against those of k_sym<.., LEAN> + k_tscan1 of the same round, word by word
+__global__ __launch_bounds__(256) void k_lean_compare(Ctl *ctl, int side, const TileRecs a, const TileRecs b, const ChunkPart *pa, const ChunkPart *pb)
+{
+	const uint32_t nt = ctl->seg[side].tile0[NR], t = blockIdx.x * 256 + threadIdx.x;
+	uint32_t bad = 0;
+	if (t < nt) for (int col = 0; col < 20; ++col) bad += a.p[(uint64_t)col * a.cap + t] != b.p[(uint64_t)col * b.cap + t];
+	if (t < (nt + SCHUNK - 1) / SCHUNK) for (int w = 0; w < 8; ++w) bad += ((const uint32_t*)&pa[t])[w] != ((const uint32_t*)&pb[t])[w];
+	if (bad) atomicAdd(&ctl->lean_mismatch, bad);
 }
 
 __device__ __forceinline__ int block_all_max(int v, int *s_w)      // maximum over the block, returned to every thread
@@ -902,7 +1036,9 @@ __device__ __forceinline__ void group_setup(GroupLds &G, const TileCtx &t, const
 		uint32_t all = G.fix.nexthead & 1u;
 #pragma unroll
 		for (int c = 0; c < 8; ++c) all &= G.okc[c];
-		G.allsingle = all;
+		// ... or the tile's record says so (TILE_SINGLE -> nexthead bit 2).  k_sym wrote the head flags into A then and this changes nothing; k_count_lean
+		// ("the lean count") wrote the record from the symbols alone and nobody wrote the flags: group_member takes the short way and never looks at G.head
+		G.allsingle = all | (G.fix.nexthead >> 2 & 1u);
 	}
 	__syncthreads();
 }

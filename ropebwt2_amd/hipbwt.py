@@ -98,6 +98,7 @@ def load_hip_lib():
         "rb2_hip_rewind_stats": (None, [vp, vp]),
         "rb2_hip_steady_stats": (None, [vp, vp]),
         "rb2_hip_lean_stats": (None, [vp, vp]),
+        "rb2_hip_lean_count_stats": (None, [vp, vp]),
         "rb2_hip_window_stats": (None, [vp, vp]),
         "rb2_hip_host_register": (C.c_int, [vp, C.c_int64]),
         "rb2_hip_host_unregister": (C.c_int, [vp]),
@@ -158,7 +159,7 @@ ABI_SYMBOLS = [
     "rb2_hip_unpack", "rb2_hip_unpack_dev", "rb2_hip_merge",
     "rb2_hip_string_graph", "rb2_hip_string_graph_dev",
     "rb2_hip_num_subropes", "rb2_hip_memcpy", "rb2_hip_use_stream",
-    "rb2_hip_dev_free", "rb2_hip_synth_reads", "rb2_hip_synth_reads_cov", "rb2_hip_synth_reads_skew", "rb2_hip_sync", "rb2_hip_sparse_stats", "rb2_hip_layout_stats", "rb2_hip_rewind_stats", "rb2_hip_steady_stats", "rb2_hip_lean_stats", "rb2_hip_window_stats", "rb2_hip_host_register", "rb2_hip_host_unregister", "rb2_hip_profile",
+    "rb2_hip_dev_free", "rb2_hip_synth_reads", "rb2_hip_synth_reads_cov", "rb2_hip_synth_reads_skew", "rb2_hip_sync", "rb2_hip_sparse_stats", "rb2_hip_layout_stats", "rb2_hip_rewind_stats", "rb2_hip_steady_stats", "rb2_hip_lean_stats", "rb2_hip_lean_count_stats", "rb2_hip_window_stats", "rb2_hip_host_register", "rb2_hip_host_unregister", "rb2_hip_profile",
     "rb2_hip_profile_get", "rb2_hip_kernel_name", "rb2_hip_layout",
     "rb2_hip_multi_create", "rb2_hip_multi_unique_id", "rb2_hip_multi_create_rank", "rb2_hip_multi_destroy", "rb2_hip_default_owners",
     "rb2_hip_multi_nranks", "rb2_hip_multi_transport", "rb2_hip_multi_nlocal", "rb2_hip_multi_engine", "rb2_hip_multi_insert_multi", "rb2_hip_multi_insert_multi_dev",
@@ -952,10 +953,18 @@ class HipBwt:
         return {"advance_single": int(a[0]), "prep_skipped": int(a[1]), "reported_at": int(a[2]), "used_from": int(a[3])}
 
     def lean_stats(self):
-        """lean rounds (rb2_hip_lean_stats): dense rounds run without an insert list since create / the stage in force (0: off; RB2_STEADY_LEAN)"""
+        """lean rounds (rb2_hip_lean_stats): dense rounds run without an insert list since create / the stage in force (0: off; 2 once a lean round
+        with the three-launch counting tail has been queued, 1 until then; RB2_STEADY_LEAN)"""
         a = np.zeros(2, np.int64)
         self.L.rb2_hip_lean_stats(self.h, a.ctypes.data)
         return {"rounds": int(a[0]), "stage": int(a[1])}
+
+    def lean_count_stats(self):
+        """stage 2 of the lean round (rb2_hip_lean_count_stats): rounds counted by k_count_lean since create / audit rounds (counted by k_sym as in
+        stage 1; RB2_LEAN_AUDIT) / rounds in which both ways ran and were compared (RB2_LEAN_VERIFY=1) / words in which they differed"""
+        a = np.zeros(4, np.int64)
+        self.L.rb2_hip_lean_count_stats(self.h, a.ctypes.data)
+        return {"counted": int(a[0]), "audit": int(a[1]), "verified": int(a[2]), "mismatches": int(a[3])}
 
     def window_stats(self):
         a = np.zeros(6, np.int64)

@@ -1,0 +1,23 @@
+#!/bin/bash
+# A/B of the lean count ("the lean count") on the GPU box: the driver's bench job (no extras), the sides alternating --
+#   parent   ropebwt2_amd/lib/librb2hip_<tag>.so (the parent commit's library: tools/build_variant.sh in a checkout of it)
+#   lean1    the working tree's library with RB2_STEADY_LEAN=1 (k_sym<.., LEAN> + k_tscan1 count every lean round: the launches are the parent's)
+#   lean2    the working tree's library with RB2_STEADY_LEAN=2 (k_count_lean counts the lean rounds but the audit rounds)
+#   tree     the working tree's library as it comes (whichever stage is the default)
+# value + per-kernel-group milliseconds per step (hipEvent scopes); one run of the tree in front of the repeats is printed and discarded.
+#   usage: ab_lean_count.sh <tag> [steps] [repeats]
+set -o pipefail
+TAG=$1; STEPS=${2:-20}; REP=${3:-3}
+cd $(dirname $0)/..
+one() { timeout -k 10 300 python bench.py --steps $STEPS --warmup 2 --full --no-extras --no-cpu-baseline 2>/dev/null | tail -1 | python -c "
+import json,sys
+d=json.loads(sys.stdin.readline()); n=d.get('kernels_ms_steps', d['steps'])
+print('$1', round(d['value'],3), 'counts_ok', d['config'].get('counts_ok'), {k: round(v/n,2) for k,v in d['kernels_ms'].items() if v})" || exit 1; }
+one warmup-discarded   # (the first bench run on a box that sat idle runs at other clocks than the ones behind it: not a side)
+for i in $(seq $REP); do
+  RB2_HIP_LIB=$PWD/ropebwt2_amd/lib/librb2hip_$TAG.so one parent
+  RB2_STEADY_LEAN=1 one lean1
+  RB2_STEADY_LEAN=2 one lean2
+  one tree
+done
+exit 0
