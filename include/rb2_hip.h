@@ -696,6 +696,11 @@ void rb2_hip_lean_stats(rb2_hip_t *h, int64_t out[2]);
  * and keeps the guard of the steady round alive), out[2] = rounds in which both ways ran and were compared (RB2_LEAN_VERIFY=1 at create; tests),
  * out[3] = words in which they differed (a difference is fatal at the end of its batch). */
 void rb2_hip_lean_count_stats(rb2_hip_t *h, int64_t out[4]);
+/* the forked round ("the forked round"): the counting tail of a round counted by k_count_lean runs on a side stream of the handle's
+ * own, beside the window search, the merge and the directory of the same round, which need the bucket sizes only; k_advance waits for both.
+ * out[0] = rounds forked since create, out[1] = 1 when such rounds are forked (RB2_LEAN_FORK, default 1; 0 at create: one stream, the launches as
+ * before), 0 when not -- the switch is off, the handle runs on a caller's stream (rb2_hip_use_stream), or RB2_LEAN_VERIFY / RB2_HIP_DEBUG is set. */
+void rb2_hip_lean_fork_stats(rb2_hip_t *h, int64_t out[2]);
 /* window formats of the dense layout (a window = 4 leaves = 4096 symbols; csrc/rb2_merge.h): out[0..3] = windows the dense merge wrote
  * plain (three bit planes) / compact with no, one, two lines of exception positions -- counted on the device only when the handle was
  * created with RB2_COMPACT_STATS=1 in the environment (zeros otherwise) --, out[4] = dense rounds that were allowed to write compact

@@ -239,6 +239,13 @@ struct rb2_hip_s {
 	int lean_verify = 0;                // RB2_LEAN_VERIFY=1 (tests): k_sym + k_tscan1 of the round run as well, into buffers of their own; k_lean_compare counts the words that differ (batch_end: fatal)
 	int64_t n_lean_counted = 0, n_lean_audit = 0, n_lean_verified = 0, n_lean_mismatch = 0;   // rb2_hip_lean_count_stats
 	DevBuf<TileRec> trec_v; DevBuf<ChunkPart> cpart_v;   // (RB2_LEAN_VERIFY)
+	// the forked round: the counting tail of a round counted by k_count_lean -- k_count_lean, the tile scans, k_tfix with setup_body -- runs on a side stream
+	// beside k_part / k_merge / the directory of the same round; k_part<.., FORK> lays out the new side itself, k_advance waits for both
+	int lean_fork = 1;                  // RB2_LEAN_FORK=0: one stream, the launches as they were
+	hipStream_t st_count = nullptr;     // the side stream (created with the handle, never a caller's: rb2_hip_use_stream leaves it alone)
+	hipEvent_t ev_fork = nullptr, ev_join = nullptr;   // st_count waits for ev_fork (recorded on st), st waits for ev_join (recorded on st_count)
+	bool fork_open = false;             // ev_join is recorded and st has not been made to wait for it yet: the side stream may hold work that a drain of st does not cover (fork_join)
+	int64_t n_lean_forked = 0;          // rounds forked (rb2_hip_lean_fork_stats)
 	int64_t n_rewind = 0, n_rewound = 0, rewind_max = 0, n_rewind_even = 0;   // void rounds taken back from behind queued rounds: how many, rounds taken back, deepest, of even depth (rb2_hip_rewind_stats)
 	unsigned long long *pair_d = nullptr, *pair_h = nullptr;   // k_pair_hist: what the batch just uploaded adds to the count matrix (device, pinned host)
 	bool pair_valid = false;
@@ -318,19 +325,29 @@ hipEvent_t get_event(rb2_hip_t *h)
 
 struct Scope {          // times everything enqueued between construction and destruction
 	rb2_hip_t *h; int k; ProfRec r; bool on;
-	Scope(rb2_hip_t *h_, int k_, int64_t units) : h(h_), k(k_) {
+	hipStream_t s;   // the stream the group runs on (the side stream for the counting tail of a forked round)
+	Scope(rb2_hip_t *h_, int k_, int64_t units, hipStream_t s_ = nullptr) : h(h_), k(k_), s(s_ ? s_ : h_->st) {
 		on = h->prof == 1 || (h->prof == 2 && k == RB2_K_MERGE);   // (2: the merge launches only -- two events per round instead of sixteen; rb2_hip_profile)
 		if (!on) return;
 		r.k = k; r.units = units; r.round = h->cur_round; r.a = get_event(h); r.b = get_event(h);
-		HIPCHK(hipEventRecord(r.a, h->st));
+		HIPCHK(hipEventRecord(r.a, s));
 	}
 	~Scope() {
-		if (h->debug) { hipError_t e = hipStreamSynchronize(h->st); if (e != hipSuccess) { rb2_fatal("[rb2_hip] kernel group %s failed: %s\n", rb2_hip_kernel_name(k), hipGetErrorString(e)); } }
+		if (h->debug) { hipError_t e = hipStreamSynchronize(s); if (e != hipSuccess) { rb2_fatal("[rb2_hip] kernel group %s failed: %s\n", rb2_hip_kernel_name(k), hipGetErrorString(e)); } }
 		if (!on) return;
-		HIPCHK(hipEventRecord(r.b, h->st));
+		HIPCHK(hipEventRecord(r.b, s));
 		h->recs.push_back(r);
 	}
 };
+
+// The side stream of a forked round never holds unjoined work where the host drains h->st, reads device memory or takes rounds back: whoever is about to do that
+// (and round_merge, in front of k_advance) comes here first.  Behind it a drain of h->st covers everything queued on either stream.
+inline void fork_join(rb2_hip_t *h)
+{
+	if (!h->fork_open) return;
+	HIPCHK(hipStreamWaitEvent(h->st, h->ev_join, 0));
+	h->fork_open = false;
+}
 
 void drain_profile(rb2_hip_t *h)
 {
@@ -398,10 +415,12 @@ struct BatchState {
 	                                        // a round counted before the host heard the report holds INS_E / INS_A and is merged from them)
 	                                        // 2: counted by k_count_lean -- no head flags in A, k_advance takes every string for a head
 	bool lean_audit = false;                // ... lean == 1 because the round is an audit round of stage 2
+	bool forked = false;                    // ... lean == 2 and its counting tail was queued on the side stream (round_counts); cleared wherever lean is (drop_lean)
 	uint64_t n_lean2 = 0;                   // counting phases of this batch that stage 2 could take, audit rounds included (every lean_audit-th is one)
 	uint64_t setup_round = (uint64_t)-1;    // round whose k_setup ran inside its counting phase (k_tscan_setup) ...
 	bool setup_sparse = false; uint64_t setup_epoch = 0;   // ... for this layout, at this layout epoch (a re-layout in between: k_setup runs again)
 };
+inline void drop_lean(rb2_hip_t *h, BatchState &B) { B.lean = 0; B.forked = false; fork_join(h); }   // forget how the last counting phase was queued (it is counted again, or merged)
 inline void mark_setup(const rb2_hip_t *h, BatchState &B, uint64_t r) { B.setup_round = r; B.setup_sparse = h->sparse; B.setup_epoch = h->layout_epoch; }   // k_setup of round r is queued
 inline bool setup_done(const rb2_hip_t *h, const BatchState &B, uint64_t r, bool sparse) { return B.setup_round == r && B.setup_sparse == sparse && B.setup_epoch == h->layout_epoch; }   // ... and still stands (no re-layout since)
 
@@ -552,6 +571,7 @@ uint32_t maybe_widen(rb2_hip_t *h, BatchState &B, uint64_t r)
 	if (v != 0) { known = v & ((1ull << 40) - 1); const uint64_t q = v >> 40; since = r >= q ? r - q : r + 1; }   // (the report of round q is the size AFTER round q)
 	const char *e = getenv("RB2_POS_WIDEN_AT");
 	if (known + (since + 1) * B.m < POS32_LIMIT && !(e && (uint64_t)atoll(e) == r)) return 0;
+	fork_join(h);
 	if (const uint32_t v = verdict_check(h, true)) return v;   // (an in-place round queued behind is void)
 	// widen L and U of the current side (what the next kernels read); scratch arrays are per round
 	hipStream_t st = h->st;
@@ -561,7 +581,7 @@ uint32_t maybe_widen(rb2_hip_t *h, BatchState &B, uint64_t r)
 		hipLaunchKernelGGL(k_widen, dim3(cdiv(B.m, 256)), dim3(256), 0, st, (const uint32_t*)h->INS_E.p, a->p, B.m);
 	}
 	h->pos32 = false;
-	B.counted = (uint64_t)-1; B.lean = 0;                      // a counting phase queued ahead wrote INS_E in the narrow form (k_sym's fused k_prep): count again (INS_E above is scratch, never data)
+	B.counted = (uint64_t)-1; drop_lean(h, B);                 // a counting phase queued ahead wrote INS_E in the narrow form (k_sym's fused k_prep): count again (INS_E above is scratch, never data)
 	if (h->trace) fprintf(stderr, "[rb2_hip] round %llu: positions widened to 64 bits (largest piece known: %llu symbols, %llu rounds ago)\n", (unsigned long long)r, (unsigned long long)known, (unsigned long long)since);
 	return 0;
 }
@@ -585,6 +605,7 @@ void require_verdicts_seen(const rb2_hip_t *h, uint64_t r, const char *what)
 // allow_lean = false: a round counted lean that cannot be merged densely after all is counted again with INS_E / INS_A (round_merge_any)
 void round_counts(rb2_hip_t *h, BatchState &B, uint64_t r, bool spec = false, bool allow_lean = true)
 {
+	fork_join(h); B.forked = false;                             // (a counting phase that is queued again: behind whatever the one before left on the side stream)
 	hipStream_t st = h->st;
 	const int sd = h->side;
 	const int64_t units = (int64_t)B.m;
@@ -600,6 +621,15 @@ void round_counts(rb2_hip_t *h, BatchState &B, uint64_t r, bool spec = false, bo
 	if (B.lean == 2) h->lean2_met = true;
 	if (B.lean == 2 && h->lean_audit > 0 && ++B.n_lean2 % (uint64_t)h->lean_audit == 0) { B.lean = 1; B.lean_audit = true; }
 	if (!spec) require_verdicts_seen(h, r, "counting phase without spec of round");   // (its k_setup runs whatever ctl->overflow says)
+	// the forked round: the whole counting tail goes to the side stream, behind everything queued on h->st so far (the k_advance of the round in front wrote A and
+	// read the tile records); round_merge queues k_part<.., FORK>, k_merge and the directory on h->st beside it and joins in front of k_advance.  Never from a
+	// caller's stream; not with RB2_LEAN_VERIFY (k_sym<LEAN> writes head flags into A, which k_merge reads) and not with RB2_HIP_DEBUG (a drain per group)
+	B.forked = B.lean == 2 && h->lean_fork && h->own_stream && !h->lean_verify && !h->debug;
+	if (B.forked) {
+	  HIPCHK(hipEventRecord(h->ev_fork, h->st));
+	  HIPCHK(hipStreamWaitEvent(h->st_count, h->ev_fork, 0));
+	  st = h->st_count;
+	}
 	SplitArgs sp; memset(&sp, 0, sizeof(sp));
 	if (spec) {
 	  sp.ctl = h->ctl; sp.pool = h->pool[h->pside].view(); sp.SPL = h->SPL.p; sp.spl_cap = split_cap(h); sp.epoch = h->split_epoch;
@@ -609,7 +639,7 @@ void round_counts(rb2_hip_t *h, BatchState &B, uint64_t r, bool spec = false, bo
 	                                                             // (in a block of this launch -- or, when the counting tail is one launch, of that one: see below)
 	}
 	SbBase *scan2_tail = (spec && h->dir_ride && one_launch_tail) ? h->pool[h->pside].view().sbbase : (SbBase*)nullptr;
-	{ Scope sc(h, RB2_K_SYM, units);
+	{ Scope sc(h, RB2_K_SYM, units, st);
 	  with_pos(h, B, [&](const auto &S) { using P = std::remove_pointer_t<decltype(S.L)>;
 	    if (spec) {
 	      hipLaunchKernelGGL((k_sym<false, P, true>), dim3((unsigned)rank_share(h, B.nst_ub) + sp.nsplitb + (sp.scan2 ? 1u : 0u)), dim3(256), 0, st, h->ctl, sd, (int)(r & 1), S, trs, sp);
@@ -636,7 +666,7 @@ void round_counts(rb2_hip_t *h, BatchState &B, uint64_t r, bool spec = false, bo
 	  hipLaunchKernelGGL((h->sparse ? k_tscan_setup<true> : k_tscan_setup<false>), dim3(grid), dim3(SCHUNK), 0, st, h->ctl, sd, (int)(r & 1), trs, h->tfix.p, h->gcnt, do_setup, (int)spec, (uint32_t)r, hmax_report(h), scan2_tail, steady_report(h));
 	  if (do_setup) mark_setup(h, B, r);
 	} else
-	{ Scope sc(h, RB2_K_TSCAN, units);
+	{ Scope sc(h, RB2_K_TSCAN, units, st);
 	  if (B.lean != 2) hipLaunchKernelGGL(k_tscan1, dim3(B.nsc), dim3(SCHUNK), 0, st, h->ctl, sd, trs, h->cpart.p);   // (k_count_lean wrote the chunks' totals itself)
 	  if (B.nsc <= (unsigned)h->ts_fold) hipLaunchKernelGGL(k_tscan3<true>, dim3(B.nsc), dim3(SCHUNK), 0, st, h->ctl, sd, trs, h->cpart.p, h->tsc.p);   // (the scan over the chunks folded in)
 	  else {
@@ -644,8 +674,9 @@ void round_counts(rb2_hip_t *h, BatchState &B, uint64_t r, bool spec = false, bo
 	    hipLaunchKernelGGL(k_tscan3<false>, dim3(B.nsc), dim3(SCHUNK), 0, st, h->ctl, sd, trs, h->cpart.p, h->tsc.p);
 	  }
 	  const int do_setup = h->nranks == 1;                     // one GPU: k_setup of the round rides on block 0 of k_tfix (the local count matrix is the global one)
-	  hipLaunchKernelGGL(k_tfix, dim3(std::max<unsigned>(1u, cdiv(B.nst_ub, 256))), dim3(256), 0, st, h->ctl, sd, (int)(r & 1), trs, h->tsc.p, h->tfix.p, h->gcnt, do_setup, (int)h->sparse, (uint32_t)r, hmax_report(h), (int)spec, steady_report(h));
+	  hipLaunchKernelGGL((B.forked ? k_tfix_fork : k_tfix), dim3(std::max<unsigned>(1u, cdiv(B.nst_ub, 256))), dim3(256), 0, st, h->ctl, sd, (int)(r & 1), trs, h->tsc.p, h->tfix.p, h->gcnt, do_setup, (int)h->sparse, (uint32_t)r, hmax_report(h), (int)spec, steady_report(h));
 	  if (do_setup) mark_setup(h, B, r); }
+	if (B.forked) { HIPCHK(hipEventRecord(h->ev_join, h->st_count)); h->fork_open = true; ++h->n_lean_forked; }
 	tl_slow(h, "tile scans");
 }
 
@@ -692,6 +723,8 @@ void round_merge(rb2_hip_t *h, BatchState &B, uint64_t r, ShardRec *send, bool c
 	  hipLaunchKernelGGL(k_setup<false>, dim3(1), dim3(64), 0, st, h->ctl, sd, h->gcnt, (int)(r & 1), (uint32_t)r, hmax_report(h), (int)(h->push[0] != nullptr), steady_report(h)); }
 	// the forms of k_part / k_merge follow how the round was COUNTED (B.lean, round_counts): a lean count left no INS_E / INS_A
 	const bool lean = B.lean != 0;
+	const bool forked = B.forked;
+	if (forked && (B.lean != 2 || !setup_done(h, B, r, false) || !h->fork_open)) { rb2_fatal("[rb2_hip] internal: round %llu was forked and is not merged as the lean dense round it was counted as\n", (unsigned long long)r); }
 	if (lean && (h->nranks != 1 || h->sparse || !B.known_steady)) { rb2_fatal("[rb2_hip] internal: round %llu was counted lean and is not merged as a steady dense round\n", (unsigned long long)r); }
 	if (lean) ++h->n_lean_rounds;
 	if (B.lean == 2) ++h->n_lean_counted; else if (lean && B.lean_audit) ++h->n_lean_audit;
@@ -700,7 +733,8 @@ void round_merge(rb2_hip_t *h, BatchState &B, uint64_t r, ShardRec *send, bool c
 	tl_slow(h, "k_prep");
 	{ Scope sc(h, RB2_K_PART, units);
 	  const uint8_t *old_xh = h->pool_compact ? (const uint8_t*)oldp.xh : (const uint8_t*)nullptr;
-	  if (lean) hipLaunchKernelGGL((k_part<false, P, true>), dim3(cdiv(wg + NR, 255)), dim3(256), 0, st, h->ctl, sd, (const P*)S.L, h->LD.p, old_xh);
+	  if (forked) hipLaunchKernelGGL((k_part<false, P, true, true>), dim3(cdiv(wg + NR, 255)), dim3(256), 0, st, h->ctl, sd, (const P*)S.L, h->LD.p, old_xh);   // (lays out the new side itself)
+	  else if (lean) hipLaunchKernelGGL((k_part<false, P, true>), dim3(cdiv(wg + NR, 255)), dim3(256), 0, st, h->ctl, sd, (const P*)S.L, h->LD.p, old_xh);
 	  else RB2_LAUNCH_STRIDE(h, (k_part<true, P>), (k_part<false, P>), dim3(cdiv(wg + NR, 255)), dim3(256), 0, st, h->ctl, sd, S.INS_E, h->LD.p, old_xh); }   // (the formats of the old windows: only a pool side the compact-capable merge wrote has any but plain)
 	tl_slow(h, "k_part");
 	{ Scope sc(h, RB2_K_MERGE, units);
@@ -710,6 +744,7 @@ void round_merge(rb2_hip_t *h, BatchState &B, uint64_t r, ShardRec *send, bool c
 	{ Scope sc(h, RB2_K_META, units);
 	  build_directory(h, sd ^ 1, h->pside ^ 1, std::min<uint64_t>(B.nsb_ub, n_new_ub / (LEAF * SB) + NR + 1), false, false, (uint64_t)wg * WPL / SB + NR + 1); }
 	tl_slow(h, "directory");
+	fork_join(h);                                               // (k_advance reads what the counting tail left: the tile records' folds, count, ac, dest, the next buckets)
 	launch_advance<false>(h, B, r, newp, S, send, ScanRide{ nullptr, 0u });
 	});
 	tl_slow(h, "k_advance");
@@ -717,7 +752,7 @@ void round_merge(rb2_hip_t *h, BatchState &B, uint64_t r, ShardRec *send, bool c
 	HIPCHK(hipGetLastError());                                  // a refused launch (grid limits) must not go unnoticed until the end of the batch
 	tl_slow(h, "ne snapshot");
 	h->side ^= 1; h->pside ^= 1; B.cur ^= 1;
-	B.lean = 0;                                                 // (the record belongs to the round just merged)
+	drop_lean(h, B);                                            // (the record belongs to the round just merged)
 	h->pool_compact = compact_out;
 	if (compact_out) ++h->n_compact_rounds;
 }
@@ -744,6 +779,7 @@ void require_plain(rb2_hip_t *h, const char *who)
 void relayout(rb2_hip_t *h, bool to_sparse, uint64_t n_ub, uint64_t n_grow)
 {
 	hipStream_t st = h->st;
+	fork_join(h);
 	require_plain(h, "a re-layout");
 	struct NoWatch { int64_t *keep = t_grow_in_rounds; NoWatch() { t_grow_in_rounds = nullptr; } ~NoWatch() { t_grow_in_rounds = keep; } } nw;   // (a re-layout sizes its target pool here and waits for the device anyway)
 	const auto t_host0 = std::chrono::steady_clock::now();
@@ -837,11 +873,12 @@ int64_t take_back(rb2_hip_t *h, BatchState &B, uint64_t r_void, uint64_t r)
 {
 	if (r_void >= r || r - r_void > std::max<uint64_t>(h->spec_rounds, 1)) { rb2_fatal("[rb2_hip] internal: void round %llu reported while queueing round %llu (%llu in flight)\n", (unsigned long long)r_void, (unsigned long long)r, (unsigned long long)h->spec_rounds); }
 	const int64_t depth = (int64_t)(r - r_void);
+	fork_join(h);
 	if (depth & 1) { h->side ^= 1; B.cur ^= 1; }                // every in-place round queued from r_void on flipped the descriptor and array sides once
 	HIPCHK(hipMemsetAsync(&h->ctl->overflow, 0, 4, h->st));
 	h->spec_rounds = 0; h->mb_h->void_round = 0;
 	h->mb_h->progress = (uint32_t)r_void;                      // (the rounds behind the void one reported themselves done; wait_progress reads it)
-	B.counted = (uint64_t)-1; B.setup_round = (uint64_t)-1; B.lean = 0;
+	B.counted = (uint64_t)-1; B.setup_round = (uint64_t)-1; drop_lean(h, B);
 	return depth;
 }
 
@@ -914,7 +951,7 @@ bool round_merge_sparse(rb2_hip_t *h, BatchState &B, uint64_t r, ShardRec *send 
 uint32_t verdict_check(rb2_hip_t *h, bool drain)
 {
 	if (!h->spec_rounds) return 0;
-	if (drain) HIPCHK(hipStreamSynchronize(h->st));
+	if (drain) { fork_join(h); HIPCHK(hipStreamSynchronize(h->st)); }
 	const uint32_t v = h->mb_h->void_round;
 	if (h->mb_h->respread) { h->want_respread = true; if (drain) h->mb_h->respread = 0; }
 	if (drain && !v) h->spec_rounds = 0;
@@ -926,6 +963,7 @@ void batch_end(rb2_hip_t *h)
 {
 	h->cur_round = -1;
 	HIPCHK(hipGetLastError());
+	fork_join(h);
 	fetch_ropes(h);
 	if (h->steady_launched) {                                   // the guard of setup_body: a round that was not what the host believed
 		uint32_t bad2[2] = {0, 0};                                 // steady_bad, lean_mismatch
@@ -1093,7 +1131,7 @@ void insert_dev(rb2_hip_t *h, int64_t len64, const uint8_t *s, bool lazy = false
 			memset((void*)h->mb_h->ne, 0xff, sizeof(h->mb_h->ne));
 			// the same for the report of fused rounds (the counting tails queued behind a void round return before they report, and the stream is drained:
 			// nothing is on its way): the rounds redone from here report again
-			B.known_steady = false; h->mb_h->steady = 0; B.lean = 0;   // (... and lean with it: the redone rounds write INS_E / INS_A until the device reports again)
+			B.known_steady = false; h->mb_h->steady = 0; drop_lean(h, B);   // (... and lean with it: the redone rounds write INS_E / INS_A until the device reports again)
 			r = r_void;
 			void_to_dense(h, B, r);
 			round_counts(h, B, r);
@@ -1167,6 +1205,8 @@ rb2_hip_t *rb2_hip_create(int device, int sorting_order)
 	memset(h->mb_h, 0, sizeof(Mailbox));
 	HIPCHK(hipHostGetDevicePointer((void**)&h->mb_d, h->mb_h, 0));
 	HIPCHK(hipEventCreateWithFlags(&h->ev_flag, hipEventDisableTiming));
+	HIPCHK(hipStreamCreateWithFlags(&h->st_count, hipStreamNonBlocking));
+	HIPCHK(hipEventCreateWithFlags(&h->ev_fork, hipEventDisableTiming)); HIPCHK(hipEventCreateWithFlags(&h->ev_join, hipEventDisableTiming));
 	if (getenv("RB2_DIR_RIDE")) h->dir_ride = atoi(getenv("RB2_DIR_RIDE"));
 	if (getenv("RB2_TS_BLOCKS")) h->ts_blocks = atoi(getenv("RB2_TS_BLOCKS"));
 	if (getenv("RB2_LAZY_VERDICT")) h->lazy_verdict = atoi(getenv("RB2_LAZY_VERDICT"));
@@ -1177,6 +1217,7 @@ rb2_hip_t *rb2_hip_create(int device, int sorting_order)
 	if (!h->steady_on) h->lean = 0;
 	if (getenv("RB2_LEAN_AUDIT")) h->lean_audit = std::max(0, atoi(getenv("RB2_LEAN_AUDIT")));
 	if (getenv("RB2_LEAN_VERIFY")) h->lean_verify = atoi(getenv("RB2_LEAN_VERIFY")) != 0;
+	if (getenv("RB2_LEAN_FORK")) h->lean_fork = atoi(getenv("RB2_LEAN_FORK")) != 0;
 	if (getenv("RB2_STEADY_AHEAD")) h->steady_ahead = std::max(0, atoi(getenv("RB2_STEADY_AHEAD")));
 	{ Ctl *hc = (Ctl*)calloc(1, sizeof(Ctl)); for (int b = 0; b < NR; ++b) hc->own[b] = 1; HIPCHK(hipMemcpy(h->ctl, hc, sizeof(Ctl), hipMemcpyHostToDevice)); free(hc); }
 	HIPCHK(hipMemsetAsync(h->d_tmp, 0, 256, h->st));
@@ -1191,6 +1232,8 @@ void rb2_hip_destroy(rb2_hip_t *h)
 { finish_pending(h);
 	if (!h) return;
 	HIPCHK(hipSetDevice(h->dev));
+	if (h->own_stream) fork_join(h);
+	HIPCHK(hipStreamSynchronize(h->st_count));                  /* (nothing is left on it: every forked round was joined) */
 	if (h->own_stream) HIPCHK(hipStreamSynchronize(h->st)); else HIPCHK(hipDeviceSynchronize());   /* a caller's stream (rb2_hip_use_stream) may be gone already */
 	index_rows_change(h, true);
 	for (int i = 0; i < 2; ++i) { h->pool[i].release(); h->L[i].release(); h->U[i].release(); h->W[i].release(); }
@@ -1200,6 +1243,7 @@ void rb2_hip_destroy(rb2_hip_t *h)
 	h->trec.release(); h->tsc.release(); h->tfix.release(); h->cpart.release(); h->sbtot.release(); h->trec_v.release(); h->cpart_v.release();
 	for (auto e : h->evpool) hipEventDestroy(e);
 	HIPCHK(hipHostFree(h->mb_h)); HIPCHK(hipEventDestroy(h->ev_flag));
+	HIPCHK(hipEventDestroy(h->ev_fork)); HIPCHK(hipEventDestroy(h->ev_join)); HIPCHK(hipStreamDestroy(h->st_count));
 
 	if (h->pair_d) { HIPCHK(hipFree(h->pair_d)); HIPCHK(hipHostFree(h->pair_h)); }
 	HIPCHK(hipFree(h->ctl)); HIPCHK(hipFree(h->d_tmp)); HIPCHK(hipFree(h->gcnt)); h->xstage.release(); h->xnb.release(); h->xpack.release(); h->xoff.release();
@@ -1214,6 +1258,7 @@ int rb2_hip_sorting_order(const rb2_hip_t *h) { return h->so; }
 void rb2_hip_reset(rb2_hip_t *h)
 { finish_pending(h);
 	HIPCHK(hipSetDevice(h->dev));
+	fork_join(h);
 	index_rows_change(h);
 	memset(h->h_rope, 0, sizeof(h->h_rope));
 	h->sparse = false; h->sp_backoff = h->sp_penalty = 0;
@@ -1762,6 +1807,7 @@ void rb2_hip_use_stream(rb2_hip_t *h, void *hip_stream)
 { finish_pending(h);
 	HIPCHK(hipSetDevice(h->dev));
 	if (!h->own_stream && h->st == (hipStream_t)hip_stream) return;            /* bound already */
+	fork_join(h);                                                              /* (the side stream stays the handle's own; rounds on a caller's stream are never forked) */
 	if (h->own_stream) { HIPCHK(hipStreamSynchronize(h->st)); HIPCHK(hipStreamDestroy(h->st)); h->own_stream = false; }
 	else HIPCHK(hipDeviceSynchronize());                                       /* the previous foreign stream may be gone */
 	h->st = (hipStream_t)hip_stream;
@@ -2165,6 +2211,13 @@ void rb2_hip_lean_count_stats(rb2_hip_t *h, int64_t out[4])
 	out[0] = h->n_lean_counted; out[1] = h->n_lean_audit; out[2] = h->n_lean_verified; out[3] = h->n_lean_mismatch;
 }
 
+/* out[0]: rounds whose counting tail ran on the side stream (forked rounds); out[1]: the switch in force (RB2_LEAN_FORK; 0 as well on a caller's stream) */
+void rb2_hip_lean_fork_stats(rb2_hip_t *h, int64_t out[2])
+{
+	finish_pending(h);
+	out[0] = h->n_lean_forked; out[1] = (h->lean_fork && h->own_stream && !h->lean_verify && !h->debug) ? 1 : 0;
+}
+
 void rb2_hip_window_stats(rb2_hip_t *h, int64_t out[6])
 { finish_pending(h);
 	unsigned long long w[4] = {0, 0, 0, 0};
@@ -2175,7 +2228,7 @@ void rb2_hip_window_stats(rb2_hip_t *h, int64_t out[6])
 	out[4] = h->n_compact_rounds; out[5] = h->compact_stats ? 1 : 0;
 }
 
-void rb2_hip_sync(rb2_hip_t *h) { finish_pending(h); HIPCHK(hipSetDevice(h->dev)); HIPCHK(hipStreamSynchronize(h->st)); }
+void rb2_hip_sync(rb2_hip_t *h) { finish_pending(h); HIPCHK(hipSetDevice(h->dev)); fork_join(h); HIPCHK(hipStreamSynchronize(h->st)); }
 
 void rb2_hip_profile(rb2_hip_t *h, int enable) { finish_pending(h); h->prof = enable; }
 

@@ -694,10 +694,12 @@ template <bool FOLD> __global__ __launch_bounds__(SCHUNK) void k_tscan3(const Ct
 // Block 0 also writes the rows of the count matrix this rank can see -- gcnt[r * 6 + a] = members of (local) bucket r inserting a --
 // and word NR * 6 of the buffer (GCN, rb2_device.h), and, on one GPU (do_setup), runs k_setup of the round on its first wave: the local
 // matrix IS the global one.  (Two launches of their own before; nothing k_setup writes is read by the other blocks of this kernel.)
-template <bool SPARSE> __device__ __forceinline__ void setup_body(Ctl *ctl, int side, const uint64_t *gcnt, int par, uint32_t round, volatile unsigned long long *hmax, volatile unsigned long long *steady, bool keep_ne = false);
+template <bool SPARSE, bool FORK = false> __device__ __forceinline__ void setup_body(Ctl *ctl, int side, const uint64_t *gcnt, int par, uint32_t round, volatile unsigned long long *hmax, volatile unsigned long long *steady, bool keep_ne = false);
 // spec: as in k_tscan_setup below -- queued before the host saw the verdict of the in-place round in front of it; a void round (ctl->overflow) is redone
 // from its own counting phase, and k_setup of the NEXT round must not have replaced the descriptors it starts from.
-__global__ __launch_bounds__(256) void k_tfix(Ctl *ctl, int side, int par, const TileRecs trec, const TileScan *tsc, TileFix *tf, uint64_t *gcnt, int do_setup, int sparse,
+// FORK (k_tfix_fork): the launch of a forked lean round ("the forked round") -- it runs on the side stream beside k_part / k_merge of the same round, and its
+// setup_body leaves the layout of the new side to k_part<.., FORK>
+template <bool FORK> __device__ __forceinline__ void tfix_body(Ctl *ctl, int side, int par, const TileRecs trec, const TileScan *tsc, TileFix *tf, uint64_t *gcnt, int do_setup, int sparse,
 		uint32_t round, volatile unsigned long long *hmax, int spec, volatile unsigned long long *steady)
 {
 	__shared__ uint32_t s_t0[NR + 1];
@@ -712,7 +714,10 @@ __global__ __launch_bounds__(256) void k_tfix(Ctl *ctl, int side, int par, const
 		if (i == NR * 6) gcnt[NR * 6] = ctl->ne[par];
 		if (do_setup) {                                          // (block-uniform)
 			__syncthreads();
-			if (i < 64) { if (sparse) setup_body<true>(ctl, side, s_g, par, round, hmax, steady); else setup_body<false>(ctl, side, s_g, par, round, hmax, steady); }
+			if (i < 64) {
+				if (FORK) setup_body<false, true>(ctl, side, s_g, par, round, hmax, steady);
+				else if (sparse) setup_body<true>(ctl, side, s_g, par, round, hmax, steady); else setup_body<false>(ctl, side, s_g, par, round, hmax, steady);
+			}
 		}
 	}
 	const uint32_t tile = blockIdx.x * 256 + threadIdx.x;
@@ -738,6 +743,12 @@ __global__ __launch_bounds__(256) void k_tfix(Ctl *ctl, int side, int par, const
 	f.segstart = sg.start[b]; f.segend = sg.start[b] + sg.cnt[b];
 	tf[tile] = f;
 }
+__global__ __launch_bounds__(256) void k_tfix(Ctl *ctl, int side, int par, const TileRecs trec, const TileScan *tsc, TileFix *tf, uint64_t *gcnt, int do_setup, int sparse,
+		uint32_t round, volatile unsigned long long *hmax, int spec, volatile unsigned long long *steady)
+{ tfix_body<false>(ctl, side, par, trec, tsc, tf, gcnt, do_setup, sparse, round, hmax, spec, steady); }
+__global__ __launch_bounds__(256) void k_tfix_fork(Ctl *ctl, int side, int par, const TileRecs trec, const TileScan *tsc, TileFix *tf, uint64_t *gcnt, int do_setup, int sparse,
+		uint32_t round, volatile unsigned long long *hmax, int spec, volatile unsigned long long *steady)
+{ tfix_body<true>(ctl, side, par, trec, tsc, tf, gcnt, do_setup, sparse, round, hmax, spec, steady); }
 
 // gcnt = the GLOBAL NR x 6 count matrix of the round (== the local one on a single GPU; the sum
 // over ranks when sub-ropes are sharded).  One wave, lane r = sub-rope r; the running sums of the
@@ -750,8 +761,12 @@ __global__ __launch_bounds__(256) void k_tfix(Ctl *ctl, int side, int par, const
 // the host knows every interval empty and launches no k_prep<AE> in dense rounds once it has read that.  Reported in every round, whatever the positions' width.
 // keep_ne: the next round's "some interval is non-empty" flag is not cleared here (PEER transport of a sharded index: the other ranks'
 // k_advance set it, and they may run ahead of this rank's k_mround; the host clears it before the round's counting phase instead)
-template <bool SPARSE> __device__ __forceinline__ void setup_body(Ctl *ctl, int side, const uint64_t *gcnt /* global or LDS */, int par, uint32_t round, volatile unsigned long long *hmax, volatile unsigned long long *steady, bool keep_ne)
+// FORK (dense only): the round is forked -- k_part<.., FORK> of the same round computes the layout of the new side (n, nleaves, leaf0, sb0, wf0, nsb_total) from the old
+// sizes and the bucket sizes and block 0 of it stores them, beside this launch.  What depends on the count matrix stays here: cnt[] (field by field, never the whole
+// descriptor), count, ac, seg[side ^ 1], dest, the clears and the reports.  Every word of Ctl has one writer in such a round.
+template <bool SPARSE, bool FORK> __device__ __forceinline__ void setup_body(Ctl *ctl, int side, const uint64_t *gcnt /* global or LDS */, int par, uint32_t round, volatile unsigned long long *hmax, volatile unsigned long long *steady, bool keep_ne)
 {
+	static_assert(!(SPARSE && FORK), "an in-place round is never forked");
 	const int r = lane_id();
 	if (r == 0) { if (!keep_ne) ctl->ne[par ^ 1] = 0; ctl->overflow = 0; ctl->sbfull = 0; ctl->nsplit2[round & 1u] = 0; }   // ne: k_advance / k_munpack of this round count into it
 	if (r == 0) {                                              // k_sym of this round has run, k_sym of the next has not: report its word, clear the next one's
@@ -789,8 +804,10 @@ template <bool SPARSE> __device__ __forceinline__ void setup_body(Ctl *ctl, int 
 		const uint64_t ex = inc - n.cnt[a];
 		const uint64_t exf = __shfl(ex, first);
 		if (ok) { ctl->count[r][a] = c; ctl->ac[r][a] = ex - exf; }   // #a in this rope in front of piece r, after the round (mrope.c:332-336)
+		if (FORK && ok) ctl->rope[side ^ 1][r].cnt[a] = n.cnt[a];
 	}
-	if (SPARSE) {
+	if (FORK) { /* the layout: k_part<.., FORK> */ }
+	else if (SPARSE) {
 		n.nleaves = o.nleaves; n.leaf0 = o.leaf0; n.sb0 = o.sb0;
 		if (ok) ctl->rope[side ^ 1][r] = n;
 	} else {
@@ -1243,10 +1260,35 @@ template <bool AE, bool SPARSE = false, bool STRIDE = false, typename P = uint64
 // ---------------------------------------------------------------------------------------------
 
 // LEAN: INS_E is the L array of a lean round: L[q] is the final position E[q] + q itself.
-template <bool STRIDE, typename P = uint64_t, bool LEAN = false> __global__ __launch_bounds__(256) void k_part(const Ctl *ctl, int side, const P *INS_E, LeafDesc *LD, const uint8_t *old_xh)
+// FORK: the launch of a forked lean round ("the forked round"): the counting tail of the round, setup_body included, runs beside this launch on another
+// stream, so nobody has laid out the new side yet.  The layout needs no counts: a string of bucket r inserts into piece r, so piece r grows by the size of bucket r.
+// The first wave of every block works it out (lane = piece, the arithmetic of setup_body's dense branch) and leaves what the block needs in LDS; block 0 also stores
+// it to Ctl, for k_merge, k_meta_sb, the scans and k_advance behind this launch.  setup_body<false, FORK> makes none of these stores.
+template <bool STRIDE, typename P = uint64_t, bool LEAN = false, bool FORK = false> __global__ __launch_bounds__(256) void k_part(const Ctl *ctl, int side, const P *INS_E, LeafDesc *LD, const uint8_t *old_xh)
 {
+	static_assert(!FORK || (LEAN && !STRIDE), "only a lean round of one engine is forked");
 	__shared__ uint64_t s_wf0[NR + 1];
 	__shared__ uint32_t s_q[256];
+	__shared__ uint64_t s_leaf0[FORK ? NR : 1], s_n[FORK ? NR : 1];
+	if (FORK) {
+		if (threadIdx.x < 64) {                                   // (one whole wave)
+			const int r = (int)threadIdx.x;
+			const bool ok = r < NR;
+			const int rr = ok ? r : 0;
+			const uint64_t n = ok ? ctl->rope[side][rr].n + ctl->seg[side].cnt[rr] : 0ull;
+			const uint64_t nleaves = (n + LEAF - 1) / LEAF;
+			const uint64_t padded = (nleaves + SB - 1) / SB * SB, nwin = (nleaves + WPL - 1) / WPL;
+			const uint64_t pinc = dpp_incl_add64(padded), winc = dpp_incl_add64(nwin);
+			const uint64_t leaf0 = pinc - padded;
+			if (ok) { s_wf0[r] = winc - nwin; s_leaf0[r] = leaf0; s_n[r] = n; }
+			if (r == 63) s_wf0[NR] = winc;
+			if (blockIdx.x == 0) {
+				Ctl *wc = const_cast<Ctl*>(ctl);
+				if (ok) { RopeDesc &d = wc->rope[side ^ 1][r]; d.n = n; d.nleaves = nleaves; d.leaf0 = leaf0; d.sb0 = leaf0 / SB; wc->wf0[r] = winc - nwin; }
+				if (r == 63) { wc->wf0[NR] = winc; wc->wf0[NR + 1] = winc; wc->nsb_total = pinc / SB; }
+			}
+		}
+	} else
 	if (threadIdx.x <= NR) s_wf0[threadIdx.x] = ctl->wf0[threadIdx.x];
 	__syncthreads();
 	for (uint64_t blk = blockIdx.x; blk * 255 < s_wf0[NR] + NR; blk += gridDim.x) {   // grid stride (a sharded rank launches fewer blocks than its upper bound)
@@ -1276,7 +1318,7 @@ template <bool STRIDE, typename P = uint64_t, bool LEAN = false> __global__ __la
 	LeafDesc d;
 	d.i0 = i0;
 	d.ins0 = ctl->seg[side].start[b] + q;
-	d.gl = nrp.leaf0 + j * WPL;
+	d.gl = (FORK ? s_leaf0[FORK ? b : 0] : nrp.leaf0) + j * WPL;
 	d.oleaf0 = (uint32_t)orp.leaf0;
 	// the formats of the (at most two) old windows the merge will draw from (rb2_merge.h "window formats"): one byte per window, written by the
 	// merge that wrote the old side (old_xh == null: that side holds plain windows only -- a re-layout, the loader, or a round that was
@@ -1287,7 +1329,7 @@ template <bool STRIDE, typename P = uint64_t, bool LEAN = false> __global__ __la
 	const uint32_t h0 = ow < onw ? (xw ? (uint32_t)xw[ow] & 3u : 0u) : 1u;
 	const uint32_t h1 = ow + 1 < onw ? (xw ? (uint32_t)xw[ow + 1] & 3u : 0u) : 1u;
 	d.ni = (uint16_t)((uint32_t)(q1 - q) | h0 << 14);
-	d.nvalid = (uint16_t)((uint32_t)min((uint64_t)WIN, nrp.n - o0) | h1 << 14);
+	d.nvalid = (uint16_t)((uint32_t)min((uint64_t)WIN, (FORK ? s_n[FORK ? b : 0] : nrp.n) - o0) | h1 << 14);
 	LD[s_wf0[b] + j] = d;
 	if (!STRIDE) return;
 	}

@@ -99,6 +99,7 @@ def load_hip_lib():
         "rb2_hip_steady_stats": (None, [vp, vp]),
         "rb2_hip_lean_stats": (None, [vp, vp]),
         "rb2_hip_lean_count_stats": (None, [vp, vp]),
+        "rb2_hip_lean_fork_stats": (None, [vp, vp]),
         "rb2_hip_window_stats": (None, [vp, vp]),
         "rb2_hip_host_register": (C.c_int, [vp, C.c_int64]),
         "rb2_hip_host_unregister": (C.c_int, [vp]),
@@ -159,7 +160,7 @@ ABI_SYMBOLS = [
     "rb2_hip_unpack", "rb2_hip_unpack_dev", "rb2_hip_merge",
     "rb2_hip_string_graph", "rb2_hip_string_graph_dev",
     "rb2_hip_num_subropes", "rb2_hip_memcpy", "rb2_hip_use_stream",
-    "rb2_hip_dev_free", "rb2_hip_synth_reads", "rb2_hip_synth_reads_cov", "rb2_hip_synth_reads_skew", "rb2_hip_sync", "rb2_hip_sparse_stats", "rb2_hip_layout_stats", "rb2_hip_rewind_stats", "rb2_hip_steady_stats", "rb2_hip_lean_stats", "rb2_hip_lean_count_stats", "rb2_hip_window_stats", "rb2_hip_host_register", "rb2_hip_host_unregister", "rb2_hip_profile",
+    "rb2_hip_dev_free", "rb2_hip_synth_reads", "rb2_hip_synth_reads_cov", "rb2_hip_synth_reads_skew", "rb2_hip_sync", "rb2_hip_sparse_stats", "rb2_hip_layout_stats", "rb2_hip_rewind_stats", "rb2_hip_steady_stats", "rb2_hip_lean_stats", "rb2_hip_lean_count_stats", "rb2_hip_lean_fork_stats", "rb2_hip_window_stats", "rb2_hip_host_register", "rb2_hip_host_unregister", "rb2_hip_profile",
     "rb2_hip_profile_get", "rb2_hip_kernel_name", "rb2_hip_layout",
     "rb2_hip_multi_create", "rb2_hip_multi_unique_id", "rb2_hip_multi_create_rank", "rb2_hip_multi_destroy", "rb2_hip_default_owners",
     "rb2_hip_multi_nranks", "rb2_hip_multi_transport", "rb2_hip_multi_nlocal", "rb2_hip_multi_engine", "rb2_hip_multi_insert_multi", "rb2_hip_multi_insert_multi_dev",
@@ -965,6 +966,13 @@ class HipBwt:
         a = np.zeros(4, np.int64)
         self.L.rb2_hip_lean_count_stats(self.h, a.ctypes.data)
         return {"counted": int(a[0]), "audit": int(a[1]), "verified": int(a[2]), "mismatches": int(a[3])}
+
+    def lean_fork_stats(self):
+        """the forked round (rb2_hip_lean_fork_stats): rounds whose counting tail ran on the side stream beside their merge since create / whether
+        such rounds are forked (RB2_LEAN_FORK, default 1; never on a caller's stream or with RB2_LEAN_VERIFY)"""
+        a = np.zeros(2, np.int64)
+        self.L.rb2_hip_lean_fork_stats(self.h, a.ctypes.data)
+        return {"forked": int(a[0]), "on": int(a[1])}
 
     def window_stats(self):
         a = np.zeros(6, np.int64)
