@@ -547,6 +547,51 @@ int64_t rb2_hip_string_graph(rb2_hip_t *h, int64_t first, int64_t n, int64_t min
 int64_t rb2_hip_string_graph_dev(rb2_hip_t *h, int64_t first, int64_t n, int64_t min_ovlp, int64_t max_ext, int64_t max_steps, int64_t max_recs, int64_t max_hits, int pairs,
                                  int64_t cap, int64_t *edges, int64_t info[8]);
 
+/* ---- tip and bubble removal on an edge list (csrc/rb2_clean.h) ----
+ * The step between rb2_hip_string_graph and rb2_hip_unitig_chains: the rows of an edge list that hang short dead ends (TIPS) onto a path
+ * or run a short path beside a better one (BUBBLES) are removed, in ROUNDS, and the rows left come back in input order, unchanged.
+ * n_str vertices, m rows src, dst, l, ext as rb2_hip_unitig_chains reads them (l is not read, only copied).  No index is read: the handle
+ * gives the device and the stream, and like rb2_hip_unitig_chains the call works on any handle, one rank of a sharded index included.
+ * VALID ROWS, DEGREES, CHAINS are those of rb2_hip_unitig_chains, exactly: a row with src or dst outside [0, n_str) or ext < 1 is IGNORED
+ * (counted, part of nothing, never returned); outdeg and indeg count the other rows still ALIVE, a duplicate twice, a self loop in both;
+ * the chains are that call's chains of the rows alive.  Of an open chain c: head(c); tail(c), its vertex of the greatest rank; reads(c),
+ * its vertices; minpid(c), the smallest v >> pairs over its vertices (pairs = 1: strings 2i and 2i + 1 are one read, and a chain and its
+ * mirror image under v <-> v ^ 1 have the same minpid).  Cycles take part in no rule.
+ * A round takes every decision from the rows alive at its start, so nothing depends on an order of evaluation:
+ *   OUT-TIP  an open chain with outdeg(tail) == 0, indeg(head) >= 1 and reads <= max_tip_reads.  A row p -> head of an out-tip is removed
+ *            iff p has at least one row alive whose dst is not the head of an out-tip (a fork of nothing but short dead ends keeps them all).
+ *   IN-TIP   the mirror image: indeg(head) == 0, outdeg(tail) >= 1, reads <= max_tip_reads.  A row tail -> w of an in-tip is removed iff w
+ *            has at least one row alive into it whose src is not the tail of an in-tip.
+ *   BUBBLE   an open chain is an ARM of (p, q) when indeg(head) == 1 with that row's src = p, outdeg(tail) == 1 with that row's dst = q,
+ *            outdeg(p) >= 2 and indeg(q) >= 2.  An arm c LOSES iff reads(c) <= max_bubble_reads and another arm c' of the same (p, q) has
+ *            (reads(c'), -minpid(c')) > (reads(c), -minpid(c)) in lexicographic order; the winner may be of any size, and two arms equal
+ *            in both keep both.  Both rows of a loser, p -> head and tail -> q, are removed.
+ * A row removed by a tip rule counts as a tip row, even when a bubble rule removes it too; any other removed row as a bubble row.  The
+ * rounds repeat until one removes nothing or max_rounds have run (a tip that hangs off a tip needs two).  max_tip_reads == 0 or
+ * max_bubble_reads == 0 switches that rule off; with both 0 the call is a filter of the ignored rows.
+ * Returns m', the rows kept, whatever cap is; row k of them is stored iff k < cap, and nothing is written from row cap on.  cap == 0 with
+ * out == NULL counts only.  out must not overlap edges; edges is not written.
+ * info = m', rows stored, rounds run (the last one, which found nothing, included), tip rows removed, bubble rows removed, rows ignored,
+ * chains of the list as returned (rb2_hip_unitig_chains' info[0] on it), 0.
+ * Method: per round k_clean_deg (degrees and the single row into and out of a vertex), the chain launcher of rb2_hip_unitig_chains
+ * unchanged, per-head sums (the lanes of a wave that name one head add once), class bits per head, a CSR of the out-rows (the scan of
+ * rb2_hip_unitig_text over the out-degrees and an atomic cursor; the order inside a vertex is arbitrary and the rules do not see it), one
+ * thread per arm that walks the out-rows of its p -- sum of outdeg(p) over the arms; on a list from rb2_hip_string_graph outdeg is at most
+ * max_recs * max_hits --, two anchor bytes per vertex set per row, and one pass that marks the rows removed.  The host synchronises once
+ * per round to read that round's counters, and once more for the chains of the result when max_rounds cut the loop; the compaction into
+ * out (a keep flag per row, the same scan) is queued behind that, so the _dev variant returns with it in flight on the handle's stream.
+ * Device memory beyond the output: 9 bytes per row (a byte that marks the removed rows; 8 for the CSR, then the compaction's scan) and
+ * 187 bytes per vertex (96 of the chain launcher, 32 of vtx, 56 per head and degree, 3 flag bytes), plus 8 bytes per 4096 of either.  The
+ * host variant also holds the list and min(cap, m) rows of output on the device for the time of the call.
+ * Fatal, each with a message of its own, at the top of the call and before any kernel: n_str, m or cap negative or above 2^36; a negative
+ * max_tip_reads or max_bubble_reads; max_rounds < 1; pairs outside {0, 1}; edges NULL with m > 0; out NULL with cap > 0; out overlapping
+ * edges. */
+int64_t rb2_hip_graph_clean(rb2_hip_t *h, int64_t n_str, int64_t m, const int64_t *edges, int64_t max_tip_reads, int64_t max_bubble_reads, int pairs, int64_t max_rounds,
+                            int64_t cap, int64_t *out, int64_t info[8]);
+/* the same with edges and out (4 cap int64) in this device's memory and info in host memory: what rb2_hip_unitig_chains_dev reads next */
+int64_t rb2_hip_graph_clean_dev(rb2_hip_t *h, int64_t n_str, int64_t m, const int64_t *edges, int64_t max_tip_reads, int64_t max_bubble_reads, int pairs, int64_t max_rounds,
+                                int64_t cap, int64_t *out, int64_t info[8]);
+
 /* ---- rope sharding across GPUs ---------------------------------------------------------------
  * The unit of ownership is a SUB-ROPE: rope b is kept as six independent pieces (b,x), x = the symbol that follows b in the
  * row's suffix (piece (b,x) holds exactly the b-symbols of rope x; rope $ is one piece; NR = 31 pieces, see rb2_device.h).

@@ -18,6 +18,7 @@
 #include "rb2_kernels.h"
 #include "rb2_query.h"
 #include "rb2_unitig.h"
+#include "rb2_clean.h"
 #include "rb2_unpack.h"
 #include "rb2_graph.h"
 #include "rb2_merge_plan.h"

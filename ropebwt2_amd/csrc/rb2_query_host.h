@@ -765,6 +765,129 @@ int64_t rb2_hip_unitig_text(rb2_hip_t *h, int64_t n_str, const int64_t *vtx, int
 	return stored;
 }
 
+/* ---- tip and bubble removal on an edge list (rb2_clean.h) ---- */
+
+static void graph_clean_check(rb2_hip_t *h, const char *who, int64_t n, int64_t m, const int64_t *edges, int64_t max_tip, int64_t max_bubble, int pairs, int64_t max_rounds,
+                              int64_t cap, const int64_t *out)
+{
+	finish_pending(h);
+	HIPCHK(hipSetDevice(h->dev));
+	if (n < 0 || n > UT_MAX_N || m < 0 || m > UT_MAX_N) { rb2_fatal("[rb2_hip] %s: n_str and m must be 0 .. 2^36 (got %lld, %lld)\n", who, (long long)n, (long long)m); }
+	if (max_tip < 0 || max_bubble < 0) { rb2_fatal("[rb2_hip] %s: max_tip_reads and max_bubble_reads must not be negative (got %lld, %lld)\n", who, (long long)max_tip, (long long)max_bubble); }
+	if (pairs != 0 && pairs != 1) { rb2_fatal("[rb2_hip] %s: pairs must be 0 or 1 (got %d)\n", who, pairs); }
+	if (max_rounds < 1) { rb2_fatal("[rb2_hip] %s: max_rounds must be at least 1 (got %lld)\n", who, (long long)max_rounds); }
+	if (cap < 0 || cap > UT_MAX_N) { rb2_fatal("[rb2_hip] %s: cap must be 0 .. 2^36 (got %lld)\n", who, (long long)cap); }
+	if (m > 0 && !edges) { rb2_fatal("[rb2_hip] %s: edges is NULL but m is not 0\n", who); }
+	if (cap > 0 && !out) { rb2_fatal("[rb2_hip] %s: out is NULL but cap is not 0\n", who); }
+	if (m > 0 && cap > 0) {
+		const uintptr_t a = (uintptr_t)edges, b = (uintptr_t)out;
+		if (a < b + (uintptr_t)cap * 32 && b < a + (uintptr_t)m * 32) { rb2_fatal("[rb2_hip] %s: out overlaps edges\n", who); }
+	}
+}
+
+/* ed (m rows) and out (cap rows) in device memory, behind graph_clean_check; info = the eight counts.  One synchronise per round (and one
+ * more for the chains of the result when the last round allowed still removed rows); the compaction is queued behind the last of them */
+static int64_t graph_clean_run(rb2_hip_t *h, int64_t n, int64_t m, const int64_t *ed, int64_t max_tip, int64_t max_bubble, int pairs, int64_t max_rounds, int64_t cap, int64_t *out,
+                               int64_t info[8])
+{
+	const int64_t nb = (int64_t)cdiv((uint64_t)std::max(m, n + 1), UT_SCAN) + 1;
+	const size_t chain_words = (size_t)(UT_CTRS + 12 * n), words = (size_t)(CL_CTRS + 11 * n + 1 + m + nb);
+	h->qscr.ensure((chain_words + words) * 8 + (size_t)(m + 3 * n));   // (first, for the whole call: unitig_chain_bufs then finds its room in front and moves nothing)
+	int64_t *w = (int64_t*)h->qscr.p + chain_words;
+	unsigned long long *cctr = (unsigned long long*)w; w += CL_CTRS;
+	int64_t *vtx = w; w += 4 * n;
+	ClV V;
+	V.vtx = vtx;
+	V.cnt = (unsigned long long*)w; w += n;
+	V.mn = (unsigned long long*)w; w += n;                         // (mn and tail lie together: one memset of 0xff)
+	V.tail = w; w += n;
+	V.q = w; w += n;
+	V.outedge = w; w += n;
+	uint64_t *start = (uint64_t*)w; w += n + 1;
+	int64_t *csr = w; w += m;                                      // (and, behind the last round, the keep flags and their scan)
+	uint64_t *bsum = (uint64_t*)w; w += nb;
+	V.cls = (uint32_t*)w;
+	uint32_t *cur = V.cls + n; w += n;
+	uint8_t *dead = (uint8_t*)w, *lose = dead + m, *a_out = lose + n, *a_in = a_out + n;
+	if (m) HIPCHK(hipMemsetAsync(dead, 0, (size_t)m, h->st));
+	unsigned long long c[CL_CTRS] = {0, 0, 0, 0}, uc[UT_CTRS];
+	int64_t rounds = 0, tips = 0, bubbles = 0;
+	auto degrees = [&]() -> UtChainBufs {                          // the degrees and the chains of the rows alive
+		const UtChainBufs b = unitig_chain_bufs(h, n);
+		V.outdeg = b.outdeg; V.indeg = b.indeg; V.inedge = b.inedge;
+		HIPCHK(hipMemsetAsync(cctr, 0, CL_CTRS * 8, h->st));
+		ulaunch(h, k_clean_deg, m, ed, (const uint8_t*)dead, m, n, b.outdeg, b.indeg, b.inedge, V.outedge, cctr);
+		unitig_rank(h, b, n, vtx);
+		return b;
+	};
+	auto counters = [&](const UtChainBufs &b) {
+		HIPCHK(hipMemcpyAsync(c, cctr, sizeof(c), hipMemcpyDeviceToHost, h->st));
+		HIPCHK(hipMemcpyAsync(uc, b.ctr, sizeof(uc), hipMemcpyDeviceToHost, h->st));
+		HIPCHK(hipStreamSynchronize(h->st));
+	};
+	bool removed = true;
+	while (rounds < max_rounds && removed) {
+		const UtChainBufs b = degrees();
+		if (n) {
+			HIPCHK(hipMemsetAsync(V.cnt, 0, (size_t)n * 8, h->st));
+			HIPCHK(hipMemsetAsync(V.mn, 0xff, (size_t)n * 16, h->st));
+			HIPCHK(hipMemsetAsync(lose, 0, (size_t)n * 3, h->st));
+		}
+		ulaunch(h, k_clean_sum, n, n, pairs, V);
+		ulaunch(h, k_clean_class, n, n, max_tip, V);
+		if (max_bubble > 0 && m > 0 && n > 0) {
+			ulaunch(h, k_clean_widen, n + 1, n, (const uint32_t*)b.outdeg, start);
+			unitig_scan(h, start, n + 1, bsum, cctr + CL_TOTAL);
+			HIPCHK(hipMemsetAsync(cur, 0, (size_t)n * 4, h->st));
+			ulaunch(h, k_clean_fill, m, ed, (const uint8_t*)dead, m, n, (const uint64_t*)start, cur, csr);
+			ulaunch(h, k_clean_rival, n, n, m, max_bubble, V, (const uint64_t*)start, (const int64_t*)csr, lose);
+		}
+		if (max_tip > 0) ulaunch(h, k_clean_anchor, m, ed, (const uint8_t*)dead, m, n, V, a_out, a_in);
+		ulaunch(h, k_clean_mark, m, ed, dead, m, n, V, (const uint8_t*)a_out, (const uint8_t*)a_in, (const uint8_t*)lose, max_tip > 0 ? 1 : 0, max_bubble > 0 ? 1 : 0, cctr);
+		counters(b);
+		++rounds;
+		tips += (int64_t)c[CL_TIPS]; bubbles += (int64_t)c[CL_BUBBLES];
+		removed = c[CL_TIPS] + c[CL_BUBBLES] > 0;
+	}
+	if (removed) counters(degrees());                              // max_rounds cut the loop: the chains of what is left
+	const int64_t ignored = (int64_t)c[CL_IGNORED], kept = m - ignored - tips - bubbles, stored = std::min(kept, cap);
+	if (kept < 0) { rb2_fatal("[rb2_hip] graph_clean: %lld rows ignored and %lld removed out of %lld\n", (long long)ignored, (long long)(tips + bubbles), (long long)m); }
+	if (stored > 0) {
+		uint64_t *x = (uint64_t*)csr;
+		ulaunch(h, k_clean_keep, m, ed, (const uint8_t*)dead, m, n, x);
+		unitig_scan(h, x, m, bsum, cctr + CL_TOTAL);
+		ulaunch(h, k_clean_emit, m, ed, (const uint8_t*)dead, m, n, (const uint64_t*)x, cap, out);
+	}
+	const int64_t inf[8] = {kept, stored, rounds, tips, bubbles, ignored, (int64_t)uc[UT_CHAINS], 0};
+	if (info) memcpy(info, inf, sizeof(inf));
+	return kept;
+}
+
+int64_t rb2_hip_graph_clean_dev(rb2_hip_t *h, int64_t n_str, int64_t m, const int64_t *edges, int64_t max_tip_reads, int64_t max_bubble_reads, int pairs, int64_t max_rounds,
+                                int64_t cap, int64_t *out, int64_t info[8])
+{
+	graph_clean_check(h, "graph_clean_dev", n_str, m, edges, max_tip_reads, max_bubble_reads, pairs, max_rounds, cap, out);
+	return graph_clean_run(h, n_str, m, edges, max_tip_reads, max_bubble_reads, pairs, max_rounds, cap, out, info);
+}
+
+int64_t rb2_hip_graph_clean(rb2_hip_t *h, int64_t n_str, int64_t m, const int64_t *edges, int64_t max_tip_reads, int64_t max_bubble_reads, int pairs, int64_t max_rounds,
+                            int64_t cap, int64_t *out, int64_t info[8])
+{
+	graph_clean_check(h, "graph_clean", n_str, m, edges, max_tip_reads, max_bubble_reads, pairs, max_rounds, cap, out);
+	DevBuf<int64_t> rows;                                          // the list and, behind it, the output on the device: no more rows are kept than came
+	const int64_t dcap = std::min(cap, m);
+	if (m + dcap > 0) rows.ensure((size_t)(m + dcap) * 4);
+	if (m) HIPCHK(hipMemcpyAsync(rows.p, edges, (size_t)m * 32, hipMemcpyHostToDevice, h->st));
+	int64_t inf[8];
+	const int64_t kept = graph_clean_run(h, n_str, m, rows.p, max_tip_reads, max_bubble_reads, pairs, max_rounds, dcap, dcap ? rows.p + 4 * m : nullptr, inf);
+	inf[1] = std::min(kept, cap);
+	if (inf[1] > 0) HIPCHK(hipMemcpyAsync(out, rows.p + 4 * m, (size_t)inf[1] * 32, hipMemcpyDeviceToHost, h->st));
+	HIPCHK(hipStreamSynchronize(h->st));
+	rows.release();
+	if (info) memcpy(info, inf, sizeof(inf));
+	return kept;
+}
+
 /* ---- the strings of the index, packed, and one index merged into another (rb2_unpack.h, rb2_merge_plan.h) ---- */
 
 static void unpack_check(rb2_hip_t *h, const char *who, int64_t first, int64_t n, int64_t cap)

@@ -83,6 +83,8 @@ def load_hip_lib():
         "rb2_hip_merge": (i64, [vp, vp, i64, vp]),
         "rb2_hip_string_graph": (i64, [vp, i64, i64, i64, i64, i64, i64, i64, i32, i64, vp, vp]),
         "rb2_hip_string_graph_dev": (i64, [vp, i64, i64, i64, i64, i64, i64, i64, i32, i64, vp, vp]),
+        "rb2_hip_graph_clean": (i64, [vp, i64, i64, vp, i64, i64, i32, i64, i64, vp, vp]),
+        "rb2_hip_graph_clean_dev": (i64, [vp, i64, i64, vp, i64, i64, i32, i64, i64, vp, vp]),
         "rb2_hip_reserve": (None, [vp, i64, i64, i64]),
         "rb2_hip_num_subropes": (i32, []),
         "rb2_hip_memcpy": (None, [vp, vp, vp, i64, i32]),
@@ -158,7 +160,7 @@ ABI_SYMBOLS = [
     "rb2_hip_irreducible", "rb2_hip_irreducible_dev",
     "rb2_hip_unitig_chains", "rb2_hip_unitig_chains_dev", "rb2_hip_unitig_text", "rb2_hip_unitig_text_dev",
     "rb2_hip_unpack", "rb2_hip_unpack_dev", "rb2_hip_merge",
-    "rb2_hip_string_graph", "rb2_hip_string_graph_dev",
+    "rb2_hip_string_graph", "rb2_hip_string_graph_dev", "rb2_hip_graph_clean", "rb2_hip_graph_clean_dev",
     "rb2_hip_num_subropes", "rb2_hip_memcpy", "rb2_hip_use_stream",
     "rb2_hip_dev_free", "rb2_hip_synth_reads", "rb2_hip_synth_reads_cov", "rb2_hip_synth_reads_skew", "rb2_hip_sync", "rb2_hip_sparse_stats", "rb2_hip_layout_stats", "rb2_hip_rewind_stats", "rb2_hip_steady_stats", "rb2_hip_lean_stats", "rb2_hip_lean_count_stats", "rb2_hip_lean_fork_stats", "rb2_hip_window_stats", "rb2_hip_host_register", "rb2_hip_host_unregister", "rb2_hip_profile",
     "rb2_hip_profile_get", "rb2_hip_kernel_name", "rb2_hip_layout",
@@ -834,11 +836,41 @@ class HipBwt:
             m, edges, info = self.string_graph_raw(first, n, m, **kw)
         return edges[:m].copy(), info
 
-    def assemble(self, min_ovlp, canonical=True, min_reads=1, **kw):
+    # -- tip and bubble removal on an edge list (include/rb2_hip.h) ------------------------------------------
+    def graph_clean_dev(self, n_str, m, edges_dev, out_dev, cap, max_tip_reads=2, max_bubble_reads=3, pairs=True, max_rounds=8):
+        """rb2_hip_graph_clean_dev: edges_dev (4 m int64) and out_dev (4 cap int64; None or 0 with cap 0 counts only) in this device's
+        memory.  Returns (m', info (8,) int64 = m', rows stored, rounds, tip rows, bubble rows, rows ignored, chains of the result, 0)"""
+        info = np.zeros(8, np.int64)
+        kept = self.L.rb2_hip_graph_clean_dev(self.h, int(n_str), int(m), edges_dev or None, int(max_tip_reads), int(max_bubble_reads), int(bool(pairs)), int(max_rounds), int(cap),
+                                              out_dev or None, info.ctypes.data)
+        return int(kept), info
+
+    def graph_clean_raw(self, edges, n_str, max_tip_reads, max_bubble_reads, pairs, max_rounds, cap, fill=0):
+        """rb2_hip_graph_clean as it is: (m', out (cap, 4) int64 that starts as fill, info (8,) int64); no rows pass NULL, and so does cap 0"""
+        edges = np.ascontiguousarray(np.asarray(edges, dtype=np.int64).reshape(-1, 4))
+        out = np.full((max(int(cap), 0), 4), fill, np.int64)
+        info = np.zeros(8, np.int64)
+        kept = self.L.rb2_hip_graph_clean(self.h, int(n_str), len(edges), edges.ctypes.data if len(edges) else None, int(max_tip_reads), int(max_bubble_reads), int(pairs),
+                                          int(max_rounds), int(cap), out.ctypes.data if len(out) else None, info.ctypes.data)
+        return int(kept), out, info
+
+    def graph_clean(self, edges, n_str=None, max_tip_reads=2, max_bubble_reads=3, pairs=True, max_rounds=8):
+        """the edge list edges (m, 4) int64 = src, dst, l, ext over n_str vertices (None: the strings of the index) without its tips of at
+        most max_tip_reads reads and the losing arms of its bubbles of at most max_bubble_reads reads (the rules: include/rb2_hip.h):
+        (the rows kept, in input order, info (8,) int64 as graph_clean_dev returns it).  pairs: vertices 2i and 2i + 1 are one read"""
+        edges = np.asarray(edges, dtype=np.int64).reshape(-1, 4)
+        n = self._n_strings() if n_str is None else int(n_str)
+        kept, out, info = self.graph_clean_raw(edges, n, max_tip_reads, max_bubble_reads, int(bool(pairs)), max_rounds, len(edges))
+        return out[:kept].copy(), info
+
+    def assemble(self, min_ovlp, canonical=True, min_reads=1, clean=None, **kw):
         """what unitigs() returns, with the graph, the chains and the texts made on the device: string_graph_dev, unitig_chains_dev and
         unitig_text_dev on buffers from dev_alloc; only the unitigs' records, their text and the chain order come back.  kw: max_ext,
         max_steps, max_recs, max_hits of string_graph().  Returns (unitigs, info): info = what string_graph_dev reports (info[2:6] != 0:
-        sources whose edges were cut short, which unitigs() raises for or passes over in silence)"""
+        sources whose edges were cut short, which unitigs() raises for or passes over in silence).
+        clean: None, or a dict of max_tip_reads, max_bubble_reads, pairs, max_rounds (those left out: graph_clean_dev's defaults): the
+        edge list goes through graph_clean_dev into a second buffer before the chains are made, and info is then the pair (what
+        string_graph_dev reports, what graph_clean_dev reports)"""
         _, n, max_ext = self._graph_args("assemble", 0, None, kw.pop("max_ext", None), True)
         kw.update(min_ovlp=min_ovlp, max_ext=max_ext, pairs=True)
         ptrs = []
@@ -861,6 +893,10 @@ class HipBwt:
                 cap = m
                 d_edges = alloc(32 * cap)
                 m, info = self.string_graph_dev(0, n, d_edges, cap, **kw)
+            if clean is not None:                                   # (no more rows are kept than came: room for all of them)
+                d_raw, d_edges = d_edges, alloc(32 * m)
+                m, cinfo = self.graph_clean_dev(n, m, d_raw, d_edges, m, **clean)
+                info = (info, cinfo)
             d_vtx, d_cinfo = alloc(32 * n), alloc(32)
             self.unitig_chains_dev(n, m, d_edges, d_vtx, d_cinfo)
             _, tinfo = self.unitig_text_dev(n, d_vtx, None, None, canonical, min_reads)

@@ -62,6 +62,10 @@ With --graph only rb2_hip_string_graph is measured and stored under "string_grap
 of three after a warm-up with the fastest and the slowest beside it; (b) HipBwt.edges() on the first --unitig-sample strings against
 string_graph on the same strings (host buffers; the rows are compared: equals_fused); (c) irreducible_dev alone on the same strings, their
 texts already on the device, against string_graph_dev measured next to it: what unpacking, counting, scanning and emitting cost on top.
+With --clean only rb2_hip_graph_clean_dev is measured and stored under "clean" in the --out file, whose other entries stay: a synthetic edge
+list that needs no index (tests/graph_clean_ref.py backbone: both strands of --reads reads, default 1 000 000, a one-read tip every 50 reads
+and a one-read bubble every 70), the call's seconds (median of three after a warm-up) and seconds per round, and unitig_chains_dev on the
+same list, which every round contains (clean_case).
 With --merge only rb2_hip_unpack_dev and rb2_hip_merge are measured and stored under "merge" in the --out file, whose other entries stay:
 symbols per second of unpack_dev in both directions against rb2_hip_extract of the same strings (max_len = the read length), and the merge
 of an index of a quarter as many other reads into the benchmark index against extract + a host pass + rb2_hip_insert_multi from the host
@@ -821,6 +825,38 @@ def unitig_case(a, res):
     res["unitigs"] = {"index": index, "cases": [crow, trow, brow, frow]}
 
 
+def clean_case(a, res):
+    """--clean: rb2_hip_graph_clean_dev on a synthetic edge list that needs no index (tests/graph_clean_ref.py backbone): both strands of
+    --reads reads in a row, a one-read tip every 50 reads and a one-read bubble every 70; beside it unitig_chains_dev on the same list"""
+    import graph_clean_ref as GC
+    reads = a.reads or 1_000_000
+    t0 = time.perf_counter()
+    n, edges = GC.backbone(reads, tips=[(i, 1) for i in range(25, reads - 1, 50)], bubbles=[(i, 1, 1) for i in range(35, reads - 2, 70)])
+    m = len(edges)
+    print("clean: %d vertices, %d rows made in %.1f s" % (n, m, time.perf_counter() - t0), file=sys.stderr, flush=True)
+    g = HipBwt(0)
+    de, do, dv, di = g.dev_alloc(edges.nbytes), g.dev_alloc(edges.nbytes), g.dev_alloc(32 * n), g.dev_alloc(32)
+    g.L.rb2_hip_memcpy(g.h, de, edges.ctypes.data, edges.nbytes, 0)
+    got = {}
+
+    def run():
+        got["clean"] = g.graph_clean_dev(n, m, de, do, m)
+    sec, lo, hi = spread(run, g.sync)
+    kept, info = got["clean"]
+    rounds = int(info[2])
+    csec, clo, chi = spread(lambda: g.unitig_chains_dev(n, m, de, dv, di), g.sync)
+    for d in (de, do, dv, di):
+        g.dev_free(d)
+    g.close()
+    row = {"case": "graph_clean_dev max_tip_reads=2 max_bubble_reads=3 pairs=1, %d vertices, %d rows, cap = m" % (n, m), "measured": True, "seconds": sec, "seconds_fastest": lo,
+           "seconds_slowest": hi, "rounds": rounds, "seconds_per_round": sec / max(rounds, 1), "rows_kept": int(kept), "tip_rows": int(info[3]), "bubble_rows": int(info[4]),
+           "chains_after": int(info[6]), "rows_per_second_per_round": m * max(rounds, 1) / sec}
+    crow = {"case": "unitig_chains_dev on the same list (every round contains it)", "measured": True, "seconds": csec, "seconds_fastest": clo, "seconds_slowest": chi}
+    res["clean"] = {"list": {"vertices": n, "rows": m, "reads": reads, "tip_every": 50, "bubble_every": 70}, "cases": [row, crow],
+                    "round_over_chains": sec / max(rounds, 1) / csec}
+    print("clean: %.4f s in %d rounds, chains alone %.4f s" % (sec, rounds, csec), file=sys.stderr, flush=True)
+
+
 def graph_case(a, res):
     """--graph: rb2_hip_string_graph_dev on the both-strand read index of --unitigs (reduced, suffix array at log2_step 5)"""
     L, M, H8 = 101, 8, 8
@@ -1059,7 +1095,16 @@ def main():
     ap.add_argument("--save-fmd", action="store_true", help="only the device .fmd encoder against the host writer (added to an existing --out file)")
     ap.add_argument("--merge", action="store_true", help="only unpack and merge (added to an existing --out file)")
     ap.add_argument("--graph", action="store_true", help="only the string graph on the device (added to an existing --out file)")
+    ap.add_argument("--clean", action="store_true", help="only tip and bubble removal on a synthetic edge list of --reads reads (added to an existing --out file)")
     a = ap.parse_args()
+    if a.clean:
+        res = {"cases": []}
+        if a.out and os.path.exists(a.out):
+            with open(a.out) as f:
+                res = json.load(f)
+        clean_case(a, res)
+        finish(a, res)
+        return
     if a.graph:
         res = {"cases": []}
         if a.out and os.path.exists(a.out):
