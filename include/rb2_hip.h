@@ -746,6 +746,12 @@ void rb2_hip_lean_count_stats(rb2_hip_t *h, int64_t out[4]);
  * out[0] = rounds forked since create, out[1] = 1 when such rounds are forked (RB2_LEAN_FORK, default 1; 0 at create: one stream, the launches as
  * before), 0 when not -- the switch is off, the handle runs on a caller's stream (rb2_hip_use_stream), or RB2_LEAN_VERIFY / RB2_HIP_DEBUG is set. */
 void rb2_hip_lean_fork_stats(rb2_hip_t *h, int64_t out[2]);
+/* the window directory ("the window directory"): a lean round whose windows may be written compact keeps the rank directory of the
+ * side it writes per window of 4 leaves, not per leaf -- nothing but the merge and the round's own k_advance reads that side before the next rewrite.
+ * out[0] = rounds run that way since create, out[1] = the switch (RB2_LEAN_DIR, default 1; 0 at create: every round writes the per-leaf
+ * directory, the launches as before), out[2] = the rounds the mode applies to, counted whatever the switch says: the lean rounds among the rounds
+ * rb2_hip_window_stats counts in out[4]. */
+void rb2_hip_lean_dir_stats(rb2_hip_t *h, int64_t out[3]);
 /* window formats of the dense layout (a window = 4 leaves = 4096 symbols; csrc/rb2_merge.h): out[0..3] = windows the dense merge wrote
  * plain (three bit planes) / compact with no, one, two lines of exception positions -- counted on the device only when the handle was
  * created with RB2_COMPACT_STATS=1 in the environment (zeros otherwise) --, out[4] = dense rounds that were allowed to write compact

@@ -309,6 +309,10 @@ struct rb2_hip_s {
 	int64_t n_compact_rounds = 0;       // dense rounds that were allowed to write compact windows
 	int64_t n_plain_handover = 0;       // dense rounds that wrote plain windows over compact ones because a re-layout was pending (plain_next): rb2_hip_layout_stats out[7]
 	bool pool_compact = false;          // the last dense round wrote compact windows (only k_merge may read the pool now)
+	// the window directory: a lean round whose windows may be written compact keeps the rank directory of the new side per window (k_merge<.., LITE>, k_meta_win, k_advance<.., LITE>)
+	int lean_dir = 1;                   // RB2_LEAN_DIR=0: every round writes the per-leaf directory, the launches as they were
+	int64_t n_lean_dir = 0, n_lean_compact = 0;   // rounds run with the window directory; lean rounds that were allowed to write compact windows, whatever the switch says (rb2_hip_lean_dir_stats)
+	bool pool_win_dir = false;          // the last dense round left a window directory: own[] / meta[] of the pool hold no per-leaf entries (set and cleared with pool_compact)
 	bool plain_next = false;            // choose_layout wants to leave the dense layout: this round writes plain windows
 	int ts_fold = SCHUNK;               // up to this many chunks of string tiles k_tscan3 scans the chunk totals itself (no k_tscan2 launch); RB2_TS_FOLD lowers it (tests)
 	int ts_max = TS_MAX;                // batches with fewer string tiles run their counting tail in one single-block launch (k_tscan_setup); RB2_TS_MAX lowers it (tests)
@@ -379,7 +383,8 @@ inline uint64_t rank_share(const rb2_hip_t *h, uint64_t whole)
 }
 
 // recompute the rank directory (meta prefixes + superblock prefix) of pool side `sd`
-void build_directory(rb2_hip_t *h, int sd /* descriptors */, int pool /* arrays */, uint64_t nsb_ub, bool sparse = false, bool leaves_done = false, uint64_t nsb_grid = 0)
+// win_dir: the merge left one record per window (k_merge<.., LITE>): k_meta_win in the place of k_meta_sb
+void build_directory(rb2_hip_t *h, int sd /* descriptors */, int pool /* arrays */, uint64_t nsb_ub, bool sparse = false, bool leaves_done = false, uint64_t nsb_grid = 0, bool win_dir = false)
 {
 	if (nsb_ub == 0) return;
 	const hipStream_t st_ = h->st;
@@ -389,6 +394,10 @@ void build_directory(rb2_hip_t *h, int sd /* descriptors */, int pool /* arrays 
 	PoolView pv = h->pool[pool].view();
 	// leaves_done: an in-place round -- k_merge_leaf updated the entries of the leaves it rewrote and the superblock totals
 	// itself (h->sbtot lives on between rounds); what is left is the prefix over the totals
+	if (win_dir) {
+		if (sparse || leaves_done || h->nranks > 1) { rb2_fatal("[rb2_hip] internal: a window directory outside a dense round of one engine\n"); }
+		hipLaunchKernelGGL(k_meta_win, dim3(cdiv(nsb_grid, 32)), dim3(256), 0, st_, (const Ctl*)h->ctl, sd, pv, h->sbtot.p);
+	} else
 	if (!leaves_done) RB2_LAUNCH_STRIDE(h, k_meta_sb<true>, k_meta_sb<false>, dim3(cdiv(nsb_grid, 8)), dim3(256), 0, st_, h->ctl, sd, pv, h->sbtot.p, (int)sparse);
 	// in-chunk prefixes (SbRec) + chunk totals in one pass over the totals, then the chunk bases (the in-chunk prefixes need no base: queries add it)
 	hipLaunchKernelGGL(k_sbscan3, dim3(nchunk), dim3(SCHUNK / SBT), 0, st_, (const Ctl*)h->ctl, (const SbTot*)h->sbtot.p, pv);
@@ -695,12 +704,18 @@ template <bool SPARSE, class P> void launch_prep(rb2_hip_t *h, const BatchState 
 }
 
 // the k_advance pair of round r, likewise; the scan blocks of an in-place round (sr) ride on the all-empty variant, which always runs
-template <bool SPARSE, class P> void launch_advance(rb2_hip_t *h, const BatchState &B, uint64_t r, const PoolView &newp, const StrArrays<P> &S, ShardRec *send, ScanRide sr)
+// lite: the new side holds a window directory (round_merge): the all-empty variant that reads it, alone
+template <bool SPARSE, class P> void launch_advance(rb2_hip_t *h, const BatchState &B, uint64_t r, const PoolView &newp, const StrArrays<P> &S, ShardRec *send, ScanRide sr, bool lite = false)
 {
 	Scope sc(h, RB2_K_ADVANCE, (int64_t)B.m);
 	const int sd = h->side, is_comp = h->so == RB2_SO_RCLO;
 	const unsigned tg = grid8((unsigned)rank_share(h, B.nst_ub));
 	const PushTab *push = h->push[B.cur ^ 1];
+	if constexpr (!SPARSE) if (lite) {
+		if (!B.known_ae || h->nranks > 1 || send || push) { rb2_fatal("[rb2_hip] internal: round %llu has a window directory and is not a lean round of one engine\n", (unsigned long long)r); }
+		hipLaunchKernelGGL((k_advance<true, false, false, P, true>), dim3(tg), dim3(256), 0, h->st, h->ctl, sd, is_comp, (uint32_t)r, B.s, newp, S, send, push, sr);
+		return;
+	}
 	if (!B.known_ae) RB2_LAUNCH_STRIDE(h, (k_advance<false, SPARSE, true, P>), (k_advance<false, SPARSE, false, P>), dim3(tg), dim3(256), 0, h->st, h->ctl, sd, is_comp, (uint32_t)r, B.s, newp, S, send, push, ScanRide{ nullptr, 0u });
 	RB2_LAUNCH_STRIDE(h, (k_advance<true, SPARSE, true, P>), (k_advance<true, SPARSE, false, P>), dim3(tg + sr.nscan), dim3(256), 0, h->st, h->ctl, sd, is_comp, (uint32_t)r, B.s, newp, S, send, push, sr);
 }
@@ -725,6 +740,8 @@ void round_merge(rb2_hip_t *h, BatchState &B, uint64_t r, ShardRec *send, bool c
 	// the forms of k_part / k_merge follow how the round was COUNTED (B.lean, round_counts): a lean count left no INS_E / INS_A
 	const bool lean = B.lean != 0;
 	const bool forked = B.forked;
+	// the window directory: decided once, for k_merge, the directory launch and k_advance together (lean: one engine, dense layout, every interval empty)
+	const bool lite = lean && compact_out && h->lean_dir != 0;
 	if (forked && (B.lean != 2 || !setup_done(h, B, r, false) || !h->fork_open)) { rb2_fatal("[rb2_hip] internal: round %llu was forked and is not merged as the lean dense round it was counted as\n", (unsigned long long)r); }
 	if (lean && (h->nranks != 1 || h->sparse || !B.known_steady)) { rb2_fatal("[rb2_hip] internal: round %llu was counted lean and is not merged as a steady dense round\n", (unsigned long long)r); }
 	if (lean) ++h->n_lean_rounds;
@@ -739,14 +756,15 @@ void round_merge(rb2_hip_t *h, BatchState &B, uint64_t r, ShardRec *send, bool c
 	  else RB2_LAUNCH_STRIDE(h, (k_part<true, P>), (k_part<false, P>), dim3(cdiv(wg + NR, 255)), dim3(256), 0, st, h->ctl, sd, S.INS_E, h->LD.p, old_xh); }   // (the formats of the old windows: only a pool side the compact-capable merge wrote has any but plain)
 	tl_slow(h, "k_part");
 	{ Scope sc(h, RB2_K_MERGE, units);
-	  if (lean) hipLaunchKernelGGL((k_merge<false, P, true>), dim3(grid8(cdiv(wg, MMW))), dim3(64 * MMW), 0, st, h->ctl, h->LD.p, oldp, newp, (const P*)S.L, (const uint8_t*)S.A, S.RKREL, (int)compact_out | (h->compact_stats ? 2 : 0), (int)(r & 1));
+	  if (lite) hipLaunchKernelGGL((k_merge<false, P, true, true>), dim3(grid8(cdiv(wg, MMW))), dim3(64 * MMW), 0, st, h->ctl, h->LD.p, oldp, newp, (const P*)S.L, (const uint8_t*)S.A, S.RKREL, (int)compact_out | (h->compact_stats ? 2 : 0), (int)(r & 1));
+	  else if (lean) hipLaunchKernelGGL((k_merge<false, P, true>), dim3(grid8(cdiv(wg, MMW))), dim3(64 * MMW), 0, st, h->ctl, h->LD.p, oldp, newp, (const P*)S.L, (const uint8_t*)S.A, S.RKREL, (int)compact_out | (h->compact_stats ? 2 : 0), (int)(r & 1));
 	  else RB2_LAUNCH_STRIDE(h, (k_merge<true, P>), (k_merge<false, P>), dim3(grid8(cdiv(wg, MMW))), dim3(64 * MMW), 0, st, h->ctl, h->LD.p, oldp, newp, S.INS_E, S.INS_A, S.RKREL, (int)compact_out | (h->compact_stats ? 2 : 0), (int)(r & 1)); }
 	tl_slow(h, "k_merge");
 	{ Scope sc(h, RB2_K_META, units);
-	  build_directory(h, sd ^ 1, h->pside ^ 1, std::min<uint64_t>(B.nsb_ub, n_new_ub / (LEAF * SB) + NR + 1), false, false, (uint64_t)wg * WPL / SB + NR + 1); }
+	  build_directory(h, sd ^ 1, h->pside ^ 1, std::min<uint64_t>(B.nsb_ub, n_new_ub / (LEAF * SB) + NR + 1), false, false, (uint64_t)wg * WPL / SB + NR + 1, lite); }
 	tl_slow(h, "directory");
 	fork_join(h);                                               // (k_advance reads what the counting tail left: the tile records' folds, count, ac, dest, the next buckets)
-	launch_advance<false>(h, B, r, newp, S, send, ScanRide{ nullptr, 0u });
+	launch_advance<false>(h, B, r, newp, S, send, ScanRide{ nullptr, 0u }, lite);
 	});
 	tl_slow(h, "k_advance");
 	if (!B.known_ae && !send && h->nranks == 1) ne_snapshot(h, r);
@@ -754,8 +772,10 @@ void round_merge(rb2_hip_t *h, BatchState &B, uint64_t r, ShardRec *send, bool c
 	tl_slow(h, "ne snapshot");
 	h->side ^= 1; h->pside ^= 1; B.cur ^= 1;
 	drop_lean(h, B);                                            // (the record belongs to the round just merged)
-	h->pool_compact = compact_out;
+	h->pool_compact = compact_out; h->pool_win_dir = lite;
 	if (compact_out) ++h->n_compact_rounds;
+	if (lean && compact_out) ++h->n_lean_compact;
+	if (lite) ++h->n_lean_dir;
 }
 
 // leaf slots the pools must hold for an index of n symbols in the given layout
@@ -771,6 +791,7 @@ uint64_t slots_for(uint64_t n, bool sparse)
 void require_plain(rb2_hip_t *h, const char *who)
 {
 	if (!h->sparse && h->pool_compact) { rb2_fatal("[rb2_hip] internal: %s would read a pool that holds compact windows\n", who); }
+	if (h->pool_win_dir) { rb2_fatal("[rb2_hip] internal: %s would read a pool whose directory is kept per window\n", who); }   // (own[] / meta[] hold no per-leaf entries)
 }
 
 // copy the index pool[pside] -> pool[pside ^ 1] in the other layout (or the same one, re-spread); descriptors of
@@ -800,7 +821,7 @@ void relayout(rb2_hip_t *h, bool to_sparse, uint64_t n_ub, uint64_t n_grow)
 		build_directory(h, h->side, h->pside ^ 1, slots / SB + 1, to_sparse);
 		HIPCHK(hipGetLastError());                              // a refused launch here would leave descriptors without data
 	}
-	h->pside ^= 1; h->sparse = to_sparse; ++h->n_relayout; ++h->layout_epoch; h->pool_compact = false;   // (k_relayout writes plain windows)
+	h->pside ^= 1; h->sparse = to_sparse; ++h->n_relayout; ++h->layout_epoch; h->pool_compact = false; h->pool_win_dir = false;   // (k_relayout writes plain windows and own[]; build_directory above the per-leaf directory)
 	if (to_sparse) h->sp_nsb = slots / SB + 1;
 	if (!to_sparse && h->pool[h->pside ^ 1].cap_leaves < cap) {   // the pool just left becomes the target of the next dense round
 		HIPCHK(hipStreamSynchronize(st));
@@ -1191,6 +1212,7 @@ rb2_hip_t *rb2_hip_create(int device, int sorting_order)
 	if (getenv("RB2_SPARSE_HEAD")) h->sp_head = atoi(getenv("RB2_SPARSE_HEAD"));
 	if (getenv("RB2_LEAF_PIPE")) h->leaf_pipe = atoi(getenv("RB2_LEAF_PIPE"));
 	if (getenv("RB2_COMPACT")) h->compact_ok = atoi(getenv("RB2_COMPACT"));
+	if (getenv("RB2_LEAN_DIR")) h->lean_dir = atoi(getenv("RB2_LEAN_DIR"));
 	if (getenv("RB2_COMPACT_STATS")) h->compact_stats = atoi(getenv("RB2_COMPACT_STATS"));
 	if (getenv("RB2_TS_MAX")) h->ts_max = std::max(0, std::min((int)TS_MAX, atoi(getenv("RB2_TS_MAX"))));
 	if (getenv("RB2_TS_FOLD")) h->ts_fold = std::max(0, std::min((int)SCHUNK, atoi(getenv("RB2_TS_FOLD"))));   // tests: 0 = the scan over the chunks always as a launch of its own (k_tscan2)
@@ -1767,7 +1789,7 @@ int64_t rb2_hip_delete_strings(rb2_hip_t *h, int64_t n, const int64_t *ids)
 		HIPCHK(hipGetLastError());
 	}
 	phase();
-	h->pside = ps; h->pool_compact = false;                    // `side` stays, as in a re-layout: the descriptors are rewritten in place
+	h->pside = ps; h->pool_compact = false; h->pool_win_dir = false;                    // `side` stays, as in a re-layout: the descriptors are rewritten in place
 	ld_finish(h, rp, leaf, dst, tally.p);
 	phase();
 	if (h->trace) fprintf(stderr, "[rb2_hip] delete_strings: %lld ids, %llu rows: mark %.3f ms, count %.3f, zeroed destination %.3f, scan + compact %.3f, own counts + directory %.3f\n", (long long)n,
@@ -2217,6 +2239,13 @@ void rb2_hip_lean_fork_stats(rb2_hip_t *h, int64_t out[2])
 {
 	finish_pending(h);
 	out[0] = h->n_lean_forked; out[1] = (h->lean_fork && h->own_stream && !h->lean_verify && !h->debug) ? 1 : 0;
+}
+
+/* out[0]: rounds run with the window directory; out[1]: the switch in force (RB2_LEAN_DIR); out[2]: lean rounds that were allowed to write compact windows, whatever the switch says */
+void rb2_hip_lean_dir_stats(rb2_hip_t *h, int64_t out[3])
+{
+	finish_pending(h);
+	out[0] = h->n_lean_dir; out[1] = h->lean_dir ? 1 : 0; out[2] = h->n_lean_compact;
 }
 
 void rb2_hip_window_stats(rb2_hip_t *h, int64_t out[6])

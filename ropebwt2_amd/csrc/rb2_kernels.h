@@ -1850,6 +1850,51 @@ template <bool STRIDE> __global__ __launch_bounds__(256) void k_meta_sb(const Ct
 	}
 }
 
+// The window directory: behind k_merge<.., LITE> the first quarter of own[] holds one record per WINDOW (its six counts, format, fill).  Lane = window,
+// eight lanes = one superblock, a wave = eight superblocks: window-exclusive prefix inside the superblock -> the first quarter of meta[], one 16-byte record per
+// window (what k_advance<.., LITE> gathers); superblock totals as k_meta_sb writes them.  A window past its piece's last leaf counts as zero and is never read
+// (decided from the rope descriptor; windows and pieces start on multiples of WPL leaves, so a window lies in the piece exactly when its first leaf does).
+static_assert(SB % WPL == 0 && SB / WPL == 8, "k_meta_win: eight windows per superblock");
+__global__ __launch_bounds__(256) void k_meta_win(const Ctl *ctl, int nside, PoolView newp, SbTot *sbtot)
+{
+	const int ln = lane_id();
+	const uint64_t nsb = ctl->nsb_total;
+	const uint64_t sb = ((uint64_t)blockIdx.x * 4 + wave_id()) * 8 + (uint32_t)(ln >> 3);
+	const bool live = sb < nsb;
+	const uint64_t gl = sb * SB + (uint32_t)(ln & 7) * WPL;    // the window's first leaf
+	// sub-ropes start on superblock boundaries, in ascending order: the one that owns a superblock is the last with sb0 <= sb
+	int r = 0;
+	for (int i = 1; i < NR; ++i) r += ctl->rope[nside][i].sb0 <= sb ? 1 : 0;
+	const RopeDesc &rp = ctl->rope[nside][r];
+	const bool ok = live && gl >= rp.leaf0 && gl < rp.leaf0 + rp.nleaves;
+	LeafMeta m;
+	for (int s = 0; s < 6; ++s) m.c[s] = 0;
+	m.npre = 0; m.n = 0;
+	if (ok) m = newp.own[gl / WPL];                            // the window's counts + fill (k_merge<.., LITE>)
+	const uint32_t e01 = m.c[0] | (uint32_t)m.c[1] << 16, e23 = m.c[2] | (uint32_t)m.c[3] << 16, e45 = m.c[4] | (uint32_t)m.c[5] << 16;
+	const uint32_t k = (uint32_t)ln & 7u;
+	auto seg8 = [&](uint32_t v) {                                // inclusive prefix inside my eight lanes (a DPP row holds two superblocks)
+		uint32_t t;
+		t = dpp0<0x111, 0xf>(v); v += k >= 1u ? t : 0u;           // (row_shr 1 / 2 / 4, every lane takes part; what comes from the other superblock of the row is dropped)
+		t = dpp0<0x112, 0xf>(v); v += k >= 2u ? t : 0u;
+		t = dpp0<0x114, 0xf>(v); v += k >= 4u ? t : 0u;
+		return v;
+	};
+	const uint32_t s01 = seg8(e01), s23 = seg8(e23), s45 = seg8(e45);   // (<= SB * LEAF per field)
+	if (ok) {
+		const uint32_t x01 = s01 - e01, x23 = s23 - e23, x45 = s45 - e45;
+		m.c[0] = (uint16_t)x01; m.c[1] = (uint16_t)(x01 >> 16); m.c[2] = (uint16_t)x23; m.c[3] = (uint16_t)(x23 >> 16);
+		m.c[4] = (uint16_t)x45; m.c[5] = (uint16_t)(x45 >> 16);
+		m.npre = (uint16_t)((x01 & 0xffffu) + (x01 >> 16) + (x23 & 0xffffu) + (x23 >> 16) + (x45 & 0xffffu) + (x45 >> 16));   // <= SB * LEAF < 2^16
+		newp.meta[gl / WPL] = m;
+	}
+	if (k == 7u && live) {                                       // inclusive prefix of the last window = superblock total
+		SbTot c;
+		c.p01 = s01; c.p23 = s23; c.p45 = s45; c.pad = 0;
+		sbtot[sb] = c;
+	}
+}
+
 // the two-kernel prefix over the superblock totals (k_sbscan3: prefixes inside every chunk + the chunk totals; k_sbscan2: the chunk bases).  A total is six 16-bit counts (<= SB * LEAF = 32768 each) in 16 bytes; inside
 // a chunk of 1024 superblocks sums stay below 2^25, so the chunk-level work is 32-bit DPP scans with one LDS exchange and what is
 // stored per superblock is a 32-byte record of 32-bit prefixes (SbRec); only the chunk bases (SbBase) are 64 bit.
@@ -2012,7 +2057,7 @@ __global__ __launch_bounds__(SCHUNK / SBT) void k_sbscan3(const Ctl *ctl, const 
 #ifndef RB2_ADV_STAGE
 #define RB2_ADV_STAGE 1
 #endif
-template <bool AE, bool SPARSE, typename P> __device__ __forceinline__ bool advance_tile(const uint32_t tile, const Ctl *ctl, int side, int is_comp, uint32_t round, const uint8_t *s, const PoolView &newp,
+template <bool AE, bool SPARSE, typename P, bool LITE = false> __device__ __forceinline__ bool advance_tile(const uint32_t tile, const Ctl *ctl, int side, int is_comp, uint32_t round, const uint8_t *s, const PoolView &newp,
 		const StrArrays<P> &S, ShardRec *send, const PushTab *push)
 {
 	const P *L = S.L, *SIZE = S.SIZE, *INS_E = S.INS_E, *RKOLD = S.RKOLD; const uint64_t *W = S.W; const uint8_t *A = S.A; const TileFix *tf = S.tf; const uint16_t *RKREL = S.RKREL;
@@ -2068,7 +2113,10 @@ template <bool AE, bool SPARSE, typename P> __device__ __forceinline__ bool adva
 	// the piece's first leaf / superblock (a piece starts on a superblock boundary) -- as scalars whatever branch the compiler first loads them in (a value merged behind a divergent branch
 	// lives in vector registers, and so does every address built on it: seven 64-bit vector additions per string)
 	const uint64_t sb0u = uniform64(nrp.sb0), leaf0u = uniform64(nrp.leaf0);
-	const LeafMeta *metab = newp.meta + leaf0u; const SbRec *sbrb = newp.sbrec + sb0u;
+	// LITE (the window directory): behind k_meta_win the first quarter of meta[] holds one entry per WINDOW, RKREL is the rank inside the window
+	constexpr int DIR_SH = LITE ? 2 : 0;
+	static_assert(WPL == 4 && (!LITE || (AE && !SPARSE)), "a window-directory round is a lean dense round; WPL = 1 << 2");
+	const LeafMeta *metab = newp.meta + (leaf0u >> DIR_SH); const SbRec *sbrb = newp.sbrec + sb0u;
 	const uint16_t *RKb = RKREL + t.segstart; const P *Eb = INS_E + t.segstart; const P *ROb = SPARSE ? RKOLD + t.segstart : nullptr;
 	auto rank_issue = [&](int h, int a, uint32_t slot, P F, bool flag, RankRaw &q) {
 		if (SPARSE) {                                          // in-place rounds: the rank on the rope as it was BEFORE the round, taken on the way down: in front of the leaf (k_part_sparse) + inside it (k_merge_leaf)
@@ -2081,12 +2129,12 @@ template <bool AE, bool SPARSE, typename P> __device__ __forceinline__ bool adva
 			const uint32_t ua = (uint32_t)a;
 			q.sbb = *(const P*)((const char*)newp.sbbase + ((sbq >> SCHUNK_SH) * (uint32_t)sizeof(SbBase) + ua * 8u));   // (little endian: the low half of the 64-bit sum)
 			q.sbr = *(const uint32_t*)((const char*)sbrb + ((lf / SB) * (uint32_t)sizeof(SbRec) + ua * 4u));
-			q.meta = *(const uint16_t*)((const char*)metab + (lf * (uint32_t)sizeof(LeafMeta) + ua * 2u));
+			q.meta = *(const uint16_t*)((const char*)metab + ((lf >> DIR_SH) * (uint32_t)sizeof(LeafMeta) + ua * 2u));
 			q.rkrel = *(const uint16_t*)((const char*)RKb + slot * 2u);
 			return;
 		}
 		const P *bb = (const P*)&newp.sbbase[sbq >> SCHUNK_SH].cum[a];                       // (little endian: the low half when positions are stored in 32 bits)
-		q.sbb = *bb; q.sbr = sbrb[lf / SB].cum[a]; q.meta = metab[lf].c[a]; q.rkrel = RKb[slot];
+		q.sbb = *bb; q.sbr = sbrb[lf / SB].cum[a]; q.meta = metab[lf >> DIR_SH].c[a]; q.rkrel = RKb[slot];
 	};
 	auto rank_sum = [](const RankRaw &q) -> P { return (P)(q.sbb + q.sbr + q.meta + q.rkrel); };
 	RankRaw rq[2];
@@ -2209,7 +2257,7 @@ template <bool AE, bool SPARSE, typename P> __device__ __forceinline__ bool adva
 
 struct ScanRide { const SbTot *sbtot; uint32_t nscan; };     // in-place rounds: the first nscan blocks of the k_advance launch do k_sbscan3's work (see k_advance)
 
-template <bool AE, bool SPARSE = false, bool STRIDE = false, typename P = uint64_t> __global__ __launch_bounds__(256) void k_advance(const Ctl *ctl, int side, int is_comp, uint32_t round, const uint8_t *s, PoolView newp,
+template <bool AE, bool SPARSE = false, bool STRIDE = false, typename P = uint64_t, bool LITE = false> __global__ __launch_bounds__(256) void k_advance(const Ctl *ctl, int side, int is_comp, uint32_t round, const uint8_t *s, PoolView newp,
 		StrArrays<P> S, ShardRec *send, const PushTab *push, ScanRide sr)
 {
 	// THE DIRECTORY RIDES ALONG.  An in-place round leaves the superblock totals current (k_merge_leaf); what is left is the prefix over them
@@ -2224,7 +2272,7 @@ template <bool AE, bool SPARSE = false, bool STRIDE = false, typename P = uint64
 		if (blockIdx.x < nsc) { __shared__ uint32_t s_p[6][4]; sbscan3_body(ctl, sr.sbtot, newp, blockIdx.x, s_p); return; }
 	}
 	for (uint32_t tile = (SPARSE && nsc) ? blockIdx.x - nsc : (STRIDE ? blockIdx.x : xcd_item()); ; ) {   // first tile as a one-tile-per-block kernel would run it, then a grid stride (see k_prep)
-		if (!advance_tile<AE, SPARSE, P>(tile, ctl, side, is_comp, round, s, newp, S, send, push)) return;
+		if (!advance_tile<AE, SPARSE, P, LITE>(tile, ctl, side, is_comp, round, s, newp, S, send, push)) return;
 		if (!STRIDE) return;
 		tile += gridDim.x - nsc;
 		if (tile >= ctl->seg[side].tile0[NR]) return;

@@ -126,7 +126,10 @@ __device__ __forceinline__ uint64_t stage_bits(const uint32_t *pl, uint32_t dk, 
 // LEAN ("the lean round"): INS_E / INS_A are the round's L and A arrays -- every string is a group of its own with an empty interval, so
 // L[q] is the final position of insert q in its piece and, windows being WIN-aligned inside a piece, its low bits are the place in the window; A
 // carries flags above the symbol.
-template <bool FULL, int GPL_, typename P, bool LEAN = false> __device__ __forceinline__ void merge_window(const LeafDesc &d, uint64_t *lds, const int ln,
+// LITE ("the window directory"): a lean round whose windows may be written compact keeps its rank directory per WINDOW -- the three row scans are
+// carried over the wave, RKREL is the rank inside the window, and instead of four LeafMeta entries the wave stores one 16-byte record (the window's six counts,
+// its format, its fill) at own[gl / WPL]: the first quarter of the side's own[] array, which nothing else reads before the next rewrite (k_meta_win, k_advance<.., LITE>).
+template <bool FULL, int GPL_, typename P, bool LEAN = false, bool LITE = false> __device__ __forceinline__ void merge_window(const LeafDesc &d, uint64_t *lds, const int ln,
 		const PoolView &oldp, const PoolView &newp, const P *__restrict__ INS_E, const uint8_t *__restrict__ INS_A, uint16_t *RKREL, const int compact_out, unsigned long long *wfmt)
 {
 	static_assert(GPL_ == 1, "one group per lane");
@@ -248,12 +251,17 @@ template <bool FULL, int GPL_, typename P, bool LEAN = false> __device__ __force
 		const uint32_t t4 = c[0]; c[0] = c[4]; c[4] = t4;         // (the planes are in the swapped coding)
 	}
 	const uint32_t e01 = c[0] | c[1] << 16, e23 = c[2] | c[3] << 16, e45 = c[4] | c[5] << 16;
-	const uint32_t s01 = row_incl_add(e01), s23 = row_incl_add(e23), s45 = row_incl_add(e45);
+	uint32_t s01 = row_incl_add(e01), s23 = row_incl_add(e23), s45 = row_incl_add(e45);
+	if (LITE) {                                                 // the row prefixes carried over the wave (row_bcast 15 / 31): a field holds at most WIN
+		s01 += dpp0<0x142, 0xa>(s01); s01 += dpp0<0x143, 0xc>(s01);
+		s23 += dpp0<0x142, 0xa>(s23); s23 += dpp0<0x143, 0xc>(s23);
+		s45 += dpp0<0x142, 0xa>(s45); s45 += dpp0<0x143, 0xc>(s45);
+	}
 	// the format of the new window: its exceptions are its $ and N symbols, already counted and scanned
-	const uint32_t nx = c[0] + c[5], xs = (s01 & 0xffffu) + (s45 >> 16);   // mine / inclusive prefix inside my row
+	const uint32_t nx = c[0] + c[5], xs = (s01 & 0xffffu) + (s45 >> 16);   // mine / inclusive prefix inside my row (LITE: inside the window)
 	uint32_t fmt = WF_PLAIN, xw = xs, xt = 0;
 	if (compact_out & 1) {
-		xw += dpp0<0x142, 0xa>(xw); xw += dpp0<0x143, 0xc>(xw);  // the row prefixes carried over the wave (row_bcast 15 / 31): two instructions, and the list below starts where it ends
+		if (!LITE) { xw += dpp0<0x142, 0xa>(xw); xw += dpp0<0x143, 0xc>(xw); }  // the row prefixes carried over the wave (row_bcast 15 / 31): two instructions, and the list below starts where it ends
 		xt = lane63(xw);
 		fmt = xt == 0 ? WF_C0 : (xt <= XCAP1 ? WF_C1 : (xt <= XCAP2 ? WF_C2 : WF_PLAIN));
 	}
@@ -292,6 +300,16 @@ template <bool FULL, int GPL_, typename P, bool LEAN = false> __device__ __force
 		RK0[jj] = (uint16_t)r;
 	}
 	const uint32_t lf = ln32 >> 4;                              // my leaf of the window
+	if (LITE) {
+		if (ln32 == 63u) {                                       // last lane of the window: the inclusive prefixes are the window's counts
+			LeafMeta m;
+			m.c[0] = (uint16_t)s01; m.c[1] = (uint16_t)(s01 >> 16); m.c[2] = (uint16_t)s23; m.c[3] = (uint16_t)(s23 >> 16);
+			m.c[4] = (uint16_t)s45; m.c[5] = (uint16_t)(s45 >> 16);
+			m.npre = (uint16_t)fmt; m.n = (uint16_t)nvalid;
+			newp.own[d.gl / WPL] = m;                              // one record per window, in the first quarter of own[]; k_meta_win turns them into prefixes
+			if (nvalid != 0) newp.xh[d.gl / WPL] = (uint8_t)fmt;
+		}
+	} else
 	if ((ln32 & 15u) == 15u && lf * (uint32_t)LEAF < nvalid) {  // last lane of a leaf that exists: the inclusive row prefixes are the leaf's counts
 		LeafMeta m;
 		m.c[0] = (uint16_t)s01; m.c[1] = (uint16_t)(s01 >> 16); m.c[2] = (uint16_t)s23; m.c[3] = (uint16_t)(s23 >> 16);
@@ -312,11 +330,12 @@ template <bool FULL, int GPL_, typename P, bool LEAN = false> __device__ __force
 #define RB2_MMW 4                            // waves (= windows) per block of k_merge
 #endif
 constexpr int MMW = RB2_MMW;
-template <bool STRIDE, typename P = uint64_t, bool LEAN = false> __global__ __launch_bounds__(64 * MMW) void k_merge(const Ctl *ctl, const LeafDesc *__restrict__ LD, PoolView oldp, PoolView newp,
+template <bool STRIDE, typename P = uint64_t, bool LEAN = false, bool LITE = false> __global__ __launch_bounds__(64 * MMW) void k_merge(const Ctl *ctl, const LeafDesc *__restrict__ LD, PoolView oldp, PoolView newp,
 		const P *__restrict__ INS_E, const uint8_t *__restrict__ INS_A, uint16_t *RKREL, int compact_out, int par)
 {
 	__shared__ __align__(16) uint64_t lds[MMW][MergeLds<GPL>::WORDS];
 	static_assert(!LEAN || !STRIDE, "the lean round is a dense round of one engine");
+	static_assert(!LITE || LEAN, "a window-directory round is a lean round");
 	const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
 	const int ln = lane_id();
 	// Compact windows only when the device itself knows that no string has a non-empty interval any more (ctl->ne of this round: once zero
@@ -331,8 +350,8 @@ template <bool STRIDE, typename P = uint64_t, bool LEAN = false> __global__ __la
 	LeafDesc d = LD[gw];
 	const uint64_t nwin = ctl->wf0[NR];
 	for (; gw < nwin; gw += (uint64_t)gridDim.x * MMW, d = LD[gw < nwin ? gw : 0]) {
-		if ((d.nvalid & 0x3fffu) == WIN) merge_window<true, GPL, P, LEAN>(d, lds[wv], ln, oldp, newp, INS_E, INS_A, RKREL, compact_out, (unsigned long long*)ctl->wfmt);
-		else merge_window<false, GPL, P, LEAN>(d, lds[wv], ln, oldp, newp, INS_E, INS_A, RKREL, compact_out, (unsigned long long*)ctl->wfmt);
+		if ((d.nvalid & 0x3fffu) == WIN) merge_window<true, GPL, P, LEAN, LITE>(d, lds[wv], ln, oldp, newp, INS_E, INS_A, RKREL, compact_out, (unsigned long long*)ctl->wfmt);
+		else merge_window<false, GPL, P, LEAN, LITE>(d, lds[wv], ln, oldp, newp, INS_E, INS_A, RKREL, compact_out, (unsigned long long*)ctl->wfmt);
 		if (!STRIDE) return;                                    // (one GPU: the grid covers every window; no loop, no extra registers)
 		if (gw + (uint64_t)gridDim.x * MMW < nwin) { __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront"); __builtin_amdgcn_wave_barrier(); }   // the wave's LDS arrays are reused
 	}

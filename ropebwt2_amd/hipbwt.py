@@ -102,6 +102,7 @@ def load_hip_lib():
         "rb2_hip_lean_stats": (None, [vp, vp]),
         "rb2_hip_lean_count_stats": (None, [vp, vp]),
         "rb2_hip_lean_fork_stats": (None, [vp, vp]),
+        "rb2_hip_lean_dir_stats": (None, [vp, vp]),
         "rb2_hip_window_stats": (None, [vp, vp]),
         "rb2_hip_host_register": (C.c_int, [vp, C.c_int64]),
         "rb2_hip_host_unregister": (C.c_int, [vp]),
@@ -162,7 +163,7 @@ ABI_SYMBOLS = [
     "rb2_hip_unpack", "rb2_hip_unpack_dev", "rb2_hip_merge",
     "rb2_hip_string_graph", "rb2_hip_string_graph_dev", "rb2_hip_graph_clean", "rb2_hip_graph_clean_dev",
     "rb2_hip_num_subropes", "rb2_hip_memcpy", "rb2_hip_use_stream",
-    "rb2_hip_dev_free", "rb2_hip_synth_reads", "rb2_hip_synth_reads_cov", "rb2_hip_synth_reads_skew", "rb2_hip_sync", "rb2_hip_sparse_stats", "rb2_hip_layout_stats", "rb2_hip_rewind_stats", "rb2_hip_steady_stats", "rb2_hip_lean_stats", "rb2_hip_lean_count_stats", "rb2_hip_lean_fork_stats", "rb2_hip_window_stats", "rb2_hip_host_register", "rb2_hip_host_unregister", "rb2_hip_profile",
+    "rb2_hip_dev_free", "rb2_hip_synth_reads", "rb2_hip_synth_reads_cov", "rb2_hip_synth_reads_skew", "rb2_hip_sync", "rb2_hip_sparse_stats", "rb2_hip_layout_stats", "rb2_hip_rewind_stats", "rb2_hip_steady_stats", "rb2_hip_lean_stats", "rb2_hip_lean_count_stats", "rb2_hip_lean_fork_stats", "rb2_hip_lean_dir_stats", "rb2_hip_window_stats", "rb2_hip_host_register", "rb2_hip_host_unregister", "rb2_hip_profile",
     "rb2_hip_profile_get", "rb2_hip_kernel_name", "rb2_hip_layout",
     "rb2_hip_multi_create", "rb2_hip_multi_unique_id", "rb2_hip_multi_create_rank", "rb2_hip_multi_destroy", "rb2_hip_default_owners",
     "rb2_hip_multi_nranks", "rb2_hip_multi_transport", "rb2_hip_multi_nlocal", "rb2_hip_multi_engine", "rb2_hip_multi_insert_multi", "rb2_hip_multi_insert_multi_dev",
@@ -1009,6 +1010,13 @@ class HipBwt:
         a = np.zeros(2, np.int64)
         self.L.rb2_hip_lean_fork_stats(self.h, a.ctypes.data)
         return {"forked": int(a[0]), "on": int(a[1])}
+
+    def lean_dir_stats(self):
+        """the window directory (rb2_hip_lean_dir_stats): lean rounds that kept the rank directory of the side they wrote per window since create /
+        the switch (RB2_LEAN_DIR, default 1) / the lean rounds that were allowed to write compact windows, whatever the switch says"""
+        a = np.zeros(3, np.int64)
+        self.L.rb2_hip_lean_dir_stats(self.h, a.ctypes.data)
+        return {"rounds": int(a[0]), "on": int(a[1]), "lean_compact": int(a[2])}
 
     def window_stats(self):
         a = np.zeros(6, np.int64)
