@@ -22,6 +22,7 @@
 #include "rb2_unpack.h"
 #include "rb2_graph.h"
 #include "rb2_merge_plan.h"
+#include "rb2_round_plan.h"
 #include "rb2_fmd_load.h"
 #include "rb2_delete.h"
 #include "rb2_fmd_save.h"
@@ -192,6 +193,53 @@ struct Pool {
 struct ProfRec { int k; hipEvent_t a, b; int64_t units; int round; };
 constexpr uint64_t POS32_LIMIT = (1ull << 32) - (1ull << 24);   // narrow position storage only while every position stays below this
 
+// The environment switches of a handle, read once when it is created (read_knobs).  RoundKnobs (rb2_round_plan.h): those that decide a round's form.
+struct Knobs : RoundKnobs {
+	// in-place rounds: the prefix over the superblock totals (k_sbscan*) is needed by the NEXT round's descent only (k_advance takes its ranks
+	// from before the merge: RKOLD), so it rides in blocks of their own of the launches that follow the merge anyway (k_advance; k_sym / k_split)
+	int dir_ride = 1;                   // RB2_DIR_RIDE=0: two launches of its own behind k_merge_leaf, as in rounds 2-5
+	int ts_blocks = TSB;                // RB2_TS_BLOCKS=1: the single-launch counting tail on one block, as in rounds 4-5 (A/B)
+	int ts_fold = SCHUNK;               // RB2_TS_FOLD (tests): up to this many chunks of string tiles k_tscan3 scans the chunk totals itself; 0 = always a k_tscan2 launch
+	int lazy_verdict = 1;               // RB2_LAZY_VERDICT=0: an event and a wait per in-place round, as in rounds 2-5
+	int run_ahead = 3;                  // RB2_RUN_AHEAD: in-place rounds are queued at most this many ahead of what the device reports done (mb_h->progress): a re-spread asked
+	                                    // for by round r takes place this many rounds late at worst
+	int verdict_poll = 1;               // RB2_VERDICT_POLL=0 (tests): the host does not poll the verdict word while it queues rounds -- it learns of a void round only when it
+	                                    // drains the stream (a re-layout, a widening, the end of the batch), so a void round is taken back from behind every round queued since
+	int steady_ahead = 3;               // RB2_STEADY_AHEAD: until the report says so (or round STEADY_BOUND_ROUNDS of the batch), an insert that is waited for queues at most this many rounds ahead of the last round reported; 0: no bound
+	double sp_lambda = 0.6;             // RB2_SPARSE_LAMBDA: go sparse when (strings per round) / (leaves of the index) falls below this; 0: never leave the dense layout
+	int sp_head = 8;                    // RB2_SPARSE_HEAD: dense rounds at the start of a batch while the index is sparse (see insert_dev)
+	int sp_maxpen = 6;                  // RB2_SPARSE_MAXPEN: at most 64 dense rounds between two attempts (a failed attempt costs about four dense rounds); tests: 0 = retry after every dense fallback round
+	int leaf_pipe = 8192;               // RB2_LEAF_PIPE: in-place rounds use the software-pipelined k_merge_leaf_pipe with at most this many workgroups (0: one wave per four work
+	                                    // orders, k_merge_leaf).  1 M inserts per round: 232 us with k_merge_leaf, 259 / 228 / 212 / 207 / 212 us with 1024 / 1536 / 4096 / 8192 / 16384
+	int compact_stats = 0;              // RB2_COMPACT_STATS=1: k_merge counts the windows it writes per format (rb2_hip_window_stats)
+	int lazy_insert = 1;                // RB2_HIP_LAZY_INSERT=0 / rb2_hip_set_lazy(h, 0): every insert returns only when the device is done
+	int timeline = 0;                   // RB2_HIP_TIMELINE=1: host timestamps of the phases of a host-buffer insert on stderr (changes nothing else)
+	int trace = 0;                      // RB2_HIP_TRACE=1: per-round kernel times + merge path statistics on stderr (turns profiling on)
+};
+enum KnobClamp { KNOB_ANY, KNOB_BOOL, KNOB_RANGE };   // the value as it is; != 0; clamped to [lo, hi]
+struct KnobRow { const char *name; int Knobs::*field; KnobClamp clamp = KNOB_ANY; int lo = 0, hi = 0; };
+const KnobRow KNOB_TABLE[] = {                        // (the defaults are the member initialisers; ts_max: TS_MAX)
+	{ "RB2_HIP_DEBUG", &Knobs::debug }, { "RB2_HIP_TRACE", &Knobs::trace }, { "RB2_HIP_TIMELINE", &Knobs::timeline }, { "RB2_HIP_LAZY_INSERT", &Knobs::lazy_insert },
+	{ "RB2_SPARSE_HEAD", &Knobs::sp_head }, { "RB2_SPARSE_MAXPEN", &Knobs::sp_maxpen }, { "RB2_LEAF_PIPE", &Knobs::leaf_pipe }, { "RB2_DIR_RIDE", &Knobs::dir_ride },
+	{ "RB2_COMPACT", &Knobs::compact_ok }, { "RB2_COMPACT_STATS", &Knobs::compact_stats }, { "RB2_LEAN_DIR", &Knobs::lean_dir }, { "RB2_TS_BLOCKS", &Knobs::ts_blocks },
+	{ "RB2_LAZY_VERDICT", &Knobs::lazy_verdict }, { "RB2_VERDICT_POLL", &Knobs::verdict_poll },
+	{ "RB2_STEADY", &Knobs::steady_on, KNOB_BOOL }, { "RB2_LEAN_VERIFY", &Knobs::lean_verify, KNOB_BOOL }, { "RB2_LEAN_FORK", &Knobs::lean_fork, KNOB_BOOL },
+	{ "RB2_TS_MAX", &Knobs::ts_max, KNOB_RANGE, 0, (int)TS_MAX }, { "RB2_TS_FOLD", &Knobs::ts_fold, KNOB_RANGE, 0, (int)SCHUNK }, { "RB2_STEADY_LEAN", &Knobs::lean, KNOB_RANGE, 0, 2 },
+	{ "RB2_RUN_AHEAD", &Knobs::run_ahead, KNOB_RANGE, 1, INT_MAX }, { "RB2_LEAN_AUDIT", &Knobs::lean_audit, KNOB_RANGE, 0, INT_MAX }, { "RB2_STEADY_AHEAD", &Knobs::steady_ahead, KNOB_RANGE, 0, INT_MAX },
+};
+Knobs read_knobs()
+{
+	Knobs k;
+	k.ts_max = TS_MAX;
+	for (const KnobRow &row : KNOB_TABLE) if (const char *e = getenv(row.name)) {
+		const int v = atoi(e);
+		k.*row.field = row.clamp == KNOB_BOOL ? (v != 0) : row.clamp == KNOB_RANGE ? std::max(row.lo, std::min(row.hi, v)) : v;
+	}
+	if (const char *e = getenv("RB2_SPARSE_LAMBDA")) k.sp_lambda = atof(e);
+	if (!k.steady_on) k.lean = 0;                       // (RB2_STEADY=0 switches the lean rounds off as well)
+	return k;
+}
+
 } // namespace
 
 struct rb2_hip_s {
@@ -201,48 +249,29 @@ struct rb2_hip_s {
 	int side = 0;                       // descriptor parity: ctl->rope[side] / ctl->seg[side] describe the current BWT (flips every round)
 	int pside = 0;                      // pool that physically holds it (flips with `side` in dense rounds, stays in sparse ones)
 	bool sparse = false;                // the pool is in the sparse layout (leaves with slack, in-place rounds)
-	double sp_lambda = 0.6;             // go sparse when (strings per round) / (leaves of the index) falls below this
+	Knobs k;                            // the environment switches (read_knobs)
 	int sp_backoff = 0, sp_penalty = 0; // after a void sparse round: dense rounds to run before trying again / its growth
-	int sp_head = 8;                    // dense rounds at the start of a batch while the index is sparse (see insert_dev)
-	int sp_maxpen = 6;                  // at most 64 dense rounds between two attempts (a failed attempt costs about four dense rounds)
-	int leaf_pipe = 8192;               // in-place rounds use the software-pipelined k_merge_leaf_pipe with at most this many workgroups (RB2_LEAF_PIPE; 0: one wave per
-	                                    // four work orders, k_merge_leaf).  1 M inserts per round: 232 us with k_merge_leaf, 259 / 228 / 212 / 207 / 212 us with 1024 / 1536 / 4096 / 8192 / 16384
 	Mailbox *mb_h = nullptr;            // pinned: what the kernels report to the host without a synchronisation (rb2_device.h) ...
 	Mailbox *mb_d = nullptr;            // ... its device address
 	uint64_t layout_epoch = 0;          // counts the re-layouts: what k_setup derived from the piece descriptors before one is stale after it
 	hipEvent_t ev_flag = nullptr;
-	// in-place rounds: the prefix over the superblock totals (k_sbscan*) is needed by the NEXT round's descent only (k_advance takes its ranks
-	// from before the merge: RKOLD), so it rides in blocks of their own of the launches that follow the merge anyway (k_advance; k_sym / k_split)
-	int dir_ride = 1;                   // RB2_DIR_RIDE=0: two launches of its own behind k_merge_leaf, as in rounds 2-5
-	int ts_blocks = TSB;                // RB2_TS_BLOCKS=1: the single-launch counting tail on one block, as in rounds 4-5 (A/B)
 	// in-place rounds of one engine are queued without waiting for their verdict (a void round is sticky on the device: rb2_kernels.h k_part_sparse);
 	// spec_rounds = in-place rounds queued since the host last looked with the stream drained (verdict_check)
-	int lazy_verdict = 1;               // RB2_LAZY_VERDICT=0: an event and a wait per in-place round, as in rounds 2-5
 	uint64_t spec_rounds = 0;
-	int run_ahead = 3;                  // ... and at most this many in-place rounds ahead of what the device reports done (mb_h->progress): a re-spread asked for by round r takes place this
-	                                    // many rounds late at worst (RB2_RUN_AHEAD)
-	int verdict_poll = 1;               // RB2_VERDICT_POLL=0 (tests): the host does not poll the verdict word while it queues rounds -- it learns of a void round only when it
-	                                    // drains the stream (a re-layout, a widening, the end of the batch), so a void round is taken back from behind every round queued since
 	// rounds of one-member groups ("the steady round"): once the device has reported a round in which every interval was empty and k_sym placed every
 	// tile itself (Mailbox::steady), the host knows every interval empty and the dense rounds of one engine launch no k_prep<AE> for the rest of the batch
-	int steady_on = 1;                  // RB2_STEADY=0: the report is read and the bound below holds, but k_prep<AE> is launched as before
-	int steady_ahead = 3;               // RB2_STEADY_AHEAD: until the report says so (or round STEADY_BOUND_ROUNDS of the batch), an insert that is waited for queues at most this many rounds ahead of the last round reported; 0: no bound
 	bool steady_launched = false;       // a round of this batch relied on the report: batch_end looks at Ctl::steady_bad
 	int64_t n_prep_skipped = 0, steady_seen = -1, steady_used = -1;   // rb2_hip_steady_stats
 	// ... and run "lean" ("the lean round"): k_sym writes no INS_E / INS_A, k_part and k_merge read L and A in their place
-	int lean = 2;                       // RB2_STEADY_LEAN: 0 = off, 1 = on, 2 = on and the round is counted from A alone where it can be (k_count_lean; a larger value means 2); RB2_STEADY=0 switches it off as well
 	int64_t n_lean_rounds = 0;          // dense rounds run lean (rb2_hip_lean_stats)
 	// stage 2 ("the lean count"): nothing looks at L in a round counted by k_count_lean, so every lean_audit-th lean round of a batch is counted by
 	// k_sym as in stage 1 -- a group of two never splits again: the audit round meets it and setup_body reports it (Ctl::steady_bad)
-	int lean_audit = 8;                 // RB2_LEAN_AUDIT: 0 = never
 	bool lean2_met = false;             // some lean counting phase of this handle had the three-launch tail: stage 2 took it (or audited it).  Until then the handle's lean rounds
 	                                    // are stage-1 rounds (k_tscan_setup) and rb2_hip_lean_stats says so
-	int lean_verify = 0;                // RB2_LEAN_VERIFY=1 (tests): k_sym + k_tscan1 of the round run as well, into buffers of their own; k_lean_compare counts the words that differ (batch_end: fatal)
 	int64_t n_lean_counted = 0, n_lean_audit = 0, n_lean_verified = 0, n_lean_mismatch = 0;   // rb2_hip_lean_count_stats
 	DevBuf<TileRec> trec_v; DevBuf<ChunkPart> cpart_v;   // (RB2_LEAN_VERIFY)
 	// the forked round: the counting tail of a round counted by k_count_lean -- k_count_lean, the tile scans, k_tfix with setup_body -- runs on a side stream
 	// beside k_part / k_merge / the directory of the same round; k_part<.., FORK> lays out the new side itself, k_advance waits for both
-	int lean_fork = 1;                  // RB2_LEAN_FORK=0: one stream, the launches as they were
 	hipStream_t st_count = nullptr;     // the side stream (created with the handle, never a caller's: rb2_hip_use_stream leaves it alone)
 	hipEvent_t ev_fork = nullptr, ev_join = nullptr;   // st_count waits for ev_fork (recorded on st), st waits for ev_join (recorded on st_count)
 	bool fork_open = false;             // ev_join is recorded and st has not been made to wait for it yet: the side stream may hold work that a drain of st does not cover (fork_join)
@@ -250,11 +279,9 @@ struct rb2_hip_s {
 	int64_t n_rewind = 0, n_rewound = 0, rewind_max = 0, n_rewind_even = 0;   // void rounds taken back from behind queued rounds: how many, rounds taken back, deepest, of even depth (rb2_hip_rewind_stats)
 	unsigned long long *pair_d = nullptr, *pair_h = nullptr;   // k_pair_hist: what the batch just uploaded adds to the count matrix (device, pinned host)
 	bool pair_valid = false;
-	bool pending_end = false;           // rb2_hip_insert_multi returned with the batch queued but not awaited (finish_pending); lazy_insert: it may
+	bool pending_end = false;           // rb2_hip_insert_multi returned with the batch queued but not awaited (finish_pending); Knobs::lazy_insert: it may
 	double tl_base = 0, tl_last = 0;
 	int64_t n_grow_in_rounds = 0;       // device buffers that had to grow while the rounds of a dense batch were being queued (should stay 0)
-	int timeline = 0;                   // RB2_HIP_TIMELINE=1: host timestamps of the phases of a host-buffer insert on stderr (changes nothing else)
-	int lazy_insert = 1;                // RB2_HIP_LAZY_INSERT=0 / rb2_hip_set_lazy(h, 0): every insert returns only when the device is done
 	int64_t n_relayout = 0, n_void = 0, n_sparse_rounds = 0;
 	Ctl *ctl = nullptr;                 // device
 	RopeDesc h_rope[NR];                // host mirror of ctl->rope[side] (sub-ropes)
@@ -293,7 +320,6 @@ struct rb2_hip_s {
 	std::vector<ProfRec> recs;
 	std::vector<hipEvent_t> evpool;
 	int64_t p_launch[RB2_K_COUNT]; double p_ms[RB2_K_COUNT]; int64_t p_units[RB2_K_COUNT];
-	int debug = 0;
 	int cur_round = -1;
 	uint64_t *gcnt = nullptr;           // device: NR x 6 count matrix of the current round
 	bool own_stream = true;
@@ -304,19 +330,13 @@ struct rb2_hip_s {
 	uint8_t *xhost[2] = {nullptr, nullptr}; uint64_t *xtot[2] = {nullptr, nullptr}; hipEvent_t xev[2] = {nullptr, nullptr};   // pinned double buffer
 	int64_t fmds_size = -1;             // rb2_hip_save_fmd: the size of the image of the rows as they are (-1: not known; dropped by index_rows_change, i.e. with the
 	                                    // sampled suffix array: by whatever changes the rows, and by rb2_hip_ssa_build / rb2_hip_ssa_drop, which costs one more sizing pass)
-	int compact_ok = 1;                 // RB2_COMPACT=0: dense rounds always write plain (three-plane) windows
-	int compact_stats = 0;              // RB2_COMPACT_STATS=1: k_merge counts the windows it writes per format (rb2_hip_window_stats)
 	int64_t n_compact_rounds = 0;       // dense rounds that were allowed to write compact windows
 	int64_t n_plain_handover = 0;       // dense rounds that wrote plain windows over compact ones because a re-layout was pending (plain_next): rb2_hip_layout_stats out[7]
 	bool pool_compact = false;          // the last dense round wrote compact windows (only k_merge may read the pool now)
 	// the window directory: a lean round whose windows may be written compact keeps the rank directory of the new side per window (k_merge<.., LITE>, k_meta_win, k_advance<.., LITE>)
-	int lean_dir = 1;                   // RB2_LEAN_DIR=0: every round writes the per-leaf directory, the launches as they were
 	int64_t n_lean_dir = 0, n_lean_compact = 0;   // rounds run with the window directory; lean rounds that were allowed to write compact windows, whatever the switch says (rb2_hip_lean_dir_stats)
 	bool pool_win_dir = false;          // the last dense round left a window directory: own[] / meta[] of the pool hold no per-leaf entries (set and cleared with pool_compact)
 	bool plain_next = false;            // choose_layout wants to leave the dense layout: this round writes plain windows
-	int ts_fold = SCHUNK;               // up to this many chunks of string tiles k_tscan3 scans the chunk totals itself (no k_tscan2 launch); RB2_TS_FOLD lowers it (tests)
-	int ts_max = TS_MAX;                // batches with fewer string tiles run their counting tail in one single-block launch (k_tscan_setup); RB2_TS_MAX lowers it (tests)
-	int trace = 0;                      // RB2_HIP_TRACE=1: per-round kernel times + merge path statistics on stderr
 	int64_t del_stats[5] = {0, 0, 0, 0, 0};   // the last rb2_hip_delete_strings: rows removed, source groups that held rows, those that needed the compress, source leaves, destination leaves
 };
 
@@ -338,7 +358,7 @@ struct Scope {          // times everything enqueued between construction and de
 		HIPCHK(hipEventRecord(r.a, s));
 	}
 	~Scope() {
-		if (h->debug) { hipError_t e = hipStreamSynchronize(s); if (e != hipSuccess) { rb2_fatal("[rb2_hip] kernel group %s failed: %s\n", rb2_hip_kernel_name(k), hipGetErrorString(e)); } }
+		if (h->k.debug) { hipError_t e = hipStreamSynchronize(s); if (e != hipSuccess) { rb2_fatal("[rb2_hip] kernel group %s failed: %s\n", rb2_hip_kernel_name(k), hipGetErrorString(e)); } }
 		if (!on) return;
 		HIPCHK(hipEventRecord(r.b, s));
 		h->recs.push_back(r);
@@ -360,7 +380,7 @@ void drain_profile(rb2_hip_t *h)
 		float ms = 0;
 		HIPCHK(hipEventElapsedTime(&ms, r.a, r.b));
 		h->p_launch[r.k] += 1; h->p_ms[r.k] += ms; h->p_units[r.k] += r.units;
-		if (h->trace && r.round >= 0 && (r.round < 20 || r.round % 10 == 0)) fprintf(stderr, "[rb2_hip] round %3d %-10s %8.3f ms\n", r.round, rb2_hip_kernel_name(r.k), ms);
+		if (h->k.trace && r.round >= 0 && (r.round < 20 || r.round % 10 == 0)) fprintf(stderr, "[rb2_hip] round %3d %-10s %8.3f ms\n", r.round, rb2_hip_kernel_name(r.k), ms);
 		h->evpool.push_back(r.a); h->evpool.push_back(r.b);
 	}
 	h->recs.clear();
@@ -420,19 +440,15 @@ struct BatchState {
 	bool known_ae = false;                  // the host can tell that every interval of the batch is empty: input order, or an empty index
 	bool known_ae0 = false;                 // ... from the start of the batch (what a rollback falls back to: insert_dev)
 	bool known_steady = false;              // the device has reported a round of fused tiles only (Mailbox::steady): every later round of the batch is one (insert_dev; never set on a rank)
-	uint64_t counted = (uint64_t)-1;        // round whose counting phase (round_counts) is already queued
-	int lean = 0;                           // ... and the last counting phase queued was a lean one (decided at its k_sym launch; round_merge follows THIS, never known_steady:
-	                                        // a round counted before the host heard the report holds INS_E / INS_A and is merged from them)
-	                                        // 2: counted by k_count_lean -- no head flags in A, k_advance takes every string for a head
-	bool lean_audit = false;                // ... lean == 1 because the round is an audit round of stage 2
-	bool forked = false;                    // ... lean == 2 and its counting tail was queued on the side stream (round_counts); cleared wherever lean is (drop_lean)
+	Counted c;                              // the last counting phase queued (round_counts): its round, its form, the k_setup that rode on it (rb2_round_plan.h)
 	uint64_t n_lean2 = 0;                   // counting phases of this batch that stage 2 could take, audit rounds included (every lean_audit-th is one)
-	uint64_t setup_round = (uint64_t)-1;    // round whose k_setup ran inside its counting phase (k_tscan_setup) ...
-	bool setup_sparse = false; uint64_t setup_epoch = 0;   // ... for this layout, at this layout epoch (a re-layout in between: k_setup runs again)
 };
-inline void drop_lean(rb2_hip_t *h, BatchState &B) { B.lean = 0; B.forked = false; fork_join(h); }   // forget how the last counting phase was queued (it is counted again, or merged)
-inline void mark_setup(const rb2_hip_t *h, BatchState &B, uint64_t r) { B.setup_round = r; B.setup_sparse = h->sparse; B.setup_epoch = h->layout_epoch; }   // k_setup of round r is queued
-inline bool setup_done(const rb2_hip_t *h, const BatchState &B, uint64_t r, bool sparse) { return B.setup_round == r && B.setup_sparse == sparse && B.setup_epoch == h->layout_epoch; }   // ... and still stands (no re-layout since)
+// forgetting how the last counting phase was queued leaves nothing unjoined on the side stream (a Lean2 count may have been forked)
+inline void forget_form(rb2_hip_t *h, BatchState &B) { B.c.forget_form(); fork_join(h); }     // it is merged, or counted again
+inline void forget_count(rb2_hip_t *h, BatchState &B) { B.c.forget_count(); fork_join(h); }   // ... and a count queued ahead does not stand; its k_setup does
+inline void forget_all(rb2_hip_t *h, BatchState &B) { B.c.forget_all(); fork_join(h); }       // ... nor does that
+inline void mark_setup(const rb2_hip_t *h, BatchState &B, uint64_t r) { B.c.mark_setup(r, h->sparse, h->layout_epoch); }   // k_setup of round r is queued
+inline bool setup_done(const rb2_hip_t *h, const BatchState &B, uint64_t r, bool sparse) { return B.c.setup_done(r, sparse, h->layout_epoch); }   // ... and still stands (no re-layout since)
 
 // per-string arrays + tile tables for batches of up to m strings
 void ensure_strings(rb2_hip_t *h, uint64_t m)
@@ -442,7 +458,7 @@ void ensure_strings(rb2_hip_t *h, uint64_t m)
 	h->A[0].ensure(m); h->A[1].ensure(m); h->INS_A.ensure(m); h->START.ensure(m + 1);
 	const uint64_t nst = cdiv(m, STILE) + NR;
 	h->trec.ensure(nst + 8 * XCD_RUN + 8); h->tsc.ensure(nst + 8 * XCD_RUN + 8); h->tfix.ensure(nst + 8 * XCD_RUN + 8); h->cpart.ensure(cdiv(nst, SCHUNK) + 1);
-	if (h->lean_verify) { h->trec_v.ensure(nst + 8 * XCD_RUN + 8); h->cpart_v.ensure(cdiv(nst, SCHUNK) + 1); }
+	if (h->k.lean_verify) { h->trec_v.ensure(nst + 8 * XCD_RUN + 8); h->cpart_v.ensure(cdiv(nst, SCHUNK) + 1); }
 }
 
 // the string arrays of the round as the round kernels see them: side B.cur this round, side B.cur ^ 1 the next, positions stored as P
@@ -591,20 +607,20 @@ uint32_t maybe_widen(rb2_hip_t *h, BatchState &B, uint64_t r)
 		hipLaunchKernelGGL(k_widen, dim3(cdiv(B.m, 256)), dim3(256), 0, st, (const uint32_t*)h->INS_E.p, a->p, B.m);
 	}
 	h->pos32 = false;
-	B.counted = (uint64_t)-1; drop_lean(h, B);                 // a counting phase queued ahead wrote INS_E in the narrow form (k_sym's fused k_prep): count again (INS_E above is scratch, never data)
-	if (h->trace) fprintf(stderr, "[rb2_hip] round %llu: positions widened to 64 bits (largest piece known: %llu symbols, %llu rounds ago)\n", (unsigned long long)r, (unsigned long long)known, (unsigned long long)since);
+	forget_count(h, B);                                        // a counting phase queued ahead wrote INS_E in the narrow form (k_sym's fused k_prep): count again (INS_E above is scratch, never data)
+	if (h->k.trace) fprintf(stderr, "[rb2_hip] round %llu: positions widened to 64 bits (largest piece known: %llu symbols, %llu rounds ago)\n", (unsigned long long)r, (unsigned long long)known, (unsigned long long)since);
 	return 0;
 }
 
 static inline void tl_slow(rb2_hip_t *h, const char *what)    // RB2_HIP_TIMELINE=2: which host call of a round took more than half a millisecond
 {
-	if (h->timeline < 2) return;
+	if (h->k.timeline < 2) return;
 	const double now = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count();
 	if (h->tl_last != 0 && now - h->tl_last > 0.5) fprintf(stderr, "[rb2_hip] t = %8.3f ms  round %d: %.3f ms on the host up to and including %s\n", now - h->tl_base, h->cur_round, now - h->tl_last, what);
 	h->tl_last = now;
 }
 // in-place rounds queued with spec on one engine are not waited for: the host polls their verdict (verdict_check) -- unless RB2_LAZY_VERDICT=0
-inline bool lazy_round(const rb2_hip_t *h, bool spec) { return spec && h->lazy_verdict && h->nranks == 1; }
+inline bool lazy_round(const rb2_hip_t *h, bool spec) { return spec && h->k.lazy_verdict && h->nranks == 1; }
 // The sticky-void rule: k_setup clears ctl->overflow, so it is never queued behind in-place rounds whose verdict the host has not seen (it would
 // wipe out a void round).  `what` (of round r) may run k_setup.
 void require_verdicts_seen(const rb2_hip_t *h, uint64_t r, const char *what)
@@ -615,27 +631,20 @@ void require_verdicts_seen(const rb2_hip_t *h, uint64_t r, const char *what)
 // allow_lean = false: a round counted lean that cannot be merged densely after all is counted again with INS_E / INS_A (round_merge_any)
 void round_counts(rb2_hip_t *h, BatchState &B, uint64_t r, bool spec = false, bool allow_lean = true)
 {
-	fork_join(h); B.forked = false;                             // (a counting phase that is queued again: behind whatever the one before left on the side stream)
+	fork_join(h);                                               // (a counting phase that is queued again: behind whatever the one before left on the side stream)
 	hipStream_t st = h->st;
 	const int sd = h->side;
 	const int64_t units = (int64_t)B.m;
 	h->cur_round = (int)r;
 	const TileRecs trs = { (uint32_t*)h->trec.p, (uint32_t)(h->trec.cap & ~(size_t)3) };   // (20 columns of cap words in the 80-byte records' space)
 	tl_slow(h, "start of round_counts");
-	// lean: the dense one-engine launch k_sym<false, P, false> of a batch the host knows steady (the in-place layout's k_part_sparse / k_merge_leaf need INS_E / INS_A)
-	B.lean = (allow_lean && !spec && h->nranks == 1 && !h->sparse && B.known_steady && h->steady_on) ? h->lean : 0;
-	const bool one_launch_tail = B.nst_ub < (unsigned)h->ts_max;  // few tiles (long reads): the counting tail is one launch (k_tscan_setup)
-	// stage 2: k_count_lean in the place of k_sym and k_tscan1 -- the three-launch tail only (k_tscan_setup reads the records of a k_sym launch), and not in an audit round
-	B.lean_audit = false;
-	if (B.lean == 2 && one_launch_tail) B.lean = 1;
-	if (B.lean == 2) h->lean2_met = true;
-	if (B.lean == 2 && h->lean_audit > 0 && ++B.n_lean2 % (uint64_t)h->lean_audit == 0) { B.lean = 1; B.lean_audit = true; }
+	const CountPlan cp = count_plan(h->k, CountFacts{ spec, allow_lean, h->nranks, h->sparse, B.known_steady, h->own_stream, B.nst_ub, B.n_lean2 });
+	B.c.set(cp); B.n_lean2 = cp.n_lean2;
+	if (cp.met_stage2) h->lean2_met = true;
 	if (!spec) require_verdicts_seen(h, r, "counting phase without spec of round");   // (its k_setup runs whatever ctl->overflow says)
 	// the forked round: the whole counting tail goes to the side stream, behind everything queued on h->st so far (the k_advance of the round in front wrote A and
-	// read the tile records); round_merge queues k_part<.., FORK>, k_merge and the directory on h->st beside it and joins in front of k_advance.  Never from a
-	// caller's stream; not with RB2_LEAN_VERIFY (k_sym<LEAN> writes head flags into A, which k_merge reads) and not with RB2_HIP_DEBUG (a drain per group)
-	B.forked = B.lean == 2 && h->lean_fork && h->own_stream && !h->lean_verify && !h->debug;
-	if (B.forked) {
+	// read the tile records); round_merge queues k_part<.., FORK>, k_merge and the directory on h->st beside it and joins in front of k_advance
+	if (cp.forked) {
 	  HIPCHK(hipEventRecord(h->ev_fork, h->st));
 	  HIPCHK(hipStreamWaitEvent(h->st_count, h->ev_fork, 0));
 	  st = h->st_count;
@@ -645,48 +654,47 @@ void round_counts(rb2_hip_t *h, BatchState &B, uint64_t r, bool spec = false, bo
 	  sp.ctl = h->ctl; sp.pool = h->pool[h->pside].view(); sp.SPL = h->SPL.p; sp.spl_cap = split_cap(h); sp.epoch = h->split_epoch;
 	  sp.mb = h->mb_d; sp.nsplitb = 64;
 	  sp.round1 = (uint32_t)r;                                   // (the splits of round r - 1)
-	  sp.scan2 = (h->dir_ride && !one_launch_tail) ? sp.pool.sbbase : (SbBase*)nullptr;   // the chunk bases of the directory the k_advance launch in front of this one left half-built
+	  sp.scan2 = (h->k.dir_ride && !cp.one_launch_tail) ? sp.pool.sbbase : (SbBase*)nullptr;   // the chunk bases of the directory the k_advance launch in front of this one left half-built
 	                                                             // (in a block of this launch -- or, when the counting tail is one launch, of that one: see below)
 	}
-	SbBase *scan2_tail = (spec && h->dir_ride && one_launch_tail) ? h->pool[h->pside].view().sbbase : (SbBase*)nullptr;
+	SbBase *scan2_tail = (spec && h->k.dir_ride && cp.one_launch_tail) ? h->pool[h->pside].view().sbbase : (SbBase*)nullptr;
 	{ Scope sc(h, RB2_K_SYM, units, st);
 	  with_pos(h, B, [&](const auto &S) { using P = std::remove_pointer_t<decltype(S.L)>;
-	    if (spec) {
-	      hipLaunchKernelGGL((k_sym<false, P, true>), dim3((unsigned)rank_share(h, B.nst_ub) + sp.nsplitb + (sp.scan2 ? 1u : 0u)), dim3(256), 0, st, h->ctl, sd, (int)(r & 1), S, trs, sp);
-	    } else
-	    if (h->nranks > 1) hipLaunchKernelGGL((k_sym<true, P>), dim3(grid8((unsigned)rank_share(h, B.nst_ub))), dim3(256), 0, st, h->ctl, sd, (int)(r & 1), S, trs, sp);
-	    else if (B.lean == 2) {
+	    const dim3 pairs(grid8(cdiv(B.nst_ub, (unsigned)SYM_PAIR)));   // (one engine: a block takes SYM_PAIR tiles)
+	    switch (cp.form) {
+	    case CountForm::Spec: hipLaunchKernelGGL((k_sym<false, P, true>), dim3((unsigned)rank_share(h, B.nst_ub) + sp.nsplitb + (sp.scan2 ? 1u : 0u)), dim3(256), 0, st, h->ctl, sd, (int)(r & 1), S, trs, sp); break;
+	    case CountForm::Rank: hipLaunchKernelGGL((k_sym<true, P>), dim3(grid8((unsigned)rank_share(h, B.nst_ub))), dim3(256), 0, st, h->ctl, sd, (int)(r & 1), S, trs, sp); break;
+	    case CountForm::Lean2:
 	      hipLaunchKernelGGL(k_count_lean, dim3(B.nsc), dim3(SCHUNK), 0, st, h->ctl, sd, (const uint8_t*)S.A, trs, h->cpart.p);
-	      if (h->lean_verify) {                                    // (tests) the launches this one stands for, into buffers of their own, and the comparison
+	      if (h->k.lean_verify) {                                    // (tests) the launches this one stands for, into buffers of their own, and the comparison
 	        const TileRecs trv = { (uint32_t*)h->trec_v.p, (uint32_t)(h->trec_v.cap & ~(size_t)3) };
-	        hipLaunchKernelGGL((k_sym<false, P, false, true>), dim3(grid8(cdiv(B.nst_ub, (unsigned)SYM_PAIR))), dim3(256), 0, st, h->ctl, sd, (int)(r & 1), S, trv, sp);
+	        hipLaunchKernelGGL((k_sym<false, P, false, true>), pairs, dim3(256), 0, st, h->ctl, sd, (int)(r & 1), S, trv, sp);
 	        hipLaunchKernelGGL(k_tscan1, dim3(B.nsc), dim3(SCHUNK), 0, st, h->ctl, sd, trv, h->cpart_v.p);
 	        hipLaunchKernelGGL(k_lean_compare, dim3(std::max<unsigned>(1u, cdiv(B.nst_ub, 256))), dim3(256), 0, st, h->ctl, sd, trs, trv, (const ChunkPart*)h->cpart.p, (const ChunkPart*)h->cpart_v.p);
 	        ++h->n_lean_verified;
 	      }
-	    }
-	    else if (B.lean) hipLaunchKernelGGL((k_sym<false, P, false, true>), dim3(grid8(cdiv(B.nst_ub, (unsigned)SYM_PAIR))), dim3(256), 0, st, h->ctl, sd, (int)(r & 1), S, trs, sp);
-	    else hipLaunchKernelGGL((k_sym<false, P>), dim3(grid8(cdiv(B.nst_ub, (unsigned)SYM_PAIR))), dim3(256), 0, st, h->ctl, sd, (int)(r & 1), S, trs, sp); }); }   // (one engine: a block takes SYM_PAIR tiles)
+	      break;
+	    case CountForm::Lean1: hipLaunchKernelGGL((k_sym<false, P, false, true>), pairs, dim3(256), 0, st, h->ctl, sd, (int)(r & 1), S, trs, sp); break;
+	    case CountForm::Plain: hipLaunchKernelGGL((k_sym<false, P>), pairs, dim3(256), 0, st, h->ctl, sd, (int)(r & 1), S, trs, sp); break;
+	    } }); }
 	tl_slow(h, "k_sym");
 	if (spec && !lazy_round(h, spec)) HIPCHK(hipEventRecord(h->ev_flag, st));   // (the splits left the verdict in pinned memory)
-	if (one_launch_tail) {                                      // one launch instead of six, k_setup included (one GPU)
+	const int do_setup = h->nranks == 1;                        // one GPU: k_setup of the round rides on the counting tail (the local count matrix is the global one)
+	if (cp.one_launch_tail) {                                      // one launch instead of six, k_setup included
 	  Scope sc(h, RB2_K_TSCAN, units);
-	  const int do_setup = h->nranks == 1;
-	  const unsigned grid = (unsigned)std::max(1, std::min<int>(TSB, h->ts_blocks)) + (scan2_tail ? 7u : 0u);   // (+ one block per column of the chunk bases)
+	  const unsigned grid = (unsigned)std::max(1, std::min<int>(TSB, h->k.ts_blocks)) + (scan2_tail ? 7u : 0u);   // (+ one block per column of the chunk bases)
 	  hipLaunchKernelGGL((h->sparse ? k_tscan_setup<true> : k_tscan_setup<false>), dim3(grid), dim3(SCHUNK), 0, st, h->ctl, sd, (int)(r & 1), trs, h->tfix.p, h->gcnt, do_setup, (int)spec, (uint32_t)r, hmax_report(h), scan2_tail, steady_report(h));
-	  if (do_setup) mark_setup(h, B, r);
 	} else
 	{ Scope sc(h, RB2_K_TSCAN, units, st);
-	  if (B.lean != 2) hipLaunchKernelGGL(k_tscan1, dim3(B.nsc), dim3(SCHUNK), 0, st, h->ctl, sd, trs, h->cpart.p);   // (k_count_lean wrote the chunks' totals itself)
-	  if (B.nsc <= (unsigned)h->ts_fold) hipLaunchKernelGGL(k_tscan3<true>, dim3(B.nsc), dim3(SCHUNK), 0, st, h->ctl, sd, trs, h->cpart.p, h->tsc.p);   // (the scan over the chunks folded in)
+	  if (cp.form != CountForm::Lean2) hipLaunchKernelGGL(k_tscan1, dim3(B.nsc), dim3(SCHUNK), 0, st, h->ctl, sd, trs, h->cpart.p);   // (k_count_lean wrote the chunks' totals itself)
+	  if (B.nsc <= (unsigned)h->k.ts_fold) hipLaunchKernelGGL(k_tscan3<true>, dim3(B.nsc), dim3(SCHUNK), 0, st, h->ctl, sd, trs, h->cpart.p, h->tsc.p);   // (the scan over the chunks folded in)
 	  else {
 	    hipLaunchKernelGGL(k_tscan2, dim3(1), dim3(SCHUNK), 0, st, h->ctl, sd, h->cpart.p);
 	    hipLaunchKernelGGL(k_tscan3<false>, dim3(B.nsc), dim3(SCHUNK), 0, st, h->ctl, sd, trs, h->cpart.p, h->tsc.p);
 	  }
-	  const int do_setup = h->nranks == 1;                     // one GPU: k_setup of the round rides on block 0 of k_tfix (the local count matrix is the global one)
-	  hipLaunchKernelGGL((B.forked ? k_tfix_fork : k_tfix), dim3(std::max<unsigned>(1u, cdiv(B.nst_ub, 256))), dim3(256), 0, st, h->ctl, sd, (int)(r & 1), trs, h->tsc.p, h->tfix.p, h->gcnt, do_setup, (int)h->sparse, (uint32_t)r, hmax_report(h), (int)spec, steady_report(h));
-	  if (do_setup) mark_setup(h, B, r); }
-	if (B.forked) { HIPCHK(hipEventRecord(h->ev_join, h->st_count)); h->fork_open = true; ++h->n_lean_forked; }
+	  hipLaunchKernelGGL((cp.forked ? k_tfix_fork : k_tfix), dim3(std::max<unsigned>(1u, cdiv(B.nst_ub, 256))), dim3(256), 0, st, h->ctl, sd, (int)(r & 1), trs, h->tsc.p, h->tfix.p, h->gcnt, do_setup, (int)h->sparse, (uint32_t)r, hmax_report(h), (int)spec, steady_report(h)); }   // (k_setup on block 0)
+	if (do_setup) mark_setup(h, B, r);
+	if (cp.forked) { HIPCHK(hipEventRecord(h->ev_join, h->st_count)); h->fork_open = true; ++h->n_lean_forked; }
 	tl_slow(h, "tile scans");
 }
 
@@ -695,7 +703,7 @@ void round_counts(rb2_hip_t *h, BatchState &B, uint64_t r, bool spec = false, bo
 // the kernel would return for all of them (setup_body checks that no round behind a fused one is anything else: Ctl::steady_bad)
 template <bool SPARSE, class P> void launch_prep(rb2_hip_t *h, const BatchState &B, uint64_t r, const PoolView &oldp, const StrArrays<P> &S)
 {
-	if (!SPARSE && B.known_steady && h->steady_on && h->nranks == 1) { ++h->n_prep_skipped; h->steady_launched = true; return; }
+	if (!SPARSE && B.known_steady && h->k.steady_on && h->nranks == 1) { ++h->n_prep_skipped; h->steady_launched = true; return; }
 	Scope sc(h, RB2_K_PREP, (int64_t)B.m);
 	const int sd = h->side, par = (int)(r & 1), is_comp = h->so == RB2_SO_RCLO;
 	const unsigned tg = grid8((unsigned)rank_share(h, B.nst_ub));
@@ -723,9 +731,11 @@ template <bool SPARSE, class P> void launch_advance(rb2_hip_t *h, const BatchSta
 // phase 2: with the global count matrix in h->gcnt: layout, ranks, merge, directory, new intervals.
 // send == nullptr: strings go straight to the next-round arrays; else they are written as ShardRec.
 // Dense round: every piece is rewritten pool[pside] -> pool[pside ^ 1] (k_merge).
-// compact_out: the new windows may be written in the compact format (rb2_merge.h): only k_merge reads them again before the next rewrite
-void round_merge(rb2_hip_t *h, BatchState &B, uint64_t r, ShardRec *send, bool compact_out = false)
+// mp (merge_plan, rb2_round_plan.h): the forms of k_part / k_merge follow how the round was COUNTED -- a lean count left no INS_E / INS_A; compact_out: the new
+// windows may be written in the compact format (rb2_merge.h); lite: the window directory, for k_merge, the directory launch and k_advance together
+void round_merge(rb2_hip_t *h, BatchState &B, uint64_t r, ShardRec *send, const MergePlan mp)
 {
+	const bool lean = mp.lean, forked = mp.forked, compact_out = mp.compact_out, lite = mp.lite;
 	hipStream_t st = h->st;
 	const int sd = h->side;
 	const int64_t units = (int64_t)B.m;
@@ -737,28 +747,21 @@ void round_merge(rb2_hip_t *h, BatchState &B, uint64_t r, ShardRec *send, bool c
 	if (!setup_done(h, B, r, false))
 	{ Scope sc(h, RB2_K_TSCAN, 0);
 	  hipLaunchKernelGGL(k_setup<false>, dim3(1), dim3(64), 0, st, h->ctl, sd, h->gcnt, (int)(r & 1), (uint32_t)r, hmax_report(h), (int)(h->push[0] != nullptr), steady_report(h)); }
-	// the forms of k_part / k_merge follow how the round was COUNTED (B.lean, round_counts): a lean count left no INS_E / INS_A
-	const bool lean = B.lean != 0;
-	const bool forked = B.forked;
-	// the window directory: decided once, for k_merge, the directory launch and k_advance together (lean: one engine, dense layout, every interval empty)
-	const bool lite = lean && compact_out && h->lean_dir != 0;
-	if (forked && (B.lean != 2 || !setup_done(h, B, r, false) || !h->fork_open)) { rb2_fatal("[rb2_hip] internal: round %llu was forked and is not merged as the lean dense round it was counted as\n", (unsigned long long)r); }
+	if (forked && (!mp.stage2 || !setup_done(h, B, r, false) || !h->fork_open)) { rb2_fatal("[rb2_hip] internal: round %llu was forked and is not merged as the lean dense round it was counted as\n", (unsigned long long)r); }
 	if (lean && (h->nranks != 1 || h->sparse || !B.known_steady)) { rb2_fatal("[rb2_hip] internal: round %llu was counted lean and is not merged as a steady dense round\n", (unsigned long long)r); }
 	if (lean) ++h->n_lean_rounds;
-	if (B.lean == 2) ++h->n_lean_counted; else if (lean && B.lean_audit) ++h->n_lean_audit;
+	if (mp.stage2) ++h->n_lean_counted; else if (mp.audit) ++h->n_lean_audit;
 	with_pos(h, B, [&](const auto &S) { using P = std::remove_pointer_t<decltype(S.L)>;
 	launch_prep<false>(h, B, r, oldp, S);
 	tl_slow(h, "k_prep");
 	{ Scope sc(h, RB2_K_PART, units);
 	  const uint8_t *old_xh = h->pool_compact ? (const uint8_t*)oldp.xh : (const uint8_t*)nullptr;
-	  if (forked) hipLaunchKernelGGL((k_part<false, P, true, true>), dim3(cdiv(wg + NR, 255)), dim3(256), 0, st, h->ctl, sd, (const P*)S.L, h->LD.p, old_xh);   // (lays out the new side itself)
-	  else if (lean) hipLaunchKernelGGL((k_part<false, P, true>), dim3(cdiv(wg + NR, 255)), dim3(256), 0, st, h->ctl, sd, (const P*)S.L, h->LD.p, old_xh);
+	  if (lean) hipLaunchKernelGGL((forked ? k_part<false, P, true, true> : k_part<false, P, true>), dim3(cdiv(wg + NR, 255)), dim3(256), 0, st, h->ctl, sd, (const P*)S.L, h->LD.p, old_xh);   // (FORK: lays out the new side itself)
 	  else RB2_LAUNCH_STRIDE(h, (k_part<true, P>), (k_part<false, P>), dim3(cdiv(wg + NR, 255)), dim3(256), 0, st, h->ctl, sd, S.INS_E, h->LD.p, old_xh); }   // (the formats of the old windows: only a pool side the compact-capable merge wrote has any but plain)
 	tl_slow(h, "k_part");
 	{ Scope sc(h, RB2_K_MERGE, units);
-	  if (lite) hipLaunchKernelGGL((k_merge<false, P, true, true>), dim3(grid8(cdiv(wg, MMW))), dim3(64 * MMW), 0, st, h->ctl, h->LD.p, oldp, newp, (const P*)S.L, (const uint8_t*)S.A, S.RKREL, (int)compact_out | (h->compact_stats ? 2 : 0), (int)(r & 1));
-	  else if (lean) hipLaunchKernelGGL((k_merge<false, P, true>), dim3(grid8(cdiv(wg, MMW))), dim3(64 * MMW), 0, st, h->ctl, h->LD.p, oldp, newp, (const P*)S.L, (const uint8_t*)S.A, S.RKREL, (int)compact_out | (h->compact_stats ? 2 : 0), (int)(r & 1));
-	  else RB2_LAUNCH_STRIDE(h, (k_merge<true, P>), (k_merge<false, P>), dim3(grid8(cdiv(wg, MMW))), dim3(64 * MMW), 0, st, h->ctl, h->LD.p, oldp, newp, S.INS_E, S.INS_A, S.RKREL, (int)compact_out | (h->compact_stats ? 2 : 0), (int)(r & 1)); }
+	  if (lean) hipLaunchKernelGGL((lite ? k_merge<false, P, true, true> : k_merge<false, P, true>), dim3(grid8(cdiv(wg, MMW))), dim3(64 * MMW), 0, st, h->ctl, h->LD.p, oldp, newp, (const P*)S.L, (const uint8_t*)S.A, S.RKREL, (int)compact_out | (h->k.compact_stats ? 2 : 0), (int)(r & 1));
+	  else RB2_LAUNCH_STRIDE(h, (k_merge<true, P>), (k_merge<false, P>), dim3(grid8(cdiv(wg, MMW))), dim3(64 * MMW), 0, st, h->ctl, h->LD.p, oldp, newp, S.INS_E, S.INS_A, S.RKREL, (int)compact_out | (h->k.compact_stats ? 2 : 0), (int)(r & 1)); }
 	tl_slow(h, "k_merge");
 	{ Scope sc(h, RB2_K_META, units);
 	  build_directory(h, sd ^ 1, h->pside ^ 1, std::min<uint64_t>(B.nsb_ub, n_new_ub / (LEAF * SB) + NR + 1), false, false, (uint64_t)wg * WPL / SB + NR + 1, lite); }
@@ -771,7 +774,7 @@ void round_merge(rb2_hip_t *h, BatchState &B, uint64_t r, ShardRec *send, bool c
 	HIPCHK(hipGetLastError());                                  // a refused launch (grid limits) must not go unnoticed until the end of the batch
 	tl_slow(h, "ne snapshot");
 	h->side ^= 1; h->pside ^= 1; B.cur ^= 1;
-	drop_lean(h, B);                                            // (the record belongs to the round just merged)
+	forget_form(h, B);                                          // (the record belongs to the round just merged)
 	h->pool_compact = compact_out; h->pool_win_dir = lite;
 	if (compact_out) ++h->n_compact_rounds;
 	if (lean && compact_out) ++h->n_lean_compact;
@@ -812,7 +815,7 @@ void relayout(rb2_hip_t *h, bool to_sparse, uint64_t n_ub, uint64_t n_grow)
 		HIPCHK(hipStreamSynchronize(st));
 		const auto tg0 = std::chrono::steady_clock::now();
 		h->pool[h->pside ^ 1].ensure(cap, false, st);
-		if (h->trace) fprintf(stderr, "[rb2_hip] pool grown to %.1f M leaf slots in %.3f s\n", h->pool[h->pside ^ 1].cap_leaves / 1e6, std::chrono::duration<double>(std::chrono::steady_clock::now() - tg0).count());
+		if (h->k.trace) fprintf(stderr, "[rb2_hip] pool grown to %.1f M leaf slots in %.3f s\n", h->pool[h->pside ^ 1].cap_leaves / 1e6, std::chrono::duration<double>(std::chrono::steady_clock::now() - tg0).count());
 	}
 	{
 		Scope sc(h, RB2_K_RELAYOUT, 0);
@@ -827,32 +830,37 @@ void relayout(rb2_hip_t *h, bool to_sparse, uint64_t n_ub, uint64_t n_grow)
 		HIPCHK(hipStreamSynchronize(st));
 		h->pool[h->pside ^ 1].ensure(cap, false, st);
 	}
-	if (h->trace) {
+	if (h->k.trace) {
 		HIPCHK(hipStreamSynchronize(st));
 		fprintf(stderr, "[rb2_hip] re-layout to %s: %.1f G symbols, %.3f s on the host clock, pools %.1f / %.1f -> %.1f / %.1f M leaf slots\n", to_sparse ? "sparse" : "dense", n_ub / 1e9,
 				std::chrono::duration<double>(std::chrono::steady_clock::now() - t_host0).count(), cap_before[0] / 1e6, cap_before[1] / 1e6, h->pool[0].cap_leaves / 1e6, h->pool[1].cap_leaves / 1e6);
 	}
 }
 
-// The host queues in-place rounds at most run_ahead rounds ahead of what the device reports done (Mailbox::progress, split_body): before round r
-// it waits until round r - run_ahead - 1 is over, or a void round is reported, or the stream has run dry (nothing more will be reported)
-void wait_progress(rb2_hip_t *h, uint64_t r)
+// Spin on a report in pinned memory (the mailbox) until done() says so -- or a void round is reported, or the stream has run dry (nothing more will be
+// reported), or two seconds have passed (a report that does not come: wait the plain way)
+template <class Done> void spin_until(rb2_hip_t *h, Done done)
 {
-	const uint32_t want = (uint32_t)r - (uint32_t)h->run_ahead;   // round `want - 1` at least must be over
 	const auto t_spin = std::chrono::steady_clock::now();
-	for (uint32_t spins = 0; (int32_t)(h->mb_h->progress - want) < 0 && !h->mb_h->void_round; ++spins) {
+	for (uint32_t spins = 0; !done() && !h->mb_h->void_round; ++spins) {
 		if ((spins & 1023u) == 1023u) {
-			if (hipStreamQuery(h->st) == hipSuccess) break;         // (everything queued is done: nothing more will be reported)
-			if (std::chrono::steady_clock::now() - t_spin > std::chrono::seconds(2)) { HIPCHK(hipStreamSynchronize(h->st)); break; }   // (a report that does not come: wait the plain way)
+			if (hipStreamQuery(h->st) == hipSuccess) break;
+			if (std::chrono::steady_clock::now() - t_spin > std::chrono::seconds(2)) { HIPCHK(hipStreamSynchronize(h->st)); break; }
 		}
-#if defined(__x86_64__)
 #if defined(__x86_64__) || defined(__i386__)
 		__builtin_ia32_pause();
-#endif
 #else
 		std::this_thread::yield();
 #endif
 	}
+}
+
+// The host queues in-place rounds at most run_ahead rounds ahead of what the device reports done (Mailbox::progress, split_body): before round r
+// it waits until round r - run_ahead - 1 is over
+void wait_progress(rb2_hip_t *h, uint64_t r)
+{
+	const uint32_t want = (uint32_t)r - (uint32_t)h->k.run_ahead;   // round `want - 1` at least must be over
+	spin_until(h, [&] { return (int32_t)(h->mb_h->progress - want) >= 0; });
 }
 
 // The report "every interval of round q was empty and k_sym placed every tile itself" (Mailbox::steady, setup_body) holds for every later round of the
@@ -867,25 +875,14 @@ void steady_poll(rb2_hip_t *h, BatchState &B, uint64_t r, bool bound)
 	if (B.known_steady) return;
 	auto reported = [&](unsigned long long v) -> int64_t { return v ? (int64_t)(v >> 1) - 1 : -1; };   // the round of the last report, -1: none yet
 	unsigned long long v = h->mb_h->steady;
-	if (bound && h->steady_ahead > 0 && r < STEADY_BOUND_ROUNDS && !(v & 1ull) && (int64_t)r - reported(v) > (int64_t)h->steady_ahead) {
-		const auto t_spin = std::chrono::steady_clock::now();
-		for (uint32_t spins = 0; !((v = h->mb_h->steady) & 1ull) && (int64_t)r - reported(v) > (int64_t)h->steady_ahead && !h->mb_h->void_round; ++spins) {
-			if ((spins & 1023u) == 1023u) {
-				if (hipStreamQuery(h->st) == hipSuccess) break;         // (everything queued is done: nothing more will be reported)
-				if (std::chrono::steady_clock::now() - t_spin > std::chrono::seconds(2)) { HIPCHK(hipStreamSynchronize(h->st)); break; }   // (a report that does not come: wait the plain way)
-			}
-#if defined(__x86_64__) || defined(__i386__)
-			__builtin_ia32_pause();
-#else
-			std::this_thread::yield();
-#endif
-		}
+	if (bound && h->k.steady_ahead > 0 && r < STEADY_BOUND_ROUNDS && !(v & 1ull) && (int64_t)r - reported(v) > (int64_t)h->k.steady_ahead) {
+		spin_until(h, [&] { return ((v = h->mb_h->steady) & 1ull) || (int64_t)r - reported(v) <= (int64_t)h->k.steady_ahead; });
 		v = h->mb_h->steady;
 	}
 	if (!(v & 1ull)) return;
 	B.known_steady = true; B.known_ae = true;                  // (a fused tile is a tile of empty intervals)
 	h->steady_seen = reported(v);
-	if (h->steady_on) h->steady_used = (int64_t)r;
+	if (h->k.steady_on) h->steady_used = (int64_t)r;
 }
 
 // Take back the in-place rounds r_void .. r - 1 (round r is next): every kernel of the void round and of those queued behind it returned (a void
@@ -900,7 +897,7 @@ int64_t take_back(rb2_hip_t *h, BatchState &B, uint64_t r_void, uint64_t r)
 	HIPCHK(hipMemsetAsync(&h->ctl->overflow, 0, 4, h->st));
 	h->spec_rounds = 0; h->mb_h->void_round = 0;
 	h->mb_h->progress = (uint32_t)r_void;                      // (the rounds behind the void one reported themselves done; wait_progress reads it)
-	B.counted = (uint64_t)-1; B.setup_round = (uint64_t)-1; drop_lean(h, B);
+	forget_all(h, B);
 	return depth;
 }
 
@@ -924,15 +921,15 @@ bool round_merge_sparse(rb2_hip_t *h, BatchState &B, uint64_t r, ShardRec *send 
 	  hipLaunchKernelGGL(k_setup<true>, dim3(1), dim3(64), 0, st, h->ctl, sd, h->gcnt, (int)(r & 1), (uint32_t)r, hmax_report(h), (int)(h->push[0] != nullptr), steady_report(h)); }
 	const bool lazy = lazy_round(h, spec);                     // no verdict read here: the caller polls (insert_dev)
 	if (!lazy) { h->mb_h->void_round = 0; h->mb_h->respread = 0; }   // the verdict words the splits write
-	else if (h->spec_rounds > (uint64_t)h->run_ahead) wait_progress(h, r);
-	const bool ride = h->dir_ride != 0;
+	else if (h->spec_rounds > (uint64_t)h->k.run_ahead) wait_progress(h, r);
+	const bool ride = h->k.dir_ride != 0;
 	with_pos(h, B, [&](const auto &S) { using P = std::remove_pointer_t<decltype(S.L)>;
 	launch_prep<true>(h, B, r, pv, S);
 	{ Scope sc(h, RB2_K_PART, units);
 	  RB2_LAUNCH_STRIDE(h, (k_part_sparse<true, P>), (k_part_sparse<false, P>), dim3(tg), dim3(256), 0, st, h->ctl, sd, pv, S.INS_E, S.INS_A, S.tf, (SpOrd*)h->LD.p, h->SPL.p, split_cap(h), S.RKOLD, (uint32_t)r); }
 	{ Scope sc(h, RB2_K_MERGE, units);
 	  const unsigned quads = cdiv(rank_share(h, B.m), MW * LROWS * LQ);   // a wave takes LQ x four work orders per step (one leaf per DPP row) and walks the list with a grid stride
-	  hipLaunchKernelGGL(k_merge_leaf<P>, dim3(std::max<unsigned>(WLC / MW, (h->leaf_pipe > 0 ? std::min<unsigned>(quads, (unsigned)h->leaf_pipe) : quads) / (WLC / MW) * (WLC / MW))), dim3(256), 0, st, (const Ctl*)h->ctl, (const SpOrd*)h->LD.p, pv, S.INS_E, S.INS_A, S.RKREL, h->sbtot.p); }
+	  hipLaunchKernelGGL(k_merge_leaf<P>, dim3(std::max<unsigned>(WLC / MW, (h->k.leaf_pipe > 0 ? std::min<unsigned>(quads, (unsigned)h->k.leaf_pipe) : quads) / (WLC / MW) * (WLC / MW))), dim3(256), 0, st, (const Ctl*)h->ctl, (const SpOrd*)h->LD.p, pv, S.INS_E, S.INS_A, S.RKREL, h->sbtot.p); }
 	// the prefix over the superblock totals: in blocks of their own of the k_advance launch and of the launch behind it (rb2_kernels.h "the directory rides along")
 	if (!ride)
 	{ Scope sc(h, RB2_K_META, units);
@@ -956,14 +953,14 @@ bool round_merge_sparse(rb2_hip_t *h, BatchState &B, uint64_t r, ShardRec *send 
 	h->side ^= 1; B.cur ^= 1;
 	if (sp) round_counts(h, B, r + 1, true);                   // (records the event behind its first launch)
 	if (lazy) {                                                // one engine: nobody waits; a void round makes every kernel queued behind it return (sticky: k_part_sparse)
-		B.counted = sp ? r + 1 : (uint64_t)-1;
+		B.c.round = sp ? r + 1 : Counted::NONE;
 		++h->n_sparse_rounds; ++h->spec_rounds;
 		return true;
 	}
 	HIPCHK(hipEventSynchronize(h->ev_flag));
 	if (const uint32_t v = h->mb_h->void_round) { take_back(h, B, v - 1, r + 1); return false; }   // void: nothing was changed, nothing is queued behind the round
 	if (h->mb_h->respread) h->want_respread = true;
-	B.counted = sp ? r + 1 : (uint64_t)-1;
+	B.c.round = sp ? r + 1 : Counted::NONE;
 	++h->n_sparse_rounds;
 	return true;
 }
@@ -977,7 +974,7 @@ uint32_t verdict_check(rb2_hip_t *h, bool drain)
 	const uint32_t v = h->mb_h->void_round;
 	if (h->mb_h->respread) { h->want_respread = true; if (drain) h->mb_h->respread = 0; }
 	if (drain && !v) h->spec_rounds = 0;
-	if (!drain && !h->verdict_poll) return 0;                  // (RB2_VERDICT_POLL=0: a void round waits for the next drain)
+	if (!drain && !h->k.verdict_poll) return 0;                  // (RB2_VERDICT_POLL=0: a void round waits for the next drain)
 	return v;
 }
 
@@ -1008,8 +1005,8 @@ bool choose_layout(rb2_hip_t *h, BatchState &B, uint64_t r, uint64_t m_eff)
 {
 	const uint64_t n_ub = B.n_tot + std::min<uint64_t>(B.len, r * B.m);            // symbols in the index before this round
 	const double lambda = (double)m_eff / ((double)n_ub / LEAF + 1.0);
-	bool want = h->sp_lambda > 0 && lambda < h->sp_lambda && h->sp_backoff == 0 && B.m < (1ull << 27);   // (k_merge_leaf: one wave per LROWS work orders, 2^32 threads per launch)
-	if (h->sparse && !want && lambda < 2 * h->sp_lambda && h->sp_backoff == 0) want = true;   // hysteresis
+	bool want = h->k.sp_lambda > 0 && lambda < h->k.sp_lambda && h->sp_backoff == 0 && B.m < (1ull << 27);   // (k_merge_leaf: one wave per LROWS work orders, 2^32 threads per launch)
+	if (h->sparse && !want && lambda < 2 * h->k.sp_lambda && h->sp_backoff == 0) want = true;   // hysteresis
 	if (h->sp_backoff > 0) --h->sp_backoff;
 	h->plain_next = false;
 	if (want && !h->sparse && h->pool_compact) { want = false; h->plain_next = true; ++h->n_plain_handover; }   // the re-layout reads plain windows: this round writes them, the next one switches
@@ -1023,7 +1020,7 @@ bool choose_layout(rb2_hip_t *h, BatchState &B, uint64_t r, uint64_t m_eff)
 		const double bytes = leaves_more * (LEAFB + 2 * sizeof(LeafMeta) + 2.0) * 1.02 + (256u << 20);
 		if (grow && hipMemGetInfo(&fr, &tot) == hipSuccess && bytes > (double)fr) {
 			want = false; h->sp_backoff = 1 << 30;             // not again in this handle's lifetime
-			if (h->trace) fprintf(stderr, "[rb2_hip] not enough free device memory for the sparse layout (%.1f GB needed, %.1f GB free): staying dense\n", bytes / 1e9, fr / 1e9);
+			if (h->k.trace) fprintf(stderr, "[rb2_hip] not enough free device memory for the sparse layout (%.1f GB needed, %.1f GB free): staying dense\n", bytes / 1e9, fr / 1e9);
 		}
 	}
 	if (want != h->sparse || (h->sparse && h->want_respread)) {
@@ -1031,7 +1028,7 @@ bool choose_layout(rb2_hip_t *h, BatchState &B, uint64_t r, uint64_t m_eff)
 	}
 	if (want != h->sparse) { relayout(h, want, n_ub, B.n_tot + B.len); h->want_respread = false; }
 	else if (h->sparse && h->want_respread) {               // a superblock ran out of slots: spread the index over fresh superblocks (sparse -> sparse)
-		if (h->trace) fprintf(stderr, "[rb2_hip] round %llu: re-spread (a superblock has no free slot left)\n", (unsigned long long)r);
+		if (h->k.trace) fprintf(stderr, "[rb2_hip] round %llu: re-spread (a superblock has no free slot left)\n", (unsigned long long)r);
 		relayout(h, true, n_ub, B.n_tot + B.len);
 		h->want_respread = false; ++h->n_respread;
 	}
@@ -1043,17 +1040,17 @@ bool choose_layout(rb2_hip_t *h, BatchState &B, uint64_t r, uint64_t m_eff)
 void void_to_dense(rb2_hip_t *h, BatchState &B, uint64_t r)
 {
 	++h->n_void;
-	if (h->trace) fprintf(stderr, "[rb2_hip] void round %llu (penalty %d)\n", (unsigned long long)r, h->sp_penalty);
+	if (h->k.trace) fprintf(stderr, "[rb2_hip] void round %llu (penalty %d)\n", (unsigned long long)r, h->sp_penalty);
 	const uint64_t n_ub = B.n_tot + std::min<uint64_t>(B.len, r * B.m);
 	relayout(h, false, n_ub, B.n_tot + B.len);
-	h->sp_penalty = std::min(h->sp_penalty + 1, h->sp_maxpen);
+	h->sp_penalty = std::min(h->sp_penalty + 1, h->k.sp_maxpen);
 	h->sp_backoff = 1 << h->sp_penalty;
 }
 
 void round_merge_any(rb2_hip_t *h, BatchState &B, uint64_t r, ShardRec *send, bool spec)
 {
 	if (h->sparse) {
-		if (B.lean) round_counts(h, B, r, false, false);       // counted lean, run in place after all: k_part_sparse / k_merge_leaf read INS_E / INS_A -- count again (round_counts counts no round lean on the in-place layout: a guard)
+		if (B.c.lean()) round_counts(h, B, r, false, false);       // counted lean, run in place after all: k_part_sparse / k_merge_leaf read INS_E / INS_A -- count again (round_counts counts no round lean on the in-place layout: a guard)
 		if (round_merge_sparse(h, B, r, send, spec)) { if (h->sp_penalty > 0 && (h->n_sparse_rounds & 63) == 0) --h->sp_penalty; return; }
 		// void round: redone on the dense layout
 		void_to_dense(h, B, r);
@@ -1064,12 +1061,12 @@ void round_merge_any(rb2_hip_t *h, BatchState &B, uint64_t r, ShardRec *send, bo
 	// export, rank queries, the next batch's first rounds), and no re-layout is pending
 	// (one engine: the kernel itself checks that every interval is empty -- the host learns that ~20 rounds late, from the ne snapshots; a
 	// rank of a sharded index may receive a string with a non-empty interval from another rank: there the global flag decides)
-	round_merge(h, B, r, send, h->compact_ok && (B.known_ae || h->nranks == 1) && r < B.max_len && !h->plain_next);
+	round_merge(h, B, r, send, merge_plan(h->k, B.c, MergeFacts{ B.known_ae, h->nranks, r < B.max_len, h->plain_next }));
 }
 
 void batch_trace(rb2_hip_t *h)
 {
-	if (h->trace) fprintf(stderr, "[rb2_hip] batch done: layout %s, relayouts %lld (of them re-spreads %lld), void sparse rounds %lld, sparse rounds %lld\n", h->sparse ? "sparse" : "dense",
+	if (h->k.trace) fprintf(stderr, "[rb2_hip] batch done: layout %s, relayouts %lld (of them re-spreads %lld), void sparse rounds %lld, sparse rounds %lld\n", h->sparse ? "sparse" : "dense",
 			(long long)h->n_relayout, (long long)h->n_respread, (long long)h->n_void, (long long)h->n_sparse_rounds);
 }
 
@@ -1108,12 +1105,12 @@ void insert_dev(rb2_hip_t *h, int64_t len64, const uint8_t *s, bool lazy = false
 {
 	if (h->nranks > 1) { rb2_fatal("[rb2_hip] this handle is one rank of a rope-sharded index: insert through its rb2_hip_multi_t\n"); }
 	BatchState B;
-	const bool will_lazy = lazy && h->lazy_insert && !h->prof && !h->debug;   // returns with the rounds queued (below): its caller overlaps them with its own work and is not held back
+	const bool will_lazy = lazy && h->k.lazy_insert && !h->prof && !h->k.debug;   // returns with the rounds queued (below): its caller overlaps them with its own work and is not held back
 	h->want_pos32 = true;                                       // (one engine, whole index: the narrow position storage may be used)
 	if (!batch_begin(h, B, len64, s, true)) {
 		// more strings than one batch may hold: two batches, one after the other (the second half moves to a 16-byte aligned place)
 		const int64_t p = split_point(h, s, len64);
-		if (h->trace) fprintf(stderr, "[rb2_hip] batch of %llu strings cut at byte %lld of %lld\n", (unsigned long long)B.m, (long long)p, (long long)len64);
+		if (h->k.trace) fprintf(stderr, "[rb2_hip] batch of %llu strings cut at byte %lld of %lld\n", (unsigned long long)B.m, (long long)p, (long long)len64);
 		insert_dev(h, p, s, false);
 		DevBuf<uint8_t> half;
 		half.ensure((size_t)(len64 - p) + 64);
@@ -1126,7 +1123,7 @@ void insert_dev(rb2_hip_t *h, int64_t len64, const uint8_t *s, bool lazy = false
 	// The first rounds of a batch are hot spots by construction: round 0 puts every string into rope $ (at its end in input order,
 	// at a handful of positions in the sorted orders), round k touches ~4^k places.  A sparse index would void each of them (a
 	// re-layout there and back per round); one dense phase of eight rounds costs two re-layouts for all of them.
-	if (h->sparse && h->sp_backoff < h->sp_head) h->sp_backoff = h->sp_head;
+	if (h->sparse && h->sp_backoff < h->k.sp_head) h->sp_backoff = h->k.sp_head;
 	struct GrowWatch { GrowWatch(int64_t *c) { t_grow_in_rounds = c; } ~GrowWatch() { t_grow_in_rounds = nullptr; } } gw(&h->n_grow_in_rounds);
 	for (uint64_t r = 0; ; ) {                                 // one round per string position, last symbol first (mrope.c:285, 299-342)
 		// In-place rounds are queued without a look at their verdict.  The host looks here -- at what has landed in pinned memory when it queues
@@ -1136,7 +1133,7 @@ void insert_dev(rb2_hip_t *h, int64_t len64, const uint8_t *s, bool lazy = false
 		uint32_t rv = verdict_check(h, r > B.max_len);
 		if (!rv && r > B.max_len) break;
 		if (!rv) {
-			if (h->timeline > 1 && (r < 4 || r % 10 == 0)) fprintf(stderr, "[rb2_hip] t = %8.3f ms  queueing round %llu\n", std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count() - h->tl_base, (unsigned long long)r);
+			if (h->k.timeline > 1 && (r < 4 || r % 10 == 0)) fprintf(stderr, "[rb2_hip] t = %8.3f ms  queueing round %llu\n", std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count() - h->tl_base, (unsigned long long)r);
 			if (!B.known_ae && r > 0 && ne_all_empty_from(h, r)) B.known_ae = true;
 			steady_poll(h, B, r, !will_lazy);
 			if (!(rv = maybe_widen(h, B, r)) && !(rv = verdict_check(h, false)) && !choose_layout(h, B, r, B.m)) rv = verdict_check(h, true);
@@ -1153,7 +1150,7 @@ void insert_dev(rb2_hip_t *h, int64_t len64, const uint8_t *s, bool lazy = false
 			memset((void*)h->mb_h->ne, 0xff, sizeof(h->mb_h->ne));
 			// the same for the report of fused rounds (the counting tails queued behind a void round return before they report, and the stream is drained:
 			// nothing is on its way): the rounds redone from here report again
-			B.known_steady = false; h->mb_h->steady = 0; drop_lean(h, B);   // (... and lean with it: the redone rounds write INS_E / INS_A until the device reports again)
+			B.known_steady = false; h->mb_h->steady = 0; forget_form(h, B);   // (... and lean with it: the redone rounds write INS_E / INS_A until the device reports again)
 			r = r_void;
 			void_to_dense(h, B, r);
 			round_counts(h, B, r);
@@ -1161,7 +1158,7 @@ void insert_dev(rb2_hip_t *h, int64_t len64, const uint8_t *s, bool lazy = false
 			++r;
 			continue;
 		}
-		if (B.counted != r) round_counts(h, B, r);
+		if (B.c.round != r) round_counts(h, B, r);
 		round_merge_any(h, B, r, nullptr, true);
 		++r;
 	}
@@ -1206,20 +1203,8 @@ rb2_hip_t *rb2_hip_create(int device, int sorting_order)
 	HIPCHK(hipSetDevice(device));
 	rb2_hip_t *h = new rb2_hip_s();
 	h->dev = device; h->so = sorting_order;
-	h->debug = getenv("RB2_HIP_DEBUG") ? atoi(getenv("RB2_HIP_DEBUG")) : 0;
-	h->trace = getenv("RB2_HIP_TRACE") ? atoi(getenv("RB2_HIP_TRACE")) : 0;
-	if (getenv("RB2_SPARSE_LAMBDA")) h->sp_lambda = atof(getenv("RB2_SPARSE_LAMBDA"));   // 0: never leave the dense layout
-	if (getenv("RB2_SPARSE_HEAD")) h->sp_head = atoi(getenv("RB2_SPARSE_HEAD"));
-	if (getenv("RB2_LEAF_PIPE")) h->leaf_pipe = atoi(getenv("RB2_LEAF_PIPE"));
-	if (getenv("RB2_COMPACT")) h->compact_ok = atoi(getenv("RB2_COMPACT"));
-	if (getenv("RB2_LEAN_DIR")) h->lean_dir = atoi(getenv("RB2_LEAN_DIR"));
-	if (getenv("RB2_COMPACT_STATS")) h->compact_stats = atoi(getenv("RB2_COMPACT_STATS"));
-	if (getenv("RB2_TS_MAX")) h->ts_max = std::max(0, std::min((int)TS_MAX, atoi(getenv("RB2_TS_MAX"))));
-	if (getenv("RB2_TS_FOLD")) h->ts_fold = std::max(0, std::min((int)SCHUNK, atoi(getenv("RB2_TS_FOLD"))));   // tests: 0 = the scan over the chunks always as a launch of its own (k_tscan2)
-	if (getenv("RB2_HIP_LAZY_INSERT")) h->lazy_insert = atoi(getenv("RB2_HIP_LAZY_INSERT"));
-	if (getenv("RB2_HIP_TIMELINE")) h->timeline = atoi(getenv("RB2_HIP_TIMELINE"));
-	if (getenv("RB2_SPARSE_MAXPEN")) h->sp_maxpen = atoi(getenv("RB2_SPARSE_MAXPEN"));     // tests: 0 = retry the sparse layout after every dense fallback round
-	if (h->trace) h->prof = 1;
+	h->k = read_knobs();
+	if (h->k.trace) h->prof = 1;
 	HIPCHK(hipStreamCreateWithFlags(&h->st, hipStreamNonBlocking));
 	HIPCHK(hipMalloc((void**)&h->ctl, sizeof(Ctl)));
 	HIPCHK(hipMalloc((void**)&h->d_tmp, 256));
@@ -1230,18 +1215,6 @@ rb2_hip_t *rb2_hip_create(int device, int sorting_order)
 	HIPCHK(hipEventCreateWithFlags(&h->ev_flag, hipEventDisableTiming));
 	HIPCHK(hipStreamCreateWithFlags(&h->st_count, hipStreamNonBlocking));
 	HIPCHK(hipEventCreateWithFlags(&h->ev_fork, hipEventDisableTiming)); HIPCHK(hipEventCreateWithFlags(&h->ev_join, hipEventDisableTiming));
-	if (getenv("RB2_DIR_RIDE")) h->dir_ride = atoi(getenv("RB2_DIR_RIDE"));
-	if (getenv("RB2_TS_BLOCKS")) h->ts_blocks = atoi(getenv("RB2_TS_BLOCKS"));
-	if (getenv("RB2_LAZY_VERDICT")) h->lazy_verdict = atoi(getenv("RB2_LAZY_VERDICT"));
-	if (getenv("RB2_RUN_AHEAD")) h->run_ahead = std::max(1, atoi(getenv("RB2_RUN_AHEAD")));
-	if (getenv("RB2_VERDICT_POLL")) h->verdict_poll = atoi(getenv("RB2_VERDICT_POLL"));
-	if (getenv("RB2_STEADY")) h->steady_on = atoi(getenv("RB2_STEADY")) != 0;
-	if (getenv("RB2_STEADY_LEAN")) h->lean = std::min(2, std::max(0, atoi(getenv("RB2_STEADY_LEAN"))));
-	if (!h->steady_on) h->lean = 0;
-	if (getenv("RB2_LEAN_AUDIT")) h->lean_audit = std::max(0, atoi(getenv("RB2_LEAN_AUDIT")));
-	if (getenv("RB2_LEAN_VERIFY")) h->lean_verify = atoi(getenv("RB2_LEAN_VERIFY")) != 0;
-	if (getenv("RB2_LEAN_FORK")) h->lean_fork = atoi(getenv("RB2_LEAN_FORK")) != 0;
-	if (getenv("RB2_STEADY_AHEAD")) h->steady_ahead = std::max(0, atoi(getenv("RB2_STEADY_AHEAD")));
 	{ Ctl *hc = (Ctl*)calloc(1, sizeof(Ctl)); for (int b = 0; b < NR; ++b) hc->own[b] = 1; HIPCHK(hipMemcpy(h->ctl, hc, sizeof(Ctl), hipMemcpyHostToDevice)); free(hc); }
 	HIPCHK(hipMemsetAsync(h->d_tmp, 0, 256, h->st));
 	memset(h->h_rope, 0, sizeof(h->h_rope));
@@ -1359,7 +1332,7 @@ void rb2_hip_insert_multi(rb2_hip_t *h, int64_t len, const uint8_t *s)
 	if (len <= 0 || s[len - 1] != 0) { rb2_fatal("[rb2_hip] insert_multi: buffer must be non-empty and end with a sentinel\n"); }   // mrope.c:268
 	static const double tl0 = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count();
 	h->tl_base = tl0;
-	auto tl = [&](const char *what) { if (h->timeline) fprintf(stderr, "[rb2_hip] t = %8.3f ms  %s\n", std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count() - tl0, what); };
+	auto tl = [&](const char *what) { if (h->k.timeline) fprintf(stderr, "[rb2_hip] t = %8.3f ms  %s\n", std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count() - tl0, what); };
 	tl("insert_multi: enter");
 	// The text goes into the SECOND text buffer on the copy stream -- the first may still be read by the rounds of the previous
 	// insert, which was allowed to return before they were done (finish_pending): a caller that inserts batch after batch has batch
@@ -1404,7 +1377,7 @@ int rb2_hip_last_batch_counts(rb2_hip_t *h, int64_t d[36])
 	return 1;
 }
 
-void rb2_hip_set_lazy(rb2_hip_t *h, int on) { finish_pending(h); h->lazy_insert = on; }
+void rb2_hip_set_lazy(rb2_hip_t *h, int on) { finish_pending(h); h->k.lazy_insert = on; }
 void rb2_hip_wait(rb2_hip_t *h) { finish_pending(h); }
 
 void rb2_hip_get_counts(rb2_hip_t *h, int64_t c[36])
@@ -1735,7 +1708,7 @@ int64_t rb2_hip_delete_strings(rb2_hip_t *h, int64_t n, const int64_t *ids)
 	ensure_dense(h);
 	require_plain(h, "delete_strings");
 	double t_ph[6]; int n_ph = 0;                              // RB2_HIP_TRACE=1: the host clock behind a synchronise after every phase
-	auto phase = [&]() { if (h->trace) { HIPCHK(hipStreamSynchronize(st)); t_ph[n_ph++] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); } };
+	auto phase = [&]() { if (h->k.trace) { HIPCHK(hipStreamSynchronize(st)); t_ph[n_ph++] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); } };
 	phase();
 	uint64_t nleaf = 0;                                        // leaf slots of the source, up to the end of its last piece
 	for (int r = 0; r < NR; ++r) if (h->h_rope[r].nleaves) nleaf = std::max(nleaf, h->h_rope[r].leaf0 + h->h_rope[r].nleaves);
@@ -1792,7 +1765,7 @@ int64_t rb2_hip_delete_strings(rb2_hip_t *h, int64_t n, const int64_t *ids)
 	h->pside = ps; h->pool_compact = false; h->pool_win_dir = false;                    // `side` stays, as in a re-layout: the descriptors are rewritten in place
 	ld_finish(h, rp, leaf, dst, tally.p);
 	phase();
-	if (h->trace) fprintf(stderr, "[rb2_hip] delete_strings: %lld ids, %llu rows: mark %.3f ms, count %.3f, zeroed destination %.3f, scan + compact %.3f, own counts + directory %.3f\n", (long long)n,
+	if (h->k.trace) fprintf(stderr, "[rb2_hip] delete_strings: %lld ids, %llu rows: mark %.3f ms, count %.3f, zeroed destination %.3f, scan + compact %.3f, own counts + directory %.3f\n", (long long)n,
 			(unsigned long long)removed, t_ph[1] - t_ph[0], t_ph[2] - t_ph[1], t_ph[3] - t_ph[2], t_ph[4] - t_ph[3], t_ph[5] - t_ph[4]);
 	h->del_stats[0] = (int64_t)removed; h->del_stats[1] = (int64_t)t_h[DEL_GROUPS]; h->del_stats[2] = (int64_t)t_h[DEL_SLOW];
 	h->del_stats[3] = (int64_t)nleaf; h->del_stats[4] = (int64_t)leaf;
@@ -2225,7 +2198,7 @@ void rb2_hip_rewind_stats(rb2_hip_t *h, int64_t out[4])
 
 void rb2_hip_lean_stats(rb2_hip_t *h, int64_t out[2])
 { finish_pending(h);
-	out[0] = h->n_lean_rounds; out[1] = (h->lean == 2 && !h->lean2_met) ? 1 : h->lean;   // (the stage in force: a handle that has only met the one-launch tail runs stage 1)
+	out[0] = h->n_lean_rounds; out[1] = lean_stage_in_force(h->k, h->lean2_met);   // (the stage in force: a handle that has only met the one-launch tail runs stage 1)
 }
 
 void rb2_hip_lean_count_stats(rb2_hip_t *h, int64_t out[4])
@@ -2238,14 +2211,14 @@ void rb2_hip_lean_count_stats(rb2_hip_t *h, int64_t out[4])
 void rb2_hip_lean_fork_stats(rb2_hip_t *h, int64_t out[2])
 {
 	finish_pending(h);
-	out[0] = h->n_lean_forked; out[1] = (h->lean_fork && h->own_stream && !h->lean_verify && !h->debug) ? 1 : 0;
+	out[0] = h->n_lean_forked; out[1] = fork_in_force(h->k, h->own_stream) ? 1 : 0;
 }
 
 /* out[0]: rounds run with the window directory; out[1]: the switch in force (RB2_LEAN_DIR); out[2]: lean rounds that were allowed to write compact windows, whatever the switch says */
 void rb2_hip_lean_dir_stats(rb2_hip_t *h, int64_t out[3])
 {
 	finish_pending(h);
-	out[0] = h->n_lean_dir; out[1] = h->lean_dir ? 1 : 0; out[2] = h->n_lean_compact;
+	out[0] = h->n_lean_dir; out[1] = h->k.lean_dir ? 1 : 0; out[2] = h->n_lean_compact;
 }
 
 void rb2_hip_window_stats(rb2_hip_t *h, int64_t out[6])
@@ -2255,7 +2228,7 @@ void rb2_hip_window_stats(rb2_hip_t *h, int64_t out[6])
 	HIPCHK(hipMemcpyAsync(w, &h->ctl->wfmt[0], sizeof(w), hipMemcpyDeviceToHost, h->st));
 	HIPCHK(hipStreamSynchronize(h->st));
 	for (int i = 0; i < 4; ++i) out[i] = (int64_t)w[i];
-	out[4] = h->n_compact_rounds; out[5] = h->compact_stats ? 1 : 0;
+	out[4] = h->n_compact_rounds; out[5] = h->k.compact_stats ? 1 : 0;
 }
 
 void rb2_hip_sync(rb2_hip_t *h) { finish_pending(h); HIPCHK(hipSetDevice(h->dev)); fork_join(h); HIPCHK(hipStreamSynchronize(h->st)); }

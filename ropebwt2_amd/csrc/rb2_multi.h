@@ -299,7 +299,7 @@ void multi_rank_batch(rb2_hip_multi_t *m, int k, int64_t len)
 	batch_begin(h, B, len, R.s_dev);
 	// the layout of this rank's slice follows ITS regime: strings it expects per round against the leaves it holds (choose_layout);
 	// the first rounds of a batch are hot spots by construction (see insert_dev)
-	if (h->sparse && h->sp_backoff < h->sp_head) h->sp_backoff = h->sp_head;
+	if (h->sparse && h->sp_backoff < h->k.sp_head) h->sp_backoff = h->k.sp_head;
 	const uint64_t m_eff = std::max<uint64_t>(1, B.m / (uint64_t)std::max(1, m->active) + B.m / (uint64_t)(4 * std::max(1, m->active)));
 	const int64_t sp0 = h->n_sparse_rounds + h->n_void;
 	// exchange buffers: a rank never holds (or receives) more strings than the batch has.  They are (re)allocated between
@@ -350,8 +350,7 @@ void multi_rank_batch(rb2_hip_multi_t *m, int k, int64_t len)
 		// sum of the count rows (PEER) + exchange plan + k_setup of the round: one launch (k_mround)
 		{
 			volatile unsigned long long *hmax = hmax_report(h), *hne = &h->mb_d->hne;
-			if (h->sparse) hipLaunchKernelGGL(k_mround<true>, dim3(1), dim3(256), 0, st, h->ctl, rows, peer ? m->n : 0, h->gcnt, ow, R.grank, (int)peer, sends[r & 1], (const ShardRec*)R.recv, R.tab, h->side, (int)(r & 1), (uint32_t)r, hmax, hne);
-			else hipLaunchKernelGGL(k_mround<false>, dim3(1), dim3(256), 0, st, h->ctl, rows, peer ? m->n : 0, h->gcnt, ow, R.grank, (int)peer, sends[r & 1], (const ShardRec*)R.recv, R.tab, h->side, (int)(r & 1), (uint32_t)r, hmax, hne);
+			hipLaunchKernelGGL((h->sparse ? k_mround<true> : k_mround<false>), dim3(1), dim3(256), 0, st, h->ctl, rows, peer ? m->n : 0, h->gcnt, ow, R.grank, (int)peer, sends[r & 1], (const ShardRec*)R.recv, R.tab, h->side, (int)(r & 1), (uint32_t)r, hmax, hne);
 			mark_setup(h, B, r);
 		}
 		// dense round: the slice is rewritten pool -> pool; in-place round: only the touched leaves, and the host reads a one-word
