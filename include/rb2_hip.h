@@ -780,6 +780,14 @@ const char *rb2_hip_kernel_name(int k);
 /* device layout constants: symbols per leaf, leaves per merge tile, strings per string tile */
 void rb2_hip_layout(int *leaf_syms, int *tile_leaves, int *string_tile);
 
+/* diagnostic: one of the engine's cold-path prefix scans (rb2_scan.h) over the host array in[0 .. n), run in place on the device.
+ * op 0: sums of uint32 (in[] is narrowed), 1: sums of uint64, 2: sums that stop at 2^62, an item counting as 2^62 at the most,
+ * 3: running maximum.  out[i], i < n: the items in front of i (op 3: up to and including i); out[n] and *total: all of them.
+ * form 0: many blocks in three launches, and parts[b] = the items in front of block b, for every block that holds an item;
+ * form 1 / 2: one block of 256 / 1024 threads (op 1 only; parts is not written).  Returns the items a block takes per turn.
+ * One synchronise. */
+int64_t rb2_hip_scan_check(rb2_hip_t *h, int op, int form, int64_t n, const uint64_t *in, uint64_t *out, uint64_t *parts, uint64_t *total);
+
 #ifdef __cplusplus
 }
 #endif

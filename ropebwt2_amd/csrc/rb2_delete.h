@@ -8,13 +8,14 @@
 //   k_del_count    one DPP row per source leaf: kept symbols of the leaf; per piece the six kept symbol counts and the removed rows,
 //                  tallied in LDS and flushed once per workgroup
 //   (host)         piece table and RopeDescs of the survivors from the 31 x 6 matrix, as the loaders build them (ld_piece_table)
-//   k_del_scan     one workgroup per piece: exclusive prefix of the kept counts = first destination row of every source leaf
+//   k_del_scan     one workgroup per piece: exclusive prefix of the kept counts = first destination row of every source leaf (the loop: rb2_scan.h)
 //   k_del_compact  one DPP row per source leaf, lane = group: compress the three planes by the kept mask (rb2_delete_plan.h) and OR
 //                  them into the zeroed destination piece at the row a row-exclusive sum gives; k_ld_own and the directory follow
 // The source is dense and plain (the caller leaves the sparse layout first): row p of a piece is bit p & 63 of group p >> 6.
 // Every store and atomic is an ordinary vector one.
 #pragma once
 #include "rb2_query.h"
+#include "rb2_scan.h"
 #include "rb2_delete_plan.h"
 
 namespace rb2 {
@@ -102,13 +103,7 @@ __global__ __launch_bounds__(256) void k_del_scan(const QTab *Tg, const uint32_t
 	__shared__ uint64_t s_w[4];
 	const uint64_t leaf0 = Tg->rd[blockIdx.x].leaf0, nl = Tg->rd[blockIdx.x].nleaves;
 	uint64_t run = 0;
-	for (uint64_t i0 = 0; i0 < nl; i0 += 256) {
-		const uint64_t i = i0 + threadIdx.x, x = i < nl ? lkept[leaf0 + i] : 0;
-		uint64_t tot;
-		const uint64_t ex = block_excl_add<uint64_t>(x, s_w, &tot);
-		if (i < nl) lbase[leaf0 + i] = run + ex;
-		run += tot;
-	}
+	scan_by_block<ScanAdd<uint64_t>>(ScanIn<uint32_t>{lkept, 0}, lbase, leaf0, nl, run, s_w);
 }
 
 // out: the zeroed data of the destination side.  The host has checked that piece r keeps exactly as many rows as its destination holds.

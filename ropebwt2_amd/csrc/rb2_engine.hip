@@ -514,7 +514,7 @@ bool batch_begin(rb2_hip_t *h, BatchState &B, int64_t len64, const uint8_t *s, b
 		uint64_t res[2] = {0, 0};                                // [0] number of strings, [1] input-validation flag
 		HIPCHK(hipMemsetAsync(h->zblk.p + nzb + 1, 0, 8, st));
 		hipLaunchKernelGGL(k_count_zeros, dim3(nzb), dim3(256), 0, st, s, len, h->zblk.p, h->zblk.p + nzb + 1);
-		hipLaunchKernelGGL(k_zscan, dim3(1), dim3(SCHUNK), 0, st, h->zblk.p, nzb);
+		hipLaunchKernelGGL((k_scan_block<ScanAdd<uint64_t>, ScanIn<uint64_t>, SCHUNK>), dim3(1), dim3(SCHUNK), 0, st, ScanIn<uint64_t>{h->zblk.p, nzb}, h->zblk.p);   // in place; zblk[nzb] = the strings
 		HIPCHK(hipMemcpyAsync(res, h->zblk.p + nzb, 16, hipMemcpyDeviceToHost, st));
 		HIPCHK(hipStreamSynchronize(st));
 		m = res[0];
@@ -1420,7 +1420,7 @@ static int64_t export_piece(rb2_hip_t *h, int r, uint8_t *dst, rb2_hip_run_cb cb
 	auto launch = [&](uint64_t c0, int buf) {
 		const uint64_t nc = std::min<uint64_t>(CH, nchunks - c0);
 		hipLaunchKernelGGL(k_export, dim3(cdiv(nc, MW)), dim3(256), 0, h->st, h->pool[h->pside].view(), d.leaf0, d.n, c0, (uint32_t)nc, h->xstage.p, h->xnb.p);
-		hipLaunchKernelGGL(k_xscan, dim3(1), dim3(SCHUNK), 0, h->st, (const uint16_t*)h->xnb.p, (uint32_t)nc, h->xoff.p);
+		hipLaunchKernelGGL((k_scan_block<ScanAdd<uint64_t>, ScanIn<uint16_t>, SCHUNK>), dim3(1), dim3(SCHUNK), 0, h->st, ScanIn<uint16_t>{h->xnb.p, nc}, h->xoff.p);   // xoff[nc] = the bytes
 		HIPCHK(hipMemcpyAsync(h->xtot[buf], h->xoff.p + nc, 8, hipMemcpyDeviceToHost, h->st));
 		if (want) {
 			hipLaunchKernelGGL(k_xcompact, dim3(cdiv(nc, MW)), dim3(256), 0, h->st, (const uint8_t*)h->xstage.p, (const uint16_t*)h->xnb.p, (const uint64_t*)h->xoff.p, (uint32_t)nc, h->xpack.p);
@@ -1572,27 +1572,23 @@ void rb2_hip_load_ropes(rb2_hip_t *h, const uint8_t *const rle[6], const int64_t
 	LdPieces tab[6];
 	const uint64_t leaf = ld_piece_table(h, "load_ropes", tot, rp, tab);
 	PoolView pv = ld_zero_pool(h, leaf, h->pside);
-	std::vector<uint64_t> off;
+	DevBuf<uint64_t> part;
+	part.ensure(scan_parts(*std::max_element(nblk, nblk + 6)));
 	for (int b = 0; b < 6; ++b) {
 		if (nblk[b] == 0) continue;
-		off.resize(nblk[b] + 1);
-		HIPCHK(hipMemcpyAsync(off.data(), blk[b].p, nblk[b] * 8, hipMemcpyDeviceToHost, st));
-		HIPCHK(hipStreamSynchronize(st));
-		uint64_t run = 0;
-		for (uint64_t i = 0; i < nblk[b]; ++i) { const uint64_t v = off[i]; off[i] = run; run += v; }
-		HIPCHK(hipMemcpyAsync(blk[b].p, off.data(), nblk[b] * 8, hipMemcpyHostToDevice, st));
+		scan_launch<ScanAdd<uint64_t>>(st, ScanIn<uint64_t>{blk[b].p, nblk[b]}, nblk[b], part.p, blk[b].p, nullptr, false);   // the blocks' symbol counts become their offsets, in place
 		hipLaunchKernelGGL(k_ld_expand, dim3((unsigned)nblk[b]), dim3(256), 0, st, (const uint8_t*)dr[b].p, (uint64_t)n_bytes[b], (const uint64_t*)blk[b].p, tab[b],
 				(uint64_t*)pv.data, cnt.p + 36, longs.p, flag.p + 1, long_cap, flag.p);
 		hipLaunchKernelGGL(k_ld_long, dim3(1024), dim3(256), 0, st, (const LdLong*)longs.p, (const uint32_t*)(flag.p + 1), long_cap, (uint64_t*)pv.data);
 		HIPCHK(hipMemcpyAsync(flag_h, flag.p, 8, hipMemcpyDeviceToHost, st));
-		HIPCHK(hipStreamSynchronize(st));                      // (off is reused; the long-run list is per rope)
+		HIPCHK(hipStreamSynchronize(st));                      // (the long-run list is per rope)
 		if (flag_h[0]) { rb2_fatal("[rb2_hip] load_ropes: rope %d does not match the symbol counts of the other ropes\n", b); }
 		if (flag_h[1] > long_cap) { rb2_fatal("[rb2_hip] load_ropes: more than %u runs longer than %u symbols in rope %d\n", long_cap, LD_LONG, b); }
 		HIPCHK(hipMemsetAsync(flag.p + 1, 0, 4, st));
 	}
 	ld_finish(h, rp, leaf, pv, cnt.p + 36);
 	for (int b = 0; b < 6; ++b) { dr[b].release(); blk[b].release(); }
-	cnt.release(); flag.release(); longs.release();
+	cnt.release(); flag.release(); longs.release(); part.release();
 }
 
 /* ---- .fmd images (kernels in rb2_fmd_load.h) ------------------------------- */
@@ -1633,7 +1629,7 @@ int64_t rb2_hip_load_fmd(rb2_hip_t *h, const void *fmd, int64_t n_bytes)
 	HIPCHK(hipMemsetAsync(wg.p, 0, ((uint64_t)nwg + 1) * 8, st));
 	if (nb) {
 		hipLaunchKernelGGL(k_fmd_sizes, dim3(nwg), dim3(256), 0, st, (const uint64_t*)dw.p, nb, nwords, wg.p, flag.p);
-		hipLaunchKernelGGL(k_fmd_scan, dim3(1), dim3(256), 0, st, wg.p, (uint64_t)nwg);
+		hipLaunchKernelGGL((k_scan_block<ScanAdd<uint64_t>, ScanIn<uint64_t>, 256>), dim3(1), dim3(256), 0, st, ScanIn<uint64_t>{wg.p, nwg}, wg.p);   // in place; wg[nwg] = the rows
 		hipLaunchKernelGGL(k_fmd_count, dim3(nwg), dim3(256), 0, st, (const uint64_t*)dw.p, nb, nwords, (const uint64_t*)wg.p, ropes, cnt.p, flag.p);
 	}
 	unsigned long long tot_h[36], rows_dev; uint32_t flag_h[2];
@@ -1920,7 +1916,7 @@ static int64_t fmds_encode(rb2_hip_t *h, FmdsOut *o)
 	DevBuf<uint32_t> W, nxt, wg, part;
 	DevBuf<FmdsEntry> gst, sst;
 	DevBuf<FmdsState> dstate;
-	recb[0].ensure(RCAP + 2); recb[1].ensure(RCAP + 2); W.ensure(RCAP + 2); nxt.ensure(RCAP + 2); wg.ensure(RCAP / LEAF / 16 + 4); part.ensure(RCAP / 1024 + 4);
+	recb[0].ensure(RCAP + 2); recb[1].ensure(RCAP + 2); W.ensure(RCAP + 2); nxt.ensure(RCAP + 2); wg.ensure(RCAP / LEAF / 16 + 4); part.ensure(scan_parts(RCAP + 2));
 	tab.ensure(nseg_max * FMDS_ENTRIES); gtab.ensure(ng_max * FMDS_ENTRIES); gst.ensure(ng_max); sst.ensure(nseg_max); lastcnt.ensure(nseg_max * 7); dstate.ensure(1);
 	HIPCHK(hipMemsetAsync(dstate.p, 0, sizeof(FmdsState), st));
 	uint8_t *outh[2] = {nullptr, nullptr};
@@ -1930,7 +1926,7 @@ static int64_t fmds_encode(rb2_hip_t *h, FmdsOut *o)
 	HIPCHK(hipEventCreateWithFlags(&evS, hipEventDisableTiming));
 	for (int i = 0; i < 2; ++i) HIPCHK(hipEventCreateWithFlags(&evO[i], hipEventDisableTiming));
 	if (o) {
-		bidx.ensure(nbk); bS.ensure(nbk); bpart.ensure(nbk / 1024 + 4);
+		bidx.ensure(nbk); bS.ensure(nbk); bpart.ensure(scan_parts(nbk));
 		HIPCHK(hipMemsetAsync(bidx.p, 0, nbk * 8, st)); HIPCHK(hipMemsetAsync(bS.p, 0, nbk * 8, st));
 		for (int i = 0; i < 2; ++i) { outd[i].ensure(OUTCAP * FMDS_BW); HIPCHK(hipHostMalloc((void**)&outh[i], OUTCAP * FMDS_BW * 8, hipHostMallocDefault)); }
 	}
@@ -1967,11 +1963,8 @@ static int64_t fmds_encode(rb2_hip_t *h, FmdsOut *o)
 			nl = std::min<uint64_t>(avail, (d.n + LEAF - 1) / LEAF - lc);
 			if (nl) {
 				const uint64_t nwg = (nl + 15) / 16;
-				const FmdsInCount ic{wg.p, nwg};
 				hipLaunchKernelGGL(k_fmds_heads<false>, dim3((unsigned)nwg), dim3(256), 0, st, pv, d.leaf0, d.n, lc, (uint32_t)nl, P0, ncur, rec.p, wg.p);
-				hipLaunchKernelGGL((k_fmds_scan_part<false, uint32_t, FmdsInCount>), dim3(cdiv(nwg, 1024)), dim3(256), 0, st, ic, part.p);
-				hipLaunchKernelGGL((k_fmds_scan_top<false, uint32_t, FmdsInCount>), dim3(1), dim3(256), 0, st, ic, part.p);
-				hipLaunchKernelGGL((k_fmds_scan_apply<false, uint32_t, FmdsInCount>), dim3(cdiv(nwg, 1024)), dim3(256), 0, st, ic, (const uint32_t*)part.p, wg.p);
+				scan_launch<ScanAdd<uint32_t>>(st, ScanIn<uint32_t>{wg.p, nwg}, nwg, part.p, wg.p, nullptr, true);   /* in place; wg[nwg] = the new heads */
 				hipLaunchKernelGGL(k_fmds_heads<true>, dim3((unsigned)nwg), dim3(256), 0, st, pv, d.leaf0, d.n, lc, (uint32_t)nl, P0, ncur, rec.p, wg.p);
 				nnew = wg.p + nwg;
 				lc += nl;
@@ -1981,10 +1974,7 @@ static int64_t fmds_encode(rb2_hip_t *h, FmdsOut *o)
 		const uint32_t flush = r == NR;
 		hipLaunchKernelGGL(k_fmds_begin, dim3(1), dim3(1), 0, st, dstate.p, rec.p, ncur, nnew, flush, total, type0, blk0);
 		const uint64_t mub = ncur + nl * LEAF + 1;              /* heads at the most (the grids below are sized for them; the kernels read the count) */
-		const FmdsInWidth iw{rec.p, dstate.p};
-		hipLaunchKernelGGL((k_fmds_scan_part<false, uint32_t, FmdsInWidth>), dim3(cdiv(mub, 1024)), dim3(256), 0, st, iw, part.p);
-		hipLaunchKernelGGL((k_fmds_scan_top<false, uint32_t, FmdsInWidth>), dim3(1), dim3(256), 0, st, iw, part.p);
-		hipLaunchKernelGGL((k_fmds_scan_apply<false, uint32_t, FmdsInWidth>), dim3(cdiv(mub, 1024)), dim3(256), 0, st, iw, (const uint32_t*)part.p, W.p);
+		scan_launch<ScanAdd<uint32_t>>(st, FmdsInWidth{rec.p, dstate.p}, mub, part.p, W.p, nullptr, true);   /* W[0 .. nc] */
 		hipLaunchKernelGGL(k_fmds_next, dim3(cdiv(mub + 1, 256)), dim3(256), 0, st, (const FmdsState*)dstate.p, (const uint64_t*)rec.p, (const uint32_t*)W.p, nxt.p);
 		const uint64_t nseg = mub / SEG + 1, ng = (nseg + FMDS_GROUP - 1) / FMDS_GROUP;
 		hipLaunchKernelGGL(k_fmds_table, dim3((unsigned)nseg), dim3(320), 0, st, (const FmdsState*)dstate.p, (const uint32_t*)nxt.p, SEG, tab.p);
@@ -2022,12 +2012,7 @@ static int64_t fmds_encode(rb2_hip_t *h, FmdsOut *o)
 	const uint64_t n_frames = fmds_n_frames(total, ibits);
 	if (ibits < bbits) { give_up(); rb2_fatal("[rb2_hip] save_fmd: %llu rows need rank frames of 2^%d rows, finer than the 2^%d the encoder keeps for them (%llu buckets)\n", (unsigned long long)total, ibits, bbits, (unsigned long long)FMDS_BUCKET_CAP); }
 	if (o) {
-		for (uint64_t *b : {bidx.p, bS.p}) {                      /* every bucket: the last header up to it */
-			const FmdsInMax im{b, nbk};
-			hipLaunchKernelGGL((k_fmds_scan_part<true, uint64_t, FmdsInMax>), dim3(cdiv(nbk, 1024)), dim3(256), 0, st, im, bpart.p);
-			hipLaunchKernelGGL((k_fmds_scan_top<true, uint64_t, FmdsInMax>), dim3(1), dim3(256), 0, st, im, bpart.p);
-			hipLaunchKernelGGL((k_fmds_scan_apply<true, uint64_t, FmdsInMax>), dim3(cdiv(nbk, 1024)), dim3(256), 0, st, im, (const uint64_t*)bpart.p, b);
-		}
+		for (uint64_t *b : {bidx.p, bS.p}) scan_launch<ScanMax>(st, ScanIn<uint64_t>{b, nbk}, nbk, bpart.p, b, nullptr, false);   /* every bucket: the last header up to it */
 		h->qtab.ensure(1);
 		hipLaunchKernelGGL(k_qtab, dim3(1), dim3(64), 0, st, (const Ctl*)h->ctl, h->side, pv, h->qtab.p);
 		const uint64_t FSTEP = OUTCAP * FMDS_BW / 7;             /* frames per staging round */
@@ -2255,5 +2240,43 @@ void rb2_hip_layout(int *leaf_syms, int *tile_leaves, int *string_tile)
 }
 
 } // extern "C"
+
+/* the scans of rb2_scan.h on host arrays (tests/test_scan_gpu.py): in place on the device, one synchronise */
+template <class Op, class T = typename Op::type> static void scan_check_run(rb2_hip_t *h, int form, uint64_t n, const uint64_t *in, uint64_t *out, uint64_t *parts, uint64_t *total)
+{
+	const size_t np = form == 0 ? scan_parts(n) - 1 : 0;
+	std::vector<T> x(n + 1, 0), p(np + 1, 0);
+	for (uint64_t i = 0; i < n; ++i) x[i] = (T)in[i];
+	DevBuf<T> d;                                                /* the items and out[n], the total, the parts */
+	d.ensure(n + 2 + scan_parts(n));
+	T *tot = d.p + n + 1, *part = tot + 1;
+	HIPCHK(hipMemcpyAsync(d.p, x.data(), (n + 1) * sizeof(T), hipMemcpyHostToDevice, h->st));
+	HIPCHK(hipMemsetAsync(tot, 0xff, sizeof(T), h->st));
+	const ScanIn<T> si{d.p, n};
+	if (form == 0) scan_launch<Op>(h->st, si, n, part, d.p, tot, true);
+	else if constexpr (std::is_same<Op, ScanAdd<uint64_t>>::value) {   /* (the one op the callers scan with a single block) */
+		if (form == 1) hipLaunchKernelGGL((k_scan_block<Op, ScanIn<T>, 256>), dim3(1), dim3(256), 0, h->st, si, d.p);
+		else hipLaunchKernelGGL((k_scan_block<Op, ScanIn<T>, SCHUNK>), dim3(1), dim3(SCHUNK), 0, h->st, si, d.p);
+	}
+	HIPCHK(hipGetLastError());
+	HIPCHK(hipMemcpyAsync(x.data(), d.p, (n + 1) * sizeof(T), hipMemcpyDeviceToHost, h->st));
+	HIPCHK(hipMemcpyAsync(p.data(), tot, (np + 1) * sizeof(T), hipMemcpyDeviceToHost, h->st));
+	HIPCHK(hipStreamSynchronize(h->st));
+	d.release();
+	for (uint64_t i = 0; i <= n; ++i) out[i] = x[i];
+	*total = form == 0 ? (uint64_t)p[0] : out[n];
+	for (size_t b = 0; b < np; ++b) parts[b] = p[b + 1];
+}
+
+extern "C" int64_t rb2_hip_scan_check(rb2_hip_t *h, int op, int form, int64_t n, const uint64_t *in, uint64_t *out, uint64_t *parts, uint64_t *total)
+{ finish_pending(h);
+	HIPCHK(hipSetDevice(h->dev));
+	if (op < 0 || op > 3 || form < 0 || form > 2 || n < 0 || (form != 0 && op != 1)) { rb2_fatal("[rb2_hip] scan_check: no scan with op %d in form %d over %lld items\n", op, form, (long long)n); }
+	if (op == 0) scan_check_run<ScanAdd<uint32_t>>(h, form, (uint64_t)n, in, out, parts, total);
+	else if (op == 1) scan_check_run<ScanAdd<uint64_t>>(h, form, (uint64_t)n, in, out, parts, total);
+	else if (op == 2) scan_check_run<ScanSat>(h, form, (uint64_t)n, in, out, parts, total);
+	else scan_check_run<ScanMax>(h, form, (uint64_t)n, in, out, parts, total);
+	return form == 0 ? SCAN_ITEMS : form == 1 ? 256 : SCHUNK;
+}
 
 #include "rb2_multi.h"

@@ -5,7 +5,7 @@
 // block of the stream is such a header alone.  Behind the header, runs are coded most-significant bit first, an Elias-delta length and a
 // 3-bit symbol each, never across two blocks; the rest of the block is zero.  So every block decodes on its own, one lane per block:
 //   k_fmd_sizes   symbols of every block (the total in the NEXT header), summed per group of 256 blocks; header types checked
-//   k_fmd_scan    exclusive prefix over the groups (one workgroup): the global row of each group's first symbol
+//   k_scan_block  (rb2_scan.h) exclusive prefix over the groups, in place (one workgroup): the global row of each group's first symbol
 //   k_fmd_count   decode every block by count; the six counts checked against the next header; runs cut at the rope boundaries the
 //                 file's marginal counts give (the six ropes are concatenated and equal symbols merge across a boundary); the 6 x 6
 //                 matrix "symbol a in rope b" tallied in LDS and flushed once per workgroup
@@ -98,21 +98,6 @@ __global__ __launch_bounds__(256) void k_fmd_sizes(const uint64_t *w, uint64_t n
 	uint64_t tot;
 	block_excl_add<uint64_t>(n, s_w, &tot);
 	if (threadIdx.x == 0) wg_tot[blockIdx.x] = tot;
-}
-
-// one workgroup: v[0 .. n) becomes its exclusive prefix, v[n] the total
-__global__ __launch_bounds__(256) void k_fmd_scan(uint64_t *v, uint64_t n)
-{
-	__shared__ uint64_t s_w[4];
-	uint64_t run = 0;
-	for (uint64_t i0 = 0; i0 < n; i0 += 256) {
-		const uint64_t i = i0 + threadIdx.x, x = i < n ? v[i] : 0;
-		uint64_t tot;
-		const uint64_t ex = block_excl_add<uint64_t>(x, s_w, &tot);
-		if (i < n) v[i] = run + ex;
-		run += tot;
-	}
-	if (threadIdx.x == 0) v[n] = run;
 }
 
 // what both decoding passes begin with: stage my block, read the header behind it; returns the bit my payload starts at

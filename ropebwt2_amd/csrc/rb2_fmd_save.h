@@ -4,7 +4,8 @@
 // previous batch could not finish, then the heads found in the next leaves of the piece at hand.  The length of a run is the distance to the
 // next head, so the last head of a batch is an open run (until the batch that flushes, which ends with a head at the row count).  From the heads:
 //   k_fmds_heads<false/true>  run heads straight from the plane words by neighbour compare: counted per block, then compacted behind a scan
-//   k_fmds_scan_*             W[] = prefix sum of the code widths (the same three kernels scan the head counts and fill the frame buckets)
+//   k_scan_part/_top/_apply   (rb2_scan.h) W[] = prefix sum of the code widths; the same three launches scan the head counts (sums) and fill the frame
+//                             buckets (running maximum)
 //   k_fmds_next               for every run i and header type t: where the block that starts at i ends (bisection over W) and the type behind it
 //   k_fmds_table              per segment of RB2_FMDS_SEG runs and entry state (run < 96, type): where a walk along next[] leaves it, after how many blocks
 //   k_fmds_group              the same for 64 segments: the composition of their tables
@@ -82,78 +83,12 @@ __global__ void k_fmds_begin(FmdsState *st, uint64_t *rec, uint64_t ncur, const 
 	st->nout = 0; st->carry = 0; st->ctype = type0; st->done = 0; st->cut = 0;
 }
 
-// ---- three-kernel scans over in(i), i < in.n(), 1024 items per block ---------------------------------------------------------------------
-// MAX = false: out[i] = the sum of the items in front of i, out[n] = the total.  MAX = true: out[i] = the maximum of the items up to and including i.
-struct FmdsInCount { const uint32_t *v; uint64_t nn; __device__ uint64_t n() const { return nn; } __device__ uint32_t operator()(uint64_t i) const { return v[i]; } };
+// the code widths of the complete runs, as rb2_scan.h reads an input: their number is known on the device only
 struct FmdsInWidth {
 	const uint64_t *rec; const FmdsState *st;
 	__device__ uint64_t n() const { return st->nc; }
 	__device__ uint32_t operator()(uint64_t i) const { return fmds_width((rec[i + 1] >> 3) - (rec[i] >> 3)); }
 };
-struct FmdsInMax { const uint64_t *v; uint64_t nn; __device__ uint64_t n() const { return nn; } __device__ uint64_t operator()(uint64_t i) const { return v[i]; } };
-template <bool MAX, typename T> __device__ __forceinline__ T fmds_op(T a, T b) { return MAX ? (a > b ? a : b) : a + b; }
-// scan of v over the block of 256 threads: returns what the threads in front of this one hold together (0 for the first), *total = the block's result
-template <bool MAX, typename T> __device__ __forceinline__ T fmds_block_excl(T v, T *s_x, T *total)
-{
-	const int l = lane_id(), w = wave_id();
-#pragma unroll
-	for (int d = 1; d < 64; d <<= 1) { const T t = __shfl_up(v, d); if (l >= d) v = fmds_op<MAX>(v, t); }
-	s_x[threadIdx.x] = v;
-	__syncthreads();
-	T off = 0, tot = 0;
-	for (int i = 0; i < 4; ++i) { const T x = s_x[i * 64 + 63]; if (i < w) off = fmds_op<MAX>(off, x); tot = fmds_op<MAX>(tot, x); }
-	const T prev = l ? s_x[threadIdx.x - 1] : (T)0;
-	__syncthreads();
-	*total = tot;
-	return fmds_op<MAX>(off, prev);
-}
-template <bool MAX, typename T, class F> __global__ __launch_bounds__(256) void k_fmds_scan_part(F in, T *part)
-{
-	__shared__ T s_x[256];
-	const uint64_t n = in.n(), i0 = ((uint64_t)blockIdx.x * 256 + threadIdx.x) * 4;
-	if ((uint64_t)blockIdx.x * 1024 >= n) return;
-	T v = 0;
-#pragma unroll
-	for (int k = 0; k < 4; ++k) if (i0 + k < n) v = fmds_op<MAX>(v, (T)in(i0 + k));
-	T tot;
-	fmds_block_excl<MAX>(v, s_x, &tot);
-	if (threadIdx.x == 0) part[blockIdx.x] = tot;
-}
-// part[i] = the blocks up to and including i, in place (one block)
-template <bool MAX, typename T, class F> __global__ __launch_bounds__(256) void k_fmds_scan_top(F in, T *part)
-{
-	__shared__ T s_x[256];
-	const uint64_t np = (in.n() + 1023) / 1024;
-	T run = 0;
-	for (uint64_t i0 = 0; i0 < np; i0 += 256) {
-		const uint64_t i = i0 + threadIdx.x;
-		const T v = i < np ? part[i] : (T)0;
-		T tot;
-		const T ex = fmds_block_excl<MAX>(v, s_x, &tot);
-		if (i < np) part[i] = fmds_op<MAX>(run, fmds_op<MAX>(ex, v));
-		run = fmds_op<MAX>(run, tot);
-	}
-}
-template <bool MAX, typename T, class F> __global__ __launch_bounds__(256) void k_fmds_scan_apply(F in, const T *part, T *out)
-{
-	__shared__ T s_x[256];
-	const uint64_t n = in.n(), i0 = ((uint64_t)blockIdx.x * 256 + threadIdx.x) * 4;
-	if (n == 0 && blockIdx.x == 0 && threadIdx.x == 0 && !MAX) out[0] = 0;
-	if ((uint64_t)blockIdx.x * 1024 >= n) return;
-	T v[4], sum = 0;
-#pragma unroll
-	for (int k = 0; k < 4; ++k) { v[k] = i0 + k < n ? (T)in(i0 + k) : (T)0; sum = fmds_op<MAX>(sum, v[k]); }
-	T tot;
-	T run = fmds_op<MAX>(blockIdx.x ? part[blockIdx.x - 1] : (T)0, fmds_block_excl<MAX>(sum, s_x, &tot));
-#pragma unroll
-	for (int k = 0; k < 4; ++k) {
-		if (i0 + k >= n) break;
-		if (!MAX) out[i0 + k] = run;
-		run = fmds_op<MAX>(run, v[k]);
-		if (MAX) out[i0 + k] = run;
-		if (!MAX && i0 + k + 1 == n) out[n] = run;
-	}
-}
 
 // ---- block boundaries -----------------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void k_fmds_next(const FmdsState *st, const uint64_t *rec, const uint32_t *W, uint32_t *nxt)

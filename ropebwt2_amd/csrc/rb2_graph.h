@@ -5,7 +5,7 @@
 //   k_graph_cut     one thread, at the head of a chunk: closes the chunk before (the running base of the call moves by its edges) and
 //                   cuts the strings tried at the text budget (graph_text_cut); k_graph_lmax: the longest string taken, which sizes the stacks
 //   k_graph_count   one thread per source: its edges = the sum over its stored records of min(zhi - zlo, max_hits); the counters of info
-//   (k_unitig_scan_*: exclusive sums of the counts in place)
+//   (scan_launch<ScanSat>, rb2_scan.h: exclusive sums of the counts in place)
 //   k_graph_emit    one DPP row (16 lanes) per source: the row walks its records with a running offset, the lanes take the hits of a
 //                   record side by side, so the rows of a source are written in their order by neighbouring lanes, 32 bytes each, and
 //                   no second scan is needed.  A row at or above cap is not stored; a `$` rank that is no string is not read.

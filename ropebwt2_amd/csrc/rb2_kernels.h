@@ -17,6 +17,7 @@
 //              (mrope.c:226-229, 303-309, 332-340)
 #pragma once
 #include "rb2_device.h"
+#include "rb2_scan.h"
 
 namespace rb2 {
 
@@ -110,22 +111,6 @@ __global__ __launch_bounds__(256) void k_pair_hist(const uint8_t *s /* 16-byte a
 	}
 	__syncthreads();
 	if (threadIdx.x < 36 && h[threadIdx.x]) atomicAdd(&out[threadIdx.x], (unsigned long long)h[threadIdx.x]);
-}
-
-// in-place exclusive scan of the per-block sentinel counts (one block); blk[n] = total = number of strings
-__global__ __launch_bounds__(SCHUNK) void k_zscan(uint64_t *blk, uint32_t n)
-{
-	__shared__ uint64_t s_w[16];
-	uint64_t run = 0;
-	for (uint32_t i0 = 0; i0 < n; i0 += SCHUNK) {
-		const uint32_t i = i0 + threadIdx.x;
-		const uint64_t v = i < n ? blk[i] : 0ull;
-		uint64_t tot;
-		const uint64_t ex = block_excl_add<uint64_t>(v, s_w, &tot);
-		if (i < n) blk[i] = run + ex;
-		run += tot;
-	}
-	if (threadIdx.x == 0) blk[n] = run;
 }
 
 // START[id+1] = position after the id-th sentinel; START[0] = 0

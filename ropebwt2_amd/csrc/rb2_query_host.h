@@ -658,13 +658,10 @@ void rb2_hip_unitig_chains_dev(rb2_hip_t *h, int64_t n_str, int64_t m, const int
 	HIPCHK(hipGetLastError());
 }
 
-/* exclusive prefix sums of x[0 .. n) in place on the device, their total into *total */
+/* exclusive saturating prefix sums of x[0 .. n) in place on the device, their total into *total; bsum: scan_parts(n) words */
 static void unitig_scan(rb2_hip_t *h, uint64_t *x, int64_t n, uint64_t *bsum, unsigned long long *total)
 {
-	const uint64_t nb = cdiv((uint64_t)n, UT_SCAN);
-	hipLaunchKernelGGL(k_unitig_scan_sum, dim3((unsigned)nb), dim3(256), 0, h->st, (const uint64_t*)x, (uint64_t)n, bsum);
-	hipLaunchKernelGGL(k_unitig_scan_top, dim3(1), dim3(256), 0, h->st, bsum, nb, total);
-	hipLaunchKernelGGL(k_unitig_scan_add, dim3((unsigned)nb), dim3(256), 0, h->st, x, (uint64_t)n, (const uint64_t*)bsum);
+	scan_launch<ScanSat>(h->st, ScanIn<uint64_t>{x, (uint64_t)n}, (uint64_t)n, bsum, x, (uint64_t*)total, false);
 	HIPCHK(hipGetLastError());
 }
 
@@ -684,8 +681,7 @@ static int64_t unitig_text_run(rb2_hip_t *h, int64_t n, const int64_t *vtx, int 
 	int64_t inf[4] = {0, 0, 0, 0};
 	if (n > 0) {
 		if (cap_u == 0 || cap_txt == 0) cap_u = cap_txt = 0;       // sizes only
-		const int64_t nb = (int64_t)cdiv((uint64_t)n, UT_SCAN);
-		h->qscr.ensure((size_t)(UT_CTRS + 10 * n + nb + 1) * 8);
+		h->qscr.ensure(((size_t)(UT_CTRS + 10 * n) + scan_parts((uint64_t)n)) * 8);
 		uint64_t *w = (uint64_t*)h->qscr.p;
 		unsigned long long *ctr = (unsigned long long*)w; w += UT_CTRS;
 		UtHeads H; UtSel S;
@@ -790,7 +786,7 @@ static void graph_clean_check(rb2_hip_t *h, const char *who, int64_t n, int64_t 
 static int64_t graph_clean_run(rb2_hip_t *h, int64_t n, int64_t m, const int64_t *ed, int64_t max_tip, int64_t max_bubble, int pairs, int64_t max_rounds, int64_t cap, int64_t *out,
                                int64_t info[8])
 {
-	const int64_t nb = (int64_t)cdiv((uint64_t)std::max(m, n + 1), UT_SCAN) + 1;
+	const int64_t nb = (int64_t)scan_parts((uint64_t)std::max(m, n + 1));
 	const size_t chain_words = (size_t)(UT_CTRS + 12 * n), words = (size_t)(CL_CTRS + 11 * n + 1 + m + nb);
 	h->qscr.ensure((chain_words + words) * 8 + (size_t)(m + 3 * n));   // (first, for the whole call: unitig_chain_bufs then finds its room in front and moves nothing)
 	int64_t *w = (int64_t*)h->qscr.p + chain_words;
@@ -906,7 +902,7 @@ struct UnpackScr { unsigned long long *ctr; uint64_t *bsum; };
  * place.  Queued on the handle's stream */
 static UnpackScr unpack_offsets(rb2_hip_t *h, int64_t first, int64_t n, uint64_t *x)
 {
-	h->qscr.ensure((size_t)(2 + cdiv((uint64_t)n + 1, UT_SCAN)) * 8);
+	h->qscr.ensure((2 + scan_parts((uint64_t)n + 1)) * 8);
 	const UnpackScr s = {(unsigned long long*)h->qscr.p, (uint64_t*)h->qscr.p + 2};
 	HIPCHK(hipMemsetAsync(s.ctr, 0, 16, h->st));
 	HIPCHK(hipMemsetAsync(x + n, 0, 8, h->st));
@@ -1004,7 +1000,7 @@ int64_t rb2_hip_merge(rb2_hip_t *dst, rb2_hip_t *src, int64_t batch_bytes, int64
 	query_begin(src, "merge");
 	int64_t inf[4] = {0, 0, 0, 0};
 	if (info) memcpy(info, inf, sizeof(inf));
-	const int64_t n = (int64_t)src->h_rope[0].n, B = UT_SCAN, nb = (int64_t)cdiv((uint64_t)n, UT_SCAN);
+	const int64_t n = (int64_t)src->h_rope[0].n, B = SCAN_ITEMS, nb = (int64_t)cdiv((uint64_t)n, SCAN_ITEMS);   // (part[b] = off[b * B]: rb2_scan.h)
 	if (n == 0) return 0;
 	/* the offsets of all of src's strings in one batch text stay on the device (8 bytes a string, in src's staging buffer); the host gets the block sums */
 	src->qin.ensure((size_t)n + 1);
@@ -1078,7 +1074,7 @@ static int64_t string_graph_run(rb2_hip_t *h, const char *who, int64_t first, in
 	query_begin(h, who);
 	GraphPlan plan = graph_plan(graph_chunk(), max_recs);
 	/* qin for the whole call, so that it never moves: the offsets of a chunk, its cnt, its edge counts, their block sums, the words of the call */
-	const int64_t most = std::min(plan.limit, n), nbs = (int64_t)cdiv((uint64_t)most + 1, UT_SCAN);
+	const int64_t most = std::min(plan.limit, n), nbs = (int64_t)scan_parts((uint64_t)most + 1);
 	h->qin.ensure((size_t)(3 * most + 2 + nbs + GR_WORDS));
 	uint64_t *x = (uint64_t*)h->qin.p, *e = x + most + 1, *bsum = e + most + 1;
 	int64_t *cnt = (int64_t*)(bsum + nbs);

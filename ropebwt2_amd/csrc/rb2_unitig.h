@@ -17,20 +17,20 @@
 // without reading anything back: 2 K + 5 launches whatever the graph holds.
 //
 // Texts.  k_unitig_sum gathers per head (atomics into arrays indexed by the head's id) the vertices, the last off and the smallest id;
-// the selected heads are numbered by an exclusive scan over their flags (k_unitig_scan_*: three launches, saturating sums), their
+// the selected heads are numbered by an exclusive scan over their flags (ScanSat, rb2_scan.h: three launches, saturating sums), their
 // lengths come from one walk each (k_unitig_len), the text offsets from a second scan, and then the heads and the other vertices write
 // their symbols in launches of their own (k_unitig_text<SPARSE, HEADS>): a head walks a read's length, another vertex ext_in steps.
 // Every store is tested against the slice of its chain, and every walk is guarded as k_ssa_build's is, so a vtx that did not come from
 // k_unitig_fin, or an edge list of another index, gives wrong bytes inside the slices and nothing else.
 #pragma once
 #include "rb2_query.h"
+#include "rb2_scan.h"
 
 namespace rb2 {
 
 constexpr int UT_BLOCKS = 1 << 16;                 // blocks of a one-thread-per-item launch at the most: the threads stride over the rest
 constexpr int UT_ROWS = 16 * 4096;                 // DPP rows of a launch over the selected heads (their number is on the device only)
-constexpr int UT_SCAN = 4096;                      // items per block of the scan: 256 threads x 16
-constexpr uint64_t UT_SAT = 1ull << 62;            // sums stop here (a text that long is stored nowhere)
+constexpr uint64_t UT_SAT = SCAN_SAT;              // sums stop here (a text that long is stored nowhere)
 constexpr int64_t UT_OFF_MAX = (int64_t)1 << 48;   // an off or ext_in beyond this is no offset into a text: the row is treated as damaged
 
 // the counters of a call, in device memory
@@ -40,7 +40,7 @@ struct UtState { int64_t ptr, rank, off, min; };
 
 __device__ __forceinline__ uint64_t ut_first() { return (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; }
 __device__ __forceinline__ uint64_t ut_stride() { return (uint64_t)gridDim.x * blockDim.x; }
-__device__ __forceinline__ uint64_t ut_sat(uint64_t a, uint64_t b) { return min(a + b, UT_SAT); }   // (a, b <= UT_SAT)
+__device__ __forceinline__ uint64_t ut_sat(uint64_t a, uint64_t b) { return ScanSat::op(a, b); }   // (a, b <= UT_SAT)
 
 // edges [e0, e0 + m) of the caller's list, ed = the first of them: one thread per edge
 __global__ __launch_bounds__(256) void k_unitig_deg(const int64_t *ed, uint64_t m, uint64_t n, uint32_t *outdeg, uint32_t *indeg, int64_t *inedge, unsigned long long *ctr)
@@ -190,56 +190,6 @@ __device__ __forceinline__ bool ut_selected(const UtHeads &H, uint64_t h, int ca
 __global__ __launch_bounds__(256) void k_unitig_sel(uint64_t n, UtHeads H, int canonical, int64_t min_reads)
 {
 	for (uint64_t h = ut_first(); h < n; h += ut_stride()) H.u[h] = ut_selected(H, h, canonical, min_reads) ? 1 : 0;
-}
-
-// exclusive saturating prefix sums of x[0 .. n) in place, in three launches: the totals of the blocks' UT_SCAN items, their prefix (one
-// block), and the items again with their block's prefix in front; *total = the sum of all
-__device__ __forceinline__ uint64_t ut_block_scan(uint64_t v, uint64_t *s_w, uint64_t *total)     // exclusive over the 256 threads
-{
-	const int lane = lane_id(), w = threadIdx.x >> 6;
-	uint64_t inc = v;
-	for (int d = 1; d < 64; d <<= 1) { const uint64_t o = __shfl_up(inc, d); if (lane >= d) inc = ut_sat(inc, o); }
-	__syncthreads();                                               // (s_w may still be read from the turn before)
-	if (lane == 63) s_w[w] = inc;
-	__syncthreads();
-	uint64_t pre = 0, all = 0;
-	for (int k = 0; k < 4; ++k) { if (k < w) pre = ut_sat(pre, s_w[k]); all = ut_sat(all, s_w[k]); }
-	*total = all;
-	return ut_sat(pre, inc - v);                                   // (inc - v: the lanes in front; exact below the cap, and at the cap nothing is stored)
-}
-
-__global__ __launch_bounds__(256) void k_unitig_scan_sum(const uint64_t *x, uint64_t n, uint64_t *bsum)
-{
-	__shared__ uint64_t s_w[4];
-	const uint64_t i0 = (uint64_t)blockIdx.x * UT_SCAN + (uint64_t)threadIdx.x * 16;
-	uint64_t v = 0, all;
-	for (int k = 0; k < 16; ++k) if (i0 + k < n) v = ut_sat(v, min(x[i0 + k], UT_SAT));
-	ut_block_scan(v, s_w, &all);
-	if (threadIdx.x == 0) bsum[blockIdx.x] = all;
-}
-
-__global__ __launch_bounds__(256) void k_unitig_scan_top(uint64_t *bsum, uint64_t nb, unsigned long long *total)
-{
-	__shared__ uint64_t s_w[4];
-	uint64_t base = 0;
-	for (uint64_t b0 = 0; b0 < nb; b0 += 256) {                    // (the same turns in the whole block)
-		const uint64_t b = b0 + threadIdx.x, v = b < nb ? bsum[b] : 0;
-		uint64_t all;
-		const uint64_t pre = ut_block_scan(v, s_w, &all);
-		if (b < nb) bsum[b] = ut_sat(base, pre);
-		base = ut_sat(base, all);
-	}
-	if (threadIdx.x == 0) *total = base;
-}
-
-__global__ __launch_bounds__(256) void k_unitig_scan_add(uint64_t *x, uint64_t n, const uint64_t *bsum)
-{
-	__shared__ uint64_t s_w[4];
-	const uint64_t i0 = (uint64_t)blockIdx.x * UT_SCAN + (uint64_t)threadIdx.x * 16;
-	uint64_t a[16], v = 0, all;
-	for (int k = 0; k < 16; ++k) { a[k] = i0 + k < n ? min(x[i0 + k], UT_SAT) : 0; v = ut_sat(v, a[k]); }
-	uint64_t run = ut_sat(bsum[blockIdx.x], ut_block_scan(v, s_w, &all));
-	for (int k = 0; k < 16; ++k) if (i0 + k < n) { x[i0 + k] = run; run = ut_sat(run, a[k]); }
 }
 
 // behind the first scan: the selected heads in their order, u[h] = -1 for the others

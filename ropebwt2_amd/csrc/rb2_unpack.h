@@ -4,7 +4,7 @@
 // is `$`.  Two passes, one string per DPP row (16 lanes) each:
 //   k_unpack_len   walks string first + i and writes len + 1 into x[i] (the symbols and the closing 0); a walk that does not end counts
 //                  in *bad.  The guard is k_ssa_build's (ut_walk): steps counted against N, a row tested before it is ranked.
-//   (k_unitig_scan_*: exclusive sums of x in place -- the offsets)
+//   (scan_launch<ScanSat>, rb2_scan.h: exclusive sums of x in place -- the offsets)
 //   k_unpack_text  walks again and stores.  Lane g of the row keeps the symbol of the steps j with j & 15 == g; behind step 16 q + 15, and
 //                  behind the last step, the row stores what it holds with ONE store instruction: lane g writes the byte of step 16 q + g,
 //                  sixteen neighbouring bytes of the slice (ascending addresses when reversed, descending in text order: the same packing,

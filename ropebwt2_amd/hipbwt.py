@@ -110,6 +110,7 @@ def load_hip_lib():
         "rb2_hip_profile_get": (None, [vp, vp, vp, vp, i32]),
         "rb2_hip_kernel_name": (C.c_char_p, [i32]),
         "rb2_hip_layout": (None, [vp, vp, vp]),
+        "rb2_hip_scan_check": (i64, [vp, i32, i32, i64, vp, vp, vp, vp]),
         "rb2_hip_multi_create": (vp, [i32, vp, i32, i32, vp]),
         "rb2_hip_multi_unique_id": (None, [vp]),
         "rb2_hip_multi_create_rank": (vp, [i32, i32, i32, vp, i32, vp]),
@@ -164,7 +165,7 @@ ABI_SYMBOLS = [
     "rb2_hip_string_graph", "rb2_hip_string_graph_dev", "rb2_hip_graph_clean", "rb2_hip_graph_clean_dev",
     "rb2_hip_num_subropes", "rb2_hip_memcpy", "rb2_hip_use_stream",
     "rb2_hip_dev_free", "rb2_hip_synth_reads", "rb2_hip_synth_reads_cov", "rb2_hip_synth_reads_skew", "rb2_hip_sync", "rb2_hip_sparse_stats", "rb2_hip_layout_stats", "rb2_hip_rewind_stats", "rb2_hip_steady_stats", "rb2_hip_lean_stats", "rb2_hip_lean_count_stats", "rb2_hip_lean_fork_stats", "rb2_hip_lean_dir_stats", "rb2_hip_window_stats", "rb2_hip_host_register", "rb2_hip_host_unregister", "rb2_hip_profile",
-    "rb2_hip_profile_get", "rb2_hip_kernel_name", "rb2_hip_layout",
+    "rb2_hip_profile_get", "rb2_hip_kernel_name", "rb2_hip_layout", "rb2_hip_scan_check",
     "rb2_hip_multi_create", "rb2_hip_multi_unique_id", "rb2_hip_multi_create_rank", "rb2_hip_multi_destroy", "rb2_hip_default_owners",
     "rb2_hip_multi_nranks", "rb2_hip_multi_transport", "rb2_hip_multi_nlocal", "rb2_hip_multi_engine", "rb2_hip_multi_insert_multi", "rb2_hip_multi_insert_multi_dev",
     "rb2_hip_multi_get_counts", "rb2_hip_multi_rope_bytes", "rb2_hip_multi_download_rope", "rb2_hip_multi_stream_rope",
@@ -1034,6 +1035,18 @@ class HipBwt:
         un = np.zeros(n, np.int64)
         self.L.rb2_hip_profile_get(self.h, la.ctypes.data, ms.ctypes.data, un.ctypes.data, 1 if reset else 0)
         return {K_NAMES[i]: {"launches": int(la[i]), "ms": float(ms[i]), "units": int(un[i])} for i in range(n)}
+
+    SCAN_OPS = {"add32": 0, "add64": 1, "sat": 2, "max": 3}
+    SCAN_FORMS = {"multi": 0, "block256": 1, "block1024": 2}
+
+    def scan_check(self, op, form, values):
+        """one of the engine's cold-path prefix scans (rb2_hip_scan_check) over values: (out[0 .. n], the block prefixes, the total word, items per block)"""
+        x = np.ascontiguousarray(values, np.uint64)
+        out = np.zeros(len(x) + 1, np.uint64)
+        parts = np.zeros(len(x) // 256 + 2, np.uint64)
+        tot = np.zeros(1, np.uint64)
+        per = int(self.L.rb2_hip_scan_check(self.h, self.SCAN_OPS[op], self.SCAN_FORMS[form], len(x), x.ctypes.data, out.ctypes.data, parts.ctypes.data, tot.ctypes.data))
+        return out, parts[:(len(x) + per - 1) // per] if form == "multi" else None, int(tot[0]), per
 
     @staticmethod
     def layout():

@@ -30,6 +30,6 @@ def test_kernels_are_in_the_code_object():
     from ropebwt2_amd.build import lib_path
     build_all()
     data = open(lib_path("librb2hip.so"), "rb").read()
-    for k in (b"k_fmds_heads", b"k_fmds_scan_part", b"k_fmds_scan_top", b"k_fmds_scan_apply", b"k_fmds_next", b"k_fmds_table", b"k_fmds_group", b"k_fmds_resolve",
+    for k in (b"k_fmds_heads", b"k_scan_part", b"k_scan_top", b"k_scan_apply", b"k_fmds_next", b"k_fmds_table", b"k_fmds_group", b"k_fmds_resolve",
               b"k_fmds_down", b"k_fmds_write", b"k_fmds_hdrfix", b"k_fmds_carry", b"k_fmds_frames"):
         assert k in data, k
