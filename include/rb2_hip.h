@@ -592,6 +592,58 @@ int64_t rb2_hip_graph_clean(rb2_hip_t *h, int64_t n_str, int64_t m, const int64_
 int64_t rb2_hip_graph_clean_dev(rb2_hip_t *h, int64_t n_str, int64_t m, const int64_t *edges, int64_t max_tip_reads, int64_t max_bubble_reads, int pairs, int64_t max_rounds,
                                 int64_t cap, int64_t *out, int64_t info[8]);
 
+/* ---- correcting reads by the k-mer spectrum of the index (csrc/rb2_correct.h, csrc/rb2_correct_plan.h) ----
+ * The step in front of the overlaps: every exact query stops at the first wrong symbol, so a read with one wrong base loses what lies
+ * behind it.  The reads are corrected from the counts of their own k-mers in the index, substitutions only.
+ * occ(w) = the occurrences of the word w in the indexed strings: hi - lo of rb2_hip_backward_search on w when the whole word matched
+ * (m == k), 0 otherwise; an index of both strands counts both strands.  For a read q of L symbols (nt6 codes 1 .. 5):
+ *   WINDOW j (0 <= j <= L - k) is q[j .. j + k).  It is CLEAN when all its symbols are A C G T, SOLID when it is clean and occ >= min_occ.
+ *   Position p is WEAK when no solid window contains it.  An N is always weak.
+ *   A PROBE is one evaluation of occ on a clean word, and probes are counted; a window that is not clean costs none and is not solid.
+ *   Before every probe: if max_probes have been made, the read is OVER BUDGET and stops where it is.
+ *   PROFILE: probe the clean windows in increasing j.
+ *   LOOP, while fewer than max_fix fixes have been made: stop if no position is weak.  Otherwise go through the weak positions in
+ *   increasing p; for each try window ja = max(p - k + 1, 0) (p as far right in it as can be), then jb = min(p, L - k) (as far left; once
+ *   only when they are the same window).  A window is tried only if all its symbols other than q[p] are A C G T; trying it means
+ *   probing it with b at p for b = A, C, G, T, b != q[p], in that order.  If exactly ONE b is solid: q[p] = b, one FIX, the windows
+ *   max(0, p - k + 1) .. min(p, L - k) are evaluated again in increasing j (clean ones probed, the others not solid), and the loop starts
+ *   again.  If no weak position yields a fix, stop.
+ *   A read with L < k has no window: it comes back as it is with weak = L.
+ * Per read: its text with only the fixes changed; cnt >= 0 the fixes; cnt == -1 a malformed read (a code 0 or above 5, more than 8192
+ * symbols), its text copied unchanged; cnt <= -2 a read over budget with -2 - cnt fixes made, all of them in the text (a fix whose
+ * re-evaluation ran out of probes included); weak = the weak positions at the end, -1 for a malformed read or one over budget.
+ * The rule is a heuristic: it restores what a unique solid neighbour restores and may correct to something else where two errors share
+ * their windows.  The probe count is fixed by the rule and not by the implementation, so that a model can match budget cases exactly.
+ * A probe costs at most k - 1 pairs of ranks: a call ends after n * max_probes * k pairs whatever the index holds.
+ * rb2_hip_correct: n reads as for rb2_hip_smem.  out is indexed like qry: out[x] answers qry[x] for x in [off[0], off[n]) and nothing else
+ * is written; cnt and weak hold n values each.  Returns the sum of the fixes, those of reads over budget included.  n <= 0 returns 0
+ * before the parameters are checked; k, min_occ, max_fix or max_probes below 1 is fatal, each with a message of its own.  The host variant
+ * stages chunks of RB2_QUERY_CHUNK reads.  Like every query the call waits for a lazy insert, reads the index and nothing else (layout,
+ * rope hashes and a sampled suffix array stay as they were), works on both layouts and is fatal on one rank of a sharded index.
+ * One read per 16 lanes (k_correct); the solid bits, one per window, are 1 KiB of LDS per read in flight, so the call sizes nothing from
+ * the lengths; at most 2^15 reads are in flight and a row takes further reads a launch apart (RB2_CORRECT_ROWS in the environment, read
+ * on every call, lowers the rows: tests). */
+int64_t rb2_hip_correct(rb2_hip_t *h, int64_t n, const uint8_t *qry, const int64_t *off, int64_t k, int64_t min_occ, int64_t max_fix, int64_t max_probes, uint8_t *out, int64_t *cnt, int64_t *weak);
+/* the same with every pointer in this device's memory, asynchronous on the handle's stream (no return value: read cnt).  total = the
+ * caller's bound on off[n] - off[0] (fatal when negative; this implementation keeps the solid bits in LDS and sizes nothing from it).
+ * out == qry is allowed: the reads are then corrected where they lie. */
+void    rb2_hip_correct_dev(rb2_hip_t *h, int64_t n, const uint8_t *qry, const int64_t *off, int64_t total, int64_t k, int64_t min_occ, int64_t max_fix, int64_t max_probes,
+                            uint8_t *out, int64_t *cnt, int64_t *weak);
+/* rb2_hip_correct_into corrects EVERY string of src against src and inserts the results into dst without leaving the device: string k of
+ * src becomes string n_dst + k in input order.  The batches are cut as rb2_hip_merge cuts them (batch_bytes, its default when 0,
+ * RB2_MERGE_BATCH); each is unpacked in text order, corrected into a second buffer, compared, turned round in place (an insert batch
+ * holds every string last symbol first and 0-terminated) and inserted.  pairs != 0: strings 2i and 2i + 1 of src are reverse complements
+ * of each other (the caller's responsibility, as for rb2_hip_string_graph); only 2i is corrected and 2i + 1 is written as the reverse
+ * complement of the result, so dst stays an index of both strands at half the probes; a batch then holds whole pairs.
+ * Returns the symbols added, sentinels included.  info (may be NULL) = strings, strings whose text changed, fixes, strings left with a
+ * weak position, strings over budget, malformed strings (longer than 8192 symbols: copied as they are), batches, bytes of the largest
+ * batch; with pairs the four counts in the middle and the changed strings count the strings 2i only.
+ * src is UNCHANGED (rope hashes, layout, sampled suffix array); dst's sampled suffix array is dropped, as after any insert.  Device
+ * memory beyond the two indexes: two batch texts, 8 bytes per string of src and 16 per corrected string of a batch.
+ * Fatal, each with a message of its own and before anything is changed: dst == src; handles on different devices; either handle one rank
+ * of a sharded index; batch_bytes < 0; k, min_occ, max_fix or max_probes below 1; pairs != 0 on an odd number of strings. */
+int64_t rb2_hip_correct_into(rb2_hip_t *dst, rb2_hip_t *src, int64_t k, int64_t min_occ, int64_t max_fix, int64_t max_probes, int pairs, int64_t batch_bytes, int64_t info[8]);
+
 /* ---- rope sharding across GPUs ---------------------------------------------------------------
  * The unit of ownership is a SUB-ROPE: rope b is kept as six independent pieces (b,x), x = the symbol that follows b in the
  * row's suffix (piece (b,x) holds exactly the b-symbols of rope x; rope $ is one piece; NR = 31 pieces, see rb2_device.h).

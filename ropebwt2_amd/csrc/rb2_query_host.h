@@ -1145,3 +1145,135 @@ int64_t rb2_hip_string_graph(rb2_hip_t *h, int64_t first, int64_t n, int64_t min
 	if (info) memcpy(info, inf, sizeof(inf));
 	return m;
 }
+
+/* ---- reads corrected by the k-mer spectrum of the index (k_correct in rb2_correct.h, the rule in rb2_correct_plan.h) ---- */
+
+/* rows of a launch at the most: CORRECT_ROWS; RB2_CORRECT_ROWS in the environment, read on every call, lowers it (tests of rows that take several reads) */
+static int64_t correct_row_cap()
+{
+	const char *e = getenv("RB2_CORRECT_ROWS");
+	const int64_t v = e ? atoll(e) : 0;
+	return v > 0 ? std::min(v, CORRECT_ROWS) : CORRECT_ROWS;
+}
+
+static void correct_check(const char *who, int64_t k, int64_t min_occ, int64_t max_fix, int64_t max_probes)
+{
+	if (k < 1) { rb2_fatal("[rb2_hip] %s: k must be at least 1 (got %lld)\n", who, (long long)k); }
+	if (min_occ < 1) { rb2_fatal("[rb2_hip] %s: min_occ must be at least 1 (got %lld)\n", who, (long long)min_occ); }
+	if (max_fix < 1) { rb2_fatal("[rb2_hip] %s: max_fix must be at least 1 (got %lld)\n", who, (long long)max_fix); }
+	if (max_probes < 1) { rb2_fatal("[rb2_hip] %s: max_probes must be at least 1 (got %lld)\n", who, (long long)max_probes); }
+}
+
+/* n items, all device pointers: item i is string i * stride of the packed batch (end0: packed strings with their closing 0); one launch,
+ * the solid bits in LDS, so nothing is sized here */
+static void launch_correct(rb2_hip_t *h, int64_t n, int64_t stride, bool end0, const uint8_t *qry, const int64_t *off, int64_t base, int64_t k, int64_t min_occ, int64_t max_fix,
+                           int64_t max_probes, uint8_t *out, int64_t *cnt, int64_t *weak)
+{
+	const int64_t rows = correct_rows(n, correct_row_cap());
+	if (end0) qlaunch(h, k_correct<true, true>, k_correct<false, true>, (uint64_t)rows, qry, off, base, n, stride, k, min_occ, max_fix, max_probes, rows, out, cnt, weak);
+	else qlaunch(h, k_correct<true, false>, k_correct<false, false>, (uint64_t)rows, qry, off, base, n, stride, k, min_occ, max_fix, max_probes, rows, out, cnt, weak);
+}
+
+static int64_t correct_fixes(int64_t c) { return c >= 0 ? c : c <= -2 ? -2 - c : 0; }
+
+int64_t rb2_hip_correct(rb2_hip_t *h, int64_t n, const uint8_t *qry, const int64_t *off, int64_t k, int64_t min_occ, int64_t max_fix, int64_t max_probes, uint8_t *out, int64_t *cnt, int64_t *weak)
+{
+	query_begin(h, "correct");
+	if (n <= 0) return 0;
+	correct_check("correct", k, min_occ, max_fix, max_probes);
+	check_offsets("correct", "read", n, off);
+	const int64_t CH = query_chunk();
+	int64_t fixes = 0;
+	for (int64_t i0 = 0; i0 < n; i0 += CH) {                        // the text of a chunk comes back as it went: the same bytes of out
+		const int64_t nc = std::min(CH, n - i0), nb = off[i0 + nc] - off[i0];
+		const QStaged s = stage_inputs(h, {qry, off, 0}, i0, nc, 2 * nc);
+		h->qout.ensure((size_t)nb / 8 + 1);
+		launch_correct(h, nc, 1, false, s.bytes, s.v, s.base, k, min_occ, max_fix, max_probes, (uint8_t*)h->qout.p, s.tail, s.tail + nc);
+		HIPCHK(hipMemcpyAsync(cnt + i0, s.tail, (size_t)nc * 8, hipMemcpyDeviceToHost, h->st));
+		HIPCHK(hipMemcpyAsync(weak + i0, s.tail + nc, (size_t)nc * 8, hipMemcpyDeviceToHost, h->st));
+		if (nb) HIPCHK(hipMemcpyAsync(out + s.base, h->qout.p, (size_t)nb, hipMemcpyDeviceToHost, h->st));
+		HIPCHK(hipStreamSynchronize(h->st));
+		for (int64_t i = i0; i < i0 + nc; ++i) fixes += correct_fixes(cnt[i]);
+	}
+	return fixes;
+}
+
+void rb2_hip_correct_dev(rb2_hip_t *h, int64_t n, const uint8_t *qry, const int64_t *off, int64_t total, int64_t k, int64_t min_occ, int64_t max_fix, int64_t max_probes,
+                         uint8_t *out, int64_t *cnt, int64_t *weak)
+{
+	query_begin(h, "correct_dev");
+	if (n <= 0) return;
+	correct_check("correct_dev", k, min_occ, max_fix, max_probes);
+	if (total < 0) { rb2_fatal("[rb2_hip] correct_dev: total must not be negative (got %lld)\n", (long long)total); }
+	dev_chunks(n, [&](int64_t i0, int64_t nc) { launch_correct(h, nc, 1, false, qry, off + i0, 0, k, min_occ, max_fix, max_probes, out, cnt + i0, weak + i0); });
+}
+
+int64_t rb2_hip_correct_into(rb2_hip_t *dst, rb2_hip_t *src, int64_t k, int64_t min_occ, int64_t max_fix, int64_t max_probes, int pairs, int64_t batch_bytes, int64_t info[8])
+{
+	if (!dst || !src || dst == src) { rb2_fatal("[rb2_hip] correct_into: dst and src must be two different handles\n"); }
+	if (dst->dev != src->dev) { rb2_fatal("[rb2_hip] correct_into: dst is on device %d and src on device %d; both indexes must be on one device\n", dst->dev, src->dev); }
+	if (dst->nranks > 1 || src->nranks > 1) { rb2_fatal("[rb2_hip] correct_into: %s holds only its own sub-ropes of a sharded index; the call needs both indexes whole, each on one engine\n", dst->nranks > 1 ? "dst" : "src"); }
+	if (batch_bytes < 0) { rb2_fatal("[rb2_hip] correct_into: batch_bytes must not be negative (got %lld)\n", (long long)batch_bytes); }
+	correct_check("correct_into", k, min_occ, max_fix, max_probes);
+	finish_pending(dst);
+	query_begin(src, "correct_into");
+	int64_t inf[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+	if (info) memcpy(info, inf, sizeof(inf));
+	const int64_t n = (int64_t)src->h_rope[0].n, B = SCAN_ITEMS, nb = (int64_t)cdiv((uint64_t)n, SCAN_ITEMS);
+	if (pairs && n % 2) { rb2_fatal("[rb2_hip] correct_into: pairs needs strings 2i and 2i + 1 to be the two strands of a read, but src holds %lld strings\n", (long long)n); }
+	if (n == 0) return 0;
+	const int64_t stride = pairs ? 2 : 1;
+	/* the offsets of all of src's strings in one batch text, as rb2_hip_merge keeps them */
+	src->qin.ensure((size_t)n + 1);
+	uint64_t *x = (uint64_t*)src->qin.p;
+	const UnpackScr s = unpack_offsets(src, 0, n, x);
+	unsigned long long c[2], cc[CORRECT_CTRS];
+	std::vector<uint64_t> bsum((size_t)nb), blk((size_t)B);
+	HIPCHK(hipMemcpyAsync(c, s.ctr, sizeof(c), hipMemcpyDeviceToHost, src->st));
+	HIPCHK(hipMemcpyAsync(bsum.data(), s.bsum, (size_t)nb * 8, hipMemcpyDeviceToHost, src->st));
+	HIPCHK(hipStreamSynchronize(src->st));
+	const int64_t total = unpack_total("correct_into", c);
+	int64_t max_strings;
+	const int64_t budget = merge_budget(dst, batch_bytes, &max_strings);
+	HIPCHK(hipSetDevice(dst->dev));
+	DevBuf<uint8_t> text, batch;                                    // a batch as it was unpacked (text order), and what becomes the insert batch
+	DevBuf<int64_t> res;                                            // the counters of the call, then cnt and weak of a batch
+	text.ensure((size_t)std::min(budget, total) + 64);
+	batch.ensure((size_t)std::min(budget, total) + 64);
+	res.ensure((size_t)CORRECT_CTRS);
+	HIPCHK(hipMemsetAsync(res.p, 0, CORRECT_CTRS * 8, src->st));
+	int64_t i0 = 0, off0 = 0;
+	while (i0 < n) {
+		MergeCut cut = merge_next_cut(bsum.data(), nb, n, (uint64_t)total, B, i0, (uint64_t)off0, (uint64_t)budget, max_strings, blk.data(), [&](int64_t b, uint64_t *buf) {
+			HIPCHK(hipMemcpyAsync(buf, x + b * B, (size_t)std::min(B, n - b * B) * 8, hipMemcpyDeviceToHost, src->st));
+			HIPCHK(hipStreamSynchronize(src->st)); });
+		if (pairs && (cut.end - i0) % 2) {                          // whole pairs: one string less, or the pair when its first string alone is a batch
+			cut.end += cut.end - i0 == 1 ? 1 : -1;
+			HIPCHK(hipMemcpyAsync(&cut.off_end, x + cut.end, 8, hipMemcpyDeviceToHost, src->st));
+			HIPCHK(hipStreamSynchronize(src->st));
+		}
+		const int64_t len = (int64_t)cut.off_end - off0, ns = cut.end - i0, items = ns / stride;
+		text.ensure((size_t)len + 64);                              // (these grow for a string longer than the budget only)
+		batch.ensure((size_t)len + 64);
+		res.ensure((size_t)(CORRECT_CTRS + 2 * items), true, src->st);   // (the counters move with the array)
+		int64_t *cnt = res.p + CORRECT_CTRS, *weak = cnt + items;
+		const int64_t *o = (const int64_t*)x + i0;
+		unpack_texts(src, i0, ns, o, off0, 0, len, text.p);
+		launch_correct(src, items, stride, true, text.p, o, off0, k, min_occ, max_fix, max_probes, batch.p, cnt, weak);
+		hipLaunchKernelGGL(k_correct_mate, dim3((unsigned)cdiv((uint64_t)items, QPB)), dim3(256), 0, src->st, (uint64_t)items, (uint64_t)stride, (const uint8_t*)text.p, batch.p, o, off0,
+				(const int64_t*)cnt, (const int64_t*)weak, (unsigned long long*)res.p);
+		hipLaunchKernelGGL(k_correct_reverse, dim3((unsigned)cdiv((uint64_t)items, QPB)), dim3(256), 0, src->st, (uint64_t)items, (uint64_t)stride, batch.p, o, off0);
+		HIPCHK(hipGetLastError());
+		HIPCHK(hipStreamSynchronize(src->st));                      // the two handles have streams of their own: the batch is complete before dst reads it ...
+		rb2_hip_insert_multi_dev(dst, len, batch.p);
+		HIPCHK(hipStreamSynchronize(dst->st));                      // ... and read before src writes the next one
+		++inf[6]; inf[7] = std::max(inf[7], len);
+		i0 = cut.end; off0 = (int64_t)cut.off_end;
+	}
+	HIPCHK(hipMemcpyAsync(cc, res.p, sizeof(cc), hipMemcpyDeviceToHost, src->st));
+	HIPCHK(hipStreamSynchronize(src->st));
+	text.release(); batch.release(); res.release();
+	inf[0] = n; inf[1] = (int64_t)cc[CC_CHANGED]; inf[2] = (int64_t)cc[CC_FIXES]; inf[3] = (int64_t)cc[CC_WEAK]; inf[4] = (int64_t)cc[CC_OVER]; inf[5] = (int64_t)cc[CC_BAD];
+	if (info) memcpy(info, inf, sizeof(inf));
+	return total;
+}

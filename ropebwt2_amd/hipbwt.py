@@ -85,6 +85,9 @@ def load_hip_lib():
         "rb2_hip_string_graph_dev": (i64, [vp, i64, i64, i64, i64, i64, i64, i64, i32, i64, vp, vp]),
         "rb2_hip_graph_clean": (i64, [vp, i64, i64, vp, i64, i64, i32, i64, i64, vp, vp]),
         "rb2_hip_graph_clean_dev": (i64, [vp, i64, i64, vp, i64, i64, i32, i64, i64, vp, vp]),
+        "rb2_hip_correct": (i64, [vp, i64, vp, vp, i64, i64, i64, i64, vp, vp, vp]),
+        "rb2_hip_correct_dev": (None, [vp, i64, vp, vp, i64, i64, i64, i64, i64, vp, vp, vp]),
+        "rb2_hip_correct_into": (i64, [vp, vp, i64, i64, i64, i64, i32, i64, vp]),
         "rb2_hip_reserve": (None, [vp, i64, i64, i64]),
         "rb2_hip_num_subropes": (i32, []),
         "rb2_hip_memcpy": (None, [vp, vp, vp, i64, i32]),
@@ -163,6 +166,7 @@ ABI_SYMBOLS = [
     "rb2_hip_unitig_chains", "rb2_hip_unitig_chains_dev", "rb2_hip_unitig_text", "rb2_hip_unitig_text_dev",
     "rb2_hip_unpack", "rb2_hip_unpack_dev", "rb2_hip_merge",
     "rb2_hip_string_graph", "rb2_hip_string_graph_dev", "rb2_hip_graph_clean", "rb2_hip_graph_clean_dev",
+    "rb2_hip_correct", "rb2_hip_correct_dev", "rb2_hip_correct_into",
     "rb2_hip_num_subropes", "rb2_hip_memcpy", "rb2_hip_use_stream",
     "rb2_hip_dev_free", "rb2_hip_synth_reads", "rb2_hip_synth_reads_cov", "rb2_hip_synth_reads_skew", "rb2_hip_sync", "rb2_hip_sparse_stats", "rb2_hip_layout_stats", "rb2_hip_rewind_stats", "rb2_hip_steady_stats", "rb2_hip_lean_stats", "rb2_hip_lean_count_stats", "rb2_hip_lean_fork_stats", "rb2_hip_lean_dir_stats", "rb2_hip_window_stats", "rb2_hip_host_register", "rb2_hip_host_unregister", "rb2_hip_profile",
     "rb2_hip_profile_get", "rb2_hip_kernel_name", "rb2_hip_layout", "rb2_hip_scan_check",
@@ -236,10 +240,10 @@ def unpack_subs(subs):
 
 
 class StepBudgetExceeded(RuntimeError):
-    """HipBwt.approx, HipBwt.irreducible: some queries used up max_steps before their search ended; .queries lists them, .results holds
+    """HipBwt.approx, HipBwt.irreducible, HipBwt.correct: some queries used up max_steps before their search ended; .queries lists them, .results holds
     what the call would have returned, with what those queries had found so far"""
-    def __init__(self, queries, results, who="approx", lower="max_mm"):
-        RuntimeError.__init__(self, "%s: %d queries ran out of steps (the first: %s); raise max_steps or lower %s" % (who, len(queries), queries[:5], lower))
+    def __init__(self, queries, results, who="approx", lower="max_mm", budget="max_steps"):
+        RuntimeError.__init__(self, "%s: %d queries ran out of steps (the first: %s); raise %s or lower %s" % (who, len(queries), queries[:5], budget, lower))
         self.queries, self.results = queries, results
 
 
@@ -298,6 +302,7 @@ class HipBwt:
             raise RuntimeError("no HIP device visible: the gfx950 engine has no CPU fallback")
         self.h = self.L.rb2_hip_create(device, sorting_order)
         self.so = sorting_order
+        self.dev = device
 
     def close(self):
         if getattr(self, "h", None):
@@ -954,6 +959,64 @@ class HipBwt:
         info = np.zeros(4, np.int64)
         self.L.rb2_hip_merge(self.h, other.h, batch_bytes, info.ctypes.data)
         return tuple(int(v) for v in info)
+
+    # -- reads corrected by the k-mer spectrum of the index (include/rb2_hip.h) -----------------------
+    @staticmethod
+    def correct_default_probes(reads_len=101, k=21, attempts=32):
+        """the default max_probes, by arithmetic and not measured: the profile of a read of reads_len symbols (at most one probe per
+        symbol) plus `attempts` tried windows of three alternatives each and the k windows a fix re-evaluates: 101 + 32 * 24 = 869"""
+        return int(reads_len) + int(attempts) * (3 + int(k))
+
+    def correct_raw(self, reads, k, min_occ=3, max_fix=8, max_probes=None):
+        """rb2_hip_correct as it is: (fixes, out, off, cnt, weak) -- out[off[i]:off[i + 1]] = read i corrected, cnt[i] >= 0 its fixes,
+        -1 malformed (copied unchanged), <= -2 over budget with -2 - cnt[i] fixes made; weak[i] = weak positions left (-1 for those two)"""
+        qry, off = pack_patterns(reads)
+        n = len(off) - 1
+        if max_probes is None:
+            max_probes = self.correct_default_probes(int(np.diff(off).max(initial=0)), k)
+        out = np.zeros(len(qry), np.uint8)
+        cnt, weak = np.zeros(n, np.int64), np.zeros(n, np.int64)
+        fixes = self.L.rb2_hip_correct(self.h, n, qry.ctypes.data, off.ctypes.data, int(k), int(min_occ), int(max_fix), int(max_probes),
+                                       out.ctypes.data, cnt.ctypes.data, weak.ctypes.data)
+        return int(fixes), out, off, cnt, weak
+
+    def correct(self, reads, k, min_occ=3, max_fix=8, max_probes=None):
+        """the reads (str / bytes over ACGTN, or nt6 arrays) corrected by the k-mer spectrum of the index: (corrected nt6 arrays, cnt,
+        weak); a malformed read comes back as it is with cnt = -1.  max_probes = None: correct_default_probes of the longest read.
+        Raises StepBudgetExceeded when a read ran over its budget: the exception names the reads and carries the same triple, those
+        reads with the fixes made by then"""
+        _, out, off, cnt, weak = self.correct_raw(reads, k, min_occ, max_fix, max_probes)
+        res = ([out[off[i]:off[i + 1]].copy() for i in range(len(off) - 1)], cnt, weak)
+        if (cnt <= -2).any():
+            raise StepBudgetExceeded(np.flatnonzero(cnt <= -2).tolist(), res, "correct", "max_fix", "max_probes")
+        return res
+
+    def correct_dev(self, n, qry_dev, off_dev, total, out_dev, cnt_dev, weak_dev, k, min_occ=3, max_fix=8, max_probes=869):
+        """rb2_hip_correct_dev: all five pointers in this device's memory, total >= off[n] - off[0]; out_dev may be qry_dev;
+        asynchronous on the handle's stream"""
+        self.L.rb2_hip_correct_dev(self.h, n, qry_dev, off_dev, int(total), int(k), int(min_occ), int(max_fix), int(max_probes), out_dev, cnt_dev, weak_dev)
+
+    CORRECT_INFO = ("strings", "changed", "fixes", "weak", "over_budget", "malformed", "batches", "largest_batch")
+
+    def correct_into(self, dst, k, min_occ=3, max_fix=8, max_probes=869, pairs=False, batch_bytes=0):
+        """rb2_hip_correct_into: every string of this index corrected against this index and inserted into dst (a HipBwt on the same
+        device); this index is unchanged.  pairs: strings 2i and 2i + 1 are a read and its reverse complement, only 2i is corrected.
+        Returns the info as a dict (CORRECT_INFO) with the symbols added under the key symbols"""
+        info = np.zeros(8, np.int64)
+        added = self.L.rb2_hip_correct_into(dst.h, self.h, int(k), int(min_occ), int(max_fix), int(max_probes), int(bool(pairs)), int(batch_bytes), info.ctypes.data)
+        d = dict(zip(self.CORRECT_INFO, (int(v) for v in info)))
+        d["symbols"] = int(added)
+        return d
+
+    def corrected(self, k, min_occ=3, max_fix=8, max_probes=869, pairs=False, batch_bytes=0):
+        """a new handle of the same sorting order on the same device that holds this index's strings corrected: (handle, info)"""
+        g = HipBwt(self.so, getattr(self, "dev", 0))
+        try:
+            info = self.correct_into(g, k, min_occ, max_fix, max_probes, pairs, batch_bytes)
+        except BaseException:
+            g.close()
+            raise
+        return g, info
 
     def dev_alloc(self, nbytes):
         return self.L.rb2_hip_dev_alloc(self.h, nbytes)

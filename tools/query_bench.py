@@ -70,6 +70,13 @@ With --merge only rb2_hip_unpack_dev and rb2_hip_merge are measured and stored u
 symbols per second of unpack_dev in both directions against rb2_hip_extract of the same strings (max_len = the read length), and the merge
 of an index of a quarter as many other reads into the benchmark index against extract + a host pass + rb2_hip_insert_multi from the host
 buffer into an identical index (merge_case).
+With --correct only the read correction is measured and stored under "correct" in the --out file, whose other entries stay: on the index of
+the first cases (single strand, unique reads: min_occ = 1), correct_dev on --correct-reads reads of the index with 0, 1 and 2 planted
+substitutions in turn (k = --correct-k, max_fix 8, the default max_probes) -- reads per second, median of three after a warm-up with the
+fastest and the slowest beside it, probes per second from a lower bound (the call does not report the probes of a read: L - k + 1 for its
+profile), the reads restored.  The baseline is what could be composed before: the profile alone, count() on the host-sliced k-mers of
+--correct-sample of the same reads, which must name the same reads as untouched (no weak position <=> cnt == 0 and weak == 0: equals_fused).
+Then correct_into of the whole index into an empty one, timed the same way (the destination reset outside the timed region).
 """
 import argparse
 import json
@@ -1064,6 +1071,74 @@ def merge_case(a, res):
     res["merge"] = out
 
 
+def correct_case(a, res):
+    """rb2_hip_correct_dev and rb2_hip_correct_into on the index of the first cases; see the module docstring"""
+    L, k = 101, a.correct_k
+    n = a.reads or -(-(int(4 * 1024 ** 3 * 0.97) + 1) // (L + 1))
+    P, S = a.correct_reads, a.correct_sample
+    g = HipBwt(a.so)
+    p = g.dev_alloc(n * (L + 1))
+    g.synth_reads(p, 0, n, L, seed=42)
+    g.insert_multi_dev(p, n * (L + 1))
+    g.sync()
+    g.dev_free(p)
+    probes = HipBwt.correct_default_probes(L, k)
+    out = {"index": {"reads": n, "read_len": L, "sorting_order": a.so, "symbols": int(g.counts().sum()), "strands": 1}, "k": k, "min_occ": 1, "max_fix": 8, "max_probes": probes,
+           "measured": True}
+    rng = np.random.RandomState(13)
+    truth = hit_patterns(P, L, n, 101)
+    qs = truth.copy()
+    planted = np.arange(P) % 3
+    for r in (1, 2):                                               # (two may fall on one position: then the second stands)
+        who = np.flatnonzero(planted >= r)
+        at = rng.randint(L, size=len(who))
+        qs[who, at] = 1 + (truth[who, at] + rng.randint(3, size=len(who))) % 4
+    flat = np.ascontiguousarray(qs.reshape(-1))
+    off = np.arange(P + 1, dtype=np.int64) * L
+    dq, do, dt, dc, dw = g.dev_alloc(len(flat)), g.dev_alloc(8 * (P + 1)), g.dev_alloc(len(flat)), g.dev_alloc(8 * P), g.dev_alloc(8 * P)
+    g.L.rb2_hip_memcpy(g.h, dq, flat.ctypes.data, len(flat), 0)
+    g.L.rb2_hip_memcpy(g.h, do, off.ctypes.data, 8 * (P + 1), 0)
+    sec, lo, hi = spread(lambda: g.correct_dev(P, dq, do, P * L, dt, dc, dw, k, 1, 8, probes), g.sync)
+    cnt, weak, got = np.zeros(P, np.int64), np.zeros(P, np.int64), np.zeros(P * L, np.uint8)
+    for d, arr in ((dc, cnt), (dw, weak), (dt, got)):
+        g.L.rb2_hip_memcpy(g.h, arr.ctypes.data, d, arr.nbytes, 1)
+    for d in (dq, do, dt, dc, dw):
+        g.dev_free(d)
+    same = (got.reshape(P, L) == truth).all(1)
+    least = P * (L - k + 1)
+    out["correct_dev"] = {"reads": P, "planted": "0, 1, 2 substitutions in turn", "seconds": sec, "seconds_fastest": lo, "seconds_slowest": hi, "reads_per_s": P / sec,
+                          "probes_at_least": least, "probes_per_s_at_least": least / sec, "fixes": int(np.where(cnt <= -2, -2 - cnt, np.maximum(cnt, 0)).sum()),
+                          "reads_restored": int(same.sum()), "reads_restored_by_planted": [int(same[planted == r].sum()) for r in range(3)],
+                          "reads_over_budget": int((cnt <= -2).sum()), "reads_left_weak": int((weak > 0).sum())}
+    print("correct_dev: %d reads in %.3f s" % (P, sec), file=sys.stderr, flush=True)
+    # the baseline: the profile alone, by count() on host-sliced k-mers
+    S = min(S, P)
+
+    def profile():
+        win = np.lib.stride_tricks.sliding_window_view(qs[:S], k, axis=1).reshape(-1, k)
+        solid = (g.count(list(win)) >= 1).reshape(S, L - k + 1)
+        cover = np.zeros((S, L + 1), np.int64)                     # positions covered by a solid window, by differences
+        j = np.arange(L - k + 1)
+        np.add.at(cover, (np.nonzero(solid)[0], j[np.nonzero(solid)[1]]), 1)
+        np.add.at(cover, (np.nonzero(solid)[0], j[np.nonzero(solid)[1]] + k), -1)
+        profile.clean = (np.cumsum(cover, 1)[:, :L] > 0).all(1)
+    bsec, blo, bhi = spread(profile, lambda: None)
+    out["baseline_profile_by_count"] = {"reads": S, "kmers": S * (L - k + 1), "seconds": bsec, "seconds_fastest": blo, "seconds_slowest": bhi, "reads_per_s": S / bsec,
+                                        "equals_fused": bool(np.array_equal(profile.clean, (cnt[:S] == 0) & (weak[:S] == 0))),
+                                        "fused_over_baseline_reads_per_s": (P / sec) / (S / bsec)}
+    # correct_into: the whole index into an empty one
+    dst = HipBwt(a.so)
+    ts, info = [], None
+    for rep in range(4):                                           # the first is the warm-up
+        dst.reset()
+        t = time.perf_counter(); info = g.correct_into(dst, k, 1, 8, probes); dst.sync(); ts.append(time.perf_counter() - t)
+    med = float(np.median(ts[1:]))
+    out["correct_into"] = {"info": info, "seconds": med, "seconds_fastest": float(min(ts[1:])), "seconds_slowest": float(max(ts[1:])), "strings_per_s": n / med,
+                           "probes_per_s_at_least": n * (L - k + 1) / med, "same_index": dst.rope_hashes() == g.rope_hashes()}
+    dst.close(); g.close()
+    res["correct"] = out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default="")
@@ -1096,7 +1171,19 @@ def main():
     ap.add_argument("--merge", action="store_true", help="only unpack and merge (added to an existing --out file)")
     ap.add_argument("--graph", action="store_true", help="only the string graph on the device (added to an existing --out file)")
     ap.add_argument("--clean", action="store_true", help="only tip and bubble removal on a synthetic edge list of --reads reads (added to an existing --out file)")
+    ap.add_argument("--correct", action="store_true", help="only the read correction (added to an existing --out file)")
+    ap.add_argument("--correct-reads", type=int, default=1_000_000)
+    ap.add_argument("--correct-sample", type=int, default=2_000, help="reads of the baseline: the profile by count() on host-sliced k-mers")
+    ap.add_argument("--correct-k", type=int, default=21)
     a = ap.parse_args()
+    if a.correct:
+        res = {"cases": []}
+        if a.out and os.path.exists(a.out):
+            with open(a.out) as f:
+                res = json.load(f)
+        correct_case(a, res)
+        finish(a, res)
+        return
     if a.clean:
         res = {"cases": []}
         if a.out and os.path.exists(a.out):
