@@ -353,6 +353,46 @@ int64_t rb2_hip_approx(rb2_hip_t *h, int64_t n, const uint8_t *qry, const int64_
  * does not see the lengths, so the stacks are sized for 8192 symbols: always 256 MiB once there are more than some 500 queries */
 void    rb2_hip_approx_dev(rb2_hip_t *h, int64_t n, const uint8_t *qry, const int64_t *off, int max_mm, int64_t min_occ, int64_t max_steps, int64_t max_recs, int64_t *rec, int64_t *cnt);
 
+/* ---- approximate search with insertions and deletions: the matches of a query within a bounded edit distance ----
+ * rb2_hip_approx_ed: n queries as for rb2_hip_approx (nt6 codes 1..5 in text order, concatenated in qry[off[i] .. off[i+1]); an N (5) is legal
+ * and equals nothing; 0, a code above 5 or a length above 8192 makes the query malformed).
+ * Distance.  sub(a, c) = 0 if a == c and c is one of A C G T, else 1.  lev(X, Y) is the unit-cost Levenshtein distance with sub as the cost of
+ * a column; deleting an N of the query costs 1 like any other symbol.  For a query q of L symbols and a word S over A C G T:
+ *   L >= 2 and |S| >= 2:   ed(S, q) = sub(S[0], q[0]) + lev(S[1:-1], q[1:-1]) + sub(S[-1], q[-1])
+ *   L == 1 and |S| == 1:   ed(S, q) = sub(S[0], q[0])
+ *   otherwise              ed(S, q) is infinite
+ * so the first and the last symbols of a match are aligned to the first and the last symbols of the query: without that every hit S would
+ * drag along S[1:], S[:-1], xS, Sx, ... at one more edit each.
+ * A match of q is a word S with ed(S, q) <= max_ed and at least min_occ occurrences, occurrences = hi - lo of rb2_hip_backward_search on S.
+ * Every match is reported exactly once, as one record rec[(i*max_recs + k)*4 ..] = lo, hi, ed, len: [lo, hi) is the interval of S in global
+ * rows and can be handed to rb2_hip_locate as it is; ed = ed(S, q), the minimum and not the cost of some particular alignment; len = |S|,
+ * L - max_ed <= len <= L + max_ed.  The alignment itself is not reported: locate and len give the text.  The order of a query's records is
+ * unspecified.
+ * cnt[i] >= 0: the matches found, which may exceed max_recs: exactly max_recs records are stored then, every one a true record, none
+ * twice; which ones is unspecified.  0 for the empty query, -1 for a malformed one.  cnt <= -2: the query used up max_steps before its
+ * search ended -- a step is one pair of ranks, and those of the bound count --; -2 - cnt[i] matches had been found by then and
+ * min(-2 - cnt[i], max_recs) of them are stored, every one a true record, none twice: the convention of rb2_hip_approx.  A call ends after
+ * n * max_steps rank pairs whatever the index holds.
+ * Only the records stored are meaningful: the host variant returns the others as zeros, the device variant leaves them untouched.
+ * Returns the number of records stored.  Fatal: max_ed outside 0 .. 4; min_occ, max_steps or max_recs below 1 (n <= 0 returns first); one
+ * rank of a sharded index.
+ * Two identities: at max_ed = 0 the records are (lo, hi, 0, L) of the backward search; and every match of rb2_hip_approx at max_mm = k is
+ * a match here at max_ed = k, with ed <= n_mm and len = L (with anchored ends the Hamming alignment is one of the alignments).
+ * Depth-first search over the trie of words, built from the last symbol (k_approx_ed), one query per 16 lanes: below the last symbol z a
+ * node W'z carries the column D[j] = lev(W', q[1 + j .. L - 1)), of which only the nine cells around the diagonal can hold max_ed or less:
+ * nine 4-bit fields of one word.  The two ranks of a node's interval give its four children a; a child with min_occ rows is a match when
+ * sub(z, q[L-1]) + D[0] + sub(a, q[0]) <= max_ed, and is followed when some cell of its own column, with a lower bound for the symbols in
+ * front of the cell, stays within max_ed.  The bound is that of rb2_hip_approx: one plain backward search cuts the query into disjoint
+ * pieces that each occur fewer than min_occ times, and an alignment that leaves a piece untouched would make S contain it.
+ * The stacks live in device memory, 74 bytes per symbol of the longest query (plus max_ed) and row of the launch, 256 MiB at the most
+ * (RB2_APPROX_SCRATCH in the environment lowers that; rows take further queries a launch apart); when the queries are many and the
+ * longest is long, the short ones run in a launch of their own on many rows.  The host variant stages chunks whose records (chunk *
+ * max_recs * 32 bytes) stay under 256 MiB, one query at the least (RB2_QUERY_CHUNK lowers the chunk). */
+int64_t rb2_hip_approx_ed(rb2_hip_t *h, int64_t n, const uint8_t *qry, const int64_t *off, int max_ed, int64_t min_occ, int64_t max_steps, int64_t max_recs, int64_t *rec, int64_t *cnt);
+/* the same with qry, off, rec and cnt in this device's memory, asynchronous on the handle's stream (no return value: read cnt).  The host
+ * does not see the lengths, so the stacks are sized for 8192 symbols */
+void    rb2_hip_approx_ed_dev(rb2_hip_t *h, int64_t n, const uint8_t *qry, const int64_t *off, int max_ed, int64_t min_occ, int64_t max_steps, int64_t max_recs, int64_t *rec, int64_t *cnt);
+
 /* ---- duplicate and contained strings: which strings an overlap graph, a unitig builder or a dedup step drops first ----
  * For string k (ids as in rb2_hip_extract: rows of the `$` block) with text S, |S| >= 1, symbols compared as codes (an N equals only an N):
  *   occ      occurrences of S as a substring of all indexed strings, itself included: hi - lo of rb2_hip_backward_search on S

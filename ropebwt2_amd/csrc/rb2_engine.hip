@@ -21,6 +21,7 @@
 #include "rb2_clean.h"
 #include "rb2_unpack.h"
 #include "rb2_correct.h"
+#include "rb2_edit.h"
 #include "rb2_graph.h"
 #include "rb2_merge_plan.h"
 #include "rb2_round_plan.h"

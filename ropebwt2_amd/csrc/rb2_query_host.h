@@ -4,6 +4,7 @@
 // dev_chunks (the chunked loop of the device-pointer variants).
 #pragma once
 #include "rb2_query_plan.h"
+#include "rb2_edit_plan.h"
 #include "rb2_kmer_plan.h"
 #include "rb2_graph_plan.h"
 
@@ -477,6 +478,51 @@ void rb2_hip_approx_dev(rb2_hip_t *h, int64_t n, const uint8_t *qry, const int64
 	approx_check("approx_dev", max_mm, min_occ, max_steps, max_recs);
 	dev_chunks(n, [&](int64_t i0, int64_t nc) {
 		launch_approx(h, nc, qry, off + i0, 0, APPROX_MAX_LEN, max_mm, min_occ, max_steps, max_recs, rec + i0 * max_recs * 4, cnt + i0); });
+}
+
+/* ---- approximate search with insertions and deletions: the matches of a query within max_ed edits (k_approx_ed in rb2_edit.h) ---- */
+
+/* as launch_approx, with the stacks of rb2_edit_plan.h (edit_passes, edit_row_bytes) and the scratch of approx_scratch() */
+static void launch_approx_ed(rb2_hip_t *h, int64_t n, const uint8_t *qry, const int64_t *off, int64_t base, int64_t lmax, int max_ed, int64_t min_occ, int64_t max_steps,
+                             int64_t max_recs, int64_t *rec, int64_t *cnt)
+{
+	int64_t pass[2][4], bytes = 0;
+	const int np = edit_passes(n, std::min(std::max<int64_t>(lmax, 1), APPROX_MAX_LEN), max_ed, approx_scratch(), pass);
+	for (int k = 0; k < np; ++k) bytes = std::max(bytes, pass[k][3] * edit_row_bytes(pass[k][2], max_ed));
+	h->qscr.ensure((size_t)bytes);
+	for (int k = 0; k < np; ++k)
+		qlaunch(h, k_approx_ed<true>, k_approx_ed<false>, (uint64_t)pass[k][3], qry, off, base, n, max_ed, min_occ, max_steps, max_recs, pass[k][0], pass[k][1],
+				pass[k][3], pass[k][2], h->qscr.p, rec, cnt);
+}
+
+static void approx_ed_check(const char *who, int max_ed, int64_t min_occ, int64_t max_steps, int64_t max_recs)
+{
+	if (max_ed < 0 || max_ed > EDIT_MAX_ED) { rb2_fatal("[rb2_hip] %s: max_ed must be 0 .. %d (got %d)\n", who, EDIT_MAX_ED, max_ed); }
+	if (min_occ < 1) { rb2_fatal("[rb2_hip] %s: min_occ must be at least 1 (got %lld)\n", who, (long long)min_occ); }
+	if (max_steps < 1) { rb2_fatal("[rb2_hip] %s: max_steps must be at least 1 (got %lld)\n", who, (long long)max_steps); }
+	if (max_recs < 1) { rb2_fatal("[rb2_hip] %s: max_recs must be at least 1 (got %lld)\n", who, (long long)max_recs); }
+}
+
+int64_t rb2_hip_approx_ed(rb2_hip_t *h, int64_t n, const uint8_t *qry, const int64_t *off, int max_ed, int64_t min_occ, int64_t max_steps, int64_t max_recs, int64_t *rec, int64_t *cnt)
+{
+	query_begin(h, "approx_ed");
+	if (n <= 0) return 0;
+	approx_ed_check("approx_ed", max_ed, min_occ, max_steps, max_recs);
+	check_offsets("approx_ed", "query", n, off);
+	int64_t lmax = 1;                                              // the longest query that is not malformed by its length alone
+	for (int64_t i = 0; i < n; ++i) if (off[i + 1] - off[i] <= APPROX_MAX_LEN) lmax = std::max(lmax, off[i + 1] - off[i]);
+	return staged_records(h, n, {qry, off, 0}, 4, max_recs, rec, cnt, [&](int64_t nc, const QStaged &s, int64_t *d_rec, int64_t *d_cnt) {
+		launch_approx_ed(h, nc, s.bytes, s.v, s.base, lmax, max_ed, min_occ, max_steps, max_recs, d_rec, d_cnt); },
+		[](int64_t c) { return c >= 0 ? c : c <= -2 ? -2 - c : 0; });     // a query that ran out of steps keeps what it had found
+}
+
+void rb2_hip_approx_ed_dev(rb2_hip_t *h, int64_t n, const uint8_t *qry, const int64_t *off, int max_ed, int64_t min_occ, int64_t max_steps, int64_t max_recs, int64_t *rec, int64_t *cnt)
+{
+	query_begin(h, "approx_ed_dev");
+	if (n <= 0) return;
+	approx_ed_check("approx_ed_dev", max_ed, min_occ, max_steps, max_recs);
+	dev_chunks(n, [&](int64_t i0, int64_t nc) {
+		launch_approx_ed(h, nc, qry, off + i0, 0, APPROX_MAX_LEN, max_ed, min_occ, max_steps, max_recs, rec + i0 * max_recs * 4, cnt + i0); });
 }
 
 /* ---- duplicate and contained strings: one fused LF walk per string (k_contain) ---- */

@@ -70,6 +70,8 @@ def load_hip_lib():
         "rb2_hip_kmers": (i64, [vp, i32, i64, i32, i64, vp, i64, vp, vp]),
         "rb2_hip_approx": (i64, [vp, i64, vp, vp, i32, i64, i64, i64, vp, vp]),
         "rb2_hip_approx_dev": (None, [vp, i64, vp, vp, i32, i64, i64, i64, vp, vp]),
+        "rb2_hip_approx_ed": (i64, [vp, i64, vp, vp, i32, i64, i64, i64, vp, vp]),
+        "rb2_hip_approx_ed_dev": (None, [vp, i64, vp, vp, i32, i64, i64, i64, vp, vp]),
         "rb2_hip_contained": (i64, [vp, i64, vp, vp]),
         "rb2_hip_contained_dev": (None, [vp, i64, vp, vp]),
         "rb2_hip_irreducible": (i64, [vp, i64, vp, vp, i64, i64, i64, i64, vp, vp]),
@@ -161,7 +163,7 @@ ABI_SYMBOLS = [
     "rb2_hip_backward_search", "rb2_hip_backward_search_dev", "rb2_hip_extend", "rb2_hip_extract", "rb2_hip_smem", "rb2_hip_smem_dev", "rb2_hip_dev_alloc",
     "rb2_hip_ssa_build", "rb2_hip_ssa_drop", "rb2_hip_ssa_info", "rb2_hip_locate", "rb2_hip_locate_dev",
     "rb2_hip_overlap", "rb2_hip_overlap_dev", "rb2_hip_string_ids", "rb2_hip_string_ids_dev", "rb2_hip_kmers",
-    "rb2_hip_approx", "rb2_hip_approx_dev", "rb2_hip_contained", "rb2_hip_contained_dev",
+    "rb2_hip_approx", "rb2_hip_approx_dev", "rb2_hip_approx_ed", "rb2_hip_approx_ed_dev", "rb2_hip_contained", "rb2_hip_contained_dev",
     "rb2_hip_irreducible", "rb2_hip_irreducible_dev",
     "rb2_hip_unitig_chains", "rb2_hip_unitig_chains_dev", "rb2_hip_unitig_text", "rb2_hip_unitig_text_dev",
     "rb2_hip_unpack", "rb2_hip_unpack_dev", "rb2_hip_merge",
@@ -636,6 +638,31 @@ class HipBwt:
     def approx_dev(self, n, qry_dev, off_dev, rec_dev, cnt_dev, max_mm, min_occ=1, max_steps=1 << 16, max_recs=64):
         """rb2_hip_approx_dev: all four pointers in this device's memory; asynchronous on the handle's stream"""
         self.L.rb2_hip_approx_dev(self.h, n, qry_dev, off_dev, int(max_mm), min_occ, max_steps, max_recs, rec_dev, cnt_dev)
+
+    # -- approximate search with insertions and deletions: the matches of a query within max_ed edits (include/rb2_hip.h) -----------
+    def approx_ed_raw(self, queries, max_ed, min_occ=1, max_steps=1 << 16, max_recs=64):
+        """rb2_hip_approx_ed as it is: (records stored, rec (n, max_recs, 4) int64 = lo, hi, ed, len, cnt (n,) int64).  cnt[i] >= 0: the
+        matches found, min(cnt[i], max_recs) of them stored; -1: a malformed query; <= -2: the query ran out of steps with -2 - cnt[i]
+        matches found, min(that, max_recs) stored.  The records not stored are zeros, the order of a query's records is unspecified"""
+        qry, off = pack_patterns(queries)
+        return self._records(self.L.rb2_hip_approx_ed, len(off) - 1, (qry.ctypes.data, off.ctypes.data, int(max_ed), min_occ, max_steps, max_recs), max_recs, 4, False)
+
+    def approx_ed(self, queries, max_ed, min_occ=1, max_steps=1 << 16, max_recs=64):
+        """the words within max_ed edits (substitutions, insertions, deletions; the first and last symbols aligned to those of the query) of
+        every query (str / bytes over ACGTN, or nt6 arrays) that occur at least min_occ times: per query a sorted list of (lo, hi, ed, len)
+        -- [lo, hi) goes to locate() as it is, the match has len symbols and the edit distance ed to the query --, at most max_recs of them,
+        or None for a malformed query ('$' or a code above 5 inside, more than 8192 symbols).  Raises StepBudgetExceeded when a query used up
+        max_steps: the exception names the queries and carries the results, partial for those"""
+        _, rec, cnt = self.approx_ed_raw(queries, max_ed, min_occ, max_steps, max_recs)
+        have = np.minimum(np.where(cnt <= -2, -2 - cnt, np.maximum(cnt, 0)), max_recs)
+        out = [None if c == -1 else sorted(map(tuple, r[:k].tolist())) for r, k, c in zip(rec, have, cnt)]
+        if (cnt <= -2).any():
+            raise StepBudgetExceeded(np.flatnonzero(cnt <= -2).tolist(), out, who="approx_ed", lower="max_ed")
+        return out
+
+    def approx_ed_dev(self, n, qry_dev, off_dev, rec_dev, cnt_dev, max_ed, min_occ=1, max_steps=1 << 16, max_recs=64):
+        """rb2_hip_approx_ed_dev: all four pointers in this device's memory; asynchronous on the handle's stream"""
+        self.L.rb2_hip_approx_ed_dev(self.h, n, qry_dev, off_dev, int(max_ed), min_occ, max_steps, max_recs, rec_dev, cnt_dev)
 
     # -- duplicate and contained strings (include/rb2_hip.h) -------------------------------------------------------------------------
     def contained_raw(self, ids=None):

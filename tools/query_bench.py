@@ -70,6 +70,11 @@ With --merge only rb2_hip_unpack_dev and rb2_hip_merge are measured and stored u
 symbols per second of unpack_dev in both directions against rb2_hip_extract of the same strings (max_len = the read length), and the merge
 of an index of a quarter as many other reads into the benchmark index against extract + a host pass + rb2_hip_insert_multi from the host
 buffer into an identical index (merge_case).
+With --approx-ed only the approximate search with insertions and deletions is measured and stored under "approx_ed" in the --out file, whose
+other entries stay: on the index of the first cases, --approx-ed-queries reads of the index with 0, 1 and 2 planted edits -- one substitution,
+one deleted base, one inserted base in turn, never at the two end positions -- through approx_ed_dev at max_ed = planted (--approx-steps is
+its max_steps), queries per second, median of three after a warm-up with the fastest and the slowest run beside it.  Next to each the same
+reads with as many planted substitutions through approx_dev at max_mm = planted: what a step cost before the column.
 With --correct only the read correction is measured and stored under "correct" in the --out file, whose other entries stay: on the index of
 the first cases (single strand, unique reads: min_occ = 1), correct_dev on --correct-reads reads of the index with 0, 1 and 2 planted
 substitutions in turn (k = --correct-k, max_fix 8, the default max_probes) -- reads per second, median of three after a warm-up with the
@@ -460,6 +465,84 @@ def approx_case(a, res):
         g.dev_free(q)
     g.close()
     res["approx"] = {"index": index, "cases": rows}
+
+
+def plant_edits(rng, reads, planted):
+    """reads (P, L) with `planted` edits each -- one substitution, one deleted base, one inserted base in turn, read i starting the turn at
+    kind i % 3, never at the two end positions: (the queries concatenated, their P + 1 offsets).  The reads of one turn stay together, so
+    the queries come out in three groups of one length each"""
+    flat, lens = [], []
+    for r in range(3):
+        q = reads[r::3].copy()
+        for j in range(planted):
+            n, m = q.shape
+            kind = (r + j) % 3
+            if kind == 0:                                            # another symbol at 1 .. m - 2
+                at = rng.randint(1, m - 1, size=n)
+                q[np.arange(n), at] = 1 + (q[np.arange(n), at] + rng.randint(3, size=n)) % 4
+            elif kind == 1:                                          # the symbol at 1 .. m - 2 deleted
+                keep = np.ones((n, m), bool)
+                keep[np.arange(n), rng.randint(1, m - 1, size=n)] = False
+                q = q[keep].reshape(n, m - 1)
+            else:                                                    # a symbol inserted in front of 1 .. m - 1
+                new = np.zeros((n, m + 1), bool)
+                new[np.arange(n), rng.randint(1, m, size=n)] = True
+                t = np.empty((n, m + 1), np.uint8)
+                t[~new] = q.reshape(-1)
+                t[new] = rng.randint(1, 5, size=n)
+                q = t
+        flat.append(q.reshape(-1))
+        lens.append(np.full(len(q), q.shape[1], np.int64))
+    return np.ascontiguousarray(np.concatenate(flat)), np.concatenate([[0], np.cumsum(np.concatenate(lens))]).astype(np.int64)
+
+
+def approx_ed_case(a, res):
+    """reads of the index with 0, 1, 2 planted edits (plant_edits) through approx_ed_dev at max_ed = planted: queries per second.  Next to
+    each, the same reads with as many planted substitutions only (never at the ends either) through approx_dev at max_mm = planted, on the
+    same index with the same budget: what a step cost before the column.  Neither call reports its steps; the records are counted"""
+    L, M = 101, 16
+    n = a.reads or -(-(int(4 * 1024 ** 3 * 0.97) + 1) // (L + 1))
+    P = a.approx_ed_queries
+    g = HipBwt(a.so)
+    p = g.dev_alloc(n * (L + 1))
+    g.synth_reads(p, 0, n, L, seed=42)
+    g.insert_multi_dev(p, n * (L + 1))
+    g.sync()
+    g.dev_free(p)
+    index = {"reads": n, "read_len": L, "sorting_order": a.so, "symbols": int(g.counts().sum()), "strands": 1, "layout": g.layout_stats()}
+    rng = np.random.RandomState(13)
+    reads = hit_patterns(P, L, n, 101)
+    rows = []
+    do, dr, dc = g.dev_alloc(8 * (P + 1)), g.dev_alloc(32 * M * P), g.dev_alloc(8 * P)
+
+    def run(call, flat, off, k):
+        dq = g.dev_alloc(len(flat))
+        g.L.rb2_hip_memcpy(g.h, dq, flat.ctypes.data, len(flat), 0)
+        g.L.rb2_hip_memcpy(g.h, do, off.ctypes.data, 8 * (P + 1), 0)
+        sec, lo, hi = spread(lambda: call(P, dq, do, dr, dc, k, 1, a.approx_steps, M), g.sync)
+        cnt = np.zeros(P, np.int64)
+        g.L.rb2_hip_memcpy(g.h, cnt.ctypes.data, dc, 8 * P, 1)
+        g.dev_free(dq)
+        assert (cnt != -1).all() and ((cnt >= 1) | (cnt <= -2)).all()                             # the read itself is within reach, unless the steps ran out
+        return {"queries": P, "seconds": sec, "seconds_fastest": lo, "seconds_slowest": hi, "queries_per_s": P / sec, "matches": int(np.maximum(cnt, 0).sum()),
+                "queries_with_a_match": int((cnt >= 1).sum()), "queries_out_of_steps": int((cnt <= -2).sum()), "queries_with_more_than_max_recs": int((cnt > M).sum())}
+
+    for planted in (0, 1, 2):
+        flat, off = plant_edits(rng, reads, planted)
+        ed = run(g.approx_ed_dev, flat, off, planted)
+        subs = reads.copy()
+        for _ in range(planted):                                    # (two may fall on one position: then fewer are planted)
+            at = rng.randint(1, L - 1, size=P)
+            subs[np.arange(P), at] = 1 + (subs[np.arange(P), at] + rng.randint(3, size=P)) % 4
+        mm = run(g.approx_dev, np.ascontiguousarray(subs.reshape(-1)), np.arange(P + 1, dtype=np.int64) * L, planted)
+        rows.append({"case": "%d reads of the index (%d bp), %d planted: approx_ed_dev on edits (substitution, deletion, insertion in turn) at max_ed=%d, approx_dev on substitutions at "
+                             "max_mm=%d; min_occ=1 max_steps=%d max_recs=%d" % (P, L, planted, planted, planted, a.approx_steps, M),
+                     "measured": True, "planted": planted, "approx_ed_dev": ed, "approx_dev": mm, "seconds_ratio": ed["seconds"] / mm["seconds"]})
+        print("approx_ed: %d planted: %d queries in %.3f s (approx_dev on substitutions: %.3f s)" % (planted, P, ed["seconds"], mm["seconds"]), file=sys.stderr, flush=True)
+    for q in (do, dr, dc):
+        g.dev_free(q)
+    g.close()
+    res["approx_ed"] = {"index": index, "cases": rows}
 
 
 def composed_kmers(g, lo, hi, code, l0, k, min_occ):
@@ -1158,6 +1241,8 @@ def main():
     ap.add_argument("--approx", action="store_true", help="only the approximate search (added to an existing --out file)")
     ap.add_argument("--approx-queries", type=int, default=1_000_000)
     ap.add_argument("--approx-steps", type=int, default=1 << 16, help="max_steps of the approximate search")
+    ap.add_argument("--approx-ed", action="store_true", help="only the approximate search with insertions and deletions, beside approx_dev (added to an existing --out file)")
+    ap.add_argument("--approx-ed-queries", type=int, default=1_000_000)
     ap.add_argument("--delete", type=float, default=0.0, help="only string deletion: delete this fraction of the strings (appended to an existing --out file)")
     ap.add_argument("--contained", action="store_true", help="only the duplicate / containment query (appended to an existing --out file)")
     ap.add_argument("--contained-sample", type=int, default=1_000_000, help="strings of the sample the composition extract + backward_search is timed on")
@@ -1246,6 +1331,14 @@ def main():
             with open(a.out) as f:
                 res = json.load(f)
         delete_case(a, res)
+        finish(a, res)
+        return
+    if a.approx_ed:
+        res = {"cases": []}
+        if a.out and os.path.exists(a.out):
+            with open(a.out) as f:
+                res = json.load(f)
+        approx_ed_case(a, res)
         finish(a, res)
         return
     if a.approx:
