@@ -98,7 +98,7 @@ __global__ __launch_bounds__(256) void k_correct_mate(uint64_t n, uint64_t strid
 	for (int64_t x = R.g; x < L; x += 16) diff |= (uint32_t)(a[s0 + x] != b[s0 + x]);
 	diff = row_sum16(diff);
 	if (R.g == 0) {
-		const int64_t c = cnt[R.i], f = c <= -2 ? -2 - c : c > 0 ? c : 0;
+		const int64_t c = cnt[R.i], f = budget_found(c);
 		if (diff) atomicAdd(&ctr[CC_CHANGED], 1ull);
 		if (f) atomicAdd(&ctr[CC_FIXES], (unsigned long long)f);
 		if (weak[R.i] > 0) atomicAdd(&ctr[CC_WEAK], 1ull);

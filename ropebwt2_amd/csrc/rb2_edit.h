@@ -1,5 +1,5 @@
 // rb2_edit.h -- approximate search with insertions and deletions on the device index (include/rb2_hip.h: rb2_hip_approx_ed; DESIGN.md
-// section 27).  The arithmetic -- the packed column, the stack of a row, the launches -- is rb2_edit_plan.h, which a CPU program tests.
+// section 27).  The arithmetic -- the packed column, the stack of a row -- is rb2_edit_plan.h, which a CPU program tests.
 #pragma once
 #include "rb2_query.h"
 #include "rb2_edit_plan.h"
@@ -15,14 +15,13 @@ namespace rb2 {
 // max_ed, need being the piece bound of approx_bound over the whole query.  A trie node is a distinct word: every match is met once.
 //
 // One query per DPP row, control uniform within the row; a row takes the queries i = row, row + rows, ... with lmin < L <= lcap (the host
-// sorts the lengths into launches: edit_passes).  The stack is the path, in the row's part of scr (edit_row_bytes(lrow, max_ed) bytes), one
+// sorts the lengths into launches: stack_passes).  The stack is the path, in the row's part of scr (edit_row_bytes(lrow, max_ed) bytes), one
 // position for the root (0) and one for each node below it (p = the symbols of its word):
 //   kid[8 p + 2 (a - 1) ..] = lo, hi of child a of the node at p                (lanes 0 .. 7 store one word each: one 64-byte line)
 //   col[p] = its column          tk[p] = the child taken at p | the next one to try << 3          G[x] = approx_bound's count
 // so that coming back to a node costs loads and no rank: tk and col, and the kid line in one go when a child is left to try (the window
-// of the query and of G is read only when a child with min_occ rows asks for it).  kid is written by eight lanes and read by all sixteen:
-// the vector memory operations of one wave are performed in order, the two fences keep the compiler from moving them.  col, tk and G are
-// written by every lane with the same value, each lane reads its own.
+// of the query and of G is read only when a child with min_occ rows asks for it).  kid is the kid line of rb2_query.h (kid_store,
+// kid_line) with its two fences.  col, tk and G are written by every lane with the same value, each lane reads its own.
 // Every pair of ranks, those of the bound included, is a step: at max_steps the query ends with cnt = -2 - (matches found so far).  Between
 // two steps a row looks at four children and pops at most what it pushed, and a word below the root is never longer than L - 1 + max_ed
 // (a longer one has no live cell; the push checks the position against the stack besides), so a launch ends after n * max_steps pairs of
@@ -59,16 +58,7 @@ template <bool SPARSE> __global__ __launch_bounds__(256) void k_approx_ed(const 
 			if (steps >= max_steps) { over = true; break; }
 			++steps;
 			uint64_t klo[4], khi[4];
-			{
-				const QPair<SPARSE> Q(T, pv, lo, hi);
-				uint64_t v = 0;
-#pragma unroll
-				for (int a = 1; a <= 4; ++a) Q.child(T, a, klo[a - 1], khi[a - 1]);
-#pragma unroll
-				for (int w = 0; w < 8; ++w) if (R.g == (uint32_t)w) v = w & 1 ? khi[w >> 1] : klo[w >> 1];
-				if (R.g < 8) kid[8 * p + R.g] = v;
-				__builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-			}
+			kid_store(T, QPair<SPARSE>(T, pv, lo, hi), kid, p, R.g, klo, khi);
 			bool down = false;
 			int t = 1;
 			for (;;) {                                             // the children of the node at p from t on; with none left, back to the node above
@@ -112,10 +102,7 @@ template <bool SPARSE> __global__ __launch_bounds__(256) void k_approx_ed(const 
 				t = b >> 3;
 				col = colv[p];                                         // (of the root: never read)
 				__builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-				if (t <= 4) {                                          // the line of the node's children, in one go
-#pragma unroll
-					for (int c = 0; c < 4; ++c) { klo[c] = kid[8 * p + 2 * c]; khi[c] = kid[8 * p + 2 * c + 1]; }
-				}
+				if (t <= 4) kid_line(kid, p, klo, khi);                // the line of the node's children, in one go
 			}
 			if (!down) break;                                      // back at the root with no child left: the search is complete
 		}

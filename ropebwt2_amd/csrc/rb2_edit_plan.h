@@ -1,5 +1,6 @@
 // The arithmetic of the approximate search with insertions and deletions (rb2_hip_approx_ed: kernel k_approx_ed in rb2_edit.h, host side in
-// rb2_query_host.h): the packed column of the dynamic programme, the stack of a row and the launches of a call.
+// rb2_query_host.h): the packed column of the dynamic programme and the stack of a row.  The rows and the launches
+// of a call follow from that stack by stack_rows, stack_len_cap and stack_passes of rb2_query_plan.h, as for rb2_hip_approx.
 // Plain C++ with no HIP in it: the kernel and a CPU program (tests/edit_plan_check.cpp) compile the same text.
 #pragma once
 #include "rb2_query_plan.h"
@@ -102,33 +103,3 @@ RB2_PLAN_HD inline bool edit_live(uint64_t col, uint64_t needs, int c0, int max_
  * per symbol of the query.  The byte arrays are padded to 8 bytes. */
 constexpr int64_t edit_nodes(int64_t L, int max_ed) { return L + max_ed; }
 constexpr int64_t edit_row_bytes(int64_t L, int max_ed) { return 72 * edit_nodes(L, max_ed) + approx_pad(edit_nodes(L, max_ed)) + approx_pad(L); }
-
-/* rows of a launch over n (>= 1) queries of up to L symbols with `bytes` of scratch: at most n and APPROX_ROWS, one at the least */
-constexpr int64_t edit_rows(int64_t n, int64_t L, int max_ed, int64_t bytes)
-{
-	int64_t r = bytes / edit_row_bytes(L, max_ed);
-	if (r > APPROX_ROWS) r = APPROX_ROWS;
-	if (r > n) r = n;
-	return r < 1 ? 1 : r;
-}
-
-/* the longest query the stacks of `rows` rows hold in `bytes` of scratch (0: none), APPROX_MAX_LEN at the most */
-constexpr int64_t edit_len_cap(int64_t rows, int max_ed, int64_t bytes)
-{
-	int64_t L = bytes / rows / 74;                             /* 72 P + pad(P) + pad(L) <= 74 L + 73 max_ed + 14 */
-	while (L > 0 && edit_row_bytes(L, max_ed) * rows > bytes) --L;
-	return L > APPROX_MAX_LEN ? APPROX_MAX_LEN : L;
-}
-
-/* one launch or two, exactly as approx_passes cuts a call of rb2_hip_approx, with the row size of this search */
-static inline int edit_passes(int64_t n, int64_t lmax, int max_ed, int64_t bytes, int64_t pass[2][4])
-{
-	const int64_t all = edit_rows(n, lmax, max_ed, bytes), cut = edit_len_cap(APPROX_SHORT_ROWS, max_ed, bytes);
-	if (all >= n || all >= APPROX_SHORT_ROWS || lmax <= cut || cut < 1) {
-		pass[0][0] = INT64_MIN; pass[0][1] = INT64_MAX; pass[0][2] = lmax; pass[0][3] = all;
-		return 1;
-	}
-	pass[0][0] = INT64_MIN; pass[0][1] = cut; pass[0][2] = cut; pass[0][3] = edit_rows(n, cut, max_ed, bytes);
-	pass[1][0] = cut; pass[1][1] = INT64_MAX; pass[1][2] = lmax; pass[1][3] = all;
-	return 2;
-}

@@ -39,11 +39,7 @@ __global__ __launch_bounds__(256) void k_graph_lmax(const uint64_t *x, unsigned 
 }
 
 // the stored records of a source: cnt as rb2_hip_irreducible reports it
-__device__ __forceinline__ int64_t graph_have(int64_t c, int64_t max_recs)
-{
-	const int64_t found = c >= 0 ? c : c <= -2 ? -2 - c : 0;
-	return min(found, max_recs);
-}
+__device__ __forceinline__ int64_t graph_have(int64_t c, int64_t max_recs) { return min(budget_found(c), max_recs); }
 
 // the strings of a record's range that become edges
 __device__ __forceinline__ uint64_t graph_hits(int64_t zlo, int64_t zhi, int64_t max_hits) { return zhi > zlo ? (uint64_t)min(zhi - zlo, max_hits) : 0; }
@@ -56,7 +52,7 @@ __global__ __launch_bounds__(256) void k_graph_count(uint64_t n, const int64_t *
 		const int64_t c = cnt[i], have = graph_have(c, max_recs);
 		if (off[i + 1] - off[i] - 1 > IRRED_MAX_LEN) atomicAdd(&gc[GR_TOO_LONG], 1ull);
 		if (c <= -2) atomicAdd(&gc[GR_OVER_STEPS], 1ull);
-		if (c > max_recs || (c <= -2 && -2 - c > max_recs)) atomicAdd(&gc[GR_OVER_RECS], 1ull);
+		if (budget_found(c) > max_recs) atomicAdd(&gc[GR_OVER_RECS], 1ull);
 		uint64_t sum = 0;
 		for (int64_t k = 0; k < have; ++k) {
 			const int64_t *r = rec + (i * (uint64_t)max_recs + (uint64_t)k) * 4;

@@ -145,6 +145,30 @@ template <bool SPARSE> struct QPair {
 	template <typename I> __device__ __forceinline__ void child(const QTab &T, int c, I &nlo, I &nhi) const { const uint64_t C = qC(T, c); nlo = (I)(C + at(cl, c)); nhi = (I)(C + at(ch, c)); }
 };
 
+// The kid line: entry e of a path stack (k_approx, k_approx_ed, k_irreducible; DESIGN.md section 16, "the path stack") is the 64 bytes
+// kid[8 e + 2 (a - 1) ..] = lo, hi of the children a = 1 .. 4 of a ranked interval.  Lanes 0 .. 7 of the row store one word each and all
+// sixteen read: the vector memory operations of one wave are performed in order, and two fences keep the compiler from moving them --
+// the release fence behind the store is kid_store's, the acquire fence in front of a read is the caller's, once for all it reads next.
+// kid_store: klo, khi = the children of P, written as line e (g = the lane of the row)
+template <bool SPARSE> __device__ __forceinline__ void kid_store(const QTab &T, const QPair<SPARSE> &P, uint64_t *kid, int64_t e, uint32_t g, uint64_t (&klo)[4], uint64_t (&khi)[4])
+{
+	uint64_t v = 0;
+#pragma unroll
+	for (int a = 1; a <= 4; ++a) P.child(T, a, klo[a - 1], khi[a - 1]);
+#pragma unroll
+	for (int w = 0; w < 8; ++w) if (g == (uint32_t)w) v = w & 1 ? khi[w >> 1] : klo[w >> 1];
+	if (g < 8) kid[8 * e + g] = v;
+	__builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+}
+// child a of line e
+__device__ __forceinline__ void kid_child(const uint64_t *kid, int64_t e, int a, uint64_t &lo, uint64_t &hi) { lo = kid[8 * e + 2 * (a - 1)]; hi = kid[8 * e + 2 * (a - 1) + 1]; }
+// all four children of line e
+__device__ __forceinline__ void kid_line(const uint64_t *kid, int64_t e, uint64_t (&klo)[4], uint64_t (&khi)[4])
+{
+#pragma unroll
+	for (int c = 0; c < 4; ++c) kid_child(kid, e, c + 1, klo[c], khi[c]);
+}
+
 // one LF step from row x (x < N): returns the symbol c of the row and, unless it is `$`, moves x to the row of the suffix one longer;
 // c6 = the counts in front of the row x was (c6[0]: the `$`s in front of it, which names the string when c is `$`).  On an index that
 // is no BWT of complete strings the new x can be N or more and a walk need not end: the guard is the caller's, because the three differ.
@@ -511,12 +535,11 @@ template <bool SPARSE> __global__ __launch_bounds__(256) void k_kmer_expand(cons
 // backward search over the query computes first.  A live child at position 0 is a match.
 //
 // One query per DPP row, control uniform within the row; a row takes the queries i = row, row + rows, ... with lmin < L <= lcap (the host
-// sorts the lengths into launches that way: approx_passes).  The stack is the path, in the row's part of scr (approx_row_bytes(lrow) bytes):
+// sorts the lengths into launches that way: stack_passes).  The stack is the path, in the row's part of scr (approx_row_bytes(lrow) bytes):
 //   kid[8 p + 2 (a - 1) ..] = lo, hi of child a of the node at position p      (lanes 0 .. 7 store one word each: one 64-byte line)
 //   G[p]                      approx_bound's count                             tk[p] = the child taken at p | the next one to try << 3
-// so that coming back to a position costs two loads and no rank.  The children are tried in the order q[p], A, C, G, T.  kid is written by
-// eight lanes and read by all sixteen: the vector memory operations of one wave are performed in order, the two fences keep the compiler
-// from moving them.  G and tk are written by every lane with the same value, each lane reads its own.
+// so that coming back to a position costs two loads and no rank.  The children are tried in the order q[p], A, C, G, T.  kid is the kid
+// line above (kid_store, kid_child) with its two fences.  G and tk are written by every lane with the same value, each lane reads its own.
 // Every pair of ranks, those of the bound included, is a step: at max_steps the query ends with cnt = -2 - (matches found so far).  Between
 // two steps a row does a bounded amount of other work (four children, and one pop per push), so a launch ends after n * max_steps steps.
 // rec[(i * max_recs + k) * 4 ..] = lo, hi, n_mm, subs (approx_push) for k < max_recs, by lanes 0 .. 3; cnt[i] as in include/rb2_hip.h.
@@ -548,16 +571,7 @@ template <bool SPARSE> __global__ __launch_bounds__(256) void k_approx(const QTa
 			if (steps >= max_steps) { over = true; break; }
 			++steps;
 			uint64_t klo[4], khi[4];
-			{
-				const QPair<SPARSE> P(T, pv, lo, hi);
-				uint64_t v = 0;
-#pragma unroll
-				for (int a = 1; a <= 4; ++a) P.child(T, a, klo[a - 1], khi[a - 1]);
-#pragma unroll
-				for (int w = 0; w < 8; ++w) if (R.g == (uint32_t)w) v = w & 1 ? khi[w >> 1] : klo[w >> 1];
-				if (R.g < 8) kid[8 * p + R.g] = v;
-				__builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-			}
+			kid_store(T, QPair<SPARSE>(T, pv, lo, hi), kid, p, R.g, klo, khi);
 			bool fresh = true, down = false;
 			int t = 0;
 			for (;;) {                                             // the children of the node at p from try t on; with none left, back to the node behind
@@ -570,7 +584,7 @@ template <bool SPARSE> __global__ __launch_bounds__(256) void k_approx(const QTa
 					if (fresh) {
 #pragma unroll
 						for (int b = 0; b < 4; ++b) if (a == b + 1) { xlo = klo[b]; xhi = khi[b]; }
-					} else { xlo = kid[8 * p + 2 * (a - 1)]; xhi = kid[8 * p + 2 * (a - 1) + 1]; }
+					} else kid_child(kid, p, a, xlo, xhi);
 					if ((int64_t)(xhi - xlo) < min_occ) continue;
 					if (p == 0) {                                      // a match
 						qstore(rec, i, max_recs, k, R.g, xlo, xhi, m + cost, cost ? approx_push(subs, m, 0, a) : subs);
@@ -675,9 +689,8 @@ template <bool SPARSE> __global__ __launch_bounds__(256) __attribute__((amdgpu_w
 // row's part of scr (irred_row_bytes(cap, max_ext) bytes), the frames of its nodes behind each other; entry e is written when it is ranked:
 //   kid[8 e + 2 (a - 1) ..] = lo, hi of child a of entry e    (lanes 0 .. 7 store one word each: one 64-byte line)      el[e] = its overlap length
 //   fs[d], fa[d]              the first entry of frame d and the next child to try there, kept while frame d + 1 is the top one
-// so that coming back to a node costs loads and no rank.  kid is written by eight lanes and read by all sixteen: the vector memory
-// operations of one wave are performed in order, the fences keep the compiler from moving them.  el, fs and fa are written by every lane
-// with the same value, each lane reads its own.  The entries of the root are ranked as the search finds them, not behind it: the steps are
+// so that coming back to a node costs loads and no rank.  kid is the kid line above (kid_store, kid_child) with its fences.  el, fs and fa
+// are written by every lane with the same value, each lane reads its own.  The entries of the root are ranked as the search finds them, not behind it: the steps are
 // the same, and a query that runs out of them in either has no record yet.
 // Every pair of ranks is a step, and every entry written has cost one: at max_steps the query ends with cnt = -2 - (records so far).  The
 // frames 0 .. max_ext hold at most L - min_ovlp entries each, so e < cap = irred_entry_cap() whatever the index holds (tested all the same).
@@ -688,14 +701,9 @@ template <bool SPARSE> __device__ __forceinline__ void irred_rank(const QTab &T,
                                                                   uint32_t g, uint64_t &zlo, uint64_t &zhi)
 {
 	const QPair<SPARSE> P(T, pv, lo, hi);
-	uint64_t klo[4], khi[4], v = 0;
-#pragma unroll
-	for (int a = 1; a <= 4; ++a) P.child(T, a, klo[a - 1], khi[a - 1]);
-#pragma unroll
-	for (int w = 0; w < 8; ++w) if (g == (uint32_t)w) v = w & 1 ? khi[w >> 1] : klo[w >> 1];
-	if (g < 8) kid[8 * e + g] = v;
-	el[e] = (uint16_t)l;
-	__builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+	uint64_t klo[4], khi[4];
+	el[e] = (uint16_t)l;                                       // (in front of the release fence, as the line is)
+	kid_store(T, P, kid, e, g, klo, khi);
 	zlo = P.cl[0]; zhi = P.ch[0];
 }
 
@@ -761,7 +769,8 @@ template <bool SPARSE, bool END0 = false> __global__ __launch_bounds__(256) void
 				uint64_t bzl = 0, bzh = 0;
 				for (int64_t e = f0; e < top; ++e) {
 					__builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-					const uint64_t lo = kid[8 * e + 2 * (a - 1)], hi = kid[8 * e + 2 * (a - 1) + 1];
+					uint64_t lo, hi;
+					kid_child(kid, e, a, lo, hi);
 					if (lo >= hi) continue;
 					if (steps >= max_steps || nt >= cap) { over = true; break; }
 					++steps;

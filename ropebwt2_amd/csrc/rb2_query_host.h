@@ -1,12 +1,22 @@
 // Host side of the FM-index queries (kernels: rb2_query.h; the launch arithmetic: rb2_query_plan.h, rb2_kmer_plan.h).  Included from rb2_engine.hip, whose
 // handle, buffers and checks it uses.  Four helpers carry every query: qlaunch (one launch of a kernel in the layout of the index),
 // stage_inputs (a chunk's inputs to the device), staged_records (the chunked loop of the host variants that return records) and
-// dev_chunks (the chunked loop of the device-pointer variants).
+// dev_chunks (the chunked loop of the device-pointer variants).  Beside them: env_i64 reads the caps the environment may set, stacked_search
+// and stacked_search_dev are the whole host side of the searches that keep a path stack per query length (rb2_hip_approx, rb2_hip_approx_ed),
+// and BatchSource streams the strings of one index into another (rb2_hip_merge, rb2_hip_correct_into).
 #pragma once
 #include "rb2_query_plan.h"
 #include "rb2_edit_plan.h"
 #include "rb2_kmer_plan.h"
 #include "rb2_graph_plan.h"
+
+/* a number the environment may set, read on every call: its value when it is positive, dflt when it is unset, no number or not positive */
+static int64_t env_i64(const char *name, int64_t dflt)
+{
+	const char *e = getenv(name);
+	const int64_t v = e ? atoll(e) : 0;
+	return v > 0 ? v : dflt;
+}
 
 /* queries per launch: 16 threads each, so 2^24 stay far below the 2^32 threads of one launch; RB2_QUERY_CHUNK lowers it (tests of the chunking) */
 static int64_t query_chunk()
@@ -335,21 +345,10 @@ void rb2_hip_string_ids_dev(rb2_hip_t *h, int64_t n, const int64_t *zv, int64_t 
 
 /* items a frontier segment holds at the most: RB2_KMER_FRONTIER in the environment, read on every call; 2^22 (96 MiB a level, at most
  * 3 GiB at k = 32; a slice of 2^20 items is some hundreds of microseconds of ranks, far above what a launch and its read-back cost) */
-static int64_t kmer_frontier()
-{
-	const char *e = getenv("RB2_KMER_FRONTIER");
-	const int64_t v = e ? atoll(e) : 0;
-	return v > 0 ? std::max(v, KMER_FRONTIER_MIN) : (int64_t)1 << 22;
-}
+static int64_t kmer_frontier() { return std::max(env_i64("RB2_KMER_FRONTIER", (int64_t)1 << 22), KMER_FRONTIER_MIN); }
 
-/* records the staging buffer holds at the most: QUERY_STAGE_BYTES of them; RB2_KMER_STAGE lowers it (tests of the flushes) */
-static int64_t kmer_stage_limit()
-{
-	const int64_t lim = QUERY_STAGE_BYTES / 24;
-	const char *e = getenv("RB2_KMER_STAGE");
-	const int64_t v = e ? atoll(e) : 0;
-	return v > 0 ? std::min(std::max<int64_t>(v, 4), lim) : lim;
-}
+/* records the staging buffer holds at the most: QUERY_STAGE_BYTES of them; RB2_KMER_STAGE lowers it, to 4 at the least (tests of the flushes) */
+static int64_t kmer_stage_limit() { return std::min(std::max<int64_t>(env_i64("RB2_KMER_STAGE", QUERY_STAGE_BYTES / 24), 4), QUERY_STAGE_BYTES / 24); }
 
 int64_t rb2_hip_kmers(rb2_hip_t *h, int k, int64_t min_occ, int canonical, int64_t max_recs, int64_t *rec, int64_t hist_len, int64_t *hist, int64_t info[4])
 {
@@ -426,103 +425,96 @@ int64_t rb2_hip_kmers(rb2_hip_t *h, int k, int64_t min_occ, int canonical, int64
 	return found;
 }
 
-/* ---- approximate search: the matches of a query within max_mm substitutions (k_approx) ---- */
+/* ---- the searches with a step budget ("the path stack"): what rb2_hip_approx, rb2_hip_approx_ed and rb2_hip_irreducible share ---- */
+
+static void budget_check(const char *who, int64_t max_steps, int64_t max_recs)
+{
+	if (max_steps < 1) { rb2_fatal("[rb2_hip] %s: max_steps must be at least 1 (got %lld)\n", who, (long long)max_steps); }
+	if (max_recs < 1) { rb2_fatal("[rb2_hip] %s: max_recs must be at least 1 (got %lld)\n", who, (long long)max_recs); }
+}
+
+/* the longest of n queries that is not malformed by its length alone (longer than cap), 1 at the least */
+static int64_t longest_wellformed(int64_t n, const int64_t *off, int64_t cap)
+{
+	int64_t lmax = 1;
+	for (int64_t i = 0; i < n; ++i) if (off[i + 1] - off[i] <= cap) lmax = std::max(lmax, off[i + 1] - off[i]);
+	return lmax;
+}
+
+/* ---- approximate search: the matches of a query within max_mm substitutions (k_approx), or within max_ed edits
+ * (k_approx_ed in rb2_edit.h).  A family is its kernel, the stack of a row and the name and the range of its distance ---- */
+
+typedef void (*StackedKernel)(const QTab*, PoolView, const uint8_t*, const int64_t*, int64_t, uint64_t, int, int64_t, int64_t, int64_t, int64_t, int64_t, uint64_t, int64_t, uint8_t*,
+                              int64_t*, int64_t*);
+struct Stacked { StackedKernel sparse, dense; int64_t (*row_bytes)(int64_t L, int max_dist); const char *dist; int max_dist; };
+static const Stacked APPROX = {k_approx<true>, k_approx<false>, [](int64_t L, int) { return approx_row_bytes(L); }, "max_mm", APPROX_MAX_MM};
+static const Stacked APPROX_ED = {k_approx_ed<true>, k_approx_ed<false>, [](int64_t L, int max_ed) { return edit_row_bytes(L, max_ed); }, "max_ed", EDIT_MAX_ED};
 
 /* scratch for the stacks of a launch: APPROX_SCRATCH_BYTES; RB2_APPROX_SCRATCH in the environment lowers it (tests of the row cap) */
-static int64_t approx_scratch()
+static int64_t approx_scratch() { return std::min(env_i64("RB2_APPROX_SCRATCH", APPROX_SCRATCH_BYTES), APPROX_SCRATCH_BYTES); }
+
+static void stacked_check(const char *who, const Stacked &f, int dist, int64_t min_occ, int64_t max_steps, int64_t max_recs)
 {
-	const char *e = getenv("RB2_APPROX_SCRATCH");
-	const int64_t v = e ? atoll(e) : 0;
-	return v > 0 ? std::min(v, APPROX_SCRATCH_BYTES) : APPROX_SCRATCH_BYTES;
+	if (dist < 0 || dist > f.max_dist) { rb2_fatal("[rb2_hip] %s: %s must be 0 .. %d (got %d)\n", who, f.dist, f.max_dist, dist); }
+	if (min_occ < 1) { rb2_fatal("[rb2_hip] %s: min_occ must be at least 1 (got %lld)\n", who, (long long)min_occ); }
+	budget_check(who, max_steps, max_recs);
 }
 
 /* n queries, all device pointers, the longest of lmax symbols (APPROX_MAX_LEN when only the device knows): one launch, or one for the
- * short queries and one for the long ones (approx_passes), the stacks sized before the first */
-static void launch_approx(rb2_hip_t *h, int64_t n, const uint8_t *qry, const int64_t *off, int64_t base, int64_t lmax, int max_mm, int64_t min_occ, int64_t max_steps,
-                          int64_t max_recs, int64_t *rec, int64_t *cnt)
+ * short queries and one for the long ones (stack_passes), the stacks sized before the first */
+static void launch_stacked(rb2_hip_t *h, const Stacked &f, int64_t n, const uint8_t *qry, const int64_t *off, int64_t base, int64_t lmax, int dist, int64_t min_occ, int64_t max_steps,
+                           int64_t max_recs, int64_t *rec, int64_t *cnt)
 {
+	const auto row_bytes = [&](int64_t L) { return f.row_bytes(L, dist); };
 	int64_t pass[2][4], bytes = 0;
-	const int np = approx_passes(n, std::min(std::max<int64_t>(lmax, 1), APPROX_MAX_LEN), approx_scratch(), pass);
-	for (int k = 0; k < np; ++k) bytes = std::max(bytes, pass[k][3] * approx_row_bytes(pass[k][2]));
+	const int np = stack_passes(n, std::min(std::max<int64_t>(lmax, 1), APPROX_MAX_LEN), approx_scratch(), row_bytes, pass);
+	for (int k = 0; k < np; ++k) bytes = std::max(bytes, pass[k][3] * row_bytes(pass[k][2]));
 	h->qscr.ensure((size_t)bytes);
 	for (int k = 0; k < np; ++k)
-		qlaunch(h, k_approx<true>, k_approx<false>, (uint64_t)pass[k][3], qry, off, base, n, max_mm, min_occ, max_steps, max_recs, pass[k][0], pass[k][1],
-				pass[k][3], pass[k][2], h->qscr.p, rec, cnt);
+		qlaunch(h, f.sparse, f.dense, (uint64_t)pass[k][3], qry, off, base, n, dist, min_occ, max_steps, max_recs, pass[k][0], pass[k][1], pass[k][3], pass[k][2], h->qscr.p, rec, cnt);
 }
 
-static void approx_check(const char *who, int max_mm, int64_t min_occ, int64_t max_steps, int64_t max_recs)
+static int64_t stacked_search(rb2_hip_t *h, const Stacked &f, const char *who, int64_t n, const uint8_t *qry, const int64_t *off, int dist, int64_t min_occ, int64_t max_steps,
+                              int64_t max_recs, int64_t *rec, int64_t *cnt)
 {
-	if (max_mm < 0 || max_mm > APPROX_MAX_MM) { rb2_fatal("[rb2_hip] %s: max_mm must be 0 .. %d (got %d)\n", who, APPROX_MAX_MM, max_mm); }
-	if (min_occ < 1) { rb2_fatal("[rb2_hip] %s: min_occ must be at least 1 (got %lld)\n", who, (long long)min_occ); }
-	if (max_steps < 1) { rb2_fatal("[rb2_hip] %s: max_steps must be at least 1 (got %lld)\n", who, (long long)max_steps); }
-	if (max_recs < 1) { rb2_fatal("[rb2_hip] %s: max_recs must be at least 1 (got %lld)\n", who, (long long)max_recs); }
+	query_begin(h, who);
+	if (n <= 0) return 0;
+	stacked_check(who, f, dist, min_occ, max_steps, max_recs);
+	check_offsets(who, "query", n, off);
+	const int64_t lmax = longest_wellformed(n, off, APPROX_MAX_LEN);
+	return staged_records(h, n, {qry, off, 0}, 4, max_recs, rec, cnt, [&](int64_t nc, const QStaged &s, int64_t *d_rec, int64_t *d_cnt) {
+		launch_stacked(h, f, nc, s.bytes, s.v, s.base, lmax, dist, min_occ, max_steps, max_recs, d_rec, d_cnt); },
+		budget_found);                                             // a query that ran out of steps keeps what it had found
+}
+
+static void stacked_search_dev(rb2_hip_t *h, const Stacked &f, const char *who, int64_t n, const uint8_t *qry, const int64_t *off, int dist, int64_t min_occ, int64_t max_steps,
+                               int64_t max_recs, int64_t *rec, int64_t *cnt)
+{
+	query_begin(h, who);
+	if (n <= 0) return;
+	stacked_check(who, f, dist, min_occ, max_steps, max_recs);
+	dev_chunks(n, [&](int64_t i0, int64_t nc) {
+		launch_stacked(h, f, nc, qry, off + i0, 0, APPROX_MAX_LEN, dist, min_occ, max_steps, max_recs, rec + i0 * max_recs * 4, cnt + i0); });
 }
 
 int64_t rb2_hip_approx(rb2_hip_t *h, int64_t n, const uint8_t *qry, const int64_t *off, int max_mm, int64_t min_occ, int64_t max_steps, int64_t max_recs, int64_t *rec, int64_t *cnt)
 {
-	query_begin(h, "approx");
-	if (n <= 0) return 0;
-	approx_check("approx", max_mm, min_occ, max_steps, max_recs);
-	check_offsets("approx", "query", n, off);
-	int64_t lmax = 1;                                              // the longest query that is not malformed by its length alone
-	for (int64_t i = 0; i < n; ++i) if (off[i + 1] - off[i] <= APPROX_MAX_LEN) lmax = std::max(lmax, off[i + 1] - off[i]);
-	return staged_records(h, n, {qry, off, 0}, 4, max_recs, rec, cnt, [&](int64_t nc, const QStaged &s, int64_t *d_rec, int64_t *d_cnt) {
-		launch_approx(h, nc, s.bytes, s.v, s.base, lmax, max_mm, min_occ, max_steps, max_recs, d_rec, d_cnt); },
-		[](int64_t c) { return c >= 0 ? c : c <= -2 ? -2 - c : 0; });     // a query that ran out of steps keeps what it had found
+	return stacked_search(h, APPROX, "approx", n, qry, off, max_mm, min_occ, max_steps, max_recs, rec, cnt);
 }
 
 void rb2_hip_approx_dev(rb2_hip_t *h, int64_t n, const uint8_t *qry, const int64_t *off, int max_mm, int64_t min_occ, int64_t max_steps, int64_t max_recs, int64_t *rec, int64_t *cnt)
 {
-	query_begin(h, "approx_dev");
-	if (n <= 0) return;
-	approx_check("approx_dev", max_mm, min_occ, max_steps, max_recs);
-	dev_chunks(n, [&](int64_t i0, int64_t nc) {
-		launch_approx(h, nc, qry, off + i0, 0, APPROX_MAX_LEN, max_mm, min_occ, max_steps, max_recs, rec + i0 * max_recs * 4, cnt + i0); });
-}
-
-/* ---- approximate search with insertions and deletions: the matches of a query within max_ed edits (k_approx_ed in rb2_edit.h) ---- */
-
-/* as launch_approx, with the stacks of rb2_edit_plan.h (edit_passes, edit_row_bytes) and the scratch of approx_scratch() */
-static void launch_approx_ed(rb2_hip_t *h, int64_t n, const uint8_t *qry, const int64_t *off, int64_t base, int64_t lmax, int max_ed, int64_t min_occ, int64_t max_steps,
-                             int64_t max_recs, int64_t *rec, int64_t *cnt)
-{
-	int64_t pass[2][4], bytes = 0;
-	const int np = edit_passes(n, std::min(std::max<int64_t>(lmax, 1), APPROX_MAX_LEN), max_ed, approx_scratch(), pass);
-	for (int k = 0; k < np; ++k) bytes = std::max(bytes, pass[k][3] * edit_row_bytes(pass[k][2], max_ed));
-	h->qscr.ensure((size_t)bytes);
-	for (int k = 0; k < np; ++k)
-		qlaunch(h, k_approx_ed<true>, k_approx_ed<false>, (uint64_t)pass[k][3], qry, off, base, n, max_ed, min_occ, max_steps, max_recs, pass[k][0], pass[k][1],
-				pass[k][3], pass[k][2], h->qscr.p, rec, cnt);
-}
-
-static void approx_ed_check(const char *who, int max_ed, int64_t min_occ, int64_t max_steps, int64_t max_recs)
-{
-	if (max_ed < 0 || max_ed > EDIT_MAX_ED) { rb2_fatal("[rb2_hip] %s: max_ed must be 0 .. %d (got %d)\n", who, EDIT_MAX_ED, max_ed); }
-	if (min_occ < 1) { rb2_fatal("[rb2_hip] %s: min_occ must be at least 1 (got %lld)\n", who, (long long)min_occ); }
-	if (max_steps < 1) { rb2_fatal("[rb2_hip] %s: max_steps must be at least 1 (got %lld)\n", who, (long long)max_steps); }
-	if (max_recs < 1) { rb2_fatal("[rb2_hip] %s: max_recs must be at least 1 (got %lld)\n", who, (long long)max_recs); }
+	stacked_search_dev(h, APPROX, "approx_dev", n, qry, off, max_mm, min_occ, max_steps, max_recs, rec, cnt);
 }
 
 int64_t rb2_hip_approx_ed(rb2_hip_t *h, int64_t n, const uint8_t *qry, const int64_t *off, int max_ed, int64_t min_occ, int64_t max_steps, int64_t max_recs, int64_t *rec, int64_t *cnt)
 {
-	query_begin(h, "approx_ed");
-	if (n <= 0) return 0;
-	approx_ed_check("approx_ed", max_ed, min_occ, max_steps, max_recs);
-	check_offsets("approx_ed", "query", n, off);
-	int64_t lmax = 1;                                              // the longest query that is not malformed by its length alone
-	for (int64_t i = 0; i < n; ++i) if (off[i + 1] - off[i] <= APPROX_MAX_LEN) lmax = std::max(lmax, off[i + 1] - off[i]);
-	return staged_records(h, n, {qry, off, 0}, 4, max_recs, rec, cnt, [&](int64_t nc, const QStaged &s, int64_t *d_rec, int64_t *d_cnt) {
-		launch_approx_ed(h, nc, s.bytes, s.v, s.base, lmax, max_ed, min_occ, max_steps, max_recs, d_rec, d_cnt); },
-		[](int64_t c) { return c >= 0 ? c : c <= -2 ? -2 - c : 0; });     // a query that ran out of steps keeps what it had found
+	return stacked_search(h, APPROX_ED, "approx_ed", n, qry, off, max_ed, min_occ, max_steps, max_recs, rec, cnt);
 }
 
 void rb2_hip_approx_ed_dev(rb2_hip_t *h, int64_t n, const uint8_t *qry, const int64_t *off, int max_ed, int64_t min_occ, int64_t max_steps, int64_t max_recs, int64_t *rec, int64_t *cnt)
 {
-	query_begin(h, "approx_ed_dev");
-	if (n <= 0) return;
-	approx_ed_check("approx_ed_dev", max_ed, min_occ, max_steps, max_recs);
-	dev_chunks(n, [&](int64_t i0, int64_t nc) {
-		launch_approx_ed(h, nc, qry, off + i0, 0, APPROX_MAX_LEN, max_ed, min_occ, max_steps, max_recs, rec + i0 * max_recs * 4, cnt + i0); });
+	stacked_search_dev(h, APPROX_ED, "approx_ed_dev", n, qry, off, max_ed, min_occ, max_steps, max_recs, rec, cnt);
 }
 
 /* ---- duplicate and contained strings: one fused LF walk per string (k_contain) ---- */
@@ -563,18 +555,13 @@ void rb2_hip_contained_dev(rb2_hip_t *h, int64_t n, const int64_t *ids, int64_t 
 /* ---- irreducible overlaps: the neighbours of a read in a string graph (k_irreducible) ---- */
 
 /* scratch for the stacks of a launch: IRRED_SCRATCH_BYTES; RB2_IRRED_SCRATCH in the environment, read on every call, lowers it (tests of the row cap) */
-static int64_t irred_scratch()
-{
-	const char *e = getenv("RB2_IRRED_SCRATCH");
-	const int64_t v = e ? atoll(e) : 0;
-	return v > 0 ? std::min(v, IRRED_SCRATCH_BYTES) : IRRED_SCRATCH_BYTES;
-}
+static int64_t irred_scratch() { return std::min(env_i64("RB2_IRRED_SCRATCH", IRRED_SCRATCH_BYTES), IRRED_SCRATCH_BYTES); }
 
 /* n queries, all device pointers, none that counts longer than lmax symbols: one launch, the stacks sized from the entries a row can hold */
 static void launch_irreducible(rb2_hip_t *h, int64_t n, const uint8_t *qry, const int64_t *off, int64_t base, int64_t lmax, int64_t min_ovlp, int64_t max_ext,
                                int64_t max_steps, int64_t max_recs, int64_t *rec, int64_t *cnt)
 {
-	const int64_t cap = irred_entry_cap(lmax, min_ovlp, max_ext, max_steps), row = irred_row_bytes(cap, max_ext), rows = irred_rows(n, row, irred_scratch());
+	const int64_t cap = irred_entry_cap(lmax, min_ovlp, max_ext, max_steps), row = irred_row_bytes(cap, max_ext), rows = stack_rows(n, row, irred_scratch(), IRRED_ROWS);
 	h->qscr.ensure((size_t)(rows * row));
 	qlaunch(h, k_irreducible<true>, k_irreducible<false>, (uint64_t)rows, qry, off, base, n, min_ovlp, max_ext, max_steps, max_recs, lmax, rows, cap, h->qscr.p, rec, cnt);
 }
@@ -583,8 +570,7 @@ static void irreducible_check(const char *who, int64_t max_len, int64_t min_ovlp
 {
 	if (min_ovlp < 1) { rb2_fatal("[rb2_hip] %s: min_ovlp must be at least 1 (got %lld)\n", who, (long long)min_ovlp); }
 	if (max_ext < 1 || max_ext > IRRED_MAX_LEN) { rb2_fatal("[rb2_hip] %s: max_ext must be 1 .. %lld (got %lld)\n", who, (long long)IRRED_MAX_LEN, (long long)max_ext); }
-	if (max_steps < 1) { rb2_fatal("[rb2_hip] %s: max_steps must be at least 1 (got %lld)\n", who, (long long)max_steps); }
-	if (max_recs < 1) { rb2_fatal("[rb2_hip] %s: max_recs must be at least 1 (got %lld)\n", who, (long long)max_recs); }
+	budget_check(who, max_steps, max_recs);
 	if (max_len < 1 || max_len > IRRED_MAX_LEN) { rb2_fatal("[rb2_hip] %s: max_len must be 1 .. %lld (got %lld)\n", who, (long long)IRRED_MAX_LEN, (long long)max_len); }
 }
 
@@ -595,11 +581,10 @@ int64_t rb2_hip_irreducible(rb2_hip_t *h, int64_t n, const uint8_t *qry, const i
 	if (n <= 0) return 0;
 	irreducible_check("irreducible", 1, min_ovlp, max_ext, max_steps, max_recs);
 	check_offsets("irreducible", "query", n, off);
-	int64_t lmax = 1;                                              // the longest query that is not malformed by its length alone
-	for (int64_t i = 0; i < n; ++i) if (off[i + 1] - off[i] <= IRRED_MAX_LEN) lmax = std::max(lmax, off[i + 1] - off[i]);
+	const int64_t lmax = longest_wellformed(n, off, IRRED_MAX_LEN);
 	return staged_records(h, n, {qry, off, 0}, 4, max_recs, rec, cnt, [&](int64_t nc, const QStaged &s, int64_t *d_rec, int64_t *d_cnt) {
 		launch_irreducible(h, nc, s.bytes, s.v, s.base, lmax, min_ovlp, max_ext, max_steps, max_recs, d_rec, d_cnt); },
-		[](int64_t c) { return c >= 0 ? c : c <= -2 ? -2 - c : 0; });     // a query that ran out of steps keeps what it had found
+		budget_found);                                             // a query that ran out of steps keeps what it had found
 }
 
 void rb2_hip_irreducible_dev(rb2_hip_t *h, int64_t n, const uint8_t *qry, const int64_t *off, int64_t max_len, int64_t min_ovlp, int64_t max_ext, int64_t max_steps,
@@ -1030,11 +1015,39 @@ static int64_t merge_budget(rb2_hip_t *dst, int64_t batch_bytes, int64_t *max_st
 	int64_t fr = 0, tot = 0;
 	rb2_hip_mem_info(dst->dev, &fr, &tot);
 	*max_strings = merge_string_cap(fr, (int64_t)max_batch_strings() - 1);
-	if (batch_bytes > 0) return batch_bytes;
-	const char *e = getenv("RB2_MERGE_BATCH");
-	const int64_t v = e ? atoll(e) : 0;
-	return v > 0 ? v : merge_default_budget(fr);
+	return batch_bytes > 0 ? batch_bytes : env_i64("RB2_MERGE_BATCH", merge_default_budget(fr));
 }
+
+/* All n (>= 1) strings of src as one batch text, cut into the batches that dst takes (rb2_hip_merge, rb2_hip_correct_into).  x = their
+ * offsets, which stay on the device (8 bytes a string, in src's staging buffer); the host gets the block sums of the scan that made them
+ * (bsum[b] = off[b * B]: rb2_scan.h) and, per batch, the offsets of one block.  One synchronise of src's stream here and one per cut */
+struct BatchSource {
+	rb2_hip_t *src;
+	int64_t n, nb, total, budget, max_strings;
+	uint64_t *x;
+	std::vector<uint64_t> bsum, blk;
+	BatchSource(rb2_hip_t *dst, rb2_hip_t *src_, const char *who, int64_t n_, int64_t batch_bytes)
+		: src(src_), n(n_), nb((int64_t)cdiv((uint64_t)n_, SCAN_ITEMS)), bsum((size_t)nb), blk((size_t)SCAN_ITEMS)
+	{
+		src->qin.ensure((size_t)n + 1);
+		x = (uint64_t*)src->qin.p;
+		const UnpackScr s = unpack_offsets(src, 0, n, x);
+		unsigned long long c[2];
+		HIPCHK(hipMemcpyAsync(c, s.ctr, sizeof(c), hipMemcpyDeviceToHost, src->st));
+		HIPCHK(hipMemcpyAsync(bsum.data(), s.bsum, (size_t)nb * 8, hipMemcpyDeviceToHost, src->st));
+		HIPCHK(hipStreamSynchronize(src->st));
+		total = unpack_total(who, c);
+		budget = merge_budget(dst, batch_bytes, &max_strings);
+	}
+	/* the batch that begins with string i0, whose offset is off0 (merge_next_cut) */
+	MergeCut next_cut(int64_t i0, int64_t off0)
+	{
+		const int64_t B = SCAN_ITEMS;
+		return merge_next_cut(bsum.data(), nb, n, (uint64_t)total, B, i0, (uint64_t)off0, (uint64_t)budget, max_strings, blk.data(), [&](int64_t b, uint64_t *buf) {
+			HIPCHK(hipMemcpyAsync(buf, x + b * B, (size_t)std::min(B, n - b * B) * 8, hipMemcpyDeviceToHost, src->st));
+			HIPCHK(hipStreamSynchronize(src->st)); });
+	}
+};
 
 int64_t rb2_hip_merge(rb2_hip_t *dst, rb2_hip_t *src, int64_t batch_bytes, int64_t info[4])
 {
@@ -1046,31 +1059,19 @@ int64_t rb2_hip_merge(rb2_hip_t *dst, rb2_hip_t *src, int64_t batch_bytes, int64
 	query_begin(src, "merge");
 	int64_t inf[4] = {0, 0, 0, 0};
 	if (info) memcpy(info, inf, sizeof(inf));
-	const int64_t n = (int64_t)src->h_rope[0].n, B = SCAN_ITEMS, nb = (int64_t)cdiv((uint64_t)n, SCAN_ITEMS);   // (part[b] = off[b * B]: rb2_scan.h)
+	const int64_t n = (int64_t)src->h_rope[0].n;
 	if (n == 0) return 0;
-	/* the offsets of all of src's strings in one batch text stay on the device (8 bytes a string, in src's staging buffer); the host gets the block sums */
-	src->qin.ensure((size_t)n + 1);
-	uint64_t *x = (uint64_t*)src->qin.p;
-	const UnpackScr s = unpack_offsets(src, 0, n, x);
-	unsigned long long c[2];
-	std::vector<uint64_t> bsum((size_t)nb), blk((size_t)B);
-	HIPCHK(hipMemcpyAsync(c, s.ctr, sizeof(c), hipMemcpyDeviceToHost, src->st));
-	HIPCHK(hipMemcpyAsync(bsum.data(), s.bsum, (size_t)nb * 8, hipMemcpyDeviceToHost, src->st));
-	HIPCHK(hipStreamSynchronize(src->st));
-	const int64_t total = unpack_total("merge", c);
-	int64_t max_strings;
-	const int64_t budget = merge_budget(dst, batch_bytes, &max_strings);
+	BatchSource S(dst, src, "merge", n, batch_bytes);
+	const int64_t total = S.total;
 	HIPCHK(hipSetDevice(dst->dev));
 	DevBuf<uint8_t> text;
-	text.ensure((size_t)std::min(budget, total) + 64);
+	text.ensure((size_t)std::min(S.budget, total) + 64);
 	int64_t i0 = 0, off0 = 0;
 	while (i0 < n) {
-		const MergeCut cut = merge_next_cut(bsum.data(), nb, n, (uint64_t)total, B, i0, (uint64_t)off0, (uint64_t)budget, max_strings, blk.data(), [&](int64_t b, uint64_t *buf) {
-			HIPCHK(hipMemcpyAsync(buf, x + b * B, (size_t)std::min(B, n - b * B) * 8, hipMemcpyDeviceToHost, src->st));
-			HIPCHK(hipStreamSynchronize(src->st)); });
+		const MergeCut cut = S.next_cut(i0, off0);
 		const int64_t len = (int64_t)cut.off_end - off0;
 		text.ensure((size_t)len + 64);                              // (grows for a string longer than the budget only)
-		unpack_texts(src, i0, cut.end - i0, (const int64_t*)x + i0, off0, 1, len, text.p);
+		unpack_texts(src, i0, cut.end - i0, (const int64_t*)S.x + i0, off0, 1, len, text.p);
 		HIPCHK(hipStreamSynchronize(src->st));                      // the two handles have streams of their own: the batch is complete before dst reads it ...
 		rb2_hip_insert_multi_dev(dst, len, text.p);
 		HIPCHK(hipStreamSynchronize(dst->st));                      // ... and read before src writes the next one
@@ -1086,13 +1087,7 @@ int64_t rb2_hip_merge(rb2_hip_t *dst, rb2_hip_t *src, int64_t batch_bytes, int64
 /* ---- the string graph of the index's own strings (rb2_graph.h, rb2_graph_plan.h) ---- */
 
 /* strings of a chunk at the most: RB2_GRAPH_CHUNK in the environment, read on every call; RB2_QUERY_CHUNK's limit otherwise and at the most */
-static int64_t graph_chunk()
-{
-	const int64_t CH = 1 << 24;
-	const char *e = getenv("RB2_GRAPH_CHUNK");
-	const int64_t v = e ? atoll(e) : 0;
-	return v > 0 ? std::min(v, CH) : CH;
-}
+static int64_t graph_chunk() { return std::min<int64_t>(env_i64("RB2_GRAPH_CHUNK", 1 << 24), 1 << 24); }
 
 static void string_graph_check(rb2_hip_t *h, const char *who, int64_t first, int64_t n, int64_t min_ovlp, int64_t max_ext, int64_t max_steps, int64_t max_recs, int64_t max_hits,
                                int pairs, int64_t cap, const int64_t *edges)
@@ -1143,7 +1138,7 @@ static int64_t string_graph_run(rb2_hip_t *h, const char *who, int64_t first, in
 		h->qout.ensure((size_t)(nc * max_recs) * 4);
 		unpack_texts(h, first + i0, nc, (const int64_t*)x, 0, 0, nb, h->qbytes.p);
 		{
-			const int64_t ecap = irred_entry_cap(lmax, min_ovlp, max_ext, max_steps), row = irred_row_bytes(ecap, max_ext), rows = irred_rows(nc, row, irred_scratch());
+			const int64_t ecap = irred_entry_cap(lmax, min_ovlp, max_ext, max_steps), row = irred_row_bytes(ecap, max_ext), rows = stack_rows(nc, row, irred_scratch(), IRRED_ROWS);
 			h->qscr.ensure((size_t)(rows * row));
 			qlaunch(h, k_irreducible<true, true>, k_irreducible<false, true>, (uint64_t)rows, (const uint8_t*)h->qbytes.p, (const int64_t*)x, 0, nc, min_ovlp, max_ext, max_steps, max_recs, lmax,
 					rows, ecap, h->qscr.p, h->qout.p, cnt);
@@ -1195,12 +1190,7 @@ int64_t rb2_hip_string_graph(rb2_hip_t *h, int64_t first, int64_t n, int64_t min
 /* ---- reads corrected by the k-mer spectrum of the index (k_correct in rb2_correct.h, the rule in rb2_correct_plan.h) ---- */
 
 /* rows of a launch at the most: CORRECT_ROWS; RB2_CORRECT_ROWS in the environment, read on every call, lowers it (tests of rows that take several reads) */
-static int64_t correct_row_cap()
-{
-	const char *e = getenv("RB2_CORRECT_ROWS");
-	const int64_t v = e ? atoll(e) : 0;
-	return v > 0 ? std::min(v, CORRECT_ROWS) : CORRECT_ROWS;
-}
+static int64_t correct_row_cap() { return std::min(env_i64("RB2_CORRECT_ROWS", CORRECT_ROWS), CORRECT_ROWS); }
 
 static void correct_check(const char *who, int64_t k, int64_t min_occ, int64_t max_fix, int64_t max_probes)
 {
@@ -1220,8 +1210,6 @@ static void launch_correct(rb2_hip_t *h, int64_t n, int64_t stride, bool end0, c
 	else qlaunch(h, k_correct<true, false>, k_correct<false, false>, (uint64_t)rows, qry, off, base, n, stride, k, min_occ, max_fix, max_probes, rows, out, cnt, weak);
 }
 
-static int64_t correct_fixes(int64_t c) { return c >= 0 ? c : c <= -2 ? -2 - c : 0; }
-
 int64_t rb2_hip_correct(rb2_hip_t *h, int64_t n, const uint8_t *qry, const int64_t *off, int64_t k, int64_t min_occ, int64_t max_fix, int64_t max_probes, uint8_t *out, int64_t *cnt, int64_t *weak)
 {
 	query_begin(h, "correct");
@@ -1239,7 +1227,7 @@ int64_t rb2_hip_correct(rb2_hip_t *h, int64_t n, const uint8_t *qry, const int64
 		HIPCHK(hipMemcpyAsync(weak + i0, s.tail + nc, (size_t)nc * 8, hipMemcpyDeviceToHost, h->st));
 		if (nb) HIPCHK(hipMemcpyAsync(out + s.base, h->qout.p, (size_t)nb, hipMemcpyDeviceToHost, h->st));
 		HIPCHK(hipStreamSynchronize(h->st));
-		for (int64_t i = i0; i < i0 + nc; ++i) fixes += correct_fixes(cnt[i]);
+		for (int64_t i = i0; i < i0 + nc; ++i) fixes += budget_found(cnt[i]);
 	}
 	return fixes;
 }
@@ -1265,22 +1253,14 @@ int64_t rb2_hip_correct_into(rb2_hip_t *dst, rb2_hip_t *src, int64_t k, int64_t 
 	query_begin(src, "correct_into");
 	int64_t inf[8] = {0, 0, 0, 0, 0, 0, 0, 0};
 	if (info) memcpy(info, inf, sizeof(inf));
-	const int64_t n = (int64_t)src->h_rope[0].n, B = SCAN_ITEMS, nb = (int64_t)cdiv((uint64_t)n, SCAN_ITEMS);
+	const int64_t n = (int64_t)src->h_rope[0].n;
 	if (pairs && n % 2) { rb2_fatal("[rb2_hip] correct_into: pairs needs strings 2i and 2i + 1 to be the two strands of a read, but src holds %lld strings\n", (long long)n); }
 	if (n == 0) return 0;
 	const int64_t stride = pairs ? 2 : 1;
-	/* the offsets of all of src's strings in one batch text, as rb2_hip_merge keeps them */
-	src->qin.ensure((size_t)n + 1);
-	uint64_t *x = (uint64_t*)src->qin.p;
-	const UnpackScr s = unpack_offsets(src, 0, n, x);
-	unsigned long long c[2], cc[CORRECT_CTRS];
-	std::vector<uint64_t> bsum((size_t)nb), blk((size_t)B);
-	HIPCHK(hipMemcpyAsync(c, s.ctr, sizeof(c), hipMemcpyDeviceToHost, src->st));
-	HIPCHK(hipMemcpyAsync(bsum.data(), s.bsum, (size_t)nb * 8, hipMemcpyDeviceToHost, src->st));
-	HIPCHK(hipStreamSynchronize(src->st));
-	const int64_t total = unpack_total("correct_into", c);
-	int64_t max_strings;
-	const int64_t budget = merge_budget(dst, batch_bytes, &max_strings);
+	BatchSource S(dst, src, "correct_into", n, batch_bytes);
+	const int64_t total = S.total, budget = S.budget;
+	const uint64_t *x = S.x;
+	unsigned long long cc[CORRECT_CTRS];
 	HIPCHK(hipSetDevice(dst->dev));
 	DevBuf<uint8_t> text, batch;                                    // a batch as it was unpacked (text order), and what becomes the insert batch
 	DevBuf<int64_t> res;                                            // the counters of the call, then cnt and weak of a batch
@@ -1290,9 +1270,7 @@ int64_t rb2_hip_correct_into(rb2_hip_t *dst, rb2_hip_t *src, int64_t k, int64_t 
 	HIPCHK(hipMemsetAsync(res.p, 0, CORRECT_CTRS * 8, src->st));
 	int64_t i0 = 0, off0 = 0;
 	while (i0 < n) {
-		MergeCut cut = merge_next_cut(bsum.data(), nb, n, (uint64_t)total, B, i0, (uint64_t)off0, (uint64_t)budget, max_strings, blk.data(), [&](int64_t b, uint64_t *buf) {
-			HIPCHK(hipMemcpyAsync(buf, x + b * B, (size_t)std::min(B, n - b * B) * 8, hipMemcpyDeviceToHost, src->st));
-			HIPCHK(hipStreamSynchronize(src->st)); });
+		MergeCut cut = S.next_cut(i0, off0);
 		if (pairs && (cut.end - i0) % 2) {                          // whole pairs: one string less, or the pair when its first string alone is a batch
 			cut.end += cut.end - i0 == 1 ? 1 : -1;
 			HIPCHK(hipMemcpyAsync(&cut.off_end, x + cut.end, 8, hipMemcpyDeviceToHost, src->st));

@@ -49,36 +49,45 @@ constexpr int approx_sub_sym(uint64_t subs, int k) { return (int)(subs >> (16 * 
 constexpr int64_t approx_pad(int64_t L) { return (L + 7) & ~(int64_t)7; }
 constexpr int64_t approx_row_bytes(int64_t L) { return 64 * L + 2 * approx_pad(L); }
 
-/* rows of a launch over n (>= 1) queries of up to L symbols with `bytes` of scratch: at most n and APPROX_ROWS, one at the least */
-constexpr int64_t approx_rows(int64_t n, int64_t L, int64_t bytes)
+/* ---- the row stacks of the searches with a step budget (k_approx, k_approx_ed, k_irreducible; DESIGN.md section 16, "the path stack") ----
+ * Each family has a row layout of its own (approx_row_bytes, edit_row_bytes in rb2_edit_plan.h, irred_row_bytes); what follows takes it as
+ * row_bytes, or as row_bytes_of(L) for the two whose rows are sized by the length of a query: at least 64 L bytes, non-decreasing in L. */
+
+/* what an item has found, from its cnt as these searches (and rb2_hip_correct) report it: >= 0 found, -1 malformed, <= -2 out of steps
+ * with -2 - cnt found by then */
+constexpr int64_t budget_found(int64_t c) { return c >= 0 ? c : c <= -2 ? -2 - c : 0; }
+
+/* rows of a launch over n (>= 1) queries with stacks of row_bytes each in `bytes` of scratch: at most n and max_rows, one at the least */
+constexpr int64_t stack_rows(int64_t n, int64_t row_bytes, int64_t bytes, int64_t max_rows)
 {
-	int64_t r = bytes / approx_row_bytes(L);
-	if (r > APPROX_ROWS) r = APPROX_ROWS;
+	int64_t r = bytes / row_bytes;
+	if (r > max_rows) r = max_rows;
 	if (r > n) r = n;
 	return r < 1 ? 1 : r;
 }
 
 /* the longest query the stacks of `rows` rows hold in `bytes` of scratch (0: none), APPROX_MAX_LEN at the most */
-constexpr int64_t approx_len_cap(int64_t rows, int64_t bytes)
+template <typename RB> constexpr int64_t stack_len_cap(int64_t rows, int64_t bytes, RB row_bytes_of)
 {
-	int64_t L = bytes / rows / 66;                             /* 64 L + 2 pad(L) <= 66 L + 14 */
-	while (L > 0 && approx_row_bytes(L) * rows > bytes) --L;
-	return L > APPROX_MAX_LEN ? APPROX_MAX_LEN : L;
+	int64_t L = bytes / rows / 64;                             /* no longer one fits: a row is at least 64 L bytes */
+	if (L > APPROX_MAX_LEN) L = APPROX_MAX_LEN;
+	while (L > 0 && row_bytes_of(L) * rows > bytes) --L;
+	return L;
 }
 
 /* A call is one launch when every query is short enough for APPROX_SHORT_ROWS rows (or there are no more queries than rows anyway);
  * else two: the first takes the queries of up to `cut` symbols on many rows, the second the longer ones on the rows that lmax allows.
- * lmax = the longest query (APPROX_MAX_LEN when the lengths are not known to the host, as in the _dev variant), at least 1.
+ * lmax = the longest query (APPROX_MAX_LEN when the lengths are not known to the host, as in the _dev variants), at least 1.
  * pass[k] = {lmin, lcap, lrow, rows}: the launch takes the queries with lmin < length <= lcap on `rows` rows with stacks for lrow symbols;
  * returns the number of launches.  Every length, negative and oversized ones included, belongs to exactly one launch. */
-static inline int approx_passes(int64_t n, int64_t lmax, int64_t bytes, int64_t pass[2][4])
+template <typename RB> static inline int stack_passes(int64_t n, int64_t lmax, int64_t bytes, RB row_bytes_of, int64_t pass[2][4])
 {
-	const int64_t all = approx_rows(n, lmax, bytes), cut = approx_len_cap(APPROX_SHORT_ROWS, bytes);
+	const int64_t all = stack_rows(n, row_bytes_of(lmax), bytes, APPROX_ROWS), cut = stack_len_cap(APPROX_SHORT_ROWS, bytes, row_bytes_of);
 	if (all >= n || all >= APPROX_SHORT_ROWS || lmax <= cut || cut < 1) {
 		pass[0][0] = INT64_MIN; pass[0][1] = INT64_MAX; pass[0][2] = lmax; pass[0][3] = all;
 		return 1;
 	}
-	pass[0][0] = INT64_MIN; pass[0][1] = cut; pass[0][2] = cut; pass[0][3] = approx_rows(n, cut, bytes);
+	pass[0][0] = INT64_MIN; pass[0][1] = cut; pass[0][2] = cut; pass[0][3] = stack_rows(n, row_bytes_of(cut), bytes, APPROX_ROWS);
 	pass[1][0] = cut; pass[1][1] = INT64_MAX; pass[1][2] = lmax; pass[1][3] = all;
 	return 2;
 }
@@ -149,13 +158,4 @@ constexpr int64_t irred_pad(int64_t bytes) { return (bytes + 7) & ~(int64_t)7; }
 constexpr int64_t irred_row_bytes(int64_t cap, int64_t max_ext)
 {
 	return 64 * cap + irred_pad(4 * irred_frames(cap, max_ext)) + irred_pad(2 * cap) + irred_pad(irred_frames(cap, max_ext));
-}
-
-/* rows of a launch over n (>= 1) queries with stacks of row_bytes each in `bytes` of scratch: at most n and IRRED_ROWS, one at the least */
-constexpr int64_t irred_rows(int64_t n, int64_t row_bytes, int64_t bytes)
-{
-	int64_t r = bytes / row_bytes;
-	if (r > IRRED_ROWS) r = IRRED_ROWS;
-	if (r > n) r = n;
-	return r < 1 ? 1 : r;
 }

@@ -249,6 +249,19 @@ class StepBudgetExceeded(RuntimeError):
         self.queries, self.results = queries, results
 
 
+def budget_have(cnt, cap):
+    """the records an item holds, from cnt as the searches with a step budget report it (>= 0 found, -1 malformed, <= -2 out of steps
+    with -2 - cnt found by then): what it found, cap at the most"""
+    return np.minimum(np.where(cnt <= -2, -2 - cnt, np.maximum(cnt, 0)), cap)
+
+
+def raise_over_budget(cnt, results, *names):
+    """StepBudgetExceeded(the items with cnt <= -2, results, *names) when there is such an item"""
+    over = np.flatnonzero(cnt <= -2)
+    if len(over):
+        raise StepBudgetExceeded(over.tolist(), results, *names)
+
+
 def expand_runs(rle):
     """1-byte-run 43+3 stream (what the device emits) -> nt6 symbols."""
     rle = np.asarray(rle, dtype=np.uint8)
@@ -629,10 +642,9 @@ class HipBwt:
         above 5 inside, more than 8192 symbols).  Raises StepBudgetExceeded when a query used up max_steps: the exception names the queries
         and carries the results, partial for those"""
         _, rec, cnt = self.approx_raw(queries, max_mm, min_occ, max_steps, max_recs)
-        have = np.minimum(np.where(cnt <= -2, -2 - cnt, np.maximum(cnt, 0)), max_recs)
+        have = budget_have(cnt, max_recs)
         out = [None if c == -1 else sorted((int(lo), int(hi), int(mm), unpack_subs(sb)) for lo, hi, mm, sb in r[:k].tolist()) for r, k, c in zip(rec, have, cnt)]
-        if (cnt <= -2).any():
-            raise StepBudgetExceeded(np.flatnonzero(cnt <= -2).tolist(), out)
+        raise_over_budget(cnt, out)
         return out
 
     def approx_dev(self, n, qry_dev, off_dev, rec_dev, cnt_dev, max_mm, min_occ=1, max_steps=1 << 16, max_recs=64):
@@ -654,10 +666,9 @@ class HipBwt:
         or None for a malformed query ('$' or a code above 5 inside, more than 8192 symbols).  Raises StepBudgetExceeded when a query used up
         max_steps: the exception names the queries and carries the results, partial for those"""
         _, rec, cnt = self.approx_ed_raw(queries, max_ed, min_occ, max_steps, max_recs)
-        have = np.minimum(np.where(cnt <= -2, -2 - cnt, np.maximum(cnt, 0)), max_recs)
+        have = budget_have(cnt, max_recs)
         out = [None if c == -1 else sorted(map(tuple, r[:k].tolist())) for r, k, c in zip(rec, have, cnt)]
-        if (cnt <= -2).any():
-            raise StepBudgetExceeded(np.flatnonzero(cnt <= -2).tolist(), out, who="approx_ed", lower="max_ed")
+        raise_over_budget(cnt, out, "approx_ed", "max_ed")
         return out
 
     def approx_ed_dev(self, n, qry_dev, off_dev, rec_dev, cnt_dev, max_ed, min_occ=1, max_steps=1 << 16, max_recs=64):
@@ -739,7 +750,7 @@ class HipBwt:
         if max_ext is None:
             max_ext = min(max(max((len(encode_pattern(q)) for q in queries), default=1), 1), 8192)
         _, rec, cnt = self.irreducible_raw(queries, min_ovlp, max_ext, max_steps, max_recs)
-        have = np.minimum(np.where(cnt <= -2, -2 - cnt, np.maximum(cnt, 0)), max_recs)
+        have = budget_have(cnt, max_recs)
         live = np.arange(max_recs)[None, :] < have[:, None]
         who = np.nonzero(live)[0]
         recs = rec[live]
@@ -750,8 +761,7 @@ class HipBwt:
             for i, l, e, k, row in zip(who.tolist(), recs[:, 0].tolist(), recs[:, 1].tolist(), np.minimum(n_ids, max_hits).tolist(), ids.tolist()):
                 out[i] += [(s ^ 1 if pairs else s, l, e) for s in row[:k]]
         out = [o if o is None else sorted(o) for o in out]
-        if (cnt <= -2).any():
-            raise StepBudgetExceeded(np.flatnonzero(cnt <= -2).tolist(), out, "irreducible", "max_ext")
+        raise_over_budget(cnt, out, "irreducible", "max_ext")
         return out
 
     def edges(self, ids=None, min_ovlp=1, **kw):
@@ -1014,8 +1024,7 @@ class HipBwt:
         reads with the fixes made by then"""
         _, out, off, cnt, weak = self.correct_raw(reads, k, min_occ, max_fix, max_probes)
         res = ([out[off[i]:off[i + 1]].copy() for i in range(len(off) - 1)], cnt, weak)
-        if (cnt <= -2).any():
-            raise StepBudgetExceeded(np.flatnonzero(cnt <= -2).tolist(), res, "correct", "max_fix", "max_probes")
+        raise_over_budget(cnt, res, "correct", "max_fix", "max_probes")
         return res
 
     def correct_dev(self, n, qry_dev, off_dev, total, out_dev, cnt_dev, weak_dev, k, min_occ=3, max_fix=8, max_probes=869):

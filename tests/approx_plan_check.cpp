@@ -30,7 +30,7 @@ static long check_launches()
 	const int64_t lens[] = {1, 2, 7, 8, 9, 40, 101, 247, 248, 249, 1000, 8191, 8192};
 	for (int64_t bytes : sizes) {
 		for (int64_t rows : {(int64_t)1, (int64_t)16, (int64_t)496, APPROX_SHORT_ROWS, APPROX_ROWS}) {
-			const int64_t c = approx_len_cap(rows, bytes);
+			const int64_t c = stack_len_cap(rows, bytes, approx_row_bytes);
 			CHECK(c >= 0 && c <= APPROX_MAX_LEN, "cap");
 			CHECK(c == 0 || approx_row_bytes(c) * rows <= bytes, "rows %lld bytes %lld: cap %lld does not fit", (long long)rows, (long long)bytes, (long long)c);
 			CHECK(c == APPROX_MAX_LEN || approx_row_bytes(c + 1) * rows > bytes, "rows %lld bytes %lld: cap %lld could be larger", (long long)rows, (long long)bytes, (long long)c);
@@ -38,12 +38,12 @@ static long check_launches()
 		}
 		for (int64_t nq : ns)
 			for (int64_t lmax : lens) {
-				const int64_t r = approx_rows(nq, lmax, bytes);
+				const int64_t r = stack_rows(nq, approx_row_bytes(lmax), bytes, APPROX_ROWS);
 				CHECK(r >= 1 && r <= nq && r <= APPROX_ROWS, "rows");
 				CHECK(r == 1 || r * approx_row_bytes(lmax) <= bytes, "n %lld L %lld bytes %lld: %lld rows do not fit", (long long)nq, (long long)lmax, (long long)bytes, (long long)r);
 				CHECK(r == nq || r == APPROX_ROWS || (r + 1) * approx_row_bytes(lmax) > bytes, "n %lld L %lld bytes %lld: %lld rows could be more", (long long)nq, (long long)lmax, (long long)bytes, (long long)r);
 				int64_t pass[2][4];
-				const int np = approx_passes(nq, lmax, bytes, pass);
+				const int np = stack_passes(nq, lmax, bytes, approx_row_bytes, pass);
 				CHECK(np == 1 || np == 2, "passes");
 				two += np == 2;
 				for (int k = 0; k < np; ++k) {
@@ -65,11 +65,13 @@ static long check_launches()
 			}
 	}
 	int64_t pass[2][4];
-	CHECK(approx_passes(100000, APPROX_MAX_LEN, APPROX_SCRATCH_BYTES, pass) == 2 && pass[0][1] == 248 && pass[0][3] >= APPROX_SHORT_ROWS && pass[0][3] < APPROX_SHORT_ROWS + 64 && pass[1][3] == 496, "the _dev variant: %lld %lld %lld",
+	CHECK(stack_passes(100000, APPROX_MAX_LEN, APPROX_SCRATCH_BYTES, approx_row_bytes, pass) == 2 && pass[0][1] == 248 && pass[0][3] >= APPROX_SHORT_ROWS && pass[0][3] < APPROX_SHORT_ROWS + 64 && pass[1][3] == 496, "the _dev variant: %lld %lld %lld",
 	      (long long)pass[0][1], (long long)pass[0][3], (long long)pass[1][3]);
-	CHECK(approx_passes(100000, 101, APPROX_SCRATCH_BYTES, pass) == 1 && pass[0][3] == APPROX_ROWS, "reads of 101");
-	CHECK(approx_passes(400, APPROX_MAX_LEN, APPROX_SCRATCH_BYTES, pass) == 1 && pass[0][3] == 400, "few queries");
+	CHECK(stack_passes(100000, 101, APPROX_SCRATCH_BYTES, approx_row_bytes, pass) == 1 && pass[0][3] == APPROX_ROWS, "reads of 101");
+	CHECK(stack_passes(400, APPROX_MAX_LEN, APPROX_SCRATCH_BYTES, approx_row_bytes, pass) == 1 && pass[0][3] == 400, "few queries");
 	CHECK(two > 0, "no case had two launches");
+	CHECK(budget_found(-3) == 1 && budget_found(-2) == 0 && budget_found(-1) == 0 && budget_found(0) == 0 && budget_found(1) == 1 && budget_found(INT64_MIN + 2) == INT64_MAX - 3,
+	      "what a cnt says was found");
 	return n;
 }
 

@@ -1,7 +1,7 @@
 // Brute-force check of csrc/rb2_edit_plan.h, the arithmetic of rb2_hip_approx_ed that needs no GPU: the packed column against a full
 // Levenshtein column, a word-trie search driven by the header's functions against the definition of a match over all substrings of tiny
 // sets of strings (with the piece bound and without it), the bound against the matches below a node, and the rows, stacks and launches of
-// a call.  Built and run by tests/test_edit_plan.py, once plain and once under AddressSanitizer + UndefinedBehaviorSanitizer; prints
+// a call (stack_rows, stack_len_cap and stack_passes of csrc/rb2_query_plan.h with this search's row size).  Built and run by tests/test_edit_plan.py, once plain and once under AddressSanitizer + UndefinedBehaviorSanitizer; prints
 // "EDIT PLAN OK" and leaves with 0 when every property holds.
 #include <algorithm>
 #include <cstdio>
@@ -47,6 +47,7 @@ static long check_launches()
 	const int64_t ns[] = {1, 2, 15, 16, 17, 300, 440, 441, 16383, 16384, 16385, 40000, 1 << 20, (int64_t)1 << 24};
 	const int64_t lens[] = {1, 2, 7, 8, 9, 40, 101, 216, 217, 221, 222, 1000, 8191, 8192};
 	for (int E = 0; E <= EDIT_MAX_ED; ++E) {
+		const auto rb_of = [E](int64_t L) { return edit_row_bytes(L, E); };
 		for (int64_t L = 1; L <= APPROX_MAX_LEN; ++L) {
 			const int64_t rb = edit_row_bytes(L, E), P = edit_nodes(L, E);
 			CHECK(rb % 8 == 0 && rb >= 64 * P + 8 * P + P + L && rb < 73 * P + L + 16, "L %lld", (long long)L);
@@ -55,7 +56,7 @@ static long check_launches()
 		}
 		for (int64_t bytes : sizes) {
 			for (int64_t rows : {(int64_t)1, (int64_t)16, (int64_t)440, APPROX_SHORT_ROWS, APPROX_ROWS}) {
-				const int64_t c = edit_len_cap(rows, E, bytes);
+				const int64_t c = stack_len_cap(rows, bytes, rb_of);
 				CHECK(c >= 0 && c <= APPROX_MAX_LEN, "cap");
 				CHECK(c == 0 || edit_row_bytes(c, E) * rows <= bytes, "rows %lld bytes %lld: cap %lld does not fit", (long long)rows, (long long)bytes, (long long)c);
 				CHECK(c == APPROX_MAX_LEN || edit_row_bytes(c + 1, E) * rows > bytes, "rows %lld bytes %lld: cap %lld could be larger", (long long)rows, (long long)bytes, (long long)c);
@@ -63,12 +64,12 @@ static long check_launches()
 			}
 			for (int64_t nq : ns)
 				for (int64_t lmax : lens) {
-					const int64_t r = edit_rows(nq, lmax, E, bytes);
+					const int64_t r = stack_rows(nq, edit_row_bytes(lmax, E), bytes, APPROX_ROWS);
 					CHECK(r >= 1 && r <= nq && r <= APPROX_ROWS, "rows");
 					CHECK(r == 1 || r * edit_row_bytes(lmax, E) <= bytes, "n %lld L %lld bytes %lld: %lld rows do not fit", (long long)nq, (long long)lmax, (long long)bytes, (long long)r);
 					CHECK(r == nq || r == APPROX_ROWS || (r + 1) * edit_row_bytes(lmax, E) > bytes, "n %lld L %lld bytes %lld: %lld rows could be more", (long long)nq, (long long)lmax, (long long)bytes, (long long)r);
 					int64_t pass[2][4];
-					const int np = edit_passes(nq, lmax, E, bytes, pass);
+					const int np = stack_passes(nq, lmax, bytes, rb_of, pass);
 					CHECK(np == 1 || np == 2, "passes");
 					two += np == 2;
 					for (int k = 0; k < np; ++k) {
@@ -91,10 +92,11 @@ static long check_launches()
 		}
 	}
 	int64_t pass[2][4];
-	CHECK(edit_passes(100000, APPROX_MAX_LEN, 2, APPROX_SCRATCH_BYTES, pass) == 2 && pass[0][1] == edit_len_cap(APPROX_SHORT_ROWS, 2, APPROX_SCRATCH_BYTES) && pass[0][1] > 200 && pass[0][1] < 222 &&
+	const auto rb2 = [](int64_t L) { return edit_row_bytes(L, 2); };
+	CHECK(stack_passes(100000, APPROX_MAX_LEN, APPROX_SCRATCH_BYTES, rb2, pass) == 2 && pass[0][1] == stack_len_cap(APPROX_SHORT_ROWS, APPROX_SCRATCH_BYTES, rb2) && pass[0][1] > 200 && pass[0][1] < 222 &&
 	      pass[0][3] >= APPROX_SHORT_ROWS && pass[1][3] >= 440 && pass[1][3] <= 443, "the _dev variant: %lld %lld %lld", (long long)pass[0][1], (long long)pass[0][3], (long long)pass[1][3]);
-	CHECK(edit_passes(100000, 101, 2, APPROX_SCRATCH_BYTES, pass) == 1 && pass[0][3] == APPROX_ROWS, "reads of 101");
-	CHECK(edit_passes(400, APPROX_MAX_LEN, 4, APPROX_SCRATCH_BYTES, pass) == 1 && pass[0][3] == 400, "few queries");
+	CHECK(stack_passes(100000, 101, APPROX_SCRATCH_BYTES, rb2, pass) == 1 && pass[0][3] == APPROX_ROWS, "reads of 101");
+	CHECK(stack_passes(400, APPROX_MAX_LEN, APPROX_SCRATCH_BYTES, [](int64_t L) { return edit_row_bytes(L, 4); }, pass) == 1 && pass[0][3] == 400, "few queries");
 	CHECK(two > 0, "no case had two launches");
 	return n;
 }

@@ -45,14 +45,14 @@ static long check_rows()
 	const int64_t sizes[] = {1, 87, 88, 89, 175, 176, 177, 4096, 1 << 20, IRRED_SCRATCH_BYTES}, ns[] = {1, 2, 15, 16, 17, 300, 32767, 32768, 32769, 1 << 20};
 	const int64_t rbs[] = {88, 96, 1000, 235800, (int64_t)1 << 28, ((int64_t)1 << 28) + 8, (int64_t)1 << 32};
 	for (int64_t bytes : sizes) for (int64_t nq : ns) for (int64_t rb : rbs) {
-		const int64_t r = irred_rows(nq, rb, bytes);
+		const int64_t r = stack_rows(nq, rb, bytes, IRRED_ROWS);
 		CHECK(r >= 1 && r <= nq && r <= IRRED_ROWS, "rows");
 		CHECK(r == 1 || r * rb <= bytes, "n %lld row %lld bytes %lld: %lld rows do not fit", (long long)nq, (long long)rb, (long long)bytes, (long long)r);
 		CHECK(r == nq || r == IRRED_ROWS || (r + 1) * rb > bytes, "n %lld row %lld bytes %lld: %lld rows could be more", (long long)nq, (long long)rb, (long long)bytes, (long long)r);
 		++n;
 	}
-	CHECK(irred_rows(100, 88, 176) == 2 && irred_rows(100, 88, 175) == 1 && irred_rows(100, 88, 1) == 1 && irred_rows(1 << 20, 88, IRRED_SCRATCH_BYTES) == IRRED_ROWS, "rows at the edges");
-	CHECK(irred_rows(1000000, irred_row_bytes(irred_entry_cap(100, 50, 50, 1 << 16), 50), IRRED_SCRATCH_BYTES) == 1592, "reads of 100 at min_ovlp 50");
+	CHECK(stack_rows(100, 88, 176, IRRED_ROWS) == 2 && stack_rows(100, 88, 175, IRRED_ROWS) == 1 && stack_rows(100, 88, 1, IRRED_ROWS) == 1 && stack_rows(1 << 20, 88, IRRED_SCRATCH_BYTES, IRRED_ROWS) == IRRED_ROWS, "rows at the edges");
+	CHECK(stack_rows(1000000, irred_row_bytes(irred_entry_cap(100, 50, 50, 1 << 16), 50), IRRED_SCRATCH_BYTES, IRRED_ROWS) == 1592, "reads of 100 at min_ovlp 50");
 	return n;
 }
 
