@@ -40,7 +40,7 @@ def _run(cmd):
 def build_hip(force=False):
     os.makedirs(LIBDIR, exist_ok=True)
     out = lib_path("librb2hip.so")
-    srcs = [os.path.join(CSRC, f) for f in ("rb2_engine.hip", "rb2_kernels.h", "rb2_merge.h", "rb2_device.h", "rb2_multi.h", "rb2_query.h", "rb2_unitig.h", "rb2_clean.h", "rb2_query_host.h", "rb2_query_plan.h", "rb2_kmer_plan.h", "rb2_fmd_load.h", "rb2_delete.h", "rb2_delete_plan.h", "rb2_fmd_save.h", "rb2_fmd_plan.h", "rb2_unpack.h", "rb2_merge_plan.h", "rb2_round_plan.h", "rb2_graph.h", "rb2_graph_plan.h", "rb2_scan.h", "rb2_correct.h", "rb2_correct_plan.h", "rb2_edit.h", "rb2_edit_plan.h")] + [os.path.join(INC, "rb2_hip.h")]
+    srcs = [os.path.join(CSRC, f) for f in ("rb2_engine.hip", "rb2_kernels.h", "rb2_merge.h", "rb2_device.h", "rb2_multi.h", "rb2_query.h", "rb2_unitig.h", "rb2_clean.h", "rb2_query_host.h", "rb2_query_plan.h", "rb2_kmer_plan.h", "rb2_fmd_load.h", "rb2_delete.h", "rb2_delete_plan.h", "rb2_fmd_save.h", "rb2_fmd_plan.h", "rb2_unpack.h", "rb2_merge_plan.h", "rb2_round_plan.h", "rb2_graph.h", "rb2_graph_plan.h", "rb2_scan.h", "rb2_correct.h", "rb2_correct_plan.h", "rb2_edit.h", "rb2_edit_plan.h", "rb2_scratch.h")] + [os.path.join(INC, "rb2_hip.h")]
     if not force and _newer(out, srcs):
         return out
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")

@@ -15,6 +15,7 @@
 #include <thread>
 #include <condition_variable>
 #include "rb2_hip.h"
+#include "rb2_scratch.h"
 #include "rb2_kernels.h"
 #include "rb2_query.h"
 #include "rb2_unitig.h"
@@ -41,6 +42,7 @@ using namespace rb2;
 // must not run there, and exit() there would run the atexit handlers while the other ranks still spin at their barrier: the first
 // failure is recorded, the thread unwinds (RankAbort), the other rank threads leave at their next barrier, and the thread that called
 // the API reports it -- message, handler, abort() -- once all of them are joined.
+// Whichever way it leaves, rb2_fatal first gives back the scratch of every call open on its thread (CallScope::release_open, rb2_scratch.h).
 static rb2_hip_fatal_cb g_fatal_cb = nullptr;
 static void *g_fatal_user = nullptr;
 #include <cstdarg>
@@ -58,6 +60,7 @@ struct RankAbort {};
 	va_start(ap, fmt);
 	vsnprintf(msg, sizeof(msg), fmt, ap);
 	va_end(ap);
+	CallScope::release_open();
 	if (t_rank_fail) {
 		{ std::lock_guard<std::mutex> lk(t_rank_fail->mu); if (!t_rank_fail->failed.load()) { memcpy(t_rank_fail->msg, msg, sizeof(msg)); t_rank_fail->failed.store(1); } }
 		throw RankAbort();
@@ -173,7 +176,13 @@ template <typename T> struct DevBuf {
 		p = q; cap = ncap;
 	}
 	void release() { if (p) { if (vm_res) vm_release(); else HIPCHK(hipFree(p)); } p = nullptr; cap = 0; }
+	void release_quiet() { if (p) { if (vm_res) vm_release(); else (void)hipFree(p); } p = nullptr; cap = 0; }   // (a CallScope's: no error is reported)
 };
+// call scratch (a CallScope's, all released unchecked): n items that never grow; pinned host memory; an event; a wait for the stream, made last so that it goes first
+template <class T> static T *scratch(CallScope &cs, size_t n) { DevBuf<T> &b = cs.make<DevBuf<T>>(); b.ensure(n); return b.p; }
+struct PinBuf { void *p = nullptr; void release_quiet() { if (p) (void)hipHostFree(p); p = nullptr; } };
+struct EventBox { hipEvent_t e = nullptr; void release_quiet() { if (e) (void)hipEventDestroy(e); e = nullptr; } };
+struct StreamDrain { const hipStream_t *st = nullptr; void release_quiet() { if (st) (void)hipStreamSynchronize(*st); st = nullptr; } };
 
 struct Pool {
 	DevBuf<uint8_t> data, xh; DevBuf<LeafMeta> meta, own; DevBuf<SbRec> sbrec; DevBuf<SbBase> sbbase;
@@ -1114,12 +1123,11 @@ void insert_dev(rb2_hip_t *h, int64_t len64, const uint8_t *s, bool lazy = false
 		const int64_t p = split_point(h, s, len64);
 		if (h->k.trace) fprintf(stderr, "[rb2_hip] batch of %llu strings cut at byte %lld of %lld\n", (unsigned long long)B.m, (long long)p, (long long)len64);
 		insert_dev(h, p, s, false);
-		DevBuf<uint8_t> half;
-		half.ensure((size_t)(len64 - p) + 64);
-		HIPCHK(hipMemcpyAsync(half.p, s + p, (size_t)(len64 - p), hipMemcpyDeviceToDevice, h->st));
-		insert_dev(h, len64 - p, half.p, false);
+		CallScope cs;
+		uint8_t *half = scratch<uint8_t>(cs, (size_t)(len64 - p) + 64);
+		HIPCHK(hipMemcpyAsync(half, s + p, (size_t)(len64 - p), hipMemcpyDeviceToDevice, h->st));
+		insert_dev(h, len64 - p, half, false);
 		HIPCHK(hipStreamSynchronize(h->st));
-		half.release();
 		return;
 	}
 	// The first rounds of a batch are hot spots by construction: round 0 puts every string into rope $ (at its end in input order,
@@ -1506,6 +1514,16 @@ static uint64_t ld_piece_table(rb2_hip_t *h, const char *who, const uint64_t tot
 	}
 	return leaf;
 }
+// what a loader counts into, zeroed: cnt [0, 36): symbol a in rope b, [36, 36 + NR * 6): per piece; flag [0] bad input, [1] long runs; the long runs
+struct LdCounts { unsigned long long *cnt; uint32_t *flag; LdLong *longs; };
+constexpr uint32_t LD_LONG_CAP = 1u << 20;
+static LdCounts ld_counts(CallScope &cs, hipStream_t st)
+{
+	const LdCounts c = {scratch<unsigned long long>(cs, 36 + NR * 6), scratch<uint32_t>(cs, 2), scratch<LdLong>(cs, LD_LONG_CAP)};
+	HIPCHK(hipMemsetAsync(c.cnt, 0, (36 + NR * 6) * 8, st));
+	HIPCHK(hipMemsetAsync(c.flag, 0, 8, st));
+	return c;
+}
 // the zeroed pool of `leaf` leaves the pieces are ORed into: pool side ps (the loaders: the current one; a deletion: the other)
 static PoolView ld_zero_pool(rb2_hip_t *h, uint64_t leaf, int ps)
 {
@@ -1546,26 +1564,21 @@ void rb2_hip_load_ropes(rb2_hip_t *h, const uint8_t *const rle[6], const int64_t
 	hipStream_t st = h->st;
 	// The run bytes go to the device as they are and are decoded there (k_ld_*, rb2_kernels.h): at configs[4] size -- an index of
 	// 500 M reads, 35 GB of runs -- a host loop over the runs is minutes of one core (the first version: 17 s for 5 G symbols).
-	DevBuf<uint8_t> dr[6]; DevBuf<uint64_t> blk[6];
-	DevBuf<unsigned long long> cnt;                            // [0, 36): symbol totals of the six ropes; [36, 36 + NR * 6): per piece
-	DevBuf<uint32_t> flag;                                     // [0] bad input, [1] long runs
-	const uint32_t long_cap = 1u << 20;
-	DevBuf<LdLong> longs;
-	cnt.ensure(36 + NR * 6); flag.ensure(2); longs.ensure(long_cap);
-	HIPCHK(hipMemsetAsync(cnt.p, 0, (36 + NR * 6) * 8, st));
-	HIPCHK(hipMemsetAsync(flag.p, 0, 8, st));
+	CallScope cs;
+	const LdCounts c = ld_counts(cs, st);
+	uint8_t *dr[6] = {}; uint64_t *blk[6] = {};
 	uint64_t nblk[6];
 	for (int b = 0; b < 6; ++b) {
 		const uint64_t nb = rle[b] && n_bytes[b] > 0 ? (uint64_t)n_bytes[b] : 0;
 		nblk[b] = cdiv(nb, LDB);
 		if (nb == 0) continue;
-		dr[b].ensure(nb + 16); blk[b].ensure(nblk[b] + 1);
-		HIPCHK(hipMemcpyAsync(dr[b].p, rle[b], nb, hipMemcpyHostToDevice, st));
-		hipLaunchKernelGGL(k_ld_count, dim3((unsigned)nblk[b]), dim3(256), 0, st, (const uint8_t*)dr[b].p, nb, blk[b].p, cnt.p + b * 6, flag.p);
+		dr[b] = scratch<uint8_t>(cs, nb + 16); blk[b] = scratch<uint64_t>(cs, nblk[b] + 1);
+		HIPCHK(hipMemcpyAsync(dr[b], rle[b], nb, hipMemcpyHostToDevice, st));
+		hipLaunchKernelGGL(k_ld_count, dim3((unsigned)nblk[b]), dim3(256), 0, st, (const uint8_t*)dr[b], nb, blk[b], c.cnt + b * 6, c.flag);
 	}
 	unsigned long long tot_h[36]; uint32_t flag_h[2];
-	HIPCHK(hipMemcpyAsync(tot_h, cnt.p, sizeof(tot_h), hipMemcpyDeviceToHost, st));
-	HIPCHK(hipMemcpyAsync(flag_h, flag.p, 8, hipMemcpyDeviceToHost, st));
+	HIPCHK(hipMemcpyAsync(tot_h, c.cnt, sizeof(tot_h), hipMemcpyDeviceToHost, st));
+	HIPCHK(hipMemcpyAsync(flag_h, c.flag, 8, hipMemcpyDeviceToHost, st));
 	HIPCHK(hipStreamSynchronize(st));
 	if (flag_h[0]) { rb2_fatal("[rb2_hip] load_ropes: not run-length bytes of ropebwt2's codec (bad symbol or truncated run)\n"); }
 	uint64_t tot[6][6];
@@ -1574,23 +1587,20 @@ void rb2_hip_load_ropes(rb2_hip_t *h, const uint8_t *const rle[6], const int64_t
 	LdPieces tab[6];
 	const uint64_t leaf = ld_piece_table(h, "load_ropes", tot, rp, tab);
 	PoolView pv = ld_zero_pool(h, leaf, h->pside);
-	DevBuf<uint64_t> part;
-	part.ensure(scan_parts(*std::max_element(nblk, nblk + 6)));
+	uint64_t *part = scratch<uint64_t>(cs, scan_parts(*std::max_element(nblk, nblk + 6)));
 	for (int b = 0; b < 6; ++b) {
 		if (nblk[b] == 0) continue;
-		scan_launch<ScanAdd<uint64_t>>(st, ScanIn<uint64_t>{blk[b].p, nblk[b]}, nblk[b], part.p, blk[b].p, nullptr, false);   // the blocks' symbol counts become their offsets, in place
-		hipLaunchKernelGGL(k_ld_expand, dim3((unsigned)nblk[b]), dim3(256), 0, st, (const uint8_t*)dr[b].p, (uint64_t)n_bytes[b], (const uint64_t*)blk[b].p, tab[b],
-				(uint64_t*)pv.data, cnt.p + 36, longs.p, flag.p + 1, long_cap, flag.p);
-		hipLaunchKernelGGL(k_ld_long, dim3(1024), dim3(256), 0, st, (const LdLong*)longs.p, (const uint32_t*)(flag.p + 1), long_cap, (uint64_t*)pv.data);
-		HIPCHK(hipMemcpyAsync(flag_h, flag.p, 8, hipMemcpyDeviceToHost, st));
+		scan_launch<ScanAdd<uint64_t>>(st, ScanIn<uint64_t>{blk[b], nblk[b]}, nblk[b], part, blk[b], nullptr, false);   // the blocks' symbol counts become their offsets, in place
+		hipLaunchKernelGGL(k_ld_expand, dim3((unsigned)nblk[b]), dim3(256), 0, st, (const uint8_t*)dr[b], (uint64_t)n_bytes[b], (const uint64_t*)blk[b], tab[b],
+				(uint64_t*)pv.data, c.cnt + 36, c.longs, c.flag + 1, LD_LONG_CAP, c.flag);
+		hipLaunchKernelGGL(k_ld_long, dim3(1024), dim3(256), 0, st, (const LdLong*)c.longs, (const uint32_t*)(c.flag + 1), LD_LONG_CAP, (uint64_t*)pv.data);
+		HIPCHK(hipMemcpyAsync(flag_h, c.flag, 8, hipMemcpyDeviceToHost, st));
 		HIPCHK(hipStreamSynchronize(st));                      // (the long-run list is per rope)
 		if (flag_h[0]) { rb2_fatal("[rb2_hip] load_ropes: rope %d does not match the symbol counts of the other ropes\n", b); }
-		if (flag_h[1] > long_cap) { rb2_fatal("[rb2_hip] load_ropes: more than %u runs longer than %u symbols in rope %d\n", long_cap, LD_LONG, b); }
-		HIPCHK(hipMemsetAsync(flag.p + 1, 0, 4, st));
+		if (flag_h[1] > LD_LONG_CAP) { rb2_fatal("[rb2_hip] load_ropes: more than %u runs longer than %u symbols in rope %d\n", LD_LONG_CAP, LD_LONG, b); }
+		HIPCHK(hipMemsetAsync(c.flag + 1, 0, 4, st));
 	}
-	ld_finish(h, rp, leaf, pv, cnt.p + 36);
-	for (int b = 0; b < 6; ++b) { dr[b].release(); blk[b].release(); }
-	cnt.release(); flag.release(); longs.release(); part.release();
+	ld_finish(h, rp, leaf, pv, c.cnt + 36);
 }
 
 /* ---- .fmd images (kernels in rb2_fmd_load.h) ------------------------------- */
@@ -1619,25 +1629,20 @@ int64_t rb2_hip_load_fmd(rb2_hip_t *h, const void *fmd, int64_t n_bytes)
 	const uint64_t rows = ropes.R[6];
 	// one copy of the stream; everything else stays on the device until the 6 x 6 matrix comes back
 	const uint32_t nwg = (uint32_t)cdiv(nb, 256);
-	DevBuf<uint64_t> dw, wg;
-	DevBuf<unsigned long long> cnt;                            // [0, 36): symbol a in rope b; [36, 36 + NR * 6): per piece
-	DevBuf<uint32_t> flag;                                     // [0] FMD_BAD_* bits, [1] long runs
-	const uint32_t long_cap = 1u << 20;
-	DevBuf<LdLong> longs;
-	dw.ensure(nwords + FMD_BW); wg.ensure((uint64_t)nwg + 1); cnt.ensure(36 + NR * 6); flag.ensure(2); longs.ensure(long_cap);
-	HIPCHK(hipMemcpyAsync(dw.p, img + 80, sbytes, hipMemcpyHostToDevice, st));
-	HIPCHK(hipMemsetAsync(cnt.p, 0, (36 + NR * 6) * 8, st));
-	HIPCHK(hipMemsetAsync(flag.p, 0, 8, st));
-	HIPCHK(hipMemsetAsync(wg.p, 0, ((uint64_t)nwg + 1) * 8, st));
+	CallScope cs;
+	uint64_t *dw = scratch<uint64_t>(cs, nwords + FMD_BW), *wg = scratch<uint64_t>(cs, (uint64_t)nwg + 1);
+	HIPCHK(hipMemcpyAsync(dw, img + 80, sbytes, hipMemcpyHostToDevice, st));
+	const LdCounts c = ld_counts(cs, st);                      // (flag[0]: FMD_BAD_* bits)
+	HIPCHK(hipMemsetAsync(wg, 0, ((uint64_t)nwg + 1) * 8, st));
 	if (nb) {
-		hipLaunchKernelGGL(k_fmd_sizes, dim3(nwg), dim3(256), 0, st, (const uint64_t*)dw.p, nb, nwords, wg.p, flag.p);
-		hipLaunchKernelGGL((k_scan_block<ScanAdd<uint64_t>, ScanIn<uint64_t>, 256>), dim3(1), dim3(256), 0, st, ScanIn<uint64_t>{wg.p, nwg}, wg.p);   // in place; wg[nwg] = the rows
-		hipLaunchKernelGGL(k_fmd_count, dim3(nwg), dim3(256), 0, st, (const uint64_t*)dw.p, nb, nwords, (const uint64_t*)wg.p, ropes, cnt.p, flag.p);
+		hipLaunchKernelGGL(k_fmd_sizes, dim3(nwg), dim3(256), 0, st, (const uint64_t*)dw, nb, nwords, wg, c.flag);
+		hipLaunchKernelGGL((k_scan_block<ScanAdd<uint64_t>, ScanIn<uint64_t>, 256>), dim3(1), dim3(256), 0, st, ScanIn<uint64_t>{wg, nwg}, wg);   // in place; wg[nwg] = the rows
+		hipLaunchKernelGGL(k_fmd_count, dim3(nwg), dim3(256), 0, st, (const uint64_t*)dw, nb, nwords, (const uint64_t*)wg, ropes, c.cnt, c.flag);
 	}
 	unsigned long long tot_h[36], rows_dev; uint32_t flag_h[2];
-	HIPCHK(hipMemcpyAsync(tot_h, cnt.p, sizeof(tot_h), hipMemcpyDeviceToHost, st));
-	HIPCHK(hipMemcpyAsync(&rows_dev, wg.p + nwg, 8, hipMemcpyDeviceToHost, st));
-	HIPCHK(hipMemcpyAsync(flag_h, flag.p, 8, hipMemcpyDeviceToHost, st));
+	HIPCHK(hipMemcpyAsync(tot_h, c.cnt, sizeof(tot_h), hipMemcpyDeviceToHost, st));
+	HIPCHK(hipMemcpyAsync(&rows_dev, wg + nwg, 8, hipMemcpyDeviceToHost, st));
+	HIPCHK(hipMemcpyAsync(flag_h, c.flag, 8, hipMemcpyDeviceToHost, st));
 	HIPCHK(hipStreamSynchronize(st));
 	if (flag_h[0] & FMD_BAD_TYPE) { rb2_fatal("[rb2_hip] load_fmd: invalid block header (type 3, or the stream ends inside a header)\n"); }
 	if (flag_h[0] & FMD_BAD_SYM) { rb2_fatal("[rb2_hip] load_fmd: a run has a symbol code above 5\n"); }
@@ -1665,16 +1670,15 @@ int64_t rb2_hip_load_fmd(rb2_hip_t *h, const void *fmd, int64_t n_bytes)
 		}
 	gp.q[NR] = rows;
 	if (nb) {
-		hipLaunchKernelGGL(k_fmd_expand, dim3(nwg), dim3(256), 0, st, (const uint64_t*)dw.p, nb, nwords, (const uint64_t*)wg.p, gp, (uint64_t*)pv.data,
-				cnt.p + 36, longs.p, flag.p + 1, long_cap, flag.p);
-		hipLaunchKernelGGL(k_ld_long, dim3(1024), dim3(256), 0, st, (const LdLong*)longs.p, (const uint32_t*)(flag.p + 1), long_cap, (uint64_t*)pv.data);
-		HIPCHK(hipMemcpyAsync(flag_h, flag.p, 8, hipMemcpyDeviceToHost, st));
+		hipLaunchKernelGGL(k_fmd_expand, dim3(nwg), dim3(256), 0, st, (const uint64_t*)dw, nb, nwords, (const uint64_t*)wg, gp, (uint64_t*)pv.data,
+				c.cnt + 36, c.longs, c.flag + 1, LD_LONG_CAP, c.flag);
+		hipLaunchKernelGGL(k_ld_long, dim3(1024), dim3(256), 0, st, (const LdLong*)c.longs, (const uint32_t*)(c.flag + 1), LD_LONG_CAP, (uint64_t*)pv.data);
+		HIPCHK(hipMemcpyAsync(flag_h, c.flag, 8, hipMemcpyDeviceToHost, st));
 		HIPCHK(hipStreamSynchronize(st));
 		if (flag_h[0]) { rb2_fatal("[rb2_hip] load_fmd: internal: the second decoding pass disagrees with the first (flags %u)\n", flag_h[0]); }
-		if (flag_h[1] > long_cap) { rb2_fatal("[rb2_hip] load_fmd: more than %u runs longer than %u symbols\n", long_cap, LD_LONG); }
+		if (flag_h[1] > LD_LONG_CAP) { rb2_fatal("[rb2_hip] load_fmd: more than %u runs longer than %u symbols\n", LD_LONG_CAP, LD_LONG); }
 	}
-	ld_finish(h, rp, leaf, pv, cnt.p + 36);
-	dw.release(); wg.release(); cnt.release(); flag.release(); longs.release();
+	ld_finish(h, rp, leaf, pv, c.cnt + 36);
 	return (int64_t)rows;
 }
 
@@ -1711,28 +1715,28 @@ int64_t rb2_hip_delete_strings(rb2_hip_t *h, int64_t n, const int64_t *ids)
 	uint64_t nleaf = 0;                                        // leaf slots of the source, up to the end of its last piece
 	for (int r = 0; r < NR; ++r) if (h->h_rope[r].nleaves) nleaf = std::max(nleaf, h->h_rope[r].leaf0 + h->h_rope[r].nleaves);
 	const int64_t CH = 1 << 24;                                // DPP rows per launch
-	DevBuf<int64_t> d_ids; DevBuf<unsigned long long> marks, tally; DevBuf<uint32_t> lkept; DevBuf<uint64_t> lbase;
-	d_ids.ensure((size_t)n); marks.ensure(nleaf * LEAFG); tally.ensure(DEL_WORDS); lkept.ensure(nleaf); lbase.ensure(nleaf);
+	CallScope cs;
+	int64_t *d_ids = scratch<int64_t>(cs, (size_t)n); uint32_t *lkept = scratch<uint32_t>(cs, nleaf); uint64_t *lbase = scratch<uint64_t>(cs, nleaf);
+	unsigned long long *marks = scratch<unsigned long long>(cs, nleaf * LEAFG), *tally = scratch<unsigned long long>(cs, DEL_WORDS);
 	h->qtab.ensure(1);
-	HIPCHK(hipMemcpyAsync(d_ids.p, ids, (size_t)n * 8, hipMemcpyHostToDevice, st));
-	HIPCHK(hipMemsetAsync(marks.p, 0, nleaf * LEAFG * 8, st));
-	HIPCHK(hipMemsetAsync(tally.p, 0, DEL_WORDS * 8, st));
+	HIPCHK(hipMemcpyAsync(d_ids, ids, (size_t)n * 8, hipMemcpyHostToDevice, st));
+	HIPCHK(hipMemsetAsync(marks, 0, nleaf * LEAFG * 8, st));
+	HIPCHK(hipMemsetAsync(tally, 0, DEL_WORDS * 8, st));
 	const PoolView src = h->pool[h->pside].view();
 	hipLaunchKernelGGL(k_qtab, dim3(1), dim3(64), 0, st, (const Ctl*)h->ctl, h->side, src, h->qtab.p);
 	for (int64_t i0 = 0; i0 < n; i0 += CH)
-		hipLaunchKernelGGL(k_del_mark, dim3(cdiv((uint64_t)std::min(CH, n - i0), QPB)), dim3(256), 0, st, (const QTab*)h->qtab.p, src, (const int64_t*)d_ids.p + i0, (uint64_t)std::min(CH, n - i0),
-				marks.p, tally.p + DEL_BAD);
+		hipLaunchKernelGGL(k_del_mark, dim3(cdiv((uint64_t)std::min(CH, n - i0), QPB)), dim3(256), 0, st, (const QTab*)h->qtab.p, src, (const int64_t*)d_ids + i0, (uint64_t)std::min(CH, n - i0),
+				marks, tally + DEL_BAD);
 	phase();
 	for (uint64_t l0 = 0; l0 < nleaf; l0 += (uint64_t)CH)
 		hipLaunchKernelGGL(k_del_count, dim3(cdiv(std::min<uint64_t>((uint64_t)CH, nleaf - l0), QPB)), dim3(256), 0, st, (const QTab*)h->qtab.p, src, l0, nleaf,
-				(const unsigned long long*)marks.p, lkept.p, tally.p);
+				(const unsigned long long*)marks, lkept, tally);
 	unsigned long long t_h[DEL_WORDS];
-	HIPCHK(hipMemcpyAsync(t_h, tally.p, sizeof(t_h), hipMemcpyDeviceToHost, st));
+	HIPCHK(hipMemcpyAsync(t_h, tally, sizeof(t_h), hipMemcpyDeviceToHost, st));
 	HIPCHK(hipGetLastError());
 	HIPCHK(hipStreamSynchronize(st));
 	phase();
-	auto free_all = [&]() { d_ids.release(); marks.release(); tally.release(); lkept.release(); lbase.release(); };
-	if (t_h[DEL_BAD]) { free_all(); rb2_fatal("[rb2_hip] delete_strings: the walk of a string did not end within the rows of the index (the index is no BWT of complete strings)\n"); }
+	if (t_h[DEL_BAD]) { rb2_fatal("[rb2_hip] delete_strings: the walk of a string did not end within the rows of the index (the index is no BWT of complete strings)\n"); }
 	uint64_t tot[6][6], removed = 0;
 	memset(tot, 0, sizeof(tot));
 	for (int r = 0; r < NR; ++r) {
@@ -1746,28 +1750,27 @@ int64_t rb2_hip_delete_strings(rb2_hip_t *h, int64_t n, const int64_t *ids)
 	for (int r = 0; r < NR; ++r) {
 		uint64_t kept = 0;
 		for (int a = 0; a < 6; ++a) kept += t_h[r * 6 + a];
-		if (kept != rp[r].n) { free_all(); rb2_fatal("[rb2_hip] delete_strings: piece %d keeps %llu rows where the other ropes imply %llu (not a BWT of complete strings?)\n", r, (unsigned long long)kept, (unsigned long long)rp[r].n); }
+		if (kept != rp[r].n) { rb2_fatal("[rb2_hip] delete_strings: piece %d keeps %llu rows where the other ropes imply %llu (not a BWT of complete strings?)\n", r, (unsigned long long)kept, (unsigned long long)rp[r].n); }
 		dp.leaf0[r] = rp[r].leaf0;
 	}
 	const int ps = h->pside ^ 1;
 	PoolView dst = ld_zero_pool(h, leaf, ps);                  // (drops the sampled suffix array)
 	phase();
 	if (leaf) {
-		hipLaunchKernelGGL(k_del_scan, dim3(NR), dim3(256), 0, st, (const QTab*)h->qtab.p, (const uint32_t*)lkept.p, lbase.p);
+		hipLaunchKernelGGL(k_del_scan, dim3(NR), dim3(256), 0, st, (const QTab*)h->qtab.p, (const uint32_t*)lkept, lbase);
 		for (uint64_t l0 = 0; l0 < nleaf; l0 += (uint64_t)CH)
 			hipLaunchKernelGGL(k_del_compact, dim3(cdiv(std::min<uint64_t>((uint64_t)CH, nleaf - l0), QPB)), dim3(256), 0, st, (const QTab*)h->qtab.p, src, l0, nleaf,
-					(const unsigned long long*)marks.p, (const uint64_t*)lbase.p, dp, (unsigned long long*)dst.data);
+					(const unsigned long long*)marks, (const uint64_t*)lbase, dp, (unsigned long long*)dst.data);
 		HIPCHK(hipGetLastError());
 	}
 	phase();
 	h->pside = ps; h->pool_compact = false; h->pool_win_dir = false;                    // `side` stays, as in a re-layout: the descriptors are rewritten in place
-	ld_finish(h, rp, leaf, dst, tally.p);
+	ld_finish(h, rp, leaf, dst, tally);
 	phase();
 	if (h->k.trace) fprintf(stderr, "[rb2_hip] delete_strings: %lld ids, %llu rows: mark %.3f ms, count %.3f, zeroed destination %.3f, scan + compact %.3f, own counts + directory %.3f\n", (long long)n,
 			(unsigned long long)removed, t_ph[1] - t_ph[0], t_ph[2] - t_ph[1], t_ph[3] - t_ph[2], t_ph[4] - t_ph[3], t_ph[5] - t_ph[4]);
 	h->del_stats[0] = (int64_t)removed; h->del_stats[1] = (int64_t)t_h[DEL_GROUPS]; h->del_stats[2] = (int64_t)t_h[DEL_SLOW];
 	h->del_stats[3] = (int64_t)nleaf; h->del_stats[4] = (int64_t)leaf;
-	free_all();
 	return (int64_t)removed;
 }
 
@@ -1914,32 +1917,25 @@ static int64_t fmds_encode(rb2_hip_t *h, FmdsOut *o)
 	const uint64_t nseg_max = RCAP / SEG + 2, ng_max = nseg_max / FMDS_GROUP + 2;
 	const int bbits = fmds_bucket_bits(total, FMDS_BUCKET_CAP);
 	const uint64_t nbk = (total >> bbits) + 2;
-	DevBuf<uint64_t> recb[2], tab, gtab, lastcnt, bidx, bS, bpart, outd[2];
-	DevBuf<uint32_t> W, nxt, wg, part;
-	DevBuf<FmdsEntry> gst, sst;
-	DevBuf<FmdsState> dstate;
-	recb[0].ensure(RCAP + 2); recb[1].ensure(RCAP + 2); W.ensure(RCAP + 2); nxt.ensure(RCAP + 2); wg.ensure(RCAP / LEAF / 16 + 4); part.ensure(scan_parts(RCAP + 2));
-	tab.ensure(nseg_max * FMDS_ENTRIES); gtab.ensure(ng_max * FMDS_ENTRIES); gst.ensure(ng_max); sst.ensure(nseg_max); lastcnt.ensure(nseg_max * 7); dstate.ensure(1);
-	HIPCHK(hipMemsetAsync(dstate.p, 0, sizeof(FmdsState), st));
-	uint8_t *outh[2] = {nullptr, nullptr};
-	FmdsState *hst = nullptr;
-	hipEvent_t evS, evO[2];
-	HIPCHK(hipHostMalloc((void**)&hst, sizeof(FmdsState), hipHostMallocDefault));
-	HIPCHK(hipEventCreateWithFlags(&evS, hipEventDisableTiming));
-	for (int i = 0; i < 2; ++i) HIPCHK(hipEventCreateWithFlags(&evO[i], hipEventDisableTiming));
+	CallScope cs;                                              /* everything the call holds, on every way out */
+	auto pinned = [&](size_t n) { void *&p = cs.make<PinBuf>().p; HIPCHK(hipHostMalloc(&p, n, hipHostMallocDefault)); return p; };
+	auto event = [&]() { hipEvent_t &e = cs.make<EventBox>().e; HIPCHK(hipEventCreateWithFlags(&e, hipEventDisableTiming)); return e; };
+	uint64_t *const recb[2] = {scratch<uint64_t>(cs, RCAP + 2), scratch<uint64_t>(cs, RCAP + 2)};
+	uint32_t *const W = scratch<uint32_t>(cs, RCAP + 2), *const nxt = scratch<uint32_t>(cs, RCAP + 2), *const wg = scratch<uint32_t>(cs, RCAP / LEAF / 16 + 4), *const part = scratch<uint32_t>(cs, scan_parts(RCAP + 2));
+	uint64_t *const tab = scratch<uint64_t>(cs, nseg_max * FMDS_ENTRIES), *const gtab = scratch<uint64_t>(cs, ng_max * FMDS_ENTRIES), *const lastcnt = scratch<uint64_t>(cs, nseg_max * 7);
+	FmdsEntry *const gst = scratch<FmdsEntry>(cs, ng_max), *const sst = scratch<FmdsEntry>(cs, nseg_max);
+	FmdsState *const dstate = scratch<FmdsState>(cs, 1), *const hst = (FmdsState*)pinned(sizeof(FmdsState));
+	const hipEvent_t evS = event(), evO[2] = {event(), event()};
+	uint64_t *bidx = nullptr, *bS = nullptr, *bpart = nullptr, *outd[2] = {nullptr, nullptr};
+	void *outh[2] = {nullptr, nullptr};
 	if (o) {
-		bidx.ensure(nbk); bS.ensure(nbk); bpart.ensure(scan_parts(nbk));
-		HIPCHK(hipMemsetAsync(bidx.p, 0, nbk * 8, st)); HIPCHK(hipMemsetAsync(bS.p, 0, nbk * 8, st));
-		for (int i = 0; i < 2; ++i) { outd[i].ensure(OUTCAP * FMDS_BW); HIPCHK(hipHostMalloc((void**)&outh[i], OUTCAP * FMDS_BW * 8, hipHostMallocDefault)); }
+		bidx = scratch<uint64_t>(cs, nbk); bS = scratch<uint64_t>(cs, nbk); bpart = scratch<uint64_t>(cs, scan_parts(nbk));
+		for (int i = 0; i < 2; ++i) { outd[i] = scratch<uint64_t>(cs, OUTCAP * FMDS_BW); outh[i] = pinned(OUTCAP * FMDS_BW * 8); }
 	}
-	auto free_all = [&]() {                                    /* everything the call holds, on every way out */
-		hipStreamSynchronize(st);
-		for (int i = 0; i < 2; ++i) { if (outh[i]) hipHostFree(outh[i]); outh[i] = nullptr; hipEventDestroy(evO[i]); outd[i].release(); }
-		hipHostFree(hst); hipEventDestroy(evS);
-		recb[0].release(); recb[1].release(); W.release(); nxt.release(); wg.release(); part.release(); tab.release(); gtab.release(); gst.release(); sst.release(); lastcnt.release(); dstate.release();
-		bidx.release(); bS.release(); bpart.release();
-	};
-	auto give_up = [&]() { free_all(); if (o && o->fd >= 0) close(o->fd); };   /* in front of a fatal error: its handler may return to the caller's caller */
+	cs.make<StreamDrain>().st = &h->st;                        /* (nothing is queued before it, nothing made behind it) */
+	HIPCHK(hipMemsetAsync(dstate, 0, sizeof(FmdsState), st));
+	if (o) { HIPCHK(hipMemsetAsync(bidx, 0, nbk * 8, st)); HIPCHK(hipMemsetAsync(bS, 0, nbk * 8, st)); }
+	auto shut = [&]() { if (o && o->fd >= 0) close(o->fd); };   /* in front of a fatal error: its handler may never come back to rb2_hip_save_fmd_file */
 	const PoolView pv = h->pool[h->pside].view();
 	int r = 0, par = 0, buf = 0, rb = 0;                      /* rb: which of the two head arrays holds this batch */
 	uint64_t lc = 0, P0 = 0, ncur = 0, blk0 = 0;
@@ -1956,7 +1952,7 @@ static int64_t fmds_encode(rb2_hip_t *h, FmdsOut *o)
 	};
 	skip();
 	while (!done) {
-		DevBuf<uint64_t> &rec = recb[rb];
+		uint64_t *const rec = recb[rb];
 		uint64_t nl = 0;
 		const uint32_t *nnew = nullptr;
 		if (r < NR) {
@@ -1965,44 +1961,44 @@ static int64_t fmds_encode(rb2_hip_t *h, FmdsOut *o)
 			nl = std::min<uint64_t>(avail, (d.n + LEAF - 1) / LEAF - lc);
 			if (nl) {
 				const uint64_t nwg = (nl + 15) / 16;
-				hipLaunchKernelGGL(k_fmds_heads<false>, dim3((unsigned)nwg), dim3(256), 0, st, pv, d.leaf0, d.n, lc, (uint32_t)nl, P0, ncur, rec.p, wg.p);
-				scan_launch<ScanAdd<uint32_t>>(st, ScanIn<uint32_t>{wg.p, nwg}, nwg, part.p, wg.p, nullptr, true);   /* in place; wg[nwg] = the new heads */
-				hipLaunchKernelGGL(k_fmds_heads<true>, dim3((unsigned)nwg), dim3(256), 0, st, pv, d.leaf0, d.n, lc, (uint32_t)nl, P0, ncur, rec.p, wg.p);
-				nnew = wg.p + nwg;
+				hipLaunchKernelGGL(k_fmds_heads<false>, dim3((unsigned)nwg), dim3(256), 0, st, pv, d.leaf0, d.n, lc, (uint32_t)nl, P0, ncur, rec, wg);
+				scan_launch<ScanAdd<uint32_t>>(st, ScanIn<uint32_t>{wg, nwg}, nwg, part, wg, nullptr, true);   /* in place; wg[nwg] = the new heads */
+				hipLaunchKernelGGL(k_fmds_heads<true>, dim3((unsigned)nwg), dim3(256), 0, st, pv, d.leaf0, d.n, lc, (uint32_t)nl, P0, ncur, rec, wg);
+				nnew = wg + nwg;
 				lc += nl;
 				skip();
 			}
 		}
 		const uint32_t flush = r == NR;
-		hipLaunchKernelGGL(k_fmds_begin, dim3(1), dim3(1), 0, st, dstate.p, rec.p, ncur, nnew, flush, total, type0, blk0);
+		hipLaunchKernelGGL(k_fmds_begin, dim3(1), dim3(1), 0, st, dstate, rec, ncur, nnew, flush, total, type0, blk0);
 		const uint64_t mub = ncur + nl * LEAF + 1;              /* heads at the most (the grids below are sized for them; the kernels read the count) */
-		scan_launch<ScanAdd<uint32_t>>(st, FmdsInWidth{rec.p, dstate.p}, mub, part.p, W.p, nullptr, true);   /* W[0 .. nc] */
-		hipLaunchKernelGGL(k_fmds_next, dim3(cdiv(mub + 1, 256)), dim3(256), 0, st, (const FmdsState*)dstate.p, (const uint64_t*)rec.p, (const uint32_t*)W.p, nxt.p);
+		scan_launch<ScanAdd<uint32_t>>(st, FmdsInWidth{rec, dstate}, mub, part, W, nullptr, true);   /* W[0 .. nc] */
+		hipLaunchKernelGGL(k_fmds_next, dim3(cdiv(mub + 1, 256)), dim3(256), 0, st, (const FmdsState*)dstate, (const uint64_t*)rec, (const uint32_t*)W, nxt);
 		const uint64_t nseg = mub / SEG + 1, ng = (nseg + FMDS_GROUP - 1) / FMDS_GROUP;
-		hipLaunchKernelGGL(k_fmds_table, dim3((unsigned)nseg), dim3(320), 0, st, (const FmdsState*)dstate.p, (const uint32_t*)nxt.p, SEG, tab.p);
-		hipLaunchKernelGGL(k_fmds_group, dim3((unsigned)ng), dim3(320), 0, st, (const FmdsState*)dstate.p, (const uint64_t*)tab.p, SEG, gtab.p);
-		hipLaunchKernelGGL(k_fmds_resolve, dim3(1), dim3(1), 0, st, dstate.p, (const uint64_t*)rec.p, (const uint32_t*)W.p, (const uint32_t*)nxt.p, (const uint64_t*)tab.p, (const uint64_t*)gtab.p, SEG, gst.p);
-		HIPCHK(hipMemcpyAsync(hst, dstate.p, sizeof(FmdsState), hipMemcpyDeviceToHost, st));
+		hipLaunchKernelGGL(k_fmds_table, dim3((unsigned)nseg), dim3(320), 0, st, (const FmdsState*)dstate, (const uint32_t*)nxt, SEG, tab);
+		hipLaunchKernelGGL(k_fmds_group, dim3((unsigned)ng), dim3(320), 0, st, (const FmdsState*)dstate, (const uint64_t*)tab, SEG, gtab);
+		hipLaunchKernelGGL(k_fmds_resolve, dim3(1), dim3(1), 0, st, dstate, (const uint64_t*)rec, (const uint32_t*)W, (const uint32_t*)nxt, (const uint64_t*)tab, (const uint64_t*)gtab, SEG, gst);
+		HIPCHK(hipMemcpyAsync(hst, dstate, sizeof(FmdsState), hipMemcpyDeviceToHost, st));
 		HIPCHK(hipEventRecord(evS, st));
 		if (o) {
-			hipLaunchKernelGGL(k_fmds_down, dim3(cdiv(ng, 64)), dim3(64), 0, st, (const FmdsState*)dstate.p, (const uint64_t*)tab.p, SEG, (const FmdsEntry*)gst.p, sst.p);
-			hipLaunchKernelGGL(k_fmds_write, dim3((unsigned)nseg), dim3(256), 0, st, dstate.p, (const uint64_t*)rec.p, (const uint32_t*)W.p, (const uint32_t*)nxt.p, (const FmdsEntry*)sst.p, SEG, par,
-					outd[buf].p, lastcnt.p, bidx.p, bS.p, bbits);
-			hipLaunchKernelGGL(k_fmds_hdrfix, dim3(cdiv(nseg, 256)), dim3(256), 0, st, (const FmdsState*)dstate.p, (const FmdsEntry*)sst.p, (const uint32_t*)nxt.p, (const uint64_t*)lastcnt.p, SEG, par, outd[buf].p);
+			hipLaunchKernelGGL(k_fmds_down, dim3(cdiv(ng, 64)), dim3(64), 0, st, (const FmdsState*)dstate, (const uint64_t*)tab, SEG, (const FmdsEntry*)gst, sst);
+			hipLaunchKernelGGL(k_fmds_write, dim3((unsigned)nseg), dim3(256), 0, st, dstate, (const uint64_t*)rec, (const uint32_t*)W, (const uint32_t*)nxt, (const FmdsEntry*)sst, SEG, par,
+					outd[buf], lastcnt, bidx, bS, bbits);
+			hipLaunchKernelGGL(k_fmds_hdrfix, dim3(cdiv(nseg, 256)), dim3(256), 0, st, (const FmdsState*)dstate, (const FmdsEntry*)sst, (const uint32_t*)nxt, (const uint64_t*)lastcnt, SEG, par, outd[buf]);
 		}
-		hipLaunchKernelGGL(k_fmds_carry, dim3((unsigned)std::min<uint64_t>(cdiv(mub + 1, 256), 2048)), dim3(256), 0, st, (const FmdsState*)dstate.p, (const uint64_t*)rec.p, recb[rb ^ 1].p);
+		hipLaunchKernelGGL(k_fmds_carry, dim3((unsigned)std::min<uint64_t>(cdiv(mub + 1, 256), 2048)), dim3(256), 0, st, (const FmdsState*)dstate, (const uint64_t*)rec, recb[rb ^ 1]);
 		HIPCHK(hipGetLastError());
 		HIPCHK(hipEventSynchronize(evS));                          /* one wait per batch: what it emits and what it leaves decide the next one */
 		const FmdsState S = *hst;
-		if (S.err) { give_up(); rb2_fatal("[rb2_hip] save_fmd: a block of 2^30 symbols or more right in front of the last block of a chunk of 2^23 words: its header leaves no payload word (not supported)\n"); }
-		if (S.nout > OUTCAP || S.carry > S.m) { give_up(); rb2_fatal("[rb2_hip] save_fmd: internal: a batch of %llu runs emits %llu blocks and goes on at run %llu\n", (unsigned long long)S.m, (unsigned long long)S.nout, (unsigned long long)S.carry); }
+		if (S.err) { shut(); rb2_fatal("[rb2_hip] save_fmd: a block of 2^30 symbols or more right in front of the last block of a chunk of 2^23 words: its header leaves no payload word (not supported)\n"); }
+		if (S.nout > OUTCAP || S.carry > S.m) { shut(); rb2_fatal("[rb2_hip] save_fmd: internal: a batch of %llu runs emits %llu blocks and goes on at run %llu\n", (unsigned long long)S.m, (unsigned long long)S.nout, (unsigned long long)S.carry); }
 		if (o && S.nout) {
-			HIPCHK(hipMemcpyAsync(outh[buf], outd[buf].p, S.nout * 64, hipMemcpyDeviceToHost, st));
+			HIPCHK(hipMemcpyAsync(outh[buf], outd[buf], S.nout * 64, hipMemcpyDeviceToHost, st));
 			HIPCHK(hipEventRecord(evO[buf], st));
 		}
 		if (o) drain();                                          /* (while the device works on this batch's blocks) */
 		if (o && S.nout) { pend.on = true; pend.buf = buf; pend.blk0 = blk0; pend.nout = S.nout; pend.done = S.done != 0; pend.type = S.ctype; buf ^= 1; }
-		if (S.nout == 0 && nl == 0 && !S.done) { give_up(); rb2_fatal("[rb2_hip] save_fmd: internal: a batch of %llu runs neither emits a block nor has room for a leaf\n", (unsigned long long)S.m); }
+		if (S.nout == 0 && nl == 0 && !S.done) { shut(); rb2_fatal("[rb2_hip] save_fmd: internal: a batch of %llu runs neither emits a block nor has room for a leaf\n", (unsigned long long)S.m); }
 		if (S.nout) par ^= 1;
 		rb ^= 1;
 		ncur = S.m - S.carry; type0 = S.ctype; blk0 += S.nout;
@@ -2012,17 +2008,17 @@ static int64_t fmds_encode(rb2_hip_t *h, FmdsOut *o)
 	const uint64_t n_bytes = (blk0 - 1) * 64 + fmds_hdr_words(ftype) * 8;
 	const int ibits = fmds_ibits(total, n_bytes);
 	const uint64_t n_frames = fmds_n_frames(total, ibits);
-	if (ibits < bbits) { give_up(); rb2_fatal("[rb2_hip] save_fmd: %llu rows need rank frames of 2^%d rows, finer than the 2^%d the encoder keeps for them (%llu buckets)\n", (unsigned long long)total, ibits, bbits, (unsigned long long)FMDS_BUCKET_CAP); }
+	if (ibits < bbits) { shut(); rb2_fatal("[rb2_hip] save_fmd: %llu rows need rank frames of 2^%d rows, finer than the 2^%d the encoder keeps for them (%llu buckets)\n", (unsigned long long)total, ibits, bbits, (unsigned long long)FMDS_BUCKET_CAP); }
 	if (o) {
-		for (uint64_t *b : {bidx.p, bS.p}) scan_launch<ScanMax>(st, ScanIn<uint64_t>{b, nbk}, nbk, bpart.p, b, nullptr, false);   /* every bucket: the last header up to it */
+		for (uint64_t *b : {bidx, bS}) scan_launch<ScanMax>(st, ScanIn<uint64_t>{b, nbk}, nbk, bpart, b, nullptr, false);   /* every bucket: the last header up to it */
 		h->qtab.ensure(1);
 		hipLaunchKernelGGL(k_qtab, dim3(1), dim3(64), 0, st, (const Ctl*)h->ctl, h->side, pv, h->qtab.p);
 		const uint64_t FSTEP = OUTCAP * FMDS_BW / 7;             /* frames per staging round */
 		for (uint64_t f0 = 0; f0 < n_frames; f0 += FSTEP) {
 			const uint64_t nf = std::min(FSTEP, n_frames - f0);
-			hipLaunchKernelGGL(k_fmds_frames, dim3(cdiv(nf, QPB)), dim3(256), 0, st, (const QTab*)h->qtab.p, pv, (const uint64_t*)bidx.p, (const uint64_t*)bS.p, nbk, ibits, bbits, f0, nf, outd[0].p);
+			hipLaunchKernelGGL(k_fmds_frames, dim3(cdiv(nf, QPB)), dim3(256), 0, st, (const QTab*)h->qtab.p, pv, (const uint64_t*)bidx, (const uint64_t*)bS, nbk, ibits, bbits, f0, nf, outd[0]);
 			HIPCHK(hipGetLastError());
-			HIPCHK(hipMemcpyAsync(outh[0], outd[0].p, nf * 56, hipMemcpyDeviceToHost, st));
+			HIPCHK(hipMemcpyAsync(outh[0], outd[0], nf * 56, hipMemcpyDeviceToHost, st));
 			HIPCHK(hipStreamSynchronize(st));
 			fmds_put(*o, outh[0], (size_t)(nf * 56), 80 + n_bytes + f0 * 56);
 		}
@@ -2030,7 +2026,6 @@ static int64_t fmds_encode(rb2_hip_t *h, FmdsOut *o)
 		fmds_put(*o, hdr, 80, 0);                                 /* the header goes last */
 	}
 	HIPCHK(hipStreamSynchronize(st));
-	free_all();
 	return (int64_t)fmds_image_size(n_bytes, n_frames);
 }
 
@@ -2249,22 +2244,21 @@ template <class Op, class T = typename Op::type> static void scan_check_run(rb2_
 	const size_t np = form == 0 ? scan_parts(n) - 1 : 0;
 	std::vector<T> x(n + 1, 0), p(np + 1, 0);
 	for (uint64_t i = 0; i < n; ++i) x[i] = (T)in[i];
-	DevBuf<T> d;                                                /* the items and out[n], the total, the parts */
-	d.ensure(n + 2 + scan_parts(n));
-	T *tot = d.p + n + 1, *part = tot + 1;
-	HIPCHK(hipMemcpyAsync(d.p, x.data(), (n + 1) * sizeof(T), hipMemcpyHostToDevice, h->st));
+	CallScope cs;
+	T *d = scratch<T>(cs, n + 2 + scan_parts(n));               /* the items and out[n], the total, the parts */
+	T *tot = d + n + 1, *part = tot + 1;
+	HIPCHK(hipMemcpyAsync(d, x.data(), (n + 1) * sizeof(T), hipMemcpyHostToDevice, h->st));
 	HIPCHK(hipMemsetAsync(tot, 0xff, sizeof(T), h->st));
-	const ScanIn<T> si{d.p, n};
-	if (form == 0) scan_launch<Op>(h->st, si, n, part, d.p, tot, true);
+	const ScanIn<T> si{d, n};
+	if (form == 0) scan_launch<Op>(h->st, si, n, part, d, tot, true);
 	else if constexpr (std::is_same<Op, ScanAdd<uint64_t>>::value) {   /* (the one op the callers scan with a single block) */
-		if (form == 1) hipLaunchKernelGGL((k_scan_block<Op, ScanIn<T>, 256>), dim3(1), dim3(256), 0, h->st, si, d.p);
-		else hipLaunchKernelGGL((k_scan_block<Op, ScanIn<T>, SCHUNK>), dim3(1), dim3(SCHUNK), 0, h->st, si, d.p);
+		if (form == 1) hipLaunchKernelGGL((k_scan_block<Op, ScanIn<T>, 256>), dim3(1), dim3(256), 0, h->st, si, d);
+		else hipLaunchKernelGGL((k_scan_block<Op, ScanIn<T>, SCHUNK>), dim3(1), dim3(SCHUNK), 0, h->st, si, d);
 	}
 	HIPCHK(hipGetLastError());
-	HIPCHK(hipMemcpyAsync(x.data(), d.p, (n + 1) * sizeof(T), hipMemcpyDeviceToHost, h->st));
+	HIPCHK(hipMemcpyAsync(x.data(), d, (n + 1) * sizeof(T), hipMemcpyDeviceToHost, h->st));
 	HIPCHK(hipMemcpyAsync(p.data(), tot, (np + 1) * sizeof(T), hipMemcpyDeviceToHost, h->st));
 	HIPCHK(hipStreamSynchronize(h->st));
-	d.release();
 	for (uint64_t i = 0; i <= n; ++i) out[i] = x[i];
 	*total = form == 0 ? (uint64_t)p[0] : out[n];
 	for (size_t b = 0; b < np; ++b) parts[b] = p[b + 1];

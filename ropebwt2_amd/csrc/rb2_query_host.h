@@ -621,18 +621,21 @@ static int unitig_doublings(int64_t n)
 
 struct UtChainBufs { unsigned long long *ctr; uint32_t *outdeg, *indeg; int64_t *inedge, *pred; UtState *st[2]; };
 
-/* the scratch of a chains call in qscr, counters and degrees zeroed */
+/* the scratch of a chains call, UT_CTRS + 12 n words with the counters and the degrees in front; unitig_chain_bufs: in qscr, those two zeroed */
+static UtChainBufs unitig_chain_layout(Carve &c, int64_t n)
+{
+	UtChainBufs b;
+	b.ctr = c.take<unsigned long long>(UT_CTRS);
+	b.outdeg = c.take<uint32_t>((size_t)(2 * n)); b.indeg = b.outdeg + n;
+	b.inedge = c.take<int64_t>((size_t)(2 * n));
+	b.pred = c.take<int64_t>((size_t)n);
+	for (int i = 0; i < 2; ++i) b.st[i] = c.take<UtState>((size_t)n);
+	return b;
+}
 static UtChainBufs unitig_chain_bufs(rb2_hip_t *h, int64_t n)
 {
-	h->qscr.ensure((size_t)(UT_CTRS + 12 * n) * 8);
-	int64_t *w = (int64_t*)h->qscr.p;
 	UtChainBufs b;
-	b.ctr = (unsigned long long*)w; w += UT_CTRS;
-	b.outdeg = (uint32_t*)w; b.indeg = b.outdeg + n; w += n;
-	b.inedge = w; w += 2 * n;
-	b.pred = w; w += n;
-	b.st[0] = (UtState*)w; w += 4 * n;
-	b.st[1] = (UtState*)w;
+	carve_in(h->qscr, [&](Carve &c) { b = unitig_chain_layout(c, n); });
 	HIPCHK(hipMemsetAsync(b.ctr, 0, (size_t)(UT_CTRS + n) * 8, h->st));
 	return b;
 }
@@ -712,20 +715,21 @@ static int64_t unitig_text_run(rb2_hip_t *h, int64_t n, const int64_t *vtx, int 
 	int64_t inf[4] = {0, 0, 0, 0};
 	if (n > 0) {
 		if (cap_u == 0 || cap_txt == 0) cap_u = cap_txt = 0;       // sizes only
-		h->qscr.ensure(((size_t)(UT_CTRS + 10 * n) + scan_parts((uint64_t)n)) * 8);
-		uint64_t *w = (uint64_t*)h->qscr.p;
-		unsigned long long *ctr = (unsigned long long*)w; w += UT_CTRS;
+		unsigned long long *ctr = nullptr; uint64_t *bsum = nullptr;
 		UtHeads H; UtSel S;
-		H.cnt = (unsigned long long*)w; w += n;
-		H.off = (unsigned long long*)w; w += n;
-		S.toff = w; w += n;
-		H.flg = (uint32_t*)w; w += n;                              // (zeroed up to here)
-		H.mn = (unsigned long long*)w; w += n;
-		H.u = (int64_t*)w; w += n;
-		S.head = (int64_t*)w; w += n;
-		S.len = w; w += n;
-		S.tlen = w; w += n;
-		uint64_t *bsum = w;
+		carve_in(h->qscr, [&, N = (size_t)n](Carve &c) {           // UT_CTRS + 10 n + scan_parts(n) words
+			ctr = c.take<unsigned long long>(UT_CTRS);
+			H.cnt = c.take<unsigned long long>(N);
+			H.off = c.take<unsigned long long>(N);
+			S.toff = c.take<uint64_t>(N);
+			H.flg = (uint32_t*)c.take<uint64_t>(N);                  // (a word each; zeroed up to here)
+			H.mn = c.take<unsigned long long>(N);
+			H.u = c.take<int64_t>(N);
+			S.head = c.take<int64_t>(N);
+			S.len = c.take<uint64_t>(N);
+			S.tlen = c.take<uint64_t>(N);
+			bsum = c.take<uint64_t>(scan_parts((uint64_t)n));
+			c.take<uint64_t>(N); });                                 // (n spare words: the buffer has always been this large, nothing uses them)
 		HIPCHK(hipMemsetAsync(ctr, 0, (size_t)(UT_CTRS + 4 * n) * 8, h->st));
 		HIPCHK(hipMemsetAsync(H.mn, 0xff, (size_t)n * 8, h->st));
 		ulaunch(h, k_unitig_sum, n, n, vtx, H);
@@ -817,25 +821,25 @@ static void graph_clean_check(rb2_hip_t *h, const char *who, int64_t n, int64_t 
 static int64_t graph_clean_run(rb2_hip_t *h, int64_t n, int64_t m, const int64_t *ed, int64_t max_tip, int64_t max_bubble, int pairs, int64_t max_rounds, int64_t cap, int64_t *out,
                                int64_t info[8])
 {
-	const int64_t nb = (int64_t)scan_parts((uint64_t)std::max(m, n + 1));
-	const size_t chain_words = (size_t)(UT_CTRS + 12 * n), words = (size_t)(CL_CTRS + 11 * n + 1 + m + nb);
-	h->qscr.ensure((chain_words + words) * 8 + (size_t)(m + 3 * n));   // (first, for the whole call: unitig_chain_bufs then finds its room in front and moves nothing)
-	int64_t *w = (int64_t*)h->qscr.p + chain_words;
-	unsigned long long *cctr = (unsigned long long*)w; w += CL_CTRS;
-	int64_t *vtx = w; w += 4 * n;
+	const size_t N = (size_t)n, M = (size_t)m, nb = scan_parts((uint64_t)std::max(m, n + 1));
 	ClV V;
-	V.vtx = vtx;
-	V.cnt = (unsigned long long*)w; w += n;
-	V.mn = (unsigned long long*)w; w += n;                         // (mn and tail lie together: one memset of 0xff)
-	V.tail = w; w += n;
-	V.q = w; w += n;
-	V.outedge = w; w += n;
-	uint64_t *start = (uint64_t*)w; w += n + 1;
-	int64_t *csr = w; w += m;                                      // (and, behind the last round, the keep flags and their scan)
-	uint64_t *bsum = (uint64_t*)w; w += nb;
-	V.cls = (uint32_t*)w;
-	uint32_t *cur = V.cls + n; w += n;
-	uint8_t *dead = (uint8_t*)w, *lose = dead + m, *a_out = lose + n, *a_in = a_out + n;
+	unsigned long long *cctr = nullptr; int64_t *vtx = nullptr, *csr = nullptr;
+	uint64_t *start = nullptr, *bsum = nullptr; uint32_t *cur = nullptr; uint8_t *dead = nullptr;
+	carve_in(h->qscr, [&](Carve &c) {                              // for the whole call: CL_CTRS + 11 n + 1 + m + nb words and m + 3 n bytes ...
+		unitig_chain_layout(c, n);                                 // ... behind the room in which unitig_chain_bufs lays out the same again
+		cctr = c.take<unsigned long long>(CL_CTRS);
+		V.vtx = vtx = c.take<int64_t>(4 * N);
+		V.cnt = c.take<unsigned long long>(N);
+		V.mn = c.take<unsigned long long>(N);                      // (mn and tail lie together: one memset of 0xff)
+		V.tail = c.take<int64_t>(N);
+		V.q = c.take<int64_t>(N);
+		V.outedge = c.take<int64_t>(N);
+		start = c.take<uint64_t>(N + 1);
+		csr = c.take<int64_t>(M);                                  // (and, behind the last round, the keep flags and their scan)
+		bsum = c.take<uint64_t>(nb);
+		V.cls = c.take<uint32_t>(2 * N); cur = V.cls + n;
+		dead = c.take<uint8_t>(M + 3 * N); });                     // (dead, lose, a_out, a_in: bytes, no padding between them)
+	uint8_t *lose = dead + m, *a_out = lose + n, *a_in = a_out + n;
 	if (m) HIPCHK(hipMemsetAsync(dead, 0, (size_t)m, h->st));
 	unsigned long long c[CL_CTRS] = {0, 0, 0, 0}, uc[UT_CTRS];
 	int64_t rounds = 0, tips = 0, bubbles = 0;
@@ -901,16 +905,15 @@ int64_t rb2_hip_graph_clean(rb2_hip_t *h, int64_t n_str, int64_t m, const int64_
                             int64_t cap, int64_t *out, int64_t info[8])
 {
 	graph_clean_check(h, "graph_clean", n_str, m, edges, max_tip_reads, max_bubble_reads, pairs, max_rounds, cap, out);
-	DevBuf<int64_t> rows;                                          // the list and, behind it, the output on the device: no more rows are kept than came
+	CallScope cs;
 	const int64_t dcap = std::min(cap, m);
-	if (m + dcap > 0) rows.ensure((size_t)(m + dcap) * 4);
-	if (m) HIPCHK(hipMemcpyAsync(rows.p, edges, (size_t)m * 32, hipMemcpyHostToDevice, h->st));
+	int64_t *rows = scratch<int64_t>(cs, (size_t)(m + dcap) * 4);   // the list and, behind it, the output on the device: no more rows are kept than came
+	if (m) HIPCHK(hipMemcpyAsync(rows, edges, (size_t)m * 32, hipMemcpyHostToDevice, h->st));
 	int64_t inf[8];
-	const int64_t kept = graph_clean_run(h, n_str, m, rows.p, max_tip_reads, max_bubble_reads, pairs, max_rounds, dcap, dcap ? rows.p + 4 * m : nullptr, inf);
+	const int64_t kept = graph_clean_run(h, n_str, m, rows, max_tip_reads, max_bubble_reads, pairs, max_rounds, dcap, dcap ? rows + 4 * m : nullptr, inf);
 	inf[1] = std::min(kept, cap);
-	if (inf[1] > 0) HIPCHK(hipMemcpyAsync(out, rows.p + 4 * m, (size_t)inf[1] * 32, hipMemcpyDeviceToHost, h->st));
+	if (inf[1] > 0) HIPCHK(hipMemcpyAsync(out, rows + 4 * m, (size_t)inf[1] * 32, hipMemcpyDeviceToHost, h->st));
 	HIPCHK(hipStreamSynchronize(h->st));
-	rows.release();
 	if (info) memcpy(info, inf, sizeof(inf));
 	return kept;
 }
@@ -1064,7 +1067,8 @@ int64_t rb2_hip_merge(rb2_hip_t *dst, rb2_hip_t *src, int64_t batch_bytes, int64
 	BatchSource S(dst, src, "merge", n, batch_bytes);
 	const int64_t total = S.total;
 	HIPCHK(hipSetDevice(dst->dev));
-	DevBuf<uint8_t> text;
+	CallScope cs;
+	auto &text = cs.make<DevBuf<uint8_t>>();
 	text.ensure((size_t)std::min(S.budget, total) + 64);
 	int64_t i0 = 0, off0 = 0;
 	while (i0 < n) {
@@ -1078,7 +1082,6 @@ int64_t rb2_hip_merge(rb2_hip_t *dst, rb2_hip_t *src, int64_t batch_bytes, int64
 		++inf[2]; inf[3] = std::max(inf[3], len);
 		i0 = cut.end; off0 = (int64_t)cut.off_end;
 	}
-	text.release();
 	inf[0] = n; inf[1] = total - n;
 	if (info) memcpy(info, inf, sizeof(inf));
 	return total;
@@ -1116,10 +1119,12 @@ static int64_t string_graph_run(rb2_hip_t *h, const char *who, int64_t first, in
 	GraphPlan plan = graph_plan(graph_chunk(), max_recs);
 	/* qin for the whole call, so that it never moves: the offsets of a chunk, its cnt, its edge counts, their block sums, the words of the call */
 	const int64_t most = std::min(plan.limit, n), nbs = (int64_t)scan_parts((uint64_t)most + 1);
-	h->qin.ensure((size_t)(3 * most + 2 + nbs + GR_WORDS));
-	uint64_t *x = (uint64_t*)h->qin.p, *e = x + most + 1, *bsum = e + most + 1;
-	int64_t *cnt = (int64_t*)(bsum + nbs);
-	unsigned long long *gc = (unsigned long long*)(cnt + most);
+	uint64_t *x = nullptr, *e = nullptr, *bsum = nullptr; int64_t *cnt = nullptr; unsigned long long *gc = nullptr;
+	carve_in(h->qin, [&](Carve &c) {                               // 3 most + 2 + nbs + GR_WORDS words
+		x = c.take<uint64_t>((size_t)most + 1); e = c.take<uint64_t>((size_t)most + 1);
+		bsum = c.take<uint64_t>((size_t)nbs);
+		cnt = c.take<int64_t>((size_t)most);
+		gc = c.take<unsigned long long>(GR_WORDS); });
 	HIPCHK(hipMemsetAsync(gc, 0, GR_WORDS * 8, h->st));
 	for (int64_t i0 = 0; i0 < n; ) {
 		const int64_t tried = graph_try(plan, n - i0);
@@ -1174,15 +1179,14 @@ int64_t rb2_hip_string_graph(rb2_hip_t *h, int64_t first, int64_t n, int64_t min
 {
 	string_graph_check(h, "string_graph", first, n, min_ovlp, max_ext, max_steps, max_recs, max_hits, pairs, cap, edges);
 	HIPCHK(hipSetDevice(h->dev));
-	DevBuf<int64_t> rows;                                          // the output on the device: cap rows, of which min(m, cap) come back
-	if (cap > 0 && n > 0) rows.ensure((size_t)cap * 4);
+	CallScope cs;
+	int64_t *rows = scratch<int64_t>(cs, n > 0 ? (size_t)cap * 4 : 0);   // the output on the device: cap rows, of which min(m, cap) come back
 	int64_t inf[8];
-	const int64_t m = string_graph_run(h, "string_graph", first, n, min_ovlp, max_ext, max_steps, max_recs, max_hits, pairs, cap, rows.p, inf);
+	const int64_t m = string_graph_run(h, "string_graph", first, n, min_ovlp, max_ext, max_steps, max_recs, max_hits, pairs, cap, rows, inf);
 	if (inf[1] > 0) {
-		HIPCHK(hipMemcpyAsync(edges, rows.p, (size_t)inf[1] * 32, hipMemcpyDeviceToHost, h->st));
+		HIPCHK(hipMemcpyAsync(edges, rows, (size_t)inf[1] * 32, hipMemcpyDeviceToHost, h->st));
 		HIPCHK(hipStreamSynchronize(h->st));
 	}
-	rows.release();
 	if (info) memcpy(info, inf, sizeof(inf));
 	return m;
 }
@@ -1262,8 +1266,9 @@ int64_t rb2_hip_correct_into(rb2_hip_t *dst, rb2_hip_t *src, int64_t k, int64_t 
 	const uint64_t *x = S.x;
 	unsigned long long cc[CORRECT_CTRS];
 	HIPCHK(hipSetDevice(dst->dev));
-	DevBuf<uint8_t> text, batch;                                    // a batch as it was unpacked (text order), and what becomes the insert batch
-	DevBuf<int64_t> res;                                            // the counters of the call, then cnt and weak of a batch
+	CallScope cs;
+	auto &text = cs.make<DevBuf<uint8_t>>(), &batch = cs.make<DevBuf<uint8_t>>();   // a batch as it was unpacked (text order), and what becomes the insert batch
+	auto &res = cs.make<DevBuf<int64_t>>();                         // the counters of the call, then cnt and weak of a batch
 	text.ensure((size_t)std::min(budget, total) + 64);
 	batch.ensure((size_t)std::min(budget, total) + 64);
 	res.ensure((size_t)CORRECT_CTRS);
@@ -1296,7 +1301,6 @@ int64_t rb2_hip_correct_into(rb2_hip_t *dst, rb2_hip_t *src, int64_t k, int64_t 
 	}
 	HIPCHK(hipMemcpyAsync(cc, res.p, sizeof(cc), hipMemcpyDeviceToHost, src->st));
 	HIPCHK(hipStreamSynchronize(src->st));
-	text.release(); batch.release(); res.release();
 	inf[0] = n; inf[1] = (int64_t)cc[CC_CHANGED]; inf[2] = (int64_t)cc[CC_FIXES]; inf[3] = (int64_t)cc[CC_WEAK]; inf[4] = (int64_t)cc[CC_OVER]; inf[5] = (int64_t)cc[CC_BAD];
 	if (info) memcpy(info, inf, sizeof(inf));
 	return total;

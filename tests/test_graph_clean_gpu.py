@@ -110,6 +110,9 @@ RULES = {
     "no_vertices": (0, [], {}, (1, 0, 0)),
     "no_vertices_some_rows": (0, path(0, 1, 2), {}, (1, 0, 0)),
     "no_rows": (5, [], {}, (1, 0, 0)),
+    "one_vertex_no_rows": (1, [], {}, (1, 0, 0)),
+    # odd counts: the 32-bit arrays and the byte arrays of the scratch end inside a word.  A lone row hangs on nothing: it stays
+    "three_vertices_one_row": (3, path(0, 1), {}, (1, 0, 0)),
 }
 
 
@@ -131,6 +134,8 @@ def test_duplicates_self_loops_and_invalid_rows(g):
     assert info[3] >= 2 and info[5] == 4
     info = equal(g, n, rows, max_tip_reads=0, max_bubble_reads=0)
     assert info.tolist()[:6] == [len(rows) - 4, len(rows) - 4, 1, 0, 0, 4]
+    info = equal(g, 3, path(0, 1) + path(2, 2) + bad[:1])             # three vertices and three rows: a row, a self loop, an invalid row
+    assert info.tolist()[:6] == [2, 2, 1, 0, 0, 1]
 
 
 @pytest.mark.parametrize("name", sorted(PINNED))

@@ -169,6 +169,9 @@ def test_empty_string_n_and_a_loner(mixed, pairs):
     loner = 2 * 26                                                   # 10 reads, the empty one, 15 reads: read 26
     assert loner not in srcs and loner - 2 in srcs and loner + 2 in srcs, "no source without an edge between two with edges"
     assert 20 not in srcs and 21 not in srcs and len(want) > 100
+    assert len(_equal(ix, loner, 1, P, pairs)) == 0                  # one source, no edge
+    three = _equal(ix, loner - 2, 3, P, pairs)                       # three sources, the last one without an edge
+    assert len(three) and set(three[:, 0].tolist()) <= {loner - 2, loner - 1}
 
 
 @pytest.fixture(scope="module")

@@ -98,6 +98,8 @@ SMALL = {
     "no vertices": (0, [[0, 0, 9, 1], [1, 2, 9, 1]], [0, 0, 0, 2]),
     "nothing": (0, [], [0, 0, 0, 0]),
     "one vertex": (1, [[0, 0, 9, 3]], [1, 1, 1, 0]),
+    "one vertex, no edges": (1, [], [1, 0, 1, 0]),
+    "three vertices, one edge": (3, [[0, 1, 9, 1]], [2, 0, 2, 0]),   # odd counts: the 32-bit degree arrays end inside a word
 }
 
 
